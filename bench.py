@@ -49,6 +49,13 @@ Prints ONE JSON line (see the task contract) with extra objects:
                   gated semantics, HIP-graph replay (tools/bench_vendor.py, child process): a stated yardstick, not the target.
   cpu_baseline    the oracle (PyTorch CPU restatement, fp32) timed on this host's cores on a bounded sample: median of 5
                   steps of the headline workload (bs=4, masked) and of BASELINE configs[0] (bs=1, dense).
+
+--dump-outputs DIR
+    After the timed steps, rank 0 writes what the timed path returned in its LAST timed step as DIR/<name>.npy (float32,
+    float64 kept): infer -> ``sample`` (the U-Net output); train / finetune -> every tensor of the step's result dict
+    (losses, and for train the quantized architecture vectors).  Inputs and weights are seeded, so two builds run with
+    the same arguments can be compared array by array.  At most 64 MiB in all: beyond that, each array is replaced by a
+    fixed (seed 0) sample of its flattened elements.
 """
 import argparse
 import ctypes
@@ -66,6 +73,7 @@ if ROOT not in sys.path:
 
 PEAK_BF16_TFLOPS = 2500.0
 PEAK_HBM_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
 
 
 def parse_args(argv=None):
@@ -88,6 +96,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline legs (timing only)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo with --dryrun-cpu)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0; see the module docstring)")
     ap.add_argument("--dryrun-cpu", action="store_true",
                     help="TEST ONLY: run the launch / rendezvous / timing / reporting logic on CPU with the emulated ops of "
                          "tests/ on a tiny model (gloo); the printed line is marked as not a measurement")
@@ -96,6 +106,8 @@ def parse_args(argv=None):
         args.steps = 50 if args.config == "infer" else 10
     if args.warmup is None:
         args.warmup = 5 if args.config == "infer" else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.expert_offset is None:
         args.expert_offset = 3 if args.gpus == 1 else 0
     return args
@@ -250,6 +262,32 @@ def _dryrun_install():
     return bench_dryrun
 
 
+def dump_outputs(dirname: str, arrays: dict):
+    """arrays: name -> tensor.  Saved as float32 (float64 stays float64), DUMP_LIMIT_BYTES in all: the arrays are visited from
+    the smallest up and each keeps at most an equal share of what the earlier ones left, so small arrays stay whole and a
+    large one is cut to a seeded, sorted choice of its flat indices (the same for every run of the same shapes)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    left = DUMP_LIMIT_BYTES
+    for i, (name, a) in enumerate(sorted(host.items(), key=lambda kv: kv[1].nbytes)):
+        keep = max(1, left // (len(host) - i) // a.itemsize)
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def step_result_arrays(out: dict) -> dict:
+    """the tensors a caller of train_step receives (private entries and non-tensors left out)"""
+    import torch
+    return {k: v for k, v in out.items() if not k.startswith("_") and isinstance(v, torch.Tensor)}
+
+
 def run_infer(R: Rank):
     torch, args, dev = R.torch, R.args, R.dev
     from diffusion_pruning_amd import ops
@@ -279,8 +317,10 @@ def run_infer(R: Rank):
         R.sync()
         assert torch.isfinite(out).all()
         gout = None
+        last = {}
         if args.no_graph or R.cpu:
-            run = step
+            def run():
+                last["sample"] = step()
         else:
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
@@ -296,6 +336,8 @@ def run_infer(R: Rank):
             # the timed replays computed the same thing as the eager forward above (deterministic kernels, same inputs)
             d = float((gout.float() - out.float()).abs().max())
             assert torch.isfinite(gout).all() and d <= 1e-2 * float(out.float().abs().max()), f"graph replay differs from eager: {d}"
+        if args.dump_outputs and R.rank == 0:
+            dump_outputs(args.dump_outputs, {"sample": gout if gout is not None else last["sample"]})
         ms_per_step = elapsed / args.steps * 1e3
         value = R.world * args.steps / elapsed
         sustained = None
@@ -361,7 +403,7 @@ def run_infer(R: Rank):
     line = {
         "metric": "denoise-steps/s (SD-2.1 U-Net forward, 512x512, bs=4 per GPU, " + ("dense)" if args.dense else "50% channel mask)"),
         "value": round(value, 3), "unit": "steps/s", "n_gpus": R.n_seen, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step": round(ms_per_step, 6), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "bf16", "data": "synthetic",
         "config": {"workload": "BASELINE configs[1]: SD-2.1 UNet2DConditionModelGated.forward, 64x64 latents "
                                f"(512x512), bs={B}/GPU, {what}, seeded random-init weights, HIP graph replay",
@@ -426,6 +468,8 @@ def run_train(R: Rank, steps=None, warmup=None, extras: bool = True):
         out["o"] = step.train_step(opt, batch, pretrain=R.cpu)
 
     elapsed = R.timed(run, steps, warmup)
+    if args.dump_outputs and args.config == "train" and R.rank == 0:  # (not when run as an extra of the infer line)
+        dump_outputs(args.dump_outputs, step_result_arrays(out["o"]))     # before the probe steps below overwrite it
     # collective share: a few more steps with the device-side stopwatch around every collective of the step
     dist_utils.COLLECTIVE_TIMER = timer
     n_probe = min(steps, 5)
@@ -457,7 +501,7 @@ def run_train(R: Rank, steps=None, warmup=None, extras: bool = True):
         "metric": "pruning-train-steps/s (APTP Pruner.step: router + dense teacher fwd + soft-masked student fwd/bwd, SD-2.1, "
                   f"{latent}x{latent} latents, bs={args.batch} per GPU; summed over data-parallel ranks)",
         "value": round(value, 3), "unit": "steps/s", "n_gpus": R.n_seen, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step": round(ms_per_step, 6), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "bf16", "data": "synthetic",
         "config": {"workload": ("BASELINE configs[3]" if R.world > 1 else "BASELINE configs[2]") +
                                f": APTP pruning train step, synthetic CC3M-shape batch, bs={args.batch}/GPU, "
@@ -563,6 +607,8 @@ def run_finetune(R: Rank, steps=None, warmup=None, extras: bool = True):
 
     torch.cuda.reset_peak_memory_stats() if not R.cpu else None
     elapsed = R.timed(run, steps, warmup)
+    if args.dump_outputs and args.config == "finetune" and R.rank == 0:
+        dump_outputs(args.dump_outputs, step_result_arrays(out["o"]))
     loss = float(out["o"]["loss"])
     assert loss == loss, "fine-tune loss is NaN"
     my_rate = steps / R.last_local_elapsed                      # this rank's own rate; `elapsed` is the MAX over ranks
@@ -586,7 +632,7 @@ def run_finetune(R: Rank, steps=None, warmup=None, extras: bool = True):
                   "AdamW, SD-2.1, 64x64 latents, bs=4 per GPU; " + ("one expert on all GPUs, data-parallel)" if dp else
                                                                    "one expert per GPU, summed over ranks)"),
         "value": round(value, 3), "unit": "steps/s", "n_gpus": R.n_seen, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "ms_per_step": round(ms_per_step, 6), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "bf16", "data": "synthetic",
         "config": {"workload": f"BASELINE configs[4]: expert fine-tune, 8 seeded architecture codes (keep 0.40-0.75, 0-4 depth gates "
                                f"off), " + (f"all ranks train expert {expert}" if dp else f"rank r trains expert (r + {args.expert_offset}) % 8")

@@ -1,3 +1,4 @@
+import gc
 import os
 import sys
 
@@ -18,6 +19,28 @@ def cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _collect_between_modules():
+    gc.collect()                 # (dead cycles of the previous module's GPU tests go now, not at some later moment)
+    yield
+
+
+@pytest.fixture(autouse=True)
+def _no_gc_inside_graph_captures(request):
+    """GPU tests run with the automatic collector off; it runs again between tests.  torch no longer collects when a graph
+    capture begins, so a dead reference cycle left by an earlier test (a captured step holding its graphs and their
+    memory pool) could otherwise be collected in the middle of a capture, and its destructor would free device memory
+    inside the capture -- which aborts the process."""
+    if request.node.get_closest_marker("gpu") is None:
+        yield
+        return
+    gc.disable()
+    try:
+        yield
+    finally:
+        gc.enable()
 
 
 def pytest_sessionfinish(session, exitstatus):

@@ -1,6 +1,8 @@
 """Pins the oracle's gate semantics and the product's router / loss modules against vectors produced by the
 reference's own code (tests/golden/make_golden.py; data only).  Bit-exact where the arithmetic is elementwise
-fp32, 1e-6 where reductions may reassociate."""
+fp32 without transcendentals, 1e-6 where reductions may reassociate or where log / exp / pow enter (those are not
+correctly rounded: their last bit depends on the CPU's math library and vector width, so the generating machine's
+rounding cannot be asked for bit for bit)."""
 import os
 
 import numpy as np
@@ -38,15 +40,15 @@ def test_oracle_gates_match_reference():
 def test_estimation_utils():
     from diffusion_pruning_amd import estimation_utils as eu
     eq(eu.hard_concrete(T("hc_in")), T("hc_out"))
-    eq(eu.sample_gumbel((5, 7), fixed_seed=True), T("gumbel_fixed_5x7"))
+    eq(eu.sample_gumbel((5, 7), fixed_seed=True), T("gumbel_fixed_5x7"), 1e-6)
     lg = T("gs_logits")
-    eq(eu.gumbel_softmax_sample(lg, temperature=0.4, offset=3, fixed_seed=True), T("gs_fixed"))
+    eq(eu.gumbel_softmax_sample(lg, temperature=0.4, offset=3, fixed_seed=True), T("gs_fixed"), 1e-6)
     forced = eu.gumbel_softmax_sample(lg - 12.0, temperature=0.4, offset=3, force_width_non_zero=True, fixed_seed=True)
-    eq(forced, T("gs_fixed_force"))
+    eq(forced, T("gs_fixed_force"), 1e-6)
     assert bool((forced[:, 0] >= 0.5).all())          # the all-dead rows were bumped on entry 0
     eq(eu.importance_gumbel_softmax_sample(T("igs_logits"), temperature=0.4, offset=3, fixed_seed=True), T("igs_fixed"), 1e-6)
     torch.manual_seed(77)
-    eq(eu.gumbel_softmax_sample(lg, temperature=0.4, offset=3, force_width_non_zero=True), T("gs_global_seed77"))
+    eq(eu.gumbel_softmax_sample(lg, temperature=0.4, offset=3, force_width_non_zero=True), T("gs_global_seed77"), 1e-6)
     x = torch.tensor([0.2, 0.7], requires_grad=True)
     eu.hard_concrete(x).sum().backward()
     eq(x.grad, torch.ones(2))                           # straight-through
@@ -62,7 +64,7 @@ def test_losses_and_snr():
 
     class S:
         alphas_cumprod = T("snr_alphas_cumprod")
-    eq(compute_snr(S(), T("snr_t")), T("snr"))
+    eq(compute_snr(S(), T("snr_t")), T("snr"), 1e-6)
 
 
 def _sd(prefix):

@@ -383,8 +383,13 @@ def test_hypernet_heads_as_one_gemm_equal_the_per_head_loop(wn, bias):
     loop = copy.deepcopy(h)
     loop.fuse_heads = False
     x = torch.randn(4, 768)
+
+    def close(a, b):
+        # 1e-6 relative to the outputs' scale (they reach ~5): the fused GEMM and the per-head GEMMs may take different
+        # BLAS kernels, whose summation order -- and so the last bits -- depend on the CPU they run on
+        return float((a - b).abs().max()) <= 1e-6 * max(1.0, float(b.abs().max()))
     a, b = h(x), loop(x)
-    assert float((a - b).abs().max()) <= 1e-6
+    assert close(a, b)
     a.square().sum().backward()
     b.square().sum().backward()
     for (n, p), (n2, p2) in zip(h.named_parameters(), loop.named_parameters()):
@@ -398,8 +403,8 @@ def test_hypernet_heads_as_one_gemm_equal_the_per_head_loop(wn, bias):
     loop2 = HyperStructure(st, wn_flag=wn, linear_bias=bias)
     h.load_state_dict(loop2.state_dict())
     loop2.fuse_heads = False
-    assert float((h(x) - loop2(x)).abs().max()) <= 1e-6
-    assert float((copy.deepcopy(h)(x) - loop2(x)).abs().max()) <= 1e-6
+    assert close(h(x), loop2(x))
+    assert close(copy.deepcopy(h)(x), loop2(x))
     h.double()                                       # re-allocates the parameters: the flat buffers are rebuilt
     assert h(x.double()).dtype == torch.float64 and h._flat["v"].dtype == torch.float64
 
