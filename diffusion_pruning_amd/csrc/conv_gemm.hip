@@ -1478,6 +1478,12 @@ extern "C" int aptp_conv_gemm(const AptpConvGemmParams* p, aptp_stream_t stream)
                      "Hout*Wout %% %d == 0 (aptp_conv_gemm_colstat_rows) and colstat_ld >= N", wtm);
       return APTP_EINVAL;
     }
+    // unit statistics: lane u of a wave folds the u-th channel unit its columns touch, so a wave's columns may touch at most 64
+    const int wl = k.act == APTP_ACT_GEGLU ? wtn / 2 : wtn;
+    if (k.ustat_out && (wl % k.ustat_unit == 0 ? wl / k.ustat_unit : (wl - 1) / k.ustat_unit + 2) > 64) {
+      aptp_set_error("conv_gemm: ustat_unit %d too small for the %d columns of a wave of tile %d (at most 64 units per wave)", k.ustat_unit, wl, t);
+      return APTP_EINVAL;
+    }
   }
   if (k.act == APTP_ACT_GEGLU && (kTiles[t].bn == 160)) {
     aptp_set_error("conv_gemm: GEGLU cannot use a 160-wide tile");
@@ -1498,6 +1504,12 @@ extern "C" int aptp_conv_gemm(const AptpConvGemmParams* p, aptp_stream_t stream)
     APTP_LAUNCH_CHECK();
     return APTP_OK;
   }
+  // 3x3 convolutions take the lean kernel of the same tile (conv_lean.hip); APTP_CONV_LEAN=0 keeps them here (A/B timing, tests)
+  static const bool lean_on = !(getenv("APTP_CONV_LEAN") && getenv("APTP_CONV_LEAN")[0] == '0');
+  if (lean_on && p->epilogue == 0 && aptp_conv_lean_eligible(k, t)) {
+    const int rc2 = aptp_launch_conv_lean(k, t, s);
+    if (rc2 != APTP_OK) return rc2;
+  } else
   switch (t) {
     case APTP_TILE_128x128: launch_tile<128, 128>(k, s); break;
     case APTP_TILE_128x160: launch_tile<128, 160>(k, s); break;

@@ -441,6 +441,54 @@ __device__ __forceinline__ void emit_unit_stats(const KParams& p, const float (&
   __hip_atomic_fetch_add(dst + 1, (unsigned long long)__float2ll_rn(s2 * USTAT_SQ_SCALE), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Column statistics of a wave's stored block (p.cstat_out, and p.ustat_out on top): lane (lrow, lc8) holds in cs / cs2 the per-channel
+// (sum, sumsq) of columns cw0 + lc8*8 .. +7 over the rows it stored.  The RPP lanes with the same 8-column chunk (lrow = 0..RPP-1)
+// are folded through the wave's LDS slice, sums first, then squares (RPP*WL floats of the slice); one (sum, sumsq) per channel
+// goes to row block `rblk` of cstat_out.  Fixed order: deterministic.  Shared by tile_epilogue_lds and the lean 3x3 kernel
+// (conv_lean.hip), so both emit bit-identical statistics for the same stored values.
+template <int WL, int RPP>
+__device__ __forceinline__ void emit_col_stats(const KParams& p, const float (&cs)[8], const float (&cs2)[8], float* buf, int lane, int lrow,
+                                               int lc8, int cw0, int rblk, int row0) {
+  float tot[2][(WL + 63) / 64];
+#pragma unroll
+  for (int ph = 0; ph < 2; ++ph) {
+    if (lrow < RPP) {
+      float* dst = buf + lrow * WL + lc8 * 8;
+      if (ph == 0) {
+        *reinterpret_cast<float4*>(dst) = make_float4(cs[0], cs[1], cs[2], cs[3]);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(cs[4], cs[5], cs[6], cs[7]);
+      } else {
+        *reinterpret_cast<float4*>(dst) = make_float4(cs2[0], cs2[1], cs2[2], cs2[3]);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(cs2[4], cs2[5], cs2[6], cs2[7]);
+      }
+    }
+    // Lanes exchange data through LDS here without a workgroup barrier (one wave, in-order LDS): the compiler must
+    // still be told.  Without the fence it reasons per thread -- "a lane that skipped the store reads what it read in
+    // the previous phase" -- and reuses the phase-0 loads for the lanes with lrow >= RPP (seen: sumsq == sum there).
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < (WL + 63) / 64; ++q) {
+      const int t = lane + 64 * q;
+      float a = 0.f;
+      if (t < WL) {
+#pragma unroll
+        for (int r = 0; r < RPP; ++r) a += buf[r * WL + t];
+      }
+      tot[ph][q] = a;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  float2* dstg = reinterpret_cast<float2*>(p.cstat_out) + (int64_t)rblk * p.cstat_ld;
+#pragma unroll
+  for (int q = 0; q < (WL + 63) / 64; ++q) {
+    const int t = lane + 64 * q;
+    if (t < WL && cw0 + t < p.Nout) dstg[cw0 + t] = make_float2(tot[0][q], tot[1][q]);
+  }
+  if (p.ustat_out) emit_unit_stats<WL>(p, tot, buf, lane, cw0, row0);
+}
+
 // Coalesced epilogue (bf16 outputs whose rows are 16-byte aligned).  The MFMA accumulator layout gives a lane 4 columns
 // of 16 different rows, so storing from it costs one 8-byte access per (row, quad): 16 x 32-byte pieces per wave
 // instruction, and as many again for the residual / depth-gate operands.  The short-K launches of the masked U-Net
@@ -586,52 +634,174 @@ __device__ __forceinline__ void tile_epilogue_lds(const KParams& p, f32x4 (&acc)
   }
   APTP_EPI(4);
   if constexpr (!GEGLU && WL >= 32) {
-    if (p.cstat_out) {
-      // GroupNorm statistics for the consumer of y: per channel, the sum / sum of squares over the WTM rows this wave
-      // stored.  Lanes with the same 8-column chunk (lrow = 0..RPP-1) are folded through the wave's LDS slice, sums first,
-      // then squares (RPP*WL <= 512 floats fit the 16 x (WL+4) slice); one (sum, sumsq) per channel goes to row block
-      // m0/WTM + wm of cstat_out.  Fixed order: deterministic.
-      static_assert(RPP * WL <= 16 * PITCH, "column-statistics staging");
-      float tot[2][(WL + 63) / 64];
+    static_assert(RPP * WL <= 16 * PITCH, "column-statistics staging");
+    if (p.cstat_out) emit_col_stats<WL, RPP>(p, cs, cs2, buf, lane, lrow, lc8, n0 + wn * WTN, m0 / WTM + wm, m0 + wm * WTM);
+  }
+}
+
+// One-pass transposed epilogue of the lean 3x3 kernel (conv_lean.hip).  Same transposed layout as tile_epilogue_lds -- a
+// 16-row accumulator fragment goes through the wave's LDS slice, then lane (lrow, lc8) owns columns c0 .. c0+7 of row lrow of
+// each pass of RPF rows -- but the fragment goes through LDS RAW and the whole epilogue runs in the transposed domain, on
+// inputs requested in the kernel prologue (LeanEpiIn, before the first wait): bias, time-embedding row bias, width gate,
+// activation, GroupNorm-beta correction, residual, in the order of epilogue_pre + tile_epilogue_lds, so the stored values --
+// and, through emit_col_stats, the column and unit statistics -- are bit-identical to that epilogue's.
+// bf16 output, 16-byte aligned rows (p.epi16), no GEGLU / folded LayerNorm / row statistics / depth lerp (the host's eligibility
+// test; the lerp's multiply-adds are contracted differently element by element in tile_epilogue_lds, so a transposed-domain copy
+// of it is not bit-identical).
+template <int WTM, int WTN>
+struct LeanEpiIn {
+  static constexpr int LPR = WTN / 8, RPF = 64 / LPR, NPF = (16 + RPF - 1) / RPF, NP = (WTM / 16) * NPF;
+  float cb[8], rb[8], gm[8];        // bias, row bias, gate of the wave's first sample (one_b: its only sample)
+  float cr[NP][8];                  // beta correction of each pass's row
+  u32x4 res[NP];                    // residual of each pass's row
+  bool one_b;                       // (wave-uniform) every row of the wave's block belongs to one sample
+};
+
+// per-sample column vectors of columns cc .. cc+7: row bias, width gate
+template <int WTM, int WTN>
+__device__ __forceinline__ void lean_epi_sample(const KParams& p, int b, int cc, float (&rb)[8], float (&gm)[8]) {
+  if (p.rowbias) {
+    const float4 a = *reinterpret_cast<const float4*>(p.rowbias + (int64_t)b * p.ld_rowbias + cc);
+    const float4 c = *reinterpret_cast<const float4*>(p.rowbias + (int64_t)b * p.ld_rowbias + cc + 4);
+    rb[0] = a.x; rb[1] = a.y; rb[2] = a.z; rb[3] = a.w; rb[4] = c.x; rb[5] = c.y; rb[6] = c.z; rb[7] = c.w;
+  }
+  if (p.colgate) {
+    const float* gr = p.colgate + (int64_t)(b % p.gate_B) * (p.N / p.gate_group);
 #pragma unroll
-      for (int ph = 0; ph < 2; ++ph) {
-        if (lrow < RPP) {
-          float* dst = buf + lrow * WL + lc8 * 8;
-          if (ph == 0) {
-            *reinterpret_cast<float4*>(dst) = make_float4(cs[0], cs[1], cs[2], cs[3]);
-            *reinterpret_cast<float4*>(dst + 4) = make_float4(cs[4], cs[5], cs[6], cs[7]);
-          } else {
-            *reinterpret_cast<float4*>(dst) = make_float4(cs2[0], cs2[1], cs2[2], cs2[3]);
-            *reinterpret_cast<float4*>(dst + 4) = make_float4(cs2[4], cs2[5], cs2[6], cs2[7]);
-          }
-        }
-        // Lanes exchange data through LDS here without a workgroup barrier (one wave, in-order LDS): the compiler must
-        // still be told.  Without the fence it reasons per thread -- "a lane that skipped the store reads what it read in
-        // the previous phase" -- and reuses the phase-0 loads for the lanes with lrow >= RPP (seen: sumsq == sum there).
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+    for (int e = 0; e < 8; ++e) gm[e] = gr[(cc + e) / p.gate_group];
+  }
+}
+
+template <int WTM, int WTN>
+__device__ __forceinline__ void lean_epi_load(const KParams& p, int m0, int n0, int wm, int wn, int lane, LeanEpiIn<WTM, WTN>& in) {
+  using E = LeanEpiIn<WTM, WTN>;
+  const int lrow = lane / E::LPR, lc8 = lane - lrow * E::LPR;
+  const int c0 = n0 + wn * WTN + lc8 * 8;
+  const int cc = c0 < p.Nout ? c0 : p.Nout - 8;          // lanes past the last column read a valid chunk and store nothing
+  const int mw0 = m0 + wm * WTM;
+  const int mf = mw0 < p.M ? mw0 : p.M - 1, ml = mw0 + WTM - 1 < p.M ? mw0 + WTM - 1 : p.M - 1;
+  const int b0 = p.fd_hw.div(mf);
+  in.one_b = p.fd_hw.div(ml) == b0;
 #pragma unroll
-        for (int q = 0; q < (WL + 63) / 64; ++q) {
-          const int t = lane + 64 * q;
-          float a = 0.f;
-          if (t < WL) {
+  for (int e = 0; e < 8; ++e) { in.cb[e] = 0.f; in.rb[e] = 0.f; in.gm[e] = 1.f; }
+  if (p.bias) {
+    const float4 a = *reinterpret_cast<const float4*>(p.bias + cc), c = *reinterpret_cast<const float4*>(p.bias + cc + 4);
+    in.cb[0] = a.x; in.cb[1] = a.y; in.cb[2] = a.z; in.cb[3] = a.w; in.cb[4] = c.x; in.cb[5] = c.y; in.cb[6] = c.z; in.cb[7] = c.w;
+  }
+  lean_epi_sample<WTM, WTN>(p, b0, cc, in.rb, in.gm);
 #pragma unroll
-            for (int r = 0; r < RPP; ++r) a += buf[r * WL + t];
-          }
-          tot[ph][q] = a;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-      const int cw0 = n0 + wn * WTN;
-      float2* dstg = reinterpret_cast<float2*>(p.cstat_out) + (int64_t)(m0 / WTM + wm) * p.cstat_ld;
+  for (int q = 0; q < E::NP; ++q) {
+    const int i = q / E::NPF, ps = q - i * E::NPF;
+    const int r = ps * E::RPF + lrow, m2 = mw0 + i * 16 + (r < 16 ? r : 15);
+    const int mc = m2 < p.M ? m2 : p.M - 1;
+    in.res[q] = (u32x4){0u, 0u, 0u, 0u};
+    if (p.residual) in.res[q] = *reinterpret_cast<const u32x4*>(p.residual + (int64_t)mc * p.ldres + cc);
 #pragma unroll
-      for (int q = 0; q < (WL + 63) / 64; ++q) {
-        const int t = lane + 64 * q;
-        if (t < WL && cw0 + t < p.Nout) dstg[cw0 + t] = make_float2(tot[0][q], tot[1][q]);
-      }
-      if (p.ustat_out) emit_unit_stats<WL>(p, tot, buf, lane, cw0, m0 + wm * WTM);
+    for (int e = 0; e < 8; ++e) in.cr[q][e] = 0.f;
+    if (p.corr) {
+      RowCtx rc;
+      row_info(p, mc, rc);
+      const float* cp = p.corr + ((int64_t)(rc.b % p.corr_B) * 9 + rc.cls) * p.Nout + cc;
+      const float4 a = *reinterpret_cast<const float4*>(cp), c = *reinterpret_cast<const float4*>(cp + 4);
+      in.cr[q][0] = a.x; in.cr[q][1] = a.y; in.cr[q][2] = a.z; in.cr[q][3] = a.w;
+      in.cr[q][4] = c.x; in.cr[q][5] = c.y; in.cr[q][6] = c.z; in.cr[q][7] = c.w;
     }
+  }
+}
+
+template <int MF, int NF, int WTM, int WTN>
+__device__ __forceinline__ void lean_epilogue(const KParams& p, f32x4 (&acc)[MF][NF], int m0, int n0, int wm, int wn, int lane,
+                                              const LeanEpiIn<WTM, WTN>& in, float* buf) {
+  using E = LeanEpiIn<WTM, WTN>;
+  constexpr int WL = WTN, PITCH = WL + 4, LPR = E::LPR, RPF = E::RPF, NPF = E::NPF;
+  static_assert(WL % 8 == 0 && WL >= 32 && RPF * WL <= 16 * PITCH, "transposed layout / column-statistics staging");
+  const int frow = lane & 15, fq = lane >> 4;
+  const int lrow = lane / LPR, lc8 = lane - lrow * LPR;
+  const int c0 = n0 + wn * WTN + lc8 * 8;
+  const int cc = c0 < p.Nout ? c0 : p.Nout - 8;
+  const bool lane_on = lrow < RPF && c0 < p.Nout;
+  const int mw0 = m0 + wm * WTM;
+  __bf16* const yb = reinterpret_cast<__bf16*>(p.y);
+  float cs[8], cs2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { cs[e] = 0.f; cs2[e] = 0.f; }
+#pragma unroll
+  for (int i = 0; i < MF; ++i) {
+    if (i > 0) {                          // the previous fragment's transposed reads are done before its slots are rewritten
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int j = 0; j < NF; ++j) *reinterpret_cast<f32x4*>(buf + frow * PITCH + j * 16 + fq * 4) = acc[i][j];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // cross-lane exchange through LDS inside one wave (in-order LDS)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int ps = 0; ps < NPF; ++ps) {
+      const int q = i * NPF + ps;
+      const int r = ps * RPF + lrow, m2 = mw0 + i * 16 + r;
+      const bool on = lane_on && r < 16 && m2 < p.M;
+      float v[8];
+      {
+        const int rr = r < 16 ? r : 15;
+        const float4 a = *reinterpret_cast<const float4*>(buf + rr * PITCH + lc8 * 8);
+        const float4 b4 = *reinterpret_cast<const float4*>(buf + rr * PITCH + lc8 * 8 + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b4.x; v[5] = b4.y; v[6] = b4.z; v[7] = b4.w;
+      }
+      float rb[8], gm[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { rb[e] = in.rb[e]; gm[e] = in.gm[e]; }
+      if (!in.one_b && (p.rowbias || p.colgate)) {   // (wave-uniform) a block across a sample boundary: small maps, ragged M
+        const int mr = mw0 + i * 16 + (r < 16 ? r : 15), mc = mr < p.M ? mr : p.M - 1;
+        lean_epi_sample<WTM, WTN>(p, p.fd_hw.div(mc), cc, rb, gm);
+      }
+      // epilogue_pre order: bias, row bias, gate, activation, beta correction
+      if (p.bias) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += in.cb[e];
+      }
+      if (p.rowbias) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += rb[e];
+      }
+      if (p.colgate) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= gm[e];
+      }
+      if (p.act == APTP_ACT_SILU) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = silu_f(v[e]);
+      }
+      if (p.corr) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += in.cr[q][e];
+      }
+      // tile_epilogue_lds rounds nothing here but passes the value through LDS: keep the same floating-point contraction
+      // boundary (no multiply above fuses with the residual add below)
+#if defined(__HIP_DEVICE_COMPILE__)      // (a "v" constraint does not exist for the host pass, which would drop the kernel's stub)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(v[e]));
+#endif
+      if (p.residual) {
+        float f[8];
+        union { u32x4 v; uint4 s; } cv; cv.v = in.res[q];
+        unpack_bf16x8(cv.s, f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += f[e];
+      }
+      const uint4 o = pack_bf16x8(v);
+      if (on) *reinterpret_cast<uint4*>(yb + (int64_t)m2 * p.ldy + c0) = o;
+      if (p.cstat_out && on) {   // statistics of the values as stored (bf16-rounded): what the GroupNorm will read
+        float f[8];
+        unpack_bf16x8(o, f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { cs[e] += f[e]; cs2[e] += f[e] * f[e]; }
+      }
+    }
+  }
+  if (p.cstat_out) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    emit_col_stats<WL, RPF>(p, cs, cs2, buf, lane, lrow, lc8, n0 + wn * WTN, m0 / WTM + wm, mw0);
   }
 }
 
@@ -751,5 +921,8 @@ int aptp_launch_sk(const KParams& k, int tile, hipStream_t s);
 // lin_gemm.hip: lean kernels for plain linear layers (1x1, stride 1, one K-slice, coalesced bf16 epilogue)
 bool aptp_lin_eligible(const KParams& k, int tile);
 int aptp_launch_lin(const KParams& k, int tile, hipStream_t s);
+// conv_lean.hip: lean kernels for the 3x3 convolutions (tap offset tables, up-front epilogue inputs, one-pass epilogue)
+bool aptp_conv_lean_eligible(const KParams& k, int tile);
+int aptp_launch_conv_lean(const KParams& k, int tile, hipStream_t s);
 
 }  // namespace aptp_cg
