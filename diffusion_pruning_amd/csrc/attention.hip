@@ -659,12 +659,6 @@ __global__ __launch_bounds__(512) void attn_fwd_sp_kernel(const AttnK p) {
   // its 8 MFMAs (256 cycles) before it issues a single softmax instruction.  The body below is written slot by slot -- one
   // MFMA plus >= 32 issue cycles of independent vector work -- and sched_barrier(0) between the slots pins that order.
 #define APTP_SLOT_END() __builtin_amdgcn_sched_barrier(0)
-#ifndef APTP_ATTN_ABL
-#define APTP_ATTN_ABL 0      // timing experiments only (wrong results): 1 no exp2, 2 no loop barrier, 4 no LDS staging stores, 8 no MFMAs,
-#endif                       // 16 fragments from registers (no LDS fragment reads), 64 per-phase cycle totals of block 0 into p.lse
-  unsigned long long st_prev = 0, st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define APTP_ATTN_STAMP(i) do { if constexpr ((APTP_ATTN_ABL & 64) != 0) { const unsigned long long t_ = __builtin_readcyclecounter(); \
-    if ((i) > 0) st_acc[(i) - 1] += t_ - st_prev; st_prev = t_; } } while (0)
   // K fragment j = (s, t) = (j >> 1, j & 1) of the tile in K buffer `buf`; V fragment j = (t, s2, u) = (j >> 2, (j >> 1) & 1, j & 1)
   auto read_k = [&](bf16x8 (&kf)[8], int buf) {
     const __bf16* Ks = kv_base + buf * KV_ELEMS;
@@ -703,33 +697,29 @@ __global__ __launch_bounds__(512) void attn_fwd_sp_kernel(const AttnK p) {
                        const u32x4 (&kreg)[2], const u32x4 (&vreg)[2], u32x4 (&kreq)[2], u32x4 (&vreq)[2]) {
     constexpr bool WITH_NEXT = decltype(with_next)::value;
     bf16x8 kf[8], vf[8], pf[4];
-    APTP_ATTN_STAMP(0);
     if constexpr (WITH_NEXT) {
       load_k(kreq, tk);
       load_v(vreq, tv);
-      if constexpr ((APTP_ATTN_ABL & 16) != 0) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) kf[j] = qf[j & 3];
-      } else read_k(kf, kbuf);
+      read_k(kf, kbuf);
     }
     // score MFMA j of the next tile (accumulator t = j & 1, Q fragment s = j >> 1)
     auto qk = [&](int j) {
-      if constexpr (WITH_NEXT && !(APTP_ATTN_ABL & 8)) nxt[j & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[j], qf[j >> 1], j < 2 ? zero16 : nxt[j & 1], 0, 0, 0);
+      if constexpr (WITH_NEXT) nxt[j & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[j], qf[j >> 1], j < 2 ? zero16 : nxt[j & 1], 0, 0, 0);
     };
-    auto pv = [&](int j) { if constexpr (!(APTP_ATTN_ABL & 8)) oacc[j & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[j], pf[j >> 1], oacc[j & 1], 0, 0, 0); };
+    auto pv = [&](int j) { oacc[j & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[j], pf[j >> 1], oacc[j & 1], 0, 0, 0); };
     float rs = 0.f, m_new;
     // half a P fragment: exp2 / row sum / bf16 pack of 4 scores (fragment q = (t, s2) = (q >> 1, q & 1), half hf)
     auto exp4 = [&](int q, int hf) {
 #pragma unroll
       for (int j = 4 * hf; j < 4 * hf + 4; ++j) {
         const float x = __builtin_fmaf(cur[q >> 1][8 * (q & 1) + j], p.c, -m_new);
-        const float e = (APTP_ATTN_ABL & 1) ? x : __builtin_amdgcn_exp2f(x);
+        const float e = __builtin_amdgcn_exp2f(x);
         rs += e;
         pf[q][j] = (__bf16)e;
       }
     };
     auto stage_v = [&]() {
-      if constexpr (WITH_NEXT && !(APTP_ATTN_ABL & 4)) store_v(vreg, vst);      // V(i+1) over V(i-1)
+      if constexpr (WITH_NEXT) store_v(vreg, vst);      // V(i+1) over V(i-1)
     };
     // A: running maximum (2 slots of 16 scores) next to score MFMAs 0, 1
     float mx = -INFINITY;
@@ -750,11 +740,7 @@ __global__ __launch_bounds__(512) void attn_fwd_sp_kernel(const AttnK p) {
       }
       APTP_SLOT_END();
     }
-    APTP_ATTN_STAMP(1);
-    if constexpr ((APTP_ATTN_ABL & 16) != 0) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vf[j] = qf[j & 3];
-    } else read_v(vf, vbuf);
+    read_v(vf, vbuf);
     float mlo, mhi;
     halves(mx, mlo, mhi);
     mx = fmaxf(mlo, mhi) * p.c;
@@ -769,28 +755,23 @@ __global__ __launch_bounds__(512) void attn_fwd_sp_kernel(const AttnK p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[u][r] *= alpha;
     }
-    APTP_ATTN_STAMP(2);
     // C0: P fragment 0 next to score MFMAs 2, 3
     qk(2); exp4(0, 0); APTP_SLOT_END();
     qk(3); exp4(0, 1); APTP_SLOT_END();
-    APTP_ATTN_STAMP(3);
     // C1-C3: P fragment q next to the P.V MFMAs of fragment q - 1 and one more score MFMA
 #pragma unroll
     for (int q = 1; q < 4; ++q) {
       pv(2 * q - 2); qk(3 + q); exp4(q, 0); APTP_SLOT_END();
       pv(2 * q - 1); exp4(q, 1); APTP_SLOT_END();
     }
-    APTP_ATTN_STAMP(4);
     float slo, shi;
     halves(rs, slo, shi);
     l_run = l_run * alpha + (slo + shi);
     m_run = m_new;
     // D: the last two P.V MFMAs and the last score MFMA next to the LDS stores of V(i+1) and K(i+2)
     pv(6); stage_v(); APTP_SLOT_END();
-    pv(7); qk(7); if constexpr (WITH_NEXT && !(APTP_ATTN_ABL & 4)) store_k(kreg, kst);      // K(i+2) over K(i) (past the end: a clamped copy nobody reads)
-    APTP_ATTN_STAMP(5);
-    if constexpr (WITH_NEXT && !(APTP_ATTN_ABL & 2)) __syncthreads();
-    APTP_ATTN_STAMP(6);
+    pv(7); qk(7); if constexpr (WITH_NEXT) store_k(kreg, kst);      // K(i+2) over K(i) (past the end: a clamped copy nobody reads)
+    if constexpr (WITH_NEXT) __syncthreads();
   };
 
   // prologue: K(0), V(0), K(1) staged; S(0) computed; K(2), V(1) requested
@@ -851,10 +832,7 @@ __global__ __launch_bounds__(512) void attn_fwd_sp_kernel(const AttnK p) {
       for (int r = 0; r < 16; ++r) oacc[u][r] = oacc[u][r] * a0 + src[2 + u * 16 + r] * a1;
   }
   const int qrow = q0 + lq;
-  if constexpr ((APTP_ATTN_ABL & 64) != 0) {
-    if (p.lse && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0)
-      for (int j = 0; j < 6; ++j) p.lse[wave * 8 + j] = (float)st_acc[j] / (float)n;
-  } else if (p.lse && hh == 0) p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = m_run + log2f(l_run);
+  if (p.lse && hh == 0) p.lse[((int64_t)b * p.H + h) * p.Lq + qrow] = m_run + log2f(l_run);
   const float inv = 1.0f / l_run;
   __bf16* op = p.o + (int64_t)b * p.osb + (int64_t)qrow * p.osl + (int64_t)h * 64;
 #pragma unroll

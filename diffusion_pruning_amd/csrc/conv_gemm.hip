@@ -10,7 +10,6 @@
 // each lane ends up with 4 consecutive output channels of one pixel => 8-byte epilogue loads/stores.
 // The architecture-code gate, time-embedding bias, GEGLU, GroupNorm-beta correction, residual and depth lerp are
 // fused into the epilogue (see include/aptp_hip.h for the reference call sites each one replaces).
-#define APTP_CG_MAIN 1   // this file owns the timing-experiment stamp buffers
 #include "conv_gemm_core.h"
 
 using namespace aptp_cg;
@@ -156,11 +155,6 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const KParams p) {
     for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int frow = lane & 15, fq = lane >> 4;
-#if APTP_ABLATE & 4
-  bf16x8 abl_frag;
-  for (int e = 0; e < 8; ++e) abl_frag[e] = (__bf16)(float)(lane + e);
-  asm volatile("" : "+v"(abl_frag));
-#endif
   auto compute = [&](int buf) {
     if constexpr (F32) {
       // exact-fp32 MFMA 16x16x4: a lane supplies ONE value per operand, k = lane >> 4.  The two 16-byte chunks 2*fq and 2*fq+1
@@ -284,9 +278,6 @@ __device__ uint4 g_zero_page[512];
 //         hands its accumulators to copy 0 through LDS and retires (s_barrier counts surviving waves only), copy 0 runs the
 //         epilogue.  Twice the waves per SIMD on the same operand traffic, for the small tiles whose waves otherwise sit
 //         alone on their SIMD between DMA issue, LDS reads and MFMAs.
-#ifndef APTP_IL
-#define APTP_IL 0
-#endif
 template <int BM, int BN, int WM, int WN, int STAGES, bool PP = false, int KU = 1, int KS = 1>
 __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const KParams p) {
   constexpr int NW = WM * WN;                 // waves of one compute grid
@@ -303,10 +294,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
   __shared__ __attribute__((aligned(16))) __bf16 smem[STAGES * (BM + BN) * BK];
   __bf16* As = smem;
   __bf16* Bs = smem + STAGES * BM * BK;
-#ifdef APTP_STAMPS
-  const unsigned long long st_entry = __builtin_readcyclecounter();
-  unsigned long long st_phase[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform: LDS-DMA bases stay scalar
@@ -320,11 +307,9 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
   const int kt_begin = p.fd_sk.div(p.nK * kz);            // (nK * split_k < 2^31: checked on the host)
   const int kt_end = p.fd_sk.div(p.nK * (kz + 1));
   __shared__ unsigned pf_scratch[64];
-  APTP_PHASE(4);          // tile decoded (the first kernel-argument batches have arrived)
   prefetch_next(p, tid, NT, pf_scratch);
   LnRaw<MF> ln_raw;
   ln_rows_issue<MF, WTM>(p, m0, wm, lane, ln_raw);
-  APTP_PHASE(5);          // next-launch prefetch + LayerNorm statistics requested
 
   const int rowbase = tid >> 3;
   const int schunk = (tid & 7) ^ ((rowbase >> 1) & 7);      // source chunk that lands in this lane's LDS slot
@@ -390,14 +375,10 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
     b_ptr[i] = reinterpret_cast<const char*>(p.w) + ((int64_t)n * p.Ktot + (int64_t)kt_begin * BK + schunk * 8) * 2;
   }
   set_tap(l_cc);
-  APTP_PHASE(6);          // operand addresses ready
 
   typedef __attribute__((address_space(3))) void* lds_ptr;
   typedef const __attribute__((address_space(1))) void* gbl_ptr;
 
-#if APTP_ABLATE & 1
-  bool abl_first = true;
-#endif
   auto issue_tile = [&](int buf) {
     const bool seg2 = l_ky >= p.KH;                                 // wave-uniform
     const bool last_cc = l_cc == (seg2 ? p.ncc2 : p.ncc) - 1;
@@ -407,9 +388,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
       if (wave * 8 + RPP * i < BM) {                               // wave-uniform: the last pass may be partial
         const char* src = (last_cc && tb) ? zpage : a_ptr[i];
         __bf16* dst = As + (buf * BM + wave * 8 + RPP * i) * BK;   // wave-uniform; lane l lands at dst + l*16 B
-#if APTP_ABLATE & 1
-        if (abl_first)
-#endif
         __builtin_amdgcn_global_load_lds((gbl_ptr)src, (lds_ptr)dst, 16, 0, 0);
       }
       a_ptr[i] += BK * 2;
@@ -418,9 +396,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
     for (int i = 0; i < B_PASS; ++i) {
       if (wave * 8 + RPP * i < BN) {
         __bf16* dst = Bs + (buf * BN + wave * 8 + RPP * i) * BK;
-#if APTP_ABLATE & 1
-        if (abl_first)
-#endif
         __builtin_amdgcn_global_load_lds((gbl_ptr)b_ptr[i], (lds_ptr)dst, 16, 0, 0);
       }
       b_ptr[i] += BK * 2;
@@ -430,9 +405,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
       if (++l_kx == p.KW || seg2) { l_kx = 0; ++l_ky; }
       set_tap(0);
     }
-#if APTP_ABLATE & 1
-    abl_first = false;
-#endif
   };
 
   f32x4 acc[MF][NF];
@@ -441,16 +413,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
 #pragma unroll
     for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-#ifdef APTP_STAMPS
-  unsigned long long st_acc[3] = {0, 0, 0}, st_prev = 0;
-  const unsigned long long st_begin = __builtin_readcyclecounter();
-#endif
   const int frow = lane & 15, fq = lane >> 4;
-#if APTP_ABLATE & 4
-  bf16x8 abl_frag;
-  for (int e = 0; e < 8; ++e) abl_frag[e] = (__bf16)(float)(lane + e);
-  asm volatile("" : "+v"(abl_frag));
-#endif
   auto compute = [&](int buf) {
 #pragma unroll
     for (int s0 = 0; s0 < 2 / KS; ++s0) {
@@ -460,31 +423,19 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
       for (int i = 0; i < MF; ++i) {
         const int r = wm * WTM + i * 16 + frow;
         const int sw = (s * 4 + fq) ^ ((r >> 1) & 7);
-#if APTP_ABLATE & 4
-        af[i] = abl_frag; (void)r; (void)sw;
-#else
         af[i] = *reinterpret_cast<const bf16x8*>(As + (buf * BM + r) * BK + sw * 8);
-#endif
       }
 #pragma unroll
       for (int j = 0; j < NF; ++j) {
         const int r = wn * WTN + j * 16 + frow;
         const int sw = (s * 4 + fq) ^ ((r >> 1) & 7);
-#if APTP_ABLATE & 4
-        wf[j] = abl_frag; (void)r; (void)sw;
-#else
         wf[j] = *reinterpret_cast<const bf16x8*>(Bs + (buf * BN + r) * BK + sw * 8);
-#endif
       }
 #pragma unroll
       for (int i = 0; i < MF; ++i)
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
-#if APTP_ABLATE & 2
-          asm volatile("" :: "v"(wf[j]), "v"(af[i]));
-#else
           acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-#endif
         }
     }
   };
@@ -532,10 +483,8 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
       int cur = 0, nxt = D % STAGES;
       for (int kt = 0; kt < n; ++kt) {
         // ---- slot L(kt): the load path ----
-        APTP_STAMP(0);
         const bool issue = kt + D < n;
         if (issue) issue_tile(nxt);
-        APTP_STAMP(1);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
@@ -544,22 +493,18 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
         __builtin_amdgcn_s_setprio(1);
         compute(cur);
         __builtin_amdgcn_s_setprio(0);
-        APTP_STAMP(2);
         asm volatile("" ::: "memory");
-#if !(APTP_ABLATE & 16)
         if (issue) {
           if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
           else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 1)) : "memory");
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-#endif
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" ::: "memory");
-        APTP_STAMP(3);
         cur = cur + 1 == STAGES ? 0 : cur + 1;
         nxt = nxt + 1 == STAGES ? 0 : nxt + 1;
       }
@@ -584,7 +529,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
     if (n > 0) {
       const int pre = n < D ? n : D;
       for (int t = 0; t < pre; ++t) issue_tile(t);
-      APTP_PHASE(0);
       ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
       if (pre == D && D > 2) {   // tiles 0 and 1 landed, D-2 tiles still in flight
         if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 2)) : "memory");
@@ -594,7 +538,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
       }
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      APTP_PHASE(1);
       int cur = 0, nxt = D;
       for (int kt = 0; kt < n; kt += 2) {
         const int ni = n - (kt + D);          // tiles left to request: two per iteration while >= 2
@@ -620,21 +563,13 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
   if constexpr (STAGES == 2) {
     if (kt_begin < kt_end) {
       issue_tile(0);
-      APTP_PHASE(0);
       ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
       __syncthreads();                       // (the compiler drains vmcnt(0) for the LDS-DMA before the barrier)
-      APTP_PHASE(1);
       int buf = 0;
       for (int kt = kt_begin; kt < kt_end; ++kt) {
-        APTP_STAMP(0);
         if (kt + 1 < kt_end) issue_tile(buf ^ 1);   // in flight during the MFMAs below
-        APTP_STAMP(1);
         compute(buf);
-        APTP_STAMP(2);
-#if !(APTP_ABLATE & 8)
         __syncthreads();
-#endif
-        APTP_STAMP(3);
         buf ^= 1;
       }
     }
@@ -655,7 +590,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
     if (n > 0) {
       const int pre = n < D ? n : D;
       for (int t = 0; t < pre; ++t) issue_tile(t);
-      APTP_PHASE(0);
       ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
       if (pre == D) {   // tile 0 landed, D-1 tiles still in flight
         if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
@@ -665,103 +599,11 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
       }
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      APTP_PHASE(1);
       int cur = 0, nxt = D;          // stage of tile kt, stage of tile kt+D
-#if APTP_IL
-      // Interleaved K-step (experiment, -DAPTP_IL=1): hipcc emits a K-step as [all LDS-DMA instructions][fragment reads][MFMAs], and
-      // a DMA instruction blocks the in-order wave while the CU's 64 B/clk load path is busy -- the load path, the LDS read port and
-      // the matrix pipe take turns.  Here the wave's DMA pieces of tile kt+D and the fragment reads of the second 32-wide half are
-      // placed BETWEEN the MFMAs, by hand, pinned with sched_barrier(0).
-      if constexpr (KS == 1) {
-        constexpr int NP = A_PASS + B_PASS, NM = 2 * MF * NF;
-        auto piece = [&](int q, int buf) {
-          const bool seg2 = l_ky >= p.KH;
-          const bool last_cc = l_cc == (seg2 ? p.ncc2 : p.ncc) - 1;
-          const bool tb = seg2 ? tail_bad2 : tail_bad;
-          if (q < A_PASS) {
-            const int i = q;
-            if (wave * 8 + RPP * i < BM) {
-              const char* src = (last_cc && tb) ? zpage : a_ptr[i];
-              __builtin_amdgcn_global_load_lds((gbl_ptr)src, (lds_ptr)(As + (buf * BM + wave * 8 + RPP * i) * BK), 16, 0, 0);
-            }
-            a_ptr[i] += BK * 2;
-          } else {
-            const int i = q - A_PASS;
-            if (wave * 8 + RPP * i < BN)
-              __builtin_amdgcn_global_load_lds((gbl_ptr)b_ptr[i], (lds_ptr)(Bs + (buf * BN + wave * 8 + RPP * i) * BK), 16, 0, 0);
-            b_ptr[i] += BK * 2;
-          }
-        };
-        auto next_tap = [&]() {
-          const bool seg2 = l_ky >= p.KH;
-          if (++l_cc == (seg2 ? p.ncc2 : p.ncc)) {
-            l_cc = 0;
-            if (++l_kx == p.KW || seg2) { l_kx = 0; ++l_ky; }
-            set_tap(0);
-          }
-        };
-        auto frags = [&](int buf, int sh, bf16x8 (&af)[MF], bf16x8 (&wf)[NF]) {
-#pragma unroll
-          for (int i = 0; i < MF; ++i) {
-            const int r = wm * WTM + i * 16 + frow;
-            af[i] = *reinterpret_cast<const bf16x8*>(As + (buf * BM + r) * BK + ((sh * 4 + fq) ^ ((r >> 1) & 7)) * 8);
-          }
-#pragma unroll
-          for (int j = 0; j < NF; ++j) {
-            const int r = wn * WTN + j * 16 + frow;
-            wf[j] = *reinterpret_cast<const bf16x8*>(Bs + (buf * BN + r) * BK + ((sh * 4 + fq) ^ ((r >> 1) & 7)) * 8);
-          }
-        };
-        for (int kt = 0; kt < n; ++kt) {
-          const bool issue = kt + D < n;
-          bf16x8 af0[MF], wf0[NF], af1[MF], wf1[NF];
-          frags(cur, 0, af0, wf0);
-          if (issue) {
-            int m = 0;
-#pragma unroll
-            for (int sh = 0; sh < 2; ++sh)
-#pragma unroll
-              for (int i = 0; i < MF; ++i)
-#pragma unroll
-                for (int j = 0; j < NF; ++j, ++m) {
-                  if (sh == 0 && m == 1) frags(cur, 1, af1, wf1);
-                  acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sh ? wf1[j] : wf0[j], sh ? af1[i] : af0[i], acc[i][j], 0, 0, 0);
-                  if ((m + 1) * NP / NM > m * NP / NM) piece(m * NP / NM, nxt);
-                  __builtin_amdgcn_sched_barrier(0);
-                }
-            next_tap();
-          } else {
-            frags(cur, 1, af1, wf1);
-#pragma unroll
-            for (int sh = 0; sh < 2; ++sh)
-#pragma unroll
-              for (int i = 0; i < MF; ++i)
-#pragma unroll
-                for (int j = 0; j < NF; ++j)
-                  acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sh ? wf1[j] : wf0[j], sh ? af1[i] : af0[i], acc[i][j], 0, 0, 0);
-          }
-          asm volatile("" ::: "memory");
-          if (issue) {
-            if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 1)) : "memory");
-          } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-          cur = cur + 1 == STAGES ? 0 : cur + 1;
-          nxt = nxt + 1 == STAGES ? 0 : nxt + 1;
-        }
-      } else
-#endif
       for (int kt = 0; kt < n; ++kt) {
         const bool issue = kt + D < n;
-        APTP_STAMP(0);
         if (issue) issue_tile(nxt);
-        APTP_STAMP(1);
         compute(cur);
-        APTP_STAMP(2);
         asm volatile("" ::: "memory");
         if (issue) {
           if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
@@ -770,25 +612,14 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // tail: everything still in flight is needed soon
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // this wave's LDS reads of `cur` are done
-#if !(APTP_ABLATE & 8)
         __builtin_amdgcn_s_barrier();
-#endif
         asm volatile("" ::: "memory");
-        APTP_STAMP(3);
         cur = cur + 1 == STAGES ? 0 : cur + 1;
         nxt = nxt + 1 == STAGES ? 0 : nxt + 1;
       }
     }
   }
 
-  APTP_PHASE(2);
-#ifdef APTP_STAMPS
-  if (lane == 0 && kz == 0) {
-    const int slot = (blockIdx.x * NW + wave) & 4095;
-    g_stamps[slot * 4 + 0] = st_acc[0]; g_stamps[slot * 4 + 1] = st_acc[1]; g_stamps[slot * 4 + 2] = st_acc[2];
-    g_stamps[slot * 4 + 3] = __builtin_readcyclecounter() - st_begin;
-  }
-#endif
   if constexpr (KS == 2) {
     // every path above ends on a barrier with the DMA drained and the fragment reads done: the stages are free
     f32x4* xch = reinterpret_cast<f32x4*>(smem) + cw * (MF * NF * 64) + lane;
@@ -829,15 +660,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
   static_assert(NW * 16 * (WTN + 4) * 4 <= (int)sizeof(smem), "epilogue transpose buffer");
   static_assert(KS == 1 || NW * MF * NF * 64 * 16 <= (int)sizeof(smem), "accumulator hand-over buffer");
   run_epilogue<NW, MF, NF, WTM, WTN, WN>(p, acc, m0, n0, tn, wm, wn, lane, cw, ln_mean, ln_rstd, smem);
-#ifdef APTP_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  APTP_EPI(5);
-  APTP_PHASE(3);
-  if (lane == 0 && kz == 0) {
-    const int slot = (blockIdx.x * NW + wave) & 4095;
-    for (int i = 0; i < 8; ++i) g_phase[slot * 8 + i] = st_phase[i];
-  }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1371,18 +1193,6 @@ void launch_tile_pp(const KParams& k, hipStream_t s) {
 }
 
 }  // namespace
-
-#ifdef APTP_STAMPS
-extern "C" int aptp_debug_read_stamps(unsigned long long* dst, int n_words) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int aptp_debug_read_epi(unsigned long long* dst, int n_words) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_epi), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int aptp_debug_read_phases(unsigned long long* dst, int n_words) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_phase), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
 
 extern "C" int64_t aptp_conv_gemm_workspace_bytes(const AptpConvGemmParams* p) {
   if (!p || p->split_k <= 1) return 0;

@@ -3,29 +3,6 @@
 // the in-kernel split-K combine.  Device code only; every function is inlined into the kernels of the including file.
 #pragma once
 #include "aptp_common.h"
-// In-kernel stamps (timing experiments only, -DAPTP_STAMPS): per-wave cycle totals of the K-loop segments
-// [0->1 DMA issue, 1->2 LDS reads + MFMAs, 2->3 waits + barrier], dumped by lane 0 of every wave into g_stamps.
-#if defined(APTP_STAMPS) && defined(APTP_CG_MAIN)
-__device__ unsigned long long g_stamps[4096 * 4];
-// launch timeline of a wave (cycles since its first instruction): [0] prologue DMA issued, [1] first tile landed (first
-// barrier passed), [2] K loop done, [3] epilogue done and its stores drained
-__device__ unsigned long long g_phase[4096 * 8];   // + [4] tile decoded, [5] prefetch / statistics requested, [6] addresses ready
-#define APTP_PHASE(i) do { st_phase[i] = __builtin_readcyclecounter() - st_entry; } while (0)
-// epilogue timeline (absolute cycles): [0] entry, [1] stages free (barrier passed), [2] first fragment's per-column half in LDS,
-// [4] all stores issued, [5] stores drained
-__device__ unsigned long long g_epi[4096 * 8];
-#define APTP_EPI(k) do { if ((threadIdx.x & 63) == 0) g_epi[((blockIdx.x * 8 + (threadIdx.x >> 6)) & 4095) * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
-#define APTP_STAMP(i) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t_ = __builtin_readcyclecounter(); \
-    if ((i) > 0) st_acc[(i) - 1] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define APTP_STAMP(i) do { } while (0)
-#define APTP_PHASE(i) do { } while (0)
-#define APTP_EPI(k) do { } while (0)
-#endif
-#ifndef APTP_ABLATE
-#define APTP_ABLATE 0   // timing experiments only (tools/ablate_conv.py): 1 no LDS-DMA in the loop, 2 no MFMA, 4 no ds_read, 8 no barrier,
-                        // 32 no epilogue stores, 64 no residual / depth_in loads, 128 no LayerNorm row-statistics fetch, 256 no ln_colsum loads
-#endif
 
 namespace aptp_cg {
 
@@ -135,12 +112,8 @@ template <bool GEGLU>
 __device__ __forceinline__ void load_colvecs(const KParams& p, int n, ColVecs& c) {
   c.cs = c.cg = c.bb = c.bg = make_float4(0.f, 0.f, 0.f, 0.f);
   if (p.ln_stats) {
-#if APTP_ABLATE & 256
-    c.cs = c.cg = make_float4(1.f, 1.f, 1.f, 1.f);
-#else
     c.cs = *reinterpret_cast<const float4*>(p.ln_colsum + n);
     if (GEGLU) c.cg = *reinterpret_cast<const float4*>(p.ln_colsum + n + 16);
-#endif
   }
   if (p.bias) {
     c.bb = *reinterpret_cast<const float4*>(p.bias + n);
@@ -204,7 +177,7 @@ __device__ __forceinline__ void epilogue_quad(const KParams& p, int m, const Row
   load_colvecs<GEGLU>(p, n, cv);
   epilogue_pre<GEGLU>(p, rc, n, cv, h, g, v);
   const int c = GEGLU ? ((n >> 5) * 16 + (n & 15)) : n;   // logical output column of element 0
-  if (p.residual && !(APTP_ABLATE & 64)) {
+  if (p.residual) {
     if (p.io_f32) {           // (wave-uniform) fp32 parity instantiation: residual / depth_in / y are fp32 tensors
       const float4 rr = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.residual) + (int64_t)m * p.ldres + c);
       v[0] += rr.x; v[1] += rr.y; v[2] += rr.z; v[3] += rr.w;
@@ -215,7 +188,7 @@ __device__ __forceinline__ void epilogue_quad(const KParams& p, int m, const Row
       for (int r = 0; r < 4; ++r) v[r] += (float)ru.e[r];
     }
   }
-  if (p.depth && !(APTP_ABLATE & 64)) {
+  if (p.depth) {
     const float d = p.depth[b % p.depth_B];
     float din[4];
     if (p.io_f32) {
@@ -230,10 +203,6 @@ __device__ __forceinline__ void epilogue_quad(const KParams& p, int m, const Row
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = (1.0f - d) * din[r] + d * v[r];
   }
-#if APTP_ABLATE & 32
-  asm volatile("" :: "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
-  return;
-#endif
   if (p.out_f32) {
     float4 o; o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
     *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.y) + (int64_t)m * p.ldy + c) = o;
@@ -291,7 +260,7 @@ struct LnRaw { float4 v[4][MF]; int mr[MF]; };
 template <int MF, int WTM>
 __device__ __forceinline__ void ln_rows_issue(const KParams& p, int m0, int wm, int lane, LnRaw<MF>& raw, bool split_ok = false) {
   // (split-K: only the workgroup that combines the slices needs the rows, and asks for them then)
-  if (!p.ln_stats || (p.split_k > 1 && !split_ok) || (APTP_ABLATE & 128)) return;
+  if (!p.ln_stats || (p.split_k > 1 && !split_ok)) return;
   const int frow = lane & 15, fq = lane >> 4;
   const float4* sp = reinterpret_cast<const float4*>(p.ln_stats);     // [slots/2][M]: two slots per 16-byte element
   const int npair = p.ln_slots >> 1;
@@ -320,7 +289,7 @@ __device__ __forceinline__ void ln_rows_issue(const KParams& p, int m0, int wm, 
 template <int MF>
 __device__ __forceinline__ void ln_rows_finish(const KParams& p, int lane, const LnRaw<MF>& raw, float (&ln_mean)[MF], float (&ln_rstd)[MF],
                                                bool split_ok = false) {
-  if (!p.ln_stats || (p.split_k > 1 && !split_ok) || (APTP_ABLATE & 128)) return;
+  if (!p.ln_stats || (p.split_k > 1 && !split_ok)) return;
   const int fq = lane >> 4;
   const float4* sp = reinterpret_cast<const float4*>(p.ln_stats);
   const int npair = p.ln_slots >> 1;
@@ -527,8 +496,8 @@ __device__ __forceinline__ void tile_epilogue_lds(const KParams& p, f32x4 (&acc)
       const int r = ps * RPP + lrow, m2 = mbase + r;
       const bool on = lane_on && r < 16 && m2 < p.M;
       rres[ps] = (u32x4){0u, 0u, 0u, 0u}; rdin[ps] = (u32x4){0u, 0u, 0u, 0u};
-      if (on && p.residual && !(APTP_ABLATE & 64)) rres[ps] = *reinterpret_cast<const u32x4*>(p.residual + (int64_t)m2 * p.ldres + c0);
-      if (on && p.depth && !(APTP_ABLATE & 64)) rdin[ps] = *reinterpret_cast<const u32x4*>(p.depth_in + (int64_t)m2 * p.lddin + c0);
+      if (on && p.residual) rres[ps] = *reinterpret_cast<const u32x4*>(p.residual + (int64_t)m2 * p.ldres + c0);
+      if (on && p.depth) rdin[ps] = *reinterpret_cast<const u32x4*>(p.depth_in + (int64_t)m2 * p.lddin + c0);
     }
     // accumulator domain: per-column half of the epilogue, fp32 row fragment -> LDS
     {
@@ -570,7 +539,6 @@ __device__ __forceinline__ void tile_epilogue_lds(const KParams& p, f32x4 (&acc)
     // (cross-lane exchange through LDS inside one wave: tell the compiler, see the column-statistics staging below)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (i == 0) APTP_EPI(2);
     // transposed domain: + residual, depth lerp, round, 16-byte store, row statistics
 #pragma unroll
     for (int ps = 0; ps < NPASS; ++ps) {
@@ -583,14 +551,14 @@ __device__ __forceinline__ void tile_epilogue_lds(const KParams& p, f32x4 (&acc)
         const float4 b4 = *reinterpret_cast<const float4*>(buf + rr * PITCH + lc8 * 8 + 4);
         v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b4.x; v[5] = b4.y; v[6] = b4.z; v[7] = b4.w;
       }
-      if (p.residual && !(APTP_ABLATE & 64)) {
+      if (p.residual) {
         float f[8];
         union { u32x4 v; uint4 s; } cv; cv.v = rres[ps];
         unpack_bf16x8(cv.s, f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += f[e];
       }
-      if (p.depth && !(APTP_ABLATE & 64)) {
+      if (p.depth) {
         const float d = p.depth[p.fd_hw.div(m2 < p.M ? m2 : p.M - 1) % p.depth_B];
         float f[8];
         union { u32x4 v; uint4 s; } cv; cv.v = rdin[ps];
@@ -599,11 +567,7 @@ __device__ __forceinline__ void tile_epilogue_lds(const KParams& p, f32x4 (&acc)
         for (int e = 0; e < 8; ++e) v[e] = (1.0f - d) * f[e] + d * v[e];
       }
       const uint4 o = pack_bf16x8(v);
-#if APTP_ABLATE & 32
-      asm volatile("" :: "v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
-#else
       if (on) *reinterpret_cast<uint4*>(yb + (int64_t)m2 * p.ldy + c0) = o;
-#endif
       if constexpr (!GEGLU) {
         if (p.cstat_out && on) {   // statistics of the values as stored (bf16-rounded): what the GroupNorm will read
           float f[8];
@@ -630,9 +594,7 @@ __device__ __forceinline__ void tile_epilogue_lds(const KParams& p, f32x4 (&acc)
         }
       }
     }
-    if (i == 0) APTP_EPI(3);
   }
-  APTP_EPI(4);
   if constexpr (!GEGLU && WL >= 32) {
     static_assert(RPP * WL <= 16 * PITCH, "column-statistics staging");
     if (p.cstat_out) emit_col_stats<WL, RPP>(p, cs, cs2, buf, lane, lrow, lc8, n0 + wn * WTN, m0 / WTM + wm, m0 + wm * WTM);
@@ -888,9 +850,7 @@ __device__ __forceinline__ void run_epilogue(const KParams& p, f32x4 (&acc)[MF][
   constexpr int PITCH_MAX = WTN + 4;
   constexpr bool POW2 = ((WTN / 8) & (WTN / 8 - 1)) == 0;
   if (p.epi16 && (POW2 || !p.rstat_out)) {
-    APTP_EPI(0);
     __syncthreads();                        // every wave is done reading the operand stages
-    APTP_EPI(1);
     float* buf = reinterpret_cast<float*>(smem) + wave * 16 * PITCH_MAX;
     if (p.act == APTP_ACT_GEGLU) {
       if constexpr (NF % 2 == 0) tile_epilogue_lds<true, MF, NF, WTM, WTN, WN>(p, acc, m0, n0, tn, wm, wn, lane, ln_mean, ln_rstd, buf);

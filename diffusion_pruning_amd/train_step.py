@@ -985,8 +985,6 @@ class GraphedFineTunerStep(FineTunerStep):
         self.optimizer = None
         self._cap = None
         self.stream_probe = []          # what graph_utils.concurrent_stream measured when it chose the teacher's / router's side streams
-        self.overlap_router = os.environ.get("APTP_OVERLAP_ROUTER", "1") != "0"
-        self._finish_hooks = []
 
     def _losses(self, model_pred, full_pred, w, target):
         cfg = self.cfg

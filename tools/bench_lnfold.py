@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from diffusion_pruning_amd import _lib
 if len(sys.argv) > 1:
-    _lib.LIB_PATH = os.path.abspath(sys.argv[1])     # an ablated build (tools/build_ablations.sh)
+    _lib.LIB_PATH = os.path.abspath(sys.argv[1])     # another build of libaptp_hip.so
 from diffusion_pruning_amd import ops
 
 dev = torch.device("cuda:0")
