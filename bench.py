@@ -29,14 +29,15 @@ data-parallel pruning train step (configs[2]/[3]) behind ``--config train``.
     never communicate (scripts/aptp/finetune.py:27-28,40); N = 1 trains expert 3.  The whole step replays from a HIP graph
     (train_step.GraphedFineTunerStep).  value = steps/s summed over the ranks (each rank's own rate is listed).
 
-The default line (--config infer, one GPU) also carries:
+A plain --config infer run sets up, warms up, times the K steps, writes --dump-outputs if given and prints ONE JSON line
+(metric, value, unit, ms_per_step and the run's settings).  With --full, rank 0 then also measures the objects below and
+adds them to the same line (sustained, peak_measured, the two baselines and extra_configs at N = 1 only).  --config train
+and --config finetune are not affected by --full.
   sustained       >= 3 s of back-to-back replays of the same graph: steps/s, the slowest / median 100-step window and the
                   shader clock (sysfs pp_dpm_sclk, sampled by a host thread while the replays run) beside it.
   extra_configs   BASELINE configs[2] (train) and configs[4] (finetune, expert 3) measured after the headline in this same
                   process: steps/s, ms/step, graph nodes (launches) per step, the conv_gemm family's MFMA roofline
-                  fraction inside that step, peak memory.
-
-Prints ONE JSON line (see the task contract) with extra objects:
+                  fraction inside that step, peak memory; and the headline model at U-Net batch 16 (infer_bs16).
   roofline        MFMA roofline of the dominant kernel family (conv_gemm*: implicit-GEMM conv/linear): achieved =
                   algorithmic FLOPs of all its launches in one forward / their measured device time (HIP events on the
                   launch stream around a HIP graph that replays exactly those launches); peak = 2500 TFLOP/s dense bf16
@@ -86,15 +87,16 @@ def parse_args(argv=None):
     ap.add_argument("--data-parallel", action="store_true", help="(finetune) all ranks train ONE expert (expert --expert-offset), gradients "
                     "summed in place over the gradient arena (train_step.ArenaGradReducer), mean folded into AdamW")
     ap.add_argument("--eager-router", action="store_true", help="(train) keep the router eager between the U-Net graphs (A/B against the captured router)")
-    ap.add_argument("--no-vendor-baseline", action="store_true", help="(infer) skip the torch-ROCm vendor-library yardstick (gpu_vendor_baseline)")
-    ap.add_argument("--no-extra-configs", action="store_true", help="(infer) skip the train / finetune measurements that follow the headline")
-    ap.add_argument("--sustain-seconds", type=float, default=3.0, help="(infer) length of the sustained-replay leg; 0 = off")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the measurement legs (see the module docstring)")
+    ap.add_argument("--no-extras", dest="full", action="store_false", help="the default: timed steps only (undoes an earlier --full)")
+    ap.add_argument("--no-vendor-baseline", action="store_true", help="(infer --full) skip the torch-ROCm vendor-library yardstick (gpu_vendor_baseline)")
+    ap.add_argument("--no-extra-configs", action="store_true", help="(infer --full) skip the train / finetune measurements that follow the headline")
+    ap.add_argument("--sustain-seconds", type=float, default=3.0, help="(infer --full) length of the sustained-replay leg; 0 = off")
     ap.add_argument("--batch", type=int, default=4, help="per-GPU batch")
     ap.add_argument("--latent", type=int, default=64)
     ap.add_argument("--dense", action="store_true", help="(infer) mask == 1 instead of the fixed 50 %% mask")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(infer --full) skip the CPU oracle timing (cpu_baseline)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline legs (timing only)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo with --dryrun-cpu)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's outputs as DIR/<name>.npy (rank 0; see the module docstring)")
@@ -341,9 +343,9 @@ def run_infer(R: Rank):
         ms_per_step = elapsed / args.steps * 1e3
         value = R.world * args.steps / elapsed
         sustained = None
-        if R.rank == 0 and not R.cpu and not args.no_extras and gout is not None and R.world == 1 and args.sustain_seconds > 0:
+        if R.rank == 0 and not R.cpu and args.full and gout is not None and R.world == 1 and args.sustain_seconds > 0:
             sustained = measure_sustained(run, args.sustain_seconds, value, R.local_rank)
-        if R.rank == 0 and not R.cpu and not args.no_extras:
+        if R.rank == 0 and not R.cpu and args.full:
             # (at N > 1 the other ranks wait for these legs in the final barrier: only the short ones run there)
             roofline = measure_roofline(ops, step, dev, per_tile=R.world == 1)
             if L == 64:
@@ -358,7 +360,7 @@ def run_infer(R: Rank):
             if R.world == 1 and not args.no_vendor_baseline and L == 64:
                 vendor_baseline = measure_vendor_baseline(B, args.dense)
     infer_bs16 = None
-    if R.rank == 0 and R.world == 1 and not R.cpu and not args.no_extras and not args.no_extra_configs and L == 64 and B == 4:
+    if R.rank == 0 and R.world == 1 and not R.cpu and args.full and not args.no_extra_configs and L == 64 and B == 4:
         # the reference's own evaluation operating point: U-Net batch 16 = 8 prompts x classifier-free guidance
         # (configs/img_generation/sd-2-1_cc3m.yaml:47,50, scripts/metrics/generate_fid_images.py:104-128); same model, same mask
         try:
@@ -368,9 +370,9 @@ def run_infer(R: Rank):
             infer_bs16 = {"error": repr(e), "where": traceback.format_exc()[-500:]}
         torch.cuda.empty_cache()
     extra_configs = None
-    if R.rank == 0 and R.world == 1 and not R.cpu and not args.no_extras and not args.no_extra_configs and L == 64:
-        # BASELINE configs[2] and configs[4] in the same record (the driver runs only this default command): measured after
-        # the headline, with the inference model released first
+    if R.rank == 0 and R.world == 1 and not R.cpu and args.full and not args.no_extra_configs and L == 64:
+        # BASELINE configs[2] and configs[4] in the same record: measured after the headline, with the inference model
+        # released first
         del model, run
         if gout is not None:
             del graph, gout

@@ -65,3 +65,11 @@ def test_single_rank_default_and_world_size_mismatch():
     assert rec["n_gpus"] == 1
     bad = _bench("--gpus", "2", "--dryrun-cpu", "--steps", "1", env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert bad.returncode != 0 and "WORLD_SIZE=1" in bad.stderr
+
+
+def test_measurement_legs_only_with_full():
+    """a plain run times the steps only; --full adds the measurement legs (--no-extras spells the default)"""
+    import bench
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full"]).full is True
+    assert bench.parse_args(["--full", "--no-extras"]).full is False
