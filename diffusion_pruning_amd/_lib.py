@@ -212,6 +212,25 @@ class UnetEpilogueParams(Structure):
     ]
 
 
+class AttentionWideParams(Structure):
+    _fields_ = [
+        ("q", c_void_p), ("q_stride_b", c_int64), ("q_stride_l", c_int64),
+        ("k", c_void_p), ("k_stride_b", c_int64), ("k_stride_l", c_int64),
+        ("v", c_void_p), ("v_stride_b", c_int64), ("v_stride_l", c_int64),
+        ("o", c_void_p), ("o_stride_b", c_int64), ("o_stride_l", c_int64),
+        ("B", c_int32), ("Lq", c_int32), ("Lk", c_int32),
+        ("scale", c_float),
+        ("io_f32", c_int32),
+    ]
+
+
+class ImageOutParams(Structure):
+    _fields_ = [
+        ("y", c_void_p), ("ldy", c_int64), ("out", c_void_p), ("out_u8", c_int32),
+        ("B", c_int32), ("H", c_int32), ("W", c_int32),
+    ]
+
+
 class ColsumParams(Structure):
     _fields_ = [("x", c_void_p), ("ldx", c_int64), ("rows", c_int32), ("C", c_int32), ("partial", c_void_p), ("batch", c_int32)]
 
@@ -294,6 +313,8 @@ EXPORTS = [
     ("aptp_layernorm_pgrad", c_int, [POINTER(LayerNormPgradParams), c_void_p]),
     ("aptp_unet_prologue", c_int, [POINTER(UnetPrologueParams), c_void_p]),
     ("aptp_unet_epilogue", c_int, [POINTER(UnetEpilogueParams), c_void_p]),
+    ("aptp_attention_wide", c_int, [POINTER(AttentionWideParams), c_void_p]),
+    ("aptp_image_out", c_int, [POINTER(ImageOutParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

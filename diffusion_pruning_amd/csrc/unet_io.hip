@@ -61,7 +61,46 @@ __global__ __launch_bounds__(256) void unet_epilogue_kernel(const OutK p) {
   else reinterpret_cast<float*>(p.out)[i] = v;
 }
 
+// VAE image epilogue: one thread per output element.  fp32 form: element (b, c, r) of [B, 3, H, W] (coalesced stores);
+// uint8 form: element (pixel, c) of [B, H, W, 3].  v = y * 0.5 + 0.5 is y / 2 + 0.5 exactly (the halving is exact, one
+// rounding in the add), clamped like torch.clamp; the uint8 value is rintf(v * 255) (round half to even, like numpy's round).
+struct ImgK { const float* y; int64_t ld; void* out; int out_u8; int B, HW; };
+
+__global__ __launch_bounds__(256) void image_out_kernel(const ImgK p) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)p.B * 3 * p.HW) return;
+  int64_t pix;
+  int c;
+  if (p.out_u8) {
+    pix = i / 3;
+    c = (int)(i - pix * 3);
+  } else {
+    const int r = (int)(i % p.HW);
+    const int64_t bc = i / p.HW;
+    c = (int)(bc % 3);
+    pix = (bc / 3) * p.HW + r;
+  }
+  const float y = p.y[pix * p.ld + c];
+  const float v = fminf(fmaxf(__fadd_rn(__fmul_rn(y, 0.5f), 0.5f), 0.f), 1.f);
+  if (p.out_u8) reinterpret_cast<uint8_t*>(p.out)[i] = (uint8_t)rintf(__fmul_rn(v, 255.f));
+  else reinterpret_cast<float*>(p.out)[i] = v;
+}
+
 }  // namespace
+
+extern "C" int aptp_image_out(const AptpImageOutParams* p, aptp_stream_t stream) {
+  APTP_CHECK(p && p->y && p->out, "image_out: null pointer");
+  APTP_CHECK(p->B > 0 && p->H > 0 && p->W > 0 && p->ldy >= 3, "image_out: bad extents (ldy >= 3)");
+  APTP_CHECK(((uintptr_t)p->y % 4) == 0 && (p->out_u8 || ((uintptr_t)p->out % 4) == 0), "image_out: pointer alignment");
+  APTP_CHECK((int64_t)p->H * p->W < (1ll << 31), "image_out: H * W too large");
+  ImgK k;
+  k.y = p->y; k.ld = p->ldy; k.out = p->out; k.out_u8 = p->out_u8 ? 1 : 0; k.B = p->B; k.HW = p->H * p->W;
+  const int64_t n = (int64_t)k.B * 3 * k.HW;
+  APTP_CHECK((n + 255) / 256 < (1ll << 31), "image_out: too many elements");
+  hipLaunchKernelGGL(image_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+  APTP_LAUNCH_CHECK();
+  return APTP_OK;
+}
 
 extern "C" int aptp_unet_prologue(const AptpUnetPrologueParams* p, aptp_stream_t stream) {
   APTP_CHECK(p && p->sample && p->x && p->timesteps && p->freqs && p->t_emb, "unet_prologue: null pointer");

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import UnetEpilogueParams, UnetPrologueParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
-                   ColsumParams, LayerNormPgradParams)
+                   ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
 
 BK = 64
 # Storage type of activations and packed weights.  The HIP kernels exist for bf16 only (MFMA operands); the test-only CPU
@@ -965,16 +965,79 @@ def unet_prologue(sample: torch.Tensor, timesteps: torch.Tensor, freqs: torch.Te
     return x, temb
 
 
-def unet_epilogue(y: torch.Tensor, channels: int, out_dtype: torch.dtype) -> torch.Tensor:
-    """conv_out's fp32 [B,H,W,ld] -> [B,channels,H,W] (fp32 or bf16) in one launch."""
+def unet_epilogue(y: torch.Tensor, channels: int, out_dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_out's fp32 [B,H,W,ld] -> [B,channels,H,W] (fp32 or bf16) in one launch (into `out` when given: a contiguous
+    tensor of that shape and dtype)."""
     lib = _lib.load()
     assert y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.is_contiguous() and out_dtype in (torch.float32, torch.bfloat16)
     B, H, W, ld = y.shape
-    out = torch.empty(B, channels, H, W, dtype=out_dtype, device=y.device)
+    if out is None:
+        out = torch.empty(B, channels, H, W, dtype=out_dtype, device=y.device)
+    assert tuple(out.shape) == (B, channels, H, W) and out.dtype == out_dtype and out.is_contiguous() and out.is_cuda
     p = UnetEpilogueParams()
     p.y, p.ldy, p.out, p.out_bf16 = y.data_ptr(), ld, out.data_ptr(), int(out_dtype == torch.bfloat16)
     p.B, p.C, p.H, p.W = B, channels, H, W
     _lib.check(lib.aptp_unet_epilogue(ctypes.byref(p), _stream()), "aptp_unet_epilogue")
+    return out
+
+
+WIDE_HEAD = 512
+ATTN_WIDE_LAUNCH_LOG = None     # tools/bench_vae.py: the wide-head attention launches of one decode (re-timed on their own)
+
+
+def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Optional[float] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T * scale) v with ONE head of width 512 (the VAE decoder's mid-block attention; default scale 512^-0.5).
+    q [B, Lq, 512], k/v [B, Lk, 512] are bf16 (or, parity path, fp32) views with contiguous channels -- e.g. column slices
+    of a fused q|k|v buffer; out [B, Lq, 512] is allocated unless given."""
+    lib = _lib.load()
+    B, Lq = q.shape[0], q.shape[1]
+    Lk = k.shape[1]
+    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
+        if t.dim() != 3 or t.dtype != q.dtype or t.dtype not in (torch.bfloat16, torch.float32) or t.stride(2) != 1 \
+                or t.shape[2] != WIDE_HEAD or t.shape[0] != B or not t.is_cuda:
+            raise ValueError(f"attention_wide: {nm} must be a CUDA bf16 (or fp32) [B, L, 512] view with contiguous channels, "
+                             f"got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    if v.shape[1] != Lk:
+        raise ValueError("attention_wide: k and v must have the same length")
+    if out is None:
+        out = torch.empty(B, Lq, WIDE_HEAD, dtype=q.dtype, device=q.device)
+    if tuple(out.shape) != (B, Lq, WIDE_HEAD) or out.dtype != q.dtype or out.stride(2) != 1:
+        raise ValueError("attention_wide: out must be [B, Lq, 512] of q's dtype with contiguous channels")
+    p = AttentionWideParams()
+    p.io_f32 = int(q.dtype == torch.float32)
+    p.q, p.q_stride_b, p.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
+    p.k, p.k_stride_b, p.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
+    p.v, p.v_stride_b, p.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
+    p.o, p.o_stride_b, p.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
+    p.B, p.Lq, p.Lk = B, Lq, Lk
+    p.scale = WIDE_HEAD ** -0.5 if scale is None else float(scale)
+    if ATTN_WIDE_LAUNCH_LOG is not None and not p.io_f32:
+        ATTN_WIDE_LAUNCH_LOG.append({"params": p, "flops": 4.0 * B * Lq * Lk * WIDE_HEAD, "keep": (q, k, v, out)})
+    _lib.check(lib.aptp_attention_wide(ctypes.byref(p), _stream()), "aptp_attention_wide")
+    return out
+
+
+def image_out(y: torch.Tensor, out_dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The VAE decoder's image epilogue (diffusers postprocess, do_denormalize): conv_out's fp32 [B, H, W, ld] (3 real
+    channels) -> clamp(y / 2 + 0.5, 0, 1) as fp32 [B, 3, H, W], or as uint8 [B, H, W, 3] = round_half_even(255 v)
+    (out_dtype=torch.uint8, numpy_to_pil's rounding)."""
+    lib = _lib.load()
+    if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.shape[3] >= 3 and y.stride(3) == 1
+            and y.is_contiguous()):
+        raise ValueError(f"image_out: expected a contiguous CUDA fp32 [B, H, W, >=3] tensor, got {y.dtype} {tuple(y.shape)}")
+    if out_dtype not in (torch.float32, torch.uint8):
+        raise ValueError("image_out: out_dtype is torch.float32 or torch.uint8")
+    B, H, W, ld = y.shape
+    shape = (B, H, W, 3) if out_dtype == torch.uint8 else (B, 3, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=out_dtype, device=y.device)
+    if tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous():
+        raise ValueError(f"image_out: out must be a contiguous {out_dtype} {shape} tensor")
+    p = ImageOutParams()
+    p.y, p.ldy, p.out, p.out_u8 = y.data_ptr(), ld, out.data_ptr(), int(out_dtype == torch.uint8)
+    p.B, p.H, p.W = B, H, W
+    _lib.check(lib.aptp_image_out(ctypes.byref(p), _stream()), "aptp_image_out")
     return out
 
 

@@ -178,11 +178,13 @@ class PipelineOutput:
     arch_indices: Optional[torch.Tensor]
     arch_vectors_quantized: Optional[torch.Tensor]
     resource_ratios: Optional[torch.Tensor] = None
+    images: Optional[object] = None      # decoded images for output_type "pt" / "np" / "pil" (None for "latent")
 
 
 class PruningDenoiseLoop:
-    def __init__(self, unet, hyper_net=None, quantizer=None, scheduler=None):
+    def __init__(self, unet, hyper_net=None, quantizer=None, scheduler=None, vae=None):
         self.unet, self.hyper_net, self.quantizer = unet, hyper_net, quantizer
+        self.vae = vae                   # diffusion_pruning_amd.vae.AutoencoderKL: decodes for output_type != "latent"
         self.scheduler = scheduler or DDIMSchedulerLite()
         self._graph = None
         self._graph_key = None
@@ -209,9 +211,16 @@ class PruningDenoiseLoop:
     @torch.no_grad()
     def __call__(self, prompt_embeds: torch.Tensor, latents: torch.Tensor, num_inference_steps: int = 50,
                  guidance_scale: float = 7.5, hyper_net_input: Optional[torch.Tensor] = None,
-                 negative_prompt_embeds: Optional[torch.Tensor] = None, use_graph: bool = True) -> PipelineOutput:
+                 negative_prompt_embeds: Optional[torch.Tensor] = None, use_graph: bool = True,
+                 output_type: str = "latent") -> PipelineOutput:
         """prompt_embeds [B,77,X] (+ negative_prompt_embeds for CFG, concatenated as [uncond, cond] like the
-        reference, :765); latents [B,4,h,w] ~ N(0,1) on the device."""
+        reference, :765); latents [B,4,h,w] ~ N(0,1) on the device.  output_type "latent" returns the latents only;
+        "pt" (fp32 [B,3,H,W] in [0, 1]), "np" (fp32 [B,H,W,3] numpy) and "pil" (list of PIL images) also decode them
+        through ``vae`` and postprocess like the reference (:826-839, do_denormalize always true)."""
+        if output_type not in ("latent", "pt", "np", "pil"):
+            raise ValueError(f"output_type {output_type!r}: expected 'latent', 'pt', 'np' or 'pil'")
+        if output_type != "latent" and self.vae is None:
+            raise ValueError(f"output_type {output_type!r} needs a vae (PruningDenoiseLoop(..., vae=AutoencoderKL))")
         dev = latents.device
         arch_q = idx = None
         if self.hyper_net is not None and hyper_net_input is not None:
@@ -253,7 +262,25 @@ class PruningDenoiseLoop:
         if getattr(self.unet, "resource_info_dict", None) is not None:
             # pruning_pipelines.py:822-824
             ratios = self.unet.calc_macs()["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"]
-        return PipelineOutput(latents=latents, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios)
+        images = None
+        if output_type != "latent":
+            images = self.decode_latents(latents, output_type)
+        return PipelineOutput(latents=latents, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios,
+                              images=images)
+
+    @torch.no_grad()
+    def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
+        """vae.decode(latents / scaling_factor) + postprocess (pruning_pipelines.py:826-839) on the HIP decoder; the
+        postprocess runs in the decoder's image epilogue kernel"""
+        z = latents / self.vae.config.scaling_factor
+        if output_type == "pil":
+            from PIL import Image
+            u8 = self.vae.decode_images(z, "uint8").cpu().numpy()
+            return [Image.fromarray(im) for im in u8]
+        img = self.vae.decode_images(z, "pt")
+        if output_type == "np":
+            return img.permute(0, 2, 3, 1).float().cpu().numpy()
+        return img
 
     def _capture(self, latents, ts, ctx, B, guidance_scale, do_cfg):
         lat_buf = latents.clone()

@@ -1,0 +1,435 @@
+"""The decoder half of SD-2.1's ``AutoencoderKL`` (diffusers 0.23.1 semantics) on the HIP kernels of this package.
+
+The reference turns latents into images with ``vae.decode(latents / vae.config.scaling_factor)`` followed by
+``image_processor.postprocess`` (pdm/pipelines/pruning_pipelines.py:826-839).  This module keeps diffusers' parameter names
+(``post_quant_conv``, ``decoder.conv_in``, ``decoder.mid_block.{resnets,attentions}``, ``decoder.up_blocks.i.{resnets,
+upsamplers}``, ``decoder.conv_norm_out``, ``decoder.conv_out``) and the ``decode(z, return_dict=True).sample`` call, and runs
+every layer through the existing kernels:
+
+  * GroupNorm(32, eps 1e-6) (+SiLU): ``ops.groupnorm``, fed by the column statistics its producing convolution emitted;
+  * 3x3 convolutions: ``ops.conv_gemm``; nearest x2 upsampling folded into the gather (``ups=1``); a resnet's 1x1
+    ``conv_shortcut`` as a second K-segment of conv2 (``pack_weight_cat``); the identity residual in the epilogue;
+  * mid-block attention: one fused q|k|v linear with bias, ``ops.attention_wide`` (one head of width 512), ``to_out`` with
+    the residual in its epilogue;
+  * ``conv_out`` with an fp32 output, then ``ops.unet_epilogue`` (NCHW ``.sample``) or ``ops.image_out`` (postprocessed).
+
+The latents' NCHW -> NHWC change (4 channels, zero padded to 8) is the only torch arithmetic on the device path.
+With ``ops.ACT_DTYPE = torch.float32`` the same code runs the fp32 parity instantiations of every kernel.
+
+Batch slicing: the convolution kernels address an operand with 32-bit byte offsets (buffer resources; ``aptp_conv_gemm``
+refuses an operand of 2 GiB or more) and the GroupNorm kernels with 64-bit offsets.  ``slice_plan`` splits the batch so
+that no activation of one slice reaches ``MAX_TENSOR_BYTES`` -- diffusers' VAE slicing, done automatically.
+"""
+from __future__ import annotations
+
+import json
+import os
+import struct
+from dataclasses import dataclass, fields
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import ops
+from .unet import Conv2dP, LinearP, NormP, _versions
+
+
+@dataclass(frozen=True)
+class VAEConfig:
+    """SD-2.1 ``vae/config.json`` (the fields the decoder uses)."""
+    in_channels: int = 3
+    out_channels: int = 3
+    latent_channels: int = 4
+    block_out_channels: Tuple[int, ...] = (128, 256, 512, 512)
+    layers_per_block: int = 2
+    norm_num_groups: int = 32
+    scaling_factor: float = 0.18215
+    sample_size: int = 768
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "VAEConfig":
+        kw = {f.name: d[f.name] for f in fields(cls) if f.name in d}
+        if "block_out_channels" in kw:
+            kw["block_out_channels"] = tuple(kw["block_out_channels"])
+        return cls(**kw)
+
+
+GN_EPS = 1e-6
+# largest activation of one decode slice the kernels were verified for (bytes): aptp_conv_gemm's buffer-resource offsets are
+# 32-bit and it rejects operands of >= 2 GiB; every other kernel on the path uses 64-bit offsets
+MAX_TENSOR_BYTES = (1 << 31) - (1 << 20)
+
+
+def largest_activation_elements(cfg: VAEConfig, h: int, w: int) -> int:
+    """elements of the largest activation of ONE image (the input of the last level's first resnet for SD-2.1:
+    8h x 8w x 256)"""
+    ch = list(reversed(cfg.block_out_channels))
+    H, W = h, w
+    big = H * W * max(ch[0], cfg.latent_channels)
+    prev = ch[0]
+    for i, c in enumerate(ch):
+        big = max(big, H * W * max(prev, c))
+        prev = c
+        if i < len(ch) - 1:
+            H, W = 2 * H, 2 * W
+            big = max(big, H * W * c)
+    return big
+
+
+def slice_plan(cfg: VAEConfig, batch: int, h: int, w: int, elem_bytes: int = 2) -> List[int]:
+    """batch sizes of the decode slices: as few as possible, each below MAX_TENSOR_BYTES in every activation"""
+    per = largest_activation_elements(cfg, h, w) * elem_bytes
+    if per >= MAX_TENSOR_BYTES:
+        raise ValueError(f"decode: one {8 * h}x{8 * w} image needs a {per} B activation, above the verified {MAX_TENSOR_BYTES} B")
+    n = max(1, MAX_TENSOR_BYTES // per)
+    return [min(n, batch - s) for s in range(0, batch, n)]
+
+
+def vae_decoder_macs(cfg: VAEConfig, h: int, w: int) -> Tuple[int, int]:
+    """(MACs per image, attention MACs per image) of the decoder at an h x w latent: the layer table (one MAC = one
+    multiply-add; the two attention contractions are 2 (hw)^2 512)"""
+    macs = 0
+    ch = list(reversed(cfg.block_out_channels))
+    H, W = h, w
+
+    def conv(ci, co, k):
+        nonlocal macs
+        macs += H * W * ci * co * k * k
+
+    def res(ci, co):
+        conv(ci, co, 3)
+        conv(co, co, 3)
+        if ci != co:
+            conv(ci, co, 1)
+    lc = cfg.latent_channels
+    conv(lc, lc, 1)
+    conv(lc, ch[0], 3)
+    res(ch[0], ch[0])
+    for _ in range(4):
+        conv(ch[0], ch[0], 1)
+    attn = 2 * (H * W) ** 2 * ch[0]
+    macs += attn
+    res(ch[0], ch[0])
+    prev = ch[0]
+    for i, c in enumerate(ch):
+        for j in range(cfg.layers_per_block + 1):
+            res(prev if j == 0 else c, c)
+        prev = c
+        if i < len(ch) - 1:
+            H, W = 2 * H, 2 * W
+            conv(c, c, 3)
+    conv(ch[-1], cfg.out_channels, 3)
+    return macs, attn
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# parameter containers (diffusers names and shapes)
+# ----------------------------------------------------------------------------------------------------------------
+class ResnetBlock2DP(nn.Module):
+    def __init__(self, cin: int, cout: int, groups: int):
+        super().__init__()
+        self.in_channels, self.out_channels = cin, cout
+        self.norm1 = NormP(cin, GN_EPS, groups)
+        self.conv1 = Conv2dP(cin, cout, 3)
+        self.norm2 = NormP(cout, GN_EPS, groups)
+        self.conv2 = Conv2dP(cout, cout, 3)
+        self.conv_shortcut = Conv2dP(cin, cout, 1) if cin != cout else None
+
+
+class AttentionP(nn.Module):
+    def __init__(self, c: int, groups: int):
+        super().__init__()
+        self.group_norm = NormP(c, GN_EPS, groups)
+        self.to_q = LinearP(c, c)
+        self.to_k = LinearP(c, c)
+        self.to_v = LinearP(c, c)
+        self.to_out = nn.ModuleList([LinearP(c, c)])
+
+
+class UNetMidBlock2DP(nn.Module):
+    def __init__(self, c: int, groups: int):
+        super().__init__()
+        self.resnets = nn.ModuleList([ResnetBlock2DP(c, c, groups), ResnetBlock2DP(c, c, groups)])
+        self.attentions = nn.ModuleList([AttentionP(c, groups)])
+
+
+class Upsample2DP(nn.Module):
+    def __init__(self, c: int):
+        super().__init__()
+        self.conv = Conv2dP(c, c, 3)
+
+
+class UpDecoderBlock2DP(nn.Module):
+    def __init__(self, cin: int, cout: int, layers: int, groups: int, add_upsample: bool):
+        super().__init__()
+        self.resnets = nn.ModuleList([ResnetBlock2DP(cin if j == 0 else cout, cout, groups) for j in range(layers)])
+        self.upsamplers = nn.ModuleList([Upsample2DP(cout)]) if add_upsample else None
+
+
+class DecoderP(nn.Module):
+    def __init__(self, cfg: VAEConfig):
+        super().__init__()
+        ch = list(reversed(cfg.block_out_channels))
+        g = cfg.norm_num_groups
+        self.conv_in = Conv2dP(cfg.latent_channels, ch[0], 3)
+        self.mid_block = UNetMidBlock2DP(ch[0], g)
+        blocks, prev = [], ch[0]
+        for i, c in enumerate(ch):
+            blocks.append(UpDecoderBlock2DP(prev, c, cfg.layers_per_block + 1, g, i < len(ch) - 1))
+            prev = c
+        self.up_blocks = nn.ModuleList(blocks)
+        self.conv_norm_out = NormP(ch[-1], GN_EPS, g)
+        self.conv_out = Conv2dP(ch[-1], cfg.out_channels, 3)
+
+
+@dataclass
+class DecoderOutput:
+    sample: torch.Tensor
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# safetensors (the format is an 8-byte little-endian header length, a JSON header, then the raw tensor bytes)
+# ----------------------------------------------------------------------------------------------------------------
+_ST_DTYPES = {"F32": (np.float32, torch.float32), "F16": (np.float16, torch.float16), "F64": (np.float64, torch.float64)}
+
+
+def read_safetensors(path: str) -> Dict[str, torch.Tensor]:
+    with open(path, "rb") as f:
+        raw = f.read()
+    (n,) = struct.unpack("<Q", raw[:8])
+    header = json.loads(raw[8:8 + n].decode("utf-8"))
+    base = 8 + n
+    out = {}
+    for name, info in header.items():
+        if name == "__metadata__":
+            continue
+        b0, b1 = info["data_offsets"]
+        dt = info["dtype"]
+        if dt == "BF16":
+            a = np.frombuffer(raw, dtype=np.uint16, count=(b1 - b0) // 2, offset=base + b0).astype(np.uint32) << 16
+            t = torch.from_numpy(a.view(np.float32).copy())
+        elif dt in _ST_DTYPES:
+            npd, _ = _ST_DTYPES[dt]
+            t = torch.from_numpy(np.frombuffer(raw, dtype=npd, count=(b1 - b0) // np.dtype(npd).itemsize, offset=base + b0).copy())
+        else:
+            raise ValueError(f"{path}: tensor {name} has unsupported dtype {dt}")
+        out[name] = t.reshape(info["shape"]).float()
+    return out
+
+
+_DEPRECATED_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
+
+
+def _rename_deprecated(name: str) -> str:
+    head, _, leaf = name.rpartition(".")           # leaf = weight / bias
+    mod_path, _, mod = head.rpartition(".")
+    if mod in _DEPRECATED_ATTN and ".attentions." in name:
+        return f"{mod_path}.{_DEPRECATED_ATTN[mod]}.{leaf}"
+    return name
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the module
+# ----------------------------------------------------------------------------------------------------------------
+class AutoencoderKL(nn.Module):
+    """Decode half of diffusers' AutoencoderKL.  ``decode(z)`` equals diffusers' ``vae.decode(z)`` (z = latents /
+    scaling_factor, NCHW); ``decode_images`` returns the postprocessed image in one more launch."""
+
+    def __init__(self, config: Optional[VAEConfig] = None, **kw):
+        super().__init__()
+        cfg = config or VAEConfig(**kw)
+        self.config = cfg
+        lc = cfg.latent_channels
+        self.post_quant_conv = Conv2dP(lc, lc, 1)
+        self.decoder = DecoderP(cfg)
+        self._plan = None
+        self._plan_key = None
+
+    # ---- weights ----------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def init_synthetic(self, seed: int = 0) -> "AutoencoderKL":
+        """Deterministic weights that keep activations O(1) through the 33 3x3 convolutions: He-like convolution weights
+        (std 1 / sqrt(fan_in)), GroupNorm affine near identity, small biases; conv2 of every resnet scaled by 0.5 so that the
+        15 residual additions grow the stream slowly."""
+        g = torch.Generator().manual_seed(seed)
+        for name, p in self.named_parameters():
+            if name.endswith("bias"):
+                p.copy_(0.02 * torch.randn(p.shape, generator=g))
+            elif p.dim() == 1:                                   # GroupNorm gamma
+                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
+            else:
+                fan_in = p[0].numel()
+                std = fan_in ** -0.5 * (0.5 if name.endswith("conv2.weight") else 1.0)
+                p.copy_(std * torch.randn(p.shape, generator=g))
+        self.invalidate()
+        return self
+
+    def load_decoder_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """Load diffusers VAE weights: ``encoder.*`` / ``quant_conv.*`` are ignored, the deprecated attention names
+        (query / key / value / proj_attn) are accepted, 1x1-conv-shaped attention weights are flattened.  Missing or
+        mis-shaped keys raise."""
+        own = self.state_dict()
+        got = {}
+        for name, t in sd.items():
+            if name.startswith("encoder.") or name.startswith("quant_conv."):
+                continue
+            name = _rename_deprecated(name)
+            if name not in own:
+                raise KeyError(f"AutoencoderKL: unexpected key {name}")
+            if ".attentions." in name and name.endswith("weight") and t.dim() == 4 and t.shape[2:] == (1, 1):
+                t = t[:, :, 0, 0]
+            if tuple(t.shape) != tuple(own[name].shape):
+                raise ValueError(f"AutoencoderKL: {name} has shape {tuple(t.shape)}, expected {tuple(own[name].shape)}")
+            got[name] = t
+        missing = sorted(set(own) - set(got))
+        if missing:
+            raise KeyError(f"AutoencoderKL: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+        self.load_state_dict(got)
+        self.invalidate()
+        return self
+
+    @classmethod
+    def from_pretrained(cls, root: str, subfolder: Optional[str] = "vae") -> "AutoencoderKL":
+        """Read ``config.json`` and ``diffusion_pytorch_model.safetensors`` of a diffusers VAE folder."""
+        d = os.path.join(root, subfolder) if subfolder else root
+        with open(os.path.join(d, "config.json")) as f:
+            cfg = VAEConfig.from_dict(json.load(f))
+        m = cls(cfg)
+        m.load_decoder_state_dict(read_safetensors(os.path.join(d, "diffusion_pytorch_model.safetensors")))
+        return m
+
+    def encode(self, *a, **k):
+        raise NotImplementedError("AutoencoderKL.encode: only the decoder is implemented here (the encoder's stride-2 "
+                                  "convolutions pad asymmetrically, which aptp_conv_gemm does not do)")
+
+    def invalidate(self):
+        self._plan = None
+        self._plan_key = None
+        self.__dict__.pop("_vparams", None)
+
+    def _apply(self, fn, *a, **k):
+        self.invalidate()
+        return super()._apply(fn, *a, **k)
+
+    # ---- packed weights ---------------------------------------------------------------------------------------------
+    def plan(self, device) -> dict:
+        key = (str(device), ops.ACT_DTYPE, _versions(self))
+        if self._plan is not None and self._plan_key == key:
+            return self._plan
+        dev = device
+        f32 = lambda t: t.detach().float().to(dev).contiguous()      # noqa: E731
+
+        def conv(m):
+            return ops.pack_weight(m.weight.detach(), m.bias.detach(), device=dev)
+
+        def gn(m):
+            return f32(m.weight), f32(m.bias)
+
+        def res(r):
+            e = {"g1": gn(r.norm1), "g2": gn(r.norm2), "w1": conv(r.conv1)}
+            w2 = conv(r.conv2)
+            if r.conv_shortcut is not None:
+                w2 = ops.pack_weight_cat(w2, r.conv_shortcut.weight.detach(), r.conv_shortcut.bias.detach())
+            e["w2"], e["shortcut"] = w2, r.conv_shortcut is not None
+            return e
+        dec = self.decoder
+        a = dec.mid_block.attentions[0]
+        wqkv = torch.cat([a.to_q.weight, a.to_k.weight, a.to_v.weight], 0).detach()
+        bqkv = torch.cat([a.to_q.bias, a.to_k.bias, a.to_v.bias], 0).detach()
+        pl = {
+            "pq": conv(self.post_quant_conv),
+            "conv_in": conv(dec.conv_in),
+            "mid0": res(dec.mid_block.resnets[0]),
+            "attn": {"g": gn(a.group_norm), "qkv": ops.pack_weight(wqkv, bqkv, device=dev),
+                     "out": ops.pack_weight(a.to_out[0].weight.detach(), a.to_out[0].bias.detach(), device=dev)},
+            "mid1": res(dec.mid_block.resnets[1]),
+            "up": [{"res": [res(r) for r in blk.resnets],
+                    "ups": conv(blk.upsamplers[0].conv) if blk.upsamplers is not None else None} for blk in dec.up_blocks],
+            "gn_out": gn(dec.conv_norm_out),
+            "conv_out": conv(dec.conv_out),
+        }
+        self._plan, self._plan_key = pl, key
+        return pl
+
+    # ---- forward ----------------------------------------------------------------------------------------------------
+    def _resnet(self, x, e):
+        G = self.config.norm_num_groups
+        a1 = ops.groupnorm(x, e["g1"][0], e["g1"][1], G, GN_EPS, True)
+        h = ops.conv_gemm(a1, e["w1"], colstats=True)
+        a2 = ops.groupnorm(h, e["g2"][0], e["g2"][1], G, GN_EPS, True)
+        if e["shortcut"]:
+            return ops.conv_gemm(a2, e["w2"], x2=x, colstats=True)      # conv2(a2) + conv_shortcut(x): one GEMM
+        return ops.conv_gemm(a2, e["w2"], residual=x, colstats=True)
+
+    def _attention(self, x, e):
+        B, H, W, C = x.shape
+        a = ops.groupnorm(x, e["g"][0], e["g"][1], self.config.norm_num_groups, GN_EPS, False)
+        qkv = ops.linear(a.reshape(B, H * W, C), e["qkv"])                     # [B, HW, 3C]: to_q | to_k | to_v
+        o = ops.attention_wide(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:])
+        y = ops.linear(o, e["out"], residual=x.reshape(B, H * W, C), colstats=True)
+        return y.reshape(B, H, W, C)
+
+    def _decode_nhwc(self, z: torch.Tensor) -> torch.Tensor:
+        """z [B, 4, h, w] -> conv_out's fp32 [B, 8h, 8w, 8] (3 real channels)"""
+        pl = self.plan(z.device)
+        B, C, h, w = z.shape
+        x = torch.zeros(B, h, w, pl["pq"].Cin, dtype=ops.ACT_DTYPE, device=z.device)
+        x[..., :C] = z.permute(0, 2, 3, 1)                                       # the 4-channel layout change
+        x = ops.conv_gemm(x, pl["pq"], pad=0)                                     # post_quant_conv (bias: not folded
+        x = ops.conv_gemm(x, pl["conv_in"], colstats=True)                        #  across conv_in's zero border)
+        x = self._resnet(x, pl["mid0"])
+        x = self._attention(x, pl["attn"])
+        x = self._resnet(x, pl["mid1"])
+        for blk in pl["up"]:
+            for e in blk["res"]:
+                x = self._resnet(x, e)
+            if blk["ups"] is not None:
+                x = ops.conv_gemm(x, blk["ups"], ups=1, colstats=True)            # Upsample2D: nearest x2 + 3x3 conv
+        g, b = pl["gn_out"]
+        a = ops.groupnorm(x, g, b, self.config.norm_num_groups, GN_EPS, True)
+        return ops.conv_gemm(a, pl["conv_out"], out_f32=True)
+
+    def _check_latents(self, z: torch.Tensor):
+        if not (z.is_cuda and z.dim() == 4 and z.shape[1] == self.config.latent_channels):
+            raise ValueError(f"AutoencoderKL.decode: expected CUDA latents [B, {self.config.latent_channels}, h, w], "
+                             f"got {tuple(z.shape)} on {z.device}")
+
+    @torch.no_grad()
+    def _run(self, z: torch.Tensor, finish):
+        """decode slice by slice (slice_plan); finish(y_slice, b0, b1) writes the slice's result"""
+        self._check_latents(z)
+        B, _, h, w = z.shape
+        esz = torch.tensor([], dtype=ops.ACT_DTYPE).element_size()
+        with ops.scratch_domain("vae"):
+            b0 = 0
+            for n in slice_plan(self.config, B, h, w, esz):
+                finish(self._decode_nhwc(z[b0:b0 + n]), b0, b0 + n)
+                b0 += n
+
+    def decode(self, z: torch.Tensor, return_dict: bool = True):
+        """diffusers AutoencoderKL.decode: z = latents / scaling_factor -> DecoderOutput(sample fp32 [B, 3, 8h, 8w])"""
+        B, _, h, w = z.shape
+        sample = torch.empty(B, self.config.out_channels, 8 * h, 8 * w, dtype=torch.float32, device=z.device)
+        self._run(z, lambda y, b0, b1: ops.unet_epilogue(y, self.config.out_channels, torch.float32, out=sample[b0:b1]))
+        return DecoderOutput(sample=sample) if return_dict else (sample,)
+
+    def decode_images(self, z: torch.Tensor, output: str = "pt") -> torch.Tensor:
+        """decode + diffusers postprocess (do_denormalize) in the image epilogue kernel: "pt" -> fp32 [B, 3, H, W] in [0, 1],
+        "uint8" -> uint8 [B, H, W, 3] rounded like numpy_to_pil"""
+        if self.config.out_channels != 3:
+            raise ValueError("decode_images: the image epilogue writes 3 channels")
+        B, _, h, w = z.shape
+        if output == "pt":
+            img = torch.empty(B, 3, 8 * h, 8 * w, dtype=torch.float32, device=z.device)
+            self._run(z, lambda y, b0, b1: ops.image_out(y, torch.float32, out=img[b0:b1]))
+        elif output == "uint8":
+            img = torch.empty(B, 8 * h, 8 * w, 3, dtype=torch.uint8, device=z.device)
+            self._run(z, lambda y, b0, b1: ops.image_out(y, torch.uint8, out=img[b0:b1]))
+        else:
+            raise ValueError(f"decode_images: output {output!r} is 'pt' or 'uint8'")
+        return img
+
+    def forward(self, z, return_dict: bool = True):
+        return self.decode(z, return_dict=return_dict)

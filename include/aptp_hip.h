@@ -342,6 +342,38 @@ typedef struct {
 int aptp_unet_prologue(const AptpUnetPrologueParams* p, aptp_stream_t stream);
 int aptp_unet_epilogue(const AptpUnetEpilogueParams* p, aptp_stream_t stream);
 
+/*
+ * Single-head attention of width 512, no mask: o = softmax(q k^T * scale) v per sample, fp32 softmax statistics.
+ * Replaces the mid-block self-attention of AutoencoderKL's decoder (diffusers Attention, heads = 1, dim_head = 512,
+ * upcast_softmax; default scale 512^-0.5).  q/k/v/o are bf16 [B, L, 512] expressed through strides (elements): element
+ * (b, l, c) at ptr + b*stride_b + l*stride_l + c, so a fused q|k|v GEMM output is consumed in place.  Row and batch strides
+ * are multiples of 8 elements, pointers 16-byte aligned; any Lq, Lk >= 1.
+ */
+typedef struct {
+  const void* q; int64_t q_stride_b, q_stride_l;
+  const void* k; int64_t k_stride_b, k_stride_l;
+  const void* v; int64_t v_stride_b, v_stride_l;
+  void* o; int64_t o_stride_b, o_stride_l;
+  int32_t B, Lq, Lk;
+  float scale;       /* > 0 */
+  int32_t io_f32;    /* fp32 PARITY path: q, k, v, o are fp32 (strides multiples of 4), exact-fp32 arithmetic; never benchmarked */
+} AptpAttentionWideParams;
+
+int aptp_attention_wide(const AptpAttentionWideParams* p, aptp_stream_t stream);
+
+/*
+ * Image epilogue of the VAE decoder (diffusers VaeImageProcessor.postprocess with do_denormalize, then numpy_to_pil):
+ * y fp32 [B, H, W, ldy] (conv_out, 3 real channels) -> v = clamp(y / 2 + 0.5, 0, 1), written either as fp32 [B, 3, H, W]
+ * (out_u8 = 0) or as uint8 [B, H, W, 3] = round_half_even(v * 255) (out_u8 = 1).
+ */
+typedef struct {
+  const float* y; int64_t ldy;
+  void* out; int32_t out_u8;
+  int32_t B, H, W;
+} AptpImageOutParams;
+
+int aptp_image_out(const AptpImageOutParams* p, aptp_stream_t stream);
+
 /* Fused tail of a transformer block on the large-M levels (diffusers BasicTransformerBlock.norm3 -> ff (GEGLUGated +
  * Linear, pdm/models/unet/blocks.py:41-50,121-129,821-823) -> "+ hidden_states", then Transformer2DModel.proj_out and its
  * "+ residual", blocks.py:1294-1308) as ONE kernel per 64-token tile:
