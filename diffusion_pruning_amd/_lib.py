@@ -52,6 +52,7 @@ class ConvGemmParams(Structure):
         ("gn_eps", c_float),
         ("io_f32", c_int32),
         ("ustat_out", c_void_p), ("ustat_unit", c_int32), ("ustat_units", c_int32), ("ustat_nrep", c_int32),
+        ("pad_end", c_int32),
     ]
 
 
@@ -231,6 +232,21 @@ class ImageOutParams(Structure):
     ]
 
 
+class ImageInParams(Structure):
+    _fields_ = [
+        ("x", c_void_p), ("x_bf16", c_int32), ("out", c_void_p), ("out_f32", c_int32),
+        ("B", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32),
+    ]
+
+
+class LatentDistParams(Structure):
+    _fields_ = [
+        ("y", c_void_p), ("ldy", c_int64), ("wq", c_void_p), ("bq", c_void_p), ("moments", c_void_p), ("eps", c_void_p),
+        ("latents", c_void_p), ("latents_bf16", c_int32), ("scale", c_float),
+        ("B", c_int32), ("H", c_int32), ("W", c_int32),
+    ]
+
+
 class ColsumParams(Structure):
     _fields_ = [("x", c_void_p), ("ldx", c_int64), ("rows", c_int32), ("C", c_int32), ("partial", c_void_p), ("batch", c_int32)]
 
@@ -315,6 +331,8 @@ EXPORTS = [
     ("aptp_unet_epilogue", c_int, [POINTER(UnetEpilogueParams), c_void_p]),
     ("aptp_attention_wide", c_int, [POINTER(AttentionWideParams), c_void_p]),
     ("aptp_image_out", c_int, [POINTER(ImageOutParams), c_void_p]),
+    ("aptp_image_in", c_int, [POINTER(ImageInParams), c_void_p]),
+    ("aptp_latent_dist", c_int, [POINTER(LatentDistParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

@@ -1075,7 +1075,12 @@ int fill_kparams(const AptpConvGemmParams* p, KParams& k) {
   // geometry consistency: every output pixel's centre tap must map inside the (upsampled) input
   const int sh = p->ups ? 1 : 0;   // ups 1 = nearest x2, ups 2 = zero-insertion x2 (both double the gather extent)
   const int HinE = p->Hin << sh, WinE = p->Win << sh;
-  APTP_CHECK(p->Hout == (HinE + 2 * p->pad - p->KH) / p->stride + 1 && p->Wout == (WinE + 2 * p->pad - p->KW) / p->stride + 1,
+  // pad_end: extra zero rows / columns after the last ones (Downsample2D's F.pad(x, (0, 1, 0, 1))); the gathers' extent tests
+  // read them as zeros.  Not combined with the border correction, the second operand or the upsampling gathers
+  APTP_CHECK(p->pad_end >= 0, "conv_gemm: pad_end (%d) must be >= 0", p->pad_end);
+  APTP_CHECK(p->pad_end == 0 || (!p->corr && !p->x2 && p->ups == 0), "conv_gemm: pad_end > 0 does not go with corr, x2 or ups");
+  APTP_CHECK(p->Hout == (HinE + 2 * p->pad + p->pad_end - p->KH) / p->stride + 1 &&
+             p->Wout == (WinE + 2 * p->pad + p->pad_end - p->KW) / p->stride + 1,
              "conv_gemm: Hout/Wout inconsistent with input extent, filter, stride and padding");
   k.x = (const __bf16*)p->x; k.ldx = p->ldx;
   k.B = p->B; k.Hin = p->Hin; k.Win = p->Win; k.Cin = p->Cin; k.Hout = p->Hout; k.Wout = p->Wout;
@@ -1308,7 +1313,7 @@ extern "C" int aptp_conv_gemm(const AptpConvGemmParams* p, aptp_stream_t stream)
   }
   // plain linear layers take the lean kernel of the same tile shape (lin_gemm.hip); APTP_LIN=0 keeps them here (A/B timing, tests)
   static const bool lin_on = !(getenv("APTP_LIN") && getenv("APTP_LIN")[0] == '0');
-  if (lin_on && p->epilogue != 2 && aptp_lin_eligible(k, t)) {
+  if (lin_on && p->epilogue != 2 && p->pad_end == 0 && aptp_lin_eligible(k, t)) {
     const int rc2 = aptp_launch_lin(k, t, s);
     if (rc2 != APTP_OK) return rc2;
     APTP_LAUNCH_CHECK();
@@ -1316,7 +1321,7 @@ extern "C" int aptp_conv_gemm(const AptpConvGemmParams* p, aptp_stream_t stream)
   }
   // 3x3 convolutions take the lean kernel of the same tile (conv_lean.hip); APTP_CONV_LEAN=0 keeps them here (A/B timing, tests)
   static const bool lean_on = !(getenv("APTP_CONV_LEAN") && getenv("APTP_CONV_LEAN")[0] == '0');
-  if (lean_on && p->epilogue == 0 && aptp_conv_lean_eligible(k, t)) {
+  if (lean_on && p->epilogue == 0 && p->pad_end == 0 && aptp_conv_lean_eligible(k, t)) {
     const int rc2 = aptp_launch_conv_lean(k, t, s);
     if (rc2 != APTP_OK) return rc2;
   } else
@@ -1394,7 +1399,7 @@ extern "C" int aptp_conv_gemm(const AptpConvGemmParams* p, aptp_stream_t stream)
     case APTP_TILE_HALO_128x128: {
       // whole image rows per tile, the patch (R+2) x (W+2) must fit the 264-row LDS image, no second operand
       const int W = p->Wout;
-      if (!(p->KH == 3 && p->KW == 3 && p->stride == 1 && p->pad == 1 && p->ups == 0 && !p->x2 && W > 0 && 128 % W == 0 &&
+      if (!(p->KH == 3 && p->KW == 3 && p->stride == 1 && p->pad == 1 && p->pad_end == 0 && p->ups == 0 && !p->x2 && W > 0 && 128 % W == 0 &&
             (p->Hout * W) % 128 == 0 && (128 / W + 2) * (W + 2) <= 264)) {
         aptp_set_error("conv_gemm: the halo tiles need a 3x3 / stride-1 / pad-1 convolution without x2 whose width divides 128 (16, 32 or 64)");
         return APTP_EINVAL;

@@ -3,6 +3,8 @@
 //   prologue: sample NCHW (fp32 or bf16) -> channels-last bf16 [B, H, W, cin_pad] with zeroed padding channels, and the
 //             sinusoidal timestep embedding t_emb[b] = [cos(t_b * f_k) | sin(t_b * f_k)] as bf16 [B, 2 * half];
 //   epilogue: conv_out's fp32 [B, H, W, ld] -> NCHW [B, C, H, W] in the caller's dtype.
+// and the VAE's ends: the decoder's image epilogue (image_out), the encoder's im2col prologue (image_in) and its
+// quant_conv + DiagonalGaussianDistribution tail (latent_dist).
 // One launch each instead of the ~10 elementwise torch kernels (4.7 us apiece in the HIP graph) they replace.
 #include "aptp_common.h"
 
@@ -86,7 +88,121 @@ __global__ __launch_bounds__(256) void image_out_kernel(const ImgK p) {
   else reinterpret_cast<float*>(p.out)[i] = v;
 }
 
+// VAE encoder prologue: one thread per pixel gathers its 3x3 neighbourhood of the 3 NCHW input planes (27 values, zero outside
+// the image) in tap-major order (ky, kx, c) and writes them, then 5 zeros, as one 32-element row (bf16: 4 x 16-byte stores,
+// fp32: 8).  Pure data movement: bf16 input is copied exactly, fp32 input rounded once (round to nearest even).
+struct ImgInK { const void* x; int x_bf16; void* out; int out_f32; int B, H, W; };
+
+__global__ __launch_bounds__(256) void image_in_kernel(const ImgInK p) {
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t HW = (int64_t)p.H * p.W;
+  if (pix >= (int64_t)p.B * HW) return;
+  const int b = (int)(pix / HW), r = (int)(pix - (int64_t)b * HW);
+  const int oy = r / p.W, ox = r - oy * p.W;
+  float v[32];
+#pragma unroll
+  for (int e = 27; e < 32; ++e) v[e] = 0.f;
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int iy = oy + ky - 1, ix = ox + kx - 1;
+      const bool ok = (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float f = 0.f;
+        if (ok) {
+          const int64_t i = ((int64_t)b * 3 + c) * HW + (int64_t)iy * p.W + ix;
+          f = p.x_bf16 ? (float)reinterpret_cast<const __bf16*>(p.x)[i] : reinterpret_cast<const float*>(p.x)[i];
+        }
+        v[(ky * 3 + kx) * 3 + c] = f;
+      }
+    }
+  }
+  if (p.out_f32) {
+    float4* dst = reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + pix * 32);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) dst[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+  } else {
+    uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(p.out) + pix * 32);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) dst[q] = pack_bf16x8(v + 8 * q);
+  }
+}
+
+// VAE encoder tail: one thread per pixel.  m[o] = bq[o] + sum_i wq[o][i] y[i] (i ascending, each product and sum rounded on its
+// own); moments NCHW; optional sample scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) -- diffusers'
+// DiagonalGaussianDistribution: logvar = clamp(logvar, -30, 20), std = exp(0.5 * logvar), sample = mean + std * eps.
+struct LatK { const float* y; int64_t ld; const float* wq; const float* bq; float* mom; const float* eps; void* lat; int lat_bf16;
+              float scale; int B, HW; };
+
+__global__ __launch_bounds__(256) void latent_dist_kernel(const LatK p) {
+  const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pix >= (int64_t)p.B * p.HW) return;
+  const int b = (int)(pix / p.HW), r = (int)(pix - (int64_t)b * p.HW);
+  const float4* src = reinterpret_cast<const float4*>(p.y + pix * p.ld);
+  const float4 y0 = src[0], y1 = src[1];
+  const float y[8] = {y0.x, y0.y, y0.z, y0.w, y1.x, y1.y, y1.z, y1.w};
+  float m[8];
+#pragma unroll
+  for (int o = 0; o < 8; ++o) {
+    float acc = __fmul_rn(p.wq[o * 8], y[0]);
+#pragma unroll
+    for (int i = 1; i < 8; ++i) acc = __fadd_rn(acc, __fmul_rn(p.wq[o * 8 + i], y[i]));
+    m[o] = __fadd_rn(acc, p.bq[o]);
+  }
+  const int64_t base8 = (int64_t)b * 8 * p.HW + r;
+  if (p.mom) {
+#pragma unroll
+    for (int o = 0; o < 8; ++o) p.mom[base8 + (int64_t)o * p.HW] = m[o];
+  }
+  if (p.eps) {
+    const int64_t base4 = (int64_t)b * 4 * p.HW + r;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float lv = fminf(fmaxf(m[4 + c], -30.f), 20.f);
+      const float sd = expf(__fmul_rn(0.5f, lv));
+      const float z = __fmul_rn(p.scale, __fadd_rn(m[c], __fmul_rn(sd, p.eps[base4 + (int64_t)c * p.HW])));
+      if (p.lat_bf16) reinterpret_cast<__bf16*>(p.lat)[base4 + (int64_t)c * p.HW] = (__bf16)z;
+      else reinterpret_cast<float*>(p.lat)[base4 + (int64_t)c * p.HW] = z;
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int aptp_image_in(const AptpImageInParams* p, aptp_stream_t stream) {
+  APTP_CHECK(p && p->x && p->out, "image_in: null pointer");
+  APTP_CHECK(p->C == 3, "image_in: pixel_values must have 3 channels (got %d)", p->C);
+  APTP_CHECK(p->B > 0 && p->H > 0 && p->W > 0, "image_in: bad extents");
+  APTP_CHECK(((uintptr_t)p->x % (p->x_bf16 ? 2 : 4)) == 0 && ((uintptr_t)p->out % 16) == 0, "image_in: pointer alignment");
+  const int64_t pix = (int64_t)p->B * p->H * p->W;
+  APTP_CHECK((pix + 255) / 256 < (1ll << 31), "image_in: too many pixels");
+  ImgInK k;
+  k.x = p->x; k.x_bf16 = p->x_bf16 ? 1 : 0; k.out = p->out; k.out_f32 = p->out_f32 ? 1 : 0; k.B = p->B; k.H = p->H; k.W = p->W;
+  hipLaunchKernelGGL(image_in_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+  APTP_LAUNCH_CHECK();
+  return APTP_OK;
+}
+
+extern "C" int aptp_latent_dist(const AptpLatentDistParams* p, aptp_stream_t stream) {
+  APTP_CHECK(p && p->y && p->wq && p->bq, "latent_dist: null pointer");
+  APTP_CHECK(p->moments || p->eps, "latent_dist: nothing to write (moments and eps both NULL)");
+  APTP_CHECK(!p->eps || p->latents, "latent_dist: eps needs latents");
+  APTP_CHECK(p->B > 0 && p->H > 0 && p->W > 0 && p->ldy >= 8 && p->ldy % 4 == 0, "latent_dist: bad extents (ldy >= 8, a multiple of 4)");
+  APTP_CHECK(((uintptr_t)p->y % 16) == 0 && ((uintptr_t)p->wq % 4) == 0 && ((uintptr_t)p->bq % 4) == 0 &&
+             ((uintptr_t)p->moments % 4) == 0 && ((uintptr_t)p->eps % 4) == 0 && ((uintptr_t)p->latents % (p->latents_bf16 ? 2 : 4)) == 0,
+             "latent_dist: pointer alignment");
+  APTP_CHECK(p->scale == p->scale, "latent_dist: scale is NaN");
+  const int64_t pix = (int64_t)p->B * p->H * p->W;
+  APTP_CHECK((int64_t)p->H * p->W < (1ll << 31) && (pix + 255) / 256 < (1ll << 31), "latent_dist: too many pixels");
+  LatK k;
+  k.y = p->y; k.ld = p->ldy; k.wq = p->wq; k.bq = p->bq; k.mom = p->moments; k.eps = p->eps; k.lat = p->latents;
+  k.lat_bf16 = p->latents_bf16 ? 1 : 0; k.scale = p->scale; k.B = p->B; k.HW = p->H * p->W;
+  hipLaunchKernelGGL(latent_dist_kernel, dim3((unsigned)((pix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+  APTP_LAUNCH_CHECK();
+  return APTP_OK;
+}
 
 extern "C" int aptp_image_out(const AptpImageOutParams* p, aptp_stream_t stream) {
   APTP_CHECK(p && p->y && p->out, "image_out: null pointer");

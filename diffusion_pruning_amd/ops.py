@@ -16,7 +16,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import UnetEpilogueParams, UnetPrologueParams
+from ._lib import ImageInParams, LatentDistParams, UnetEpilogueParams, UnetPrologueParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -548,8 +548,10 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
               depth: Optional[torch.Tensor] = None, depth_in: Optional[torch.Tensor] = None,
               out_f32: bool = False, split_k: Optional[int] = None, tile: int = 0, order: int = 0,
               rowstats: bool = False, ln=None, colstats: bool = False, x2: Optional[torch.Tensor] = None,
-              prefetch=None, gn=None):
+              prefetch=None, gn=None, pad_end: int = 0):
     """y = epilogue(conv(x, w)); see include/aptp_hip.h for the epilogue order and the reference call sites.
+    pad_end: extra zero rows / columns after the input's last ones (diffusers Downsample2D with padding 0:
+    F.pad(x, (0, 1, 0, 1)) then a stride-2, pad-0 convolution is stride=2, pad=0, pad_end=1).
     gn = (gamma, beta, groups, eps, silu, C): return GroupNorm(+SiLU) of the convolution output over its first C channels
     instead of the output itself.  On the small maps, where the launch is split along K anyway, the reduce launch of the
     split applies the normalisation (AptpConvGemmParams.gn_gamma: one launch and one round trip less); otherwise this is
@@ -557,6 +559,8 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
     rowstats: also emit the per-row (sum, sumsq) partials of y a following folded LayerNorm needs; returns (y, stats)
     with stats fp32 [slots / 2, M, 4] (two (sum, sumsq) slots per element), or (y, None) when this launch is split along K (the caller then normalises with
     ops.layernorm).  ln = (stats, eps): x is the un-normalised input of a LayerNorm folded into pw (pack_weight ln_gamma)."""
+    if pad_end < 0 or (pad_end and (ups or corr is not None or x2 is not None)):
+        raise ValueError("conv_gemm: pad_end must be >= 0 and does not go with ups, corr or x2")
     lib = _lib.load()
     if gn is not None and (colgate is not None or act != ACT_NONE or pw.geglu or corr is not None or residual is not None
                            or depth is not None or out_f32 or rowstats or ln is not None or out is not None):
@@ -569,8 +573,8 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
         pad = pw.KH // 2
     sh = 1 if ups else 0            # ups 1 = nearest x2, ups 2 = zero-insertion x2 (dgrad of a stride-2 conv)
     HinE, WinE = Hin << sh, Win << sh
-    Hout = (HinE + 2 * pad - pw.KH) // stride + 1
-    Wout = (WinE + 2 * pad - pw.KW) // stride + 1
+    Hout = (HinE + 2 * pad + pad_end - pw.KH) // stride + 1
+    Wout = (WinE + 2 * pad + pad_end - pw.KW) // stride + 1
     if pw.geglu:
         act = ACT_GEGLU
     nout = pw.N // 2 if act == ACT_GEGLU else pw.N
@@ -594,6 +598,7 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
     p.x, p.ldx = x.data_ptr(), _ld(x)
     p.B, p.Hin, p.Win, p.Cin, p.Hout, p.Wout = B, Hin, Win, Cx, Hout, Wout
     p.KH, p.KW, p.stride, p.pad, p.ups = pw.KH, pw.KW, stride, pad, ups
+    p.pad_end = pad_end
     p.w, p.N, p.cin_pad = pw.w.data_ptr(), pw.N, pw.cin_pad
     if (x2 is not None) != (pw.Cin2 > 0):
         raise ValueError("conv_gemm: x2 goes with weights packed by pack_weight_cat (and only with them)")
@@ -1039,6 +1044,71 @@ def image_out(y: torch.Tensor, out_dtype: torch.dtype = torch.float32, out: Opti
     p.B, p.H, p.W = B, H, W
     _lib.check(lib.aptp_image_out(ctypes.byref(p), _stream()), "aptp_image_out")
     return out
+
+
+def image_in(x: torch.Tensor, out_f32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The VAE encoder's image prologue: pixel_values NCHW [B, 3, H, W] (fp32 or bf16) -> the 3x3 / pad-1 im2col of every
+    pixel, [B, H, W, 32] tap-major ((ky, kx, c): 27 values, then 5 zeros), bf16 (fp32 with out_f32: the parity path).
+    encoder.conv_in then runs as a 1x1 contraction over 32 channels (pack_conv_in_im2col)."""
+    lib = _lib.load()
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous()):
+        raise ValueError(f"image_in: expected a contiguous CUDA fp32 / bf16 NCHW tensor, got {x.dtype} {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    dt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty(B, H, W, 32, dtype=dt, device=x.device)
+    if tuple(out.shape) != (B, H, W, 32) or out.dtype != dt or not out.is_contiguous():
+        raise ValueError(f"image_in: out must be a contiguous {dt} {(B, H, W, 32)} tensor")
+    p = ImageInParams()
+    p.x, p.x_bf16, p.out, p.out_f32 = x.data_ptr(), int(x.dtype == torch.bfloat16), out.data_ptr(), int(out_f32)
+    p.B, p.C, p.H, p.W = B, C, H, W
+    _lib.check(lib.aptp_image_in(ctypes.byref(p), _stream()), "aptp_image_in")
+    return out
+
+
+def pack_conv_in_im2col(w: torch.Tensor, bias: Optional[torch.Tensor], device=None) -> PackedWeight:
+    """conv_in's OIHW [O, 3, 3, 3] weight as the [O, 32] weight of the 1x1 contraction over image_in's columns:
+    w'[o, (ky * 3 + kx) * 3 + c] = w[o, c, ky, kx], columns 27..31 zero"""
+    O, C, KH, KW = w.shape
+    if (C, KH, KW) != (3, 3, 3):
+        raise ValueError(f"pack_conv_in_im2col: expected a [O, 3, 3, 3] weight, got {tuple(w.shape)}")
+    w2 = torch.zeros(O, 32, dtype=torch.float32, device=w.device)
+    w2[:, :27] = w.detach().float().permute(0, 2, 3, 1).reshape(O, 27)
+    return pack_weight(w2, None if bias is None else bias.detach(), device=device)
+
+
+def latent_dist(y: torch.Tensor, wq: torch.Tensor, bq: torch.Tensor, eps: Optional[torch.Tensor] = None,
+                scale: float = 1.0, moments: bool = True, latents_dtype: torch.dtype = torch.float32,
+                moments_out: Optional[torch.Tensor] = None, latents_out: Optional[torch.Tensor] = None):
+    """The VAE encoder's tail: quant_conv (wq fp32 [8, 8], bq fp32 [8]) on conv_out's fp32 [B, h, w, ld] -> (moments fp32
+    [B, 8, h, w] NCHW or None, latents [B, 4, h, w] or None), latents = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps)
+    for the given fp32 NCHW eps [B, 4, h, w]."""
+    lib = _lib.load()
+    if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.shape[3] >= 8 and y.is_contiguous()):
+        raise ValueError(f"latent_dist: expected a contiguous CUDA fp32 [B, h, w, >=8] tensor, got {y.dtype} {tuple(y.shape)}")
+    B, H, W, ld = y.shape
+    wq = wq.to(device=y.device, dtype=torch.float32).reshape(8, 8).contiguous()
+    bq = bq.to(device=y.device, dtype=torch.float32).reshape(8).contiguous()
+    p = LatentDistParams()
+    p.y, p.ldy, p.wq, p.bq = y.data_ptr(), ld, wq.data_ptr(), bq.data_ptr()
+    p.B, p.H, p.W, p.scale = B, H, W, float(scale)
+    mom = lat = None
+    if moments:
+        mom = moments_out if moments_out is not None else torch.empty(B, 8, H, W, dtype=torch.float32, device=y.device)
+        if tuple(mom.shape) != (B, 8, H, W) or mom.dtype != torch.float32 or not mom.is_contiguous():
+            raise ValueError(f"latent_dist: moments must be a contiguous fp32 {(B, 8, H, W)} tensor")
+        p.moments = mom.data_ptr()
+    if eps is not None:
+        if tuple(eps.shape) != (B, 4, H, W) or eps.dtype != torch.float32 or not eps.is_contiguous() or eps.device != y.device:
+            raise ValueError(f"latent_dist: eps must be a contiguous fp32 {(B, 4, H, W)} tensor on {y.device}")
+        if latents_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("latent_dist: latents_dtype is torch.float32 or torch.bfloat16")
+        lat = latents_out if latents_out is not None else torch.empty(B, 4, H, W, dtype=latents_dtype, device=y.device)
+        if tuple(lat.shape) != (B, 4, H, W) or lat.dtype != latents_dtype or not lat.is_contiguous():
+            raise ValueError(f"latent_dist: latents must be a contiguous {latents_dtype} {(B, 4, H, W)} tensor")
+        p.eps, p.latents, p.latents_bf16 = eps.data_ptr(), lat.data_ptr(), int(latents_dtype == torch.bfloat16)
+    _lib.check(lib.aptp_latent_dist(ctypes.byref(p), _stream()), "aptp_latent_dist")
+    return mom, lat
 
 
 # ------------------------------------------------------------------------------------------------------------------

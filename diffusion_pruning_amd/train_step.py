@@ -859,6 +859,44 @@ def synthetic_batch(batch: int, latent: int, device, seed: int = 1234, cross_dim
     }
 
 
+def noisy_latents_and_target(latents: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor,
+                             alphas_cumprod: torch.Tensor, prediction_type: str = "v_prediction"):
+    """diffusers DDPMScheduler.add_noise and the training target (trainer.py:1097-1122):
+    noisy = sqrt(ac[t]) x0 + sqrt(1 - ac[t]) noise; target = sqrt(ac[t]) noise - sqrt(1 - ac[t]) x0 (v_prediction,
+    DDPMScheduler.get_velocity) or noise (epsilon)"""
+    ac = alphas_cumprod.to(device=latents.device, dtype=latents.dtype)
+    t = timesteps.to(latents.device)
+    sa = (ac[t] ** 0.5).flatten().reshape(-1, *([1] * (latents.dim() - 1)))
+    so = ((1 - ac[t]) ** 0.5).flatten().reshape(-1, *([1] * (latents.dim() - 1)))
+    noisy = sa * latents + so * noise
+    if prediction_type == "epsilon":
+        target = noise
+    elif prediction_type == "v_prediction":
+        target = sa * noise - so * latents
+    else:
+        raise ValueError(f"unknown prediction_type {prediction_type!r}")
+    return noisy, target
+
+
+def batch_from_images(vae, pixel_values: torch.Tensor, encoder_hidden_states: torch.Tensor, mpnet_embeddings: torch.Tensor,
+                      schedule: Optional[NoiseSchedule] = None, prediction_type: str = "v_prediction", generator=None):
+    """A training batch (synthetic_batch's keys) from images, as the reference's training steps build it
+    (trainer.py:1097-1122): latents = vae.encode(pixel_values).latent_dist.sample() * scaling_factor (vae.encode_latents, one
+    pass on the HIP encoder), then noise and timesteps, drawn in that order from ``generator``, add_noise and the target.
+    pixel_values: NCHW [B, 3, H, W] in [-1, 1] on the GPU; H and W multiples of 8."""
+    from .vae import randn_tensor
+    schedule = schedule or NoiseSchedule()
+    latents = vae.encode_latents(pixel_values, generator=generator)
+    dev = latents.device
+    noise = randn_tensor(latents.shape, generator=generator, device=dev, dtype=latents.dtype)
+    T = schedule.alphas_cumprod.shape[0]
+    tdev = generator.device if generator is not None else dev
+    timesteps = torch.randint(0, T, (latents.shape[0],), generator=generator, device=tdev).to(dev)
+    noisy, target = noisy_latents_and_target(latents, noise, timesteps, schedule.alphas_cumprod, prediction_type)
+    return {"noisy_latents": noisy, "target": target, "encoder_hidden_states": encoder_hidden_states,
+            "mpnet_embeddings": mpnet_embeddings, "timesteps": timesteps}
+
+
 @dataclass
 class FinetuneLossConfig:
     """configs/finetuning/sd-2-1_cc3m.yaml:86-95"""

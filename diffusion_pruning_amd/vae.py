@@ -13,7 +13,13 @@ every layer through the existing kernels:
     the residual in its epilogue;
   * ``conv_out`` with an fp32 output, then ``ops.unet_epilogue`` (NCHW ``.sample``) or ``ops.image_out`` (postprocessed).
 
-The latents' NCHW -> NHWC change (4 channels, zero padded to 8) is the only torch arithmetic on the device path.
+The encoder half (``AutoencoderKL(with_encoder=True)``: ``encoder.*`` and ``quant_conv``, ``encode(x).latent_dist``) runs
+the same way: ``ops.image_in`` writes the 3x3 im2col of the image so that ``encoder.conv_in`` is a 1x1 contraction over 32
+channels; resnets and the mid-block as in the decoder; Downsample2D (``F.pad(x, (0, 1, 0, 1))`` + a stride-2, pad-0 3x3
+convolution) is ``ops.conv_gemm(stride=2, pad=0, pad_end=1)``; ``conv_out`` with an fp32 output, then ``ops.latent_dist``
+applies ``quant_conv`` and writes diffusers' moments (and, for ``encode_latents``, the scaled sample) in one launch.
+
+The latents' NCHW -> NHWC change (4 channels, zero padded to 8) is the only torch arithmetic on the decode path.
 With ``ops.ACT_DTYPE = torch.float32`` the same code runs the fp32 parity instantiations of every kernel.
 
 Batch slicing: the convolution kernels address an operand with 32-bit byte offsets (buffer resources; ``aptp_conv_gemm``
@@ -124,6 +130,67 @@ def vae_decoder_macs(cfg: VAEConfig, h: int, w: int) -> Tuple[int, int]:
     return macs, attn
 
 
+def encoder_largest_activation_elements(cfg: VAEConfig, H: int, W: int) -> int:
+    """elements of the largest activation of ONE H x W image in the encoder (image_in's 32 columns or conv_in's output at
+    full resolution for SD-2.1: H x W x 128)"""
+    ch = list(cfg.block_out_channels)
+    big = H * W * max(32, ch[0])
+    prev = ch[0]
+    for i, c in enumerate(ch):
+        big = max(big, H * W * max(prev, c))
+        prev = c
+        if i < len(ch) - 1:
+            H, W = H // 2, W // 2
+            big = max(big, H * W * c)
+    return big
+
+
+def encoder_slice_plan(cfg: VAEConfig, batch: int, H: int, W: int, elem_bytes: int = 2) -> List[int]:
+    """batch sizes of the encode slices: as few as possible, each below MAX_TENSOR_BYTES in every activation"""
+    per = encoder_largest_activation_elements(cfg, H, W) * elem_bytes
+    if per >= MAX_TENSOR_BYTES:
+        raise ValueError(f"encode: one {H}x{W} image needs a {per} B activation, above the verified {MAX_TENSOR_BYTES} B")
+    n = max(1, MAX_TENSOR_BYTES // per)
+    return [min(n, batch - s) for s in range(0, batch, n)]
+
+
+def vae_encoder_macs(cfg: VAEConfig, H: int, W: int) -> Tuple[int, int]:
+    """(MACs per image, attention MACs per image) of the encoder plus quant_conv on an H x W image: the layer table (conv_in
+    counted with its 3 real input channels; the two attention contractions are 2 (hw)^2 C)"""
+    macs = 0
+    ch = list(cfg.block_out_channels)
+
+    def conv(ci, co, k):
+        nonlocal macs
+        macs += H * W * ci * co * k * k
+
+    def res(ci, co):
+        conv(ci, co, 3)
+        conv(co, co, 3)
+        if ci != co:
+            conv(ci, co, 1)
+    conv(cfg.in_channels, ch[0], 3)
+    prev = ch[0]
+    for i, c in enumerate(ch):
+        for j in range(cfg.layers_per_block):
+            res(prev if j == 0 else c, c)
+        prev = c
+        if i < len(ch) - 1:
+            H, W = H // 2, W // 2               # Downsample2D: pad (0, 1, 0, 1), 3x3 stride 2 -> H / 2 for even H
+            conv(c, c, 3)
+    c = ch[-1]
+    res(c, c)
+    for _ in range(4):
+        conv(c, c, 1)
+    attn = 2 * (H * W) ** 2 * c
+    macs += attn
+    res(c, c)
+    z2 = 2 * cfg.latent_channels
+    conv(c, z2, 3)
+    conv(z2, z2, 1)
+    return macs, attn
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # parameter containers (diffusers names and shapes)
 # ----------------------------------------------------------------------------------------------------------------
@@ -184,9 +251,102 @@ class DecoderP(nn.Module):
         self.conv_out = Conv2dP(ch[-1], cfg.out_channels, 3)
 
 
+class Downsample2DP(nn.Module):
+    def __init__(self, c: int):
+        super().__init__()
+        self.conv = Conv2dP(c, c, 3)
+
+
+class DownEncoderBlock2DP(nn.Module):
+    def __init__(self, cin: int, cout: int, layers: int, groups: int, add_downsample: bool):
+        super().__init__()
+        self.resnets = nn.ModuleList([ResnetBlock2DP(cin if j == 0 else cout, cout, groups) for j in range(layers)])
+        self.downsamplers = nn.ModuleList([Downsample2DP(cout)]) if add_downsample else None
+
+
+class EncoderP(nn.Module):
+    def __init__(self, cfg: VAEConfig):
+        super().__init__()
+        ch = list(cfg.block_out_channels)
+        g = cfg.norm_num_groups
+        self.conv_in = Conv2dP(cfg.in_channels, ch[0], 3)
+        blocks, prev = [], ch[0]
+        for i, c in enumerate(ch):
+            blocks.append(DownEncoderBlock2DP(prev, c, cfg.layers_per_block, g, i < len(ch) - 1))
+            prev = c
+        self.down_blocks = nn.ModuleList(blocks)
+        self.mid_block = UNetMidBlock2DP(ch[-1], g)
+        self.conv_norm_out = NormP(ch[-1], GN_EPS, g)
+        self.conv_out = Conv2dP(ch[-1], 2 * cfg.latent_channels, 3)      # double_z
+
+
 @dataclass
 class DecoderOutput:
     sample: torch.Tensor
+
+
+def randn_tensor(shape, generator=None, device=None, dtype=torch.float32) -> torch.Tensor:
+    """diffusers.utils.torch_utils.randn_tensor: a CPU generator draws on the CPU and the result moves to ``device``; a list of
+    generators draws one sample each"""
+    device = torch.device(device) if device is not None else torch.device("cpu")
+    if isinstance(generator, (list, tuple)):
+        if len(generator) == 1:
+            generator = generator[0]
+        else:
+            return torch.cat([randn_tensor((1,) + tuple(shape[1:]), g, device, dtype) for g in generator], 0)
+    rand_device = device
+    if generator is not None and generator.device.type != device.type and generator.device.type == "cpu":
+        rand_device = torch.device("cpu")
+    return torch.randn(tuple(shape), generator=generator, device=rand_device, dtype=dtype).to(device)
+
+
+class DiagonalGaussianDistribution:
+    """diffusers 0.23.1 ``DiagonalGaussianDistribution``.  ``parameters`` are the moments [B, 2z, h, w] (mean | logvar).
+    On the GPU ``sample`` draws eps like ``randn_tensor`` and runs ``ops.latent_dist`` (identity quant_conv, scale 1), so
+    that it is the same kernel arithmetic as ``AutoencoderKL.encode_latents``; on the CPU it is diffusers' torch formula."""
+
+    def __init__(self, parameters: torch.Tensor, deterministic: bool = False):
+        self.parameters = parameters
+        self.mean, self.logvar = torch.chunk(parameters, 2, dim=1)
+        self.logvar = torch.clamp(self.logvar, -30.0, 20.0)
+        self.deterministic = deterministic
+        self.std = torch.exp(0.5 * self.logvar)
+        self.var = torch.exp(self.logvar)
+        if self.deterministic:
+            self.var = self.std = torch.zeros_like(self.mean, device=self.parameters.device, dtype=self.parameters.dtype)
+
+    def sample(self, generator=None) -> torch.Tensor:
+        eps = randn_tensor(self.mean.shape, generator=generator, device=self.parameters.device, dtype=self.parameters.dtype)
+        p = self.parameters
+        if p.is_cuda and p.dtype == torch.float32 and p.shape[1] == 8 and not self.deterministic:
+            y = p.permute(0, 2, 3, 1).contiguous()                 # moments as [B, h, w, 8]: quant_conv = identity
+            eye = torch.eye(8, dtype=torch.float32, device=p.device)
+            _, lat = ops.latent_dist(y, eye, torch.zeros(8, dtype=torch.float32, device=p.device), eps=eps.contiguous(),
+                                     scale=1.0, moments=False)
+            return lat
+        return self.mean + self.std * eps
+
+    def kl(self, other: Optional["DiagonalGaussianDistribution"] = None) -> torch.Tensor:
+        if self.deterministic:
+            return torch.Tensor([0.0])
+        if other is None:
+            return 0.5 * torch.sum(torch.pow(self.mean, 2) + self.var - 1.0 - self.logvar, dim=[1, 2, 3])
+        return 0.5 * torch.sum(torch.pow(self.mean - other.mean, 2) / other.var + self.var / other.var - 1.0 - self.logvar
+                               + other.logvar, dim=[1, 2, 3])
+
+    def nll(self, sample: torch.Tensor, dims=(1, 2, 3)) -> torch.Tensor:
+        if self.deterministic:
+            return torch.Tensor([0.0])
+        logtwopi = np.log(2.0 * np.pi)
+        return 0.5 * torch.sum(logtwopi + self.logvar + torch.pow(sample - self.mean, 2) / self.var, dim=list(dims))
+
+    def mode(self) -> torch.Tensor:
+        return self.mean
+
+
+@dataclass
+class AutoencoderKLOutput:
+    latent_dist: DiagonalGaussianDistribution
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -235,17 +395,29 @@ def _rename_deprecated(name: str) -> str:
 # ----------------------------------------------------------------------------------------------------------------
 class AutoencoderKL(nn.Module):
     """Decode half of diffusers' AutoencoderKL.  ``decode(z)`` equals diffusers' ``vae.decode(z)`` (z = latents /
-    scaling_factor, NCHW); ``decode_images`` returns the postprocessed image in one more launch."""
+    scaling_factor, NCHW); ``decode_images`` returns the postprocessed image in one more launch.
+    ``with_encoder=True`` adds ``encoder`` and ``quant_conv``: ``encode(x).latent_dist`` equals diffusers' ``vae.encode(x)``
+    (x = pixel_values in [-1, 1], NCHW), ``encode_latents(x, g)`` is the trainer's ``encode(x).latent_dist.sample() *
+    scaling_factor`` in one pass."""
 
-    def __init__(self, config: Optional[VAEConfig] = None, **kw):
+    def __init__(self, config: Optional[VAEConfig] = None, with_encoder: bool = False, **kw):
         super().__init__()
         cfg = config or VAEConfig(**kw)
         self.config = cfg
         lc = cfg.latent_channels
         self.post_quant_conv = Conv2dP(lc, lc, 1)
         self.decoder = DecoderP(cfg)
+        self.with_encoder = bool(with_encoder)
+        if self.with_encoder:
+            self.encoder = EncoderP(cfg)
+            self.quant_conv = Conv2dP(2 * lc, 2 * lc, 1)
+        # encoder.conv_in as a 1x1 contraction over ops.image_in's im2col columns (False: a 3x3 convolution over the image
+        # zero padded to 8 channels -- the A/B form of tools/bench_vae_encode.py)
+        self.conv_in_im2col = True
         self._plan = None
         self._plan_key = None
+        self._eplan = None
+        self._eplan_key = None
 
     # ---- weights ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -254,15 +426,17 @@ class AutoencoderKL(nn.Module):
         (std 1 / sqrt(fan_in)), GroupNorm affine near identity, small biases; conv2 of every resnet scaled by 0.5 so that the
         15 residual additions grow the stream slowly."""
         g = torch.Generator().manual_seed(seed)
+        ge = torch.Generator().manual_seed(seed + 0x5EED)        # encoder weights: the decoder's draws stay as without them
         for name, p in self.named_parameters():
+            gen = ge if name.startswith("encoder.") or name.startswith("quant_conv.") else g
             if name.endswith("bias"):
-                p.copy_(0.02 * torch.randn(p.shape, generator=g))
+                p.copy_(0.02 * torch.randn(p.shape, generator=gen))
             elif p.dim() == 1:                                   # GroupNorm gamma
-                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
+                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=gen))
             else:
                 fan_in = p[0].numel()
                 std = fan_in ** -0.5 * (0.5 if name.endswith("conv2.weight") else 1.0)
-                p.copy_(std * torch.randn(p.shape, generator=g))
+                p.copy_(std * torch.randn(p.shape, generator=gen))
         self.invalidate()
         return self
 
@@ -290,23 +464,47 @@ class AutoencoderKL(nn.Module):
         self.invalidate()
         return self
 
+    def load_vae_state_dict(self, sd: Dict[str, torch.Tensor]):
+        """Load a whole diffusers VAE state dict (encoder, quant_conv, post_quant_conv, decoder) strictly: every key of this
+        module must be present with its shape and no other key may be; the deprecated attention names (query / key / value /
+        proj_attn) are accepted in both mid-blocks, 1x1-conv-shaped attention weights are flattened."""
+        own = self.state_dict()
+        got = {}
+        for name, t in sd.items():
+            name = _rename_deprecated(name)
+            if name not in own:
+                raise KeyError(f"AutoencoderKL: unexpected key {name}")
+            if ".attentions." in name and name.endswith("weight") and t.dim() == 4 and t.shape[2:] == (1, 1):
+                t = t[:, :, 0, 0]
+            if tuple(t.shape) != tuple(own[name].shape):
+                raise ValueError(f"AutoencoderKL: {name} has shape {tuple(t.shape)}, expected {tuple(own[name].shape)}")
+            got[name] = t
+        missing = sorted(set(own) - set(got))
+        if missing:
+            raise KeyError(f"AutoencoderKL: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+        self.load_state_dict(got)
+        self.invalidate()
+        return self
+
     @classmethod
-    def from_pretrained(cls, root: str, subfolder: Optional[str] = "vae") -> "AutoencoderKL":
-        """Read ``config.json`` and ``diffusion_pytorch_model.safetensors`` of a diffusers VAE folder."""
+    def from_pretrained(cls, root: str, subfolder: Optional[str] = "vae", with_encoder: bool = False) -> "AutoencoderKL":
+        """Read ``config.json`` and ``diffusion_pytorch_model.safetensors`` of a diffusers VAE folder (with_encoder: the
+        encoder and quant_conv too, strictly)."""
         d = os.path.join(root, subfolder) if subfolder else root
         with open(os.path.join(d, "config.json")) as f:
             cfg = VAEConfig.from_dict(json.load(f))
+        sd = read_safetensors(os.path.join(d, "diffusion_pytorch_model.safetensors"))
+        if with_encoder:
+            return cls(cfg, with_encoder=True).load_vae_state_dict(sd)
         m = cls(cfg)
-        m.load_decoder_state_dict(read_safetensors(os.path.join(d, "diffusion_pytorch_model.safetensors")))
+        m.load_decoder_state_dict(sd)
         return m
-
-    def encode(self, *a, **k):
-        raise NotImplementedError("AutoencoderKL.encode: only the decoder is implemented here (the encoder's stride-2 "
-                                  "convolutions pad asymmetrically, which aptp_conv_gemm does not do)")
 
     def invalidate(self):
         self._plan = None
         self._plan_key = None
+        self._eplan = None
+        self._eplan_key = None
         self.__dict__.pop("_vparams", None)
 
     def _apply(self, fn, *a, **k):
@@ -353,6 +551,52 @@ class AutoencoderKL(nn.Module):
         self._plan, self._plan_key = pl, key
         return pl
 
+    def encoder_plan(self, device) -> dict:
+        """packed encoder weights (cached like plan())"""
+        if not self.with_encoder:
+            raise NotImplementedError("AutoencoderKL.encode: this instance holds the decoder only "
+                                      "(AutoencoderKL(with_encoder=True) / from_pretrained(..., with_encoder=True))")
+        key = (str(device), ops.ACT_DTYPE, self.conv_in_im2col, _versions(self))
+        if self._eplan is not None and self._eplan_key == key:
+            return self._eplan
+        dev = device
+        f32 = lambda t: t.detach().float().to(dev).contiguous()      # noqa: E731
+
+        def conv(m):
+            return ops.pack_weight(m.weight.detach(), m.bias.detach(), device=dev)
+
+        def gn(m):
+            return f32(m.weight), f32(m.bias)
+
+        def res(r):
+            e = {"g1": gn(r.norm1), "g2": gn(r.norm2), "w1": conv(r.conv1)}
+            w2 = conv(r.conv2)
+            if r.conv_shortcut is not None:
+                w2 = ops.pack_weight_cat(w2, r.conv_shortcut.weight.detach(), r.conv_shortcut.bias.detach())
+            e["w2"], e["shortcut"] = w2, r.conv_shortcut is not None
+            return e
+        enc = self.encoder
+        a = enc.mid_block.attentions[0]
+        wqkv = torch.cat([a.to_q.weight, a.to_k.weight, a.to_v.weight], 0).detach()
+        bqkv = torch.cat([a.to_q.bias, a.to_k.bias, a.to_v.bias], 0).detach()
+        ci = enc.conv_in
+        pl = {
+            "conv_in": (ops.pack_conv_in_im2col(ci.weight, ci.bias, device=dev) if self.conv_in_im2col else conv(ci)),
+            "down": [{"res": [res(r) for r in blk.resnets],
+                      "down": conv(blk.downsamplers[0].conv) if blk.downsamplers is not None else None}
+                     for blk in enc.down_blocks],
+            "mid0": res(enc.mid_block.resnets[0]),
+            "attn": {"g": gn(a.group_norm), "qkv": ops.pack_weight(wqkv, bqkv, device=dev),
+                     "out": ops.pack_weight(a.to_out[0].weight.detach(), a.to_out[0].bias.detach(), device=dev)},
+            "mid1": res(enc.mid_block.resnets[1]),
+            "gn_out": gn(enc.conv_norm_out),
+            "conv_out": conv(enc.conv_out),
+            "wq": f32(self.quant_conv.weight[:, :, 0, 0]),
+            "bq": f32(self.quant_conv.bias),
+        }
+        self._eplan, self._eplan_key = pl, key
+        return pl
+
     # ---- forward ----------------------------------------------------------------------------------------------------
     def _resnet(self, x, e):
         G = self.config.norm_num_groups
@@ -390,6 +634,82 @@ class AutoencoderKL(nn.Module):
         g, b = pl["gn_out"]
         a = ops.groupnorm(x, g, b, self.config.norm_num_groups, GN_EPS, True)
         return ops.conv_gemm(a, pl["conv_out"], out_f32=True)
+
+    def _encode_nhwc(self, x: torch.Tensor, pl: dict) -> torch.Tensor:
+        """pixel_values [B, 3, H, W] -> conv_out's fp32 [B, H/8, W/8, 8] (diffusers' moments before quant_conv)"""
+        f32 = ops.ACT_DTYPE == torch.float32
+        if self.conv_in_im2col:
+            h = ops.conv_gemm(ops.image_in(x, out_f32=f32), pl["conv_in"], pad=0, colstats=True)   # conv_in: 1x1 over the im2col
+        else:
+            B, C, H, W = x.shape
+            xp = torch.zeros(B, H, W, pl["conv_in"].Cin, dtype=ops.ACT_DTYPE, device=x.device)
+            xp[..., :C] = x.permute(0, 2, 3, 1)
+            h = ops.conv_gemm(xp, pl["conv_in"], colstats=True)
+        for blk in pl["down"]:
+            for e in blk["res"]:
+                h = self._resnet(h, e)
+            if blk["down"] is not None:                                          # Downsample2D: F.pad (0, 1, 0, 1), 3x3 / 2
+                h = ops.conv_gemm(h, blk["down"], stride=2, pad=0, pad_end=1, colstats=True)
+        h = self._resnet(h, pl["mid0"])
+        h = self._attention(h, pl["attn"])
+        h = self._resnet(h, pl["mid1"])
+        g, b = pl["gn_out"]
+        a = ops.groupnorm(h, g, b, self.config.norm_num_groups, GN_EPS, True)
+        return ops.conv_gemm(a, pl["conv_out"], out_f32=True)
+
+    def _check_pixels(self, x: torch.Tensor):
+        if not (x.is_cuda and x.dim() == 4 and x.shape[1] == self.config.in_channels
+                and x.dtype in (torch.float32, torch.bfloat16)):
+            raise ValueError(f"AutoencoderKL.encode: expected CUDA fp32 / bf16 pixel_values [B, {self.config.in_channels}, H, W], "
+                             f"got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"AutoencoderKL.encode: H and W must be multiples of 8, got {x.shape[2]}x{x.shape[3]}")
+
+    @torch.no_grad()
+    def _encode(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, scale: float = 1.0, moments: bool = True,
+                latents_dtype: torch.dtype = torch.float32):
+        """encode slice by slice (encoder_slice_plan) -> (moments fp32 [B, 8, h, w] or None, latents [B, 4, h, w] or None)"""
+        pl = self.encoder_plan(x.device)                   # (raises NotImplementedError on a decoder-only instance)
+        self._check_pixels(x)
+        x = x.contiguous()
+        B, _, H, W = x.shape
+        h, w = H // 8, W // 8
+        z2 = 2 * self.config.latent_channels
+        mom = torch.empty(B, z2, h, w, dtype=torch.float32, device=x.device) if moments else None
+        lat = None
+        if eps is not None:
+            if tuple(eps.shape) != (B, z2 // 2, h, w):
+                raise ValueError(f"AutoencoderKL.encode: eps shape {tuple(eps.shape)} != {(B, z2 // 2, h, w)}")
+            eps = eps.to(device=x.device, dtype=torch.float32).contiguous()
+            lat = torch.empty(B, z2 // 2, h, w, dtype=latents_dtype, device=x.device)
+        esz = torch.tensor([], dtype=ops.ACT_DTYPE).element_size()
+        with ops.scratch_domain("vae_encoder"):          # never shares a GroupNorm arena with a captured decode
+            b0 = 0
+            for n in encoder_slice_plan(self.config, B, H, W, esz):
+                y = self._encode_nhwc(x[b0:b0 + n], pl)
+                ops.latent_dist(y, pl["wq"], pl["bq"], eps=None if eps is None else eps[b0:b0 + n], scale=scale,
+                                moments=moments, latents_dtype=latents_dtype,
+                                moments_out=None if mom is None else mom[b0:b0 + n],
+                                latents_out=None if lat is None else lat[b0:b0 + n])
+                b0 += n
+        return mom, lat
+
+    def encode(self, x: torch.Tensor, return_dict: bool = True):
+        """diffusers AutoencoderKL.encode: pixel_values [B, 3, H, W] in [-1, 1] -> AutoencoderKLOutput(latent_dist)"""
+        mom, _ = self._encode(x)
+        dist = DiagonalGaussianDistribution(mom)
+        return AutoencoderKLOutput(latent_dist=dist) if return_dict else (dist,)
+
+    def encode_latents(self, x: torch.Tensor, generator=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """the trainer's ``vae.encode(x).latent_dist.sample(generator) * scaling_factor`` with the scale folded into the
+        sampling launch; eps is drawn like randn_tensor.  With fp32 output it equals the two-step form bit for bit."""
+        if not self.with_encoder:
+            self.encoder_plan(x.device)                      # raises NotImplementedError
+        B, _, H, W = x.shape
+        eps = randn_tensor((B, self.config.latent_channels, H // 8, W // 8), generator=generator, device=x.device,
+                           dtype=torch.float32)
+        _, lat = self._encode(x, eps=eps, scale=self.config.scaling_factor, moments=False, latents_dtype=dtype)
+        return lat
 
     def _check_latents(self, z: torch.Tensor):
         if not (z.is_cuda and z.dim() == 4 and z.shape[1] == self.config.latent_channels):

@@ -157,6 +157,12 @@ typedef struct {
    * (nrep * B * ustat_units * 2 words, ustat_units = ceil(N_out / ustat_unit)); nobody resets it. */
   void* ustat_out;
   int32_t ustat_unit, ustat_units, ustat_nrep;
+  /* extra zero rows and columns AFTER the input's last row and column (>= 0): the output extent is
+   * Hout = (Hin' + 2 * pad + pad_end - KH) / stride + 1 (and the same for W).  diffusers Downsample2D with padding 0
+   * (the VAE encoder: F.pad(x, (0, 1, 0, 1)) followed by a stride-2, pad-0 3x3 convolution) is pad = 0, pad_end = 1.
+   * The gathers already read zeros past the input, so the general, LDS-DMA, stream-K and fp32 parity kernels take it
+   * unchanged; pad_end > 0 refuses corr, x2, ups and the halo tiles, and never takes the lean linear / 3x3 kernels. */
+  int32_t pad_end;
 } AptpConvGemmParams;
 
 enum { APTP_TILE_AUTO = 0, APTP_TILE_128x128 = 1, APTP_TILE_128x160 = 2, APTP_TILE_64x128 = 3, APTP_TILE_64x160 = 4,
@@ -373,6 +379,42 @@ typedef struct {
 } AptpImageOutParams;
 
 int aptp_image_out(const AptpImageOutParams* p, aptp_stream_t stream);
+
+/*
+ * Image prologue of the VAE encoder: pixel_values NCHW [B, 3, H, W] (fp32 or bf16, in [-1, 1]) -> the 3x3 / pad-1 im2col of
+ * every pixel, out [B, H, W, 32] tap-major: element (ky * 3 + kx) * 3 + c = x[b, c, y + ky - 1, x + kx - 1] (zero outside the
+ * image), elements 27..31 zero.  encoder.conv_in (3 -> 128, 3x3) then runs as a 1x1 contraction over 32 channels with the
+ * weight repacked as w'[o][(ky * 3 + kx) * 3 + c] = w[o][c][ky][kx].  out is bf16, or fp32 (out_f32: the parity path).
+ */
+typedef struct {
+  const void* x; int32_t x_bf16;
+  void* out; int32_t out_f32;
+  int32_t B, C, H, W;   /* C must be 3 */
+} AptpImageInParams;
+
+int aptp_image_in(const AptpImageInParams* p, aptp_stream_t stream);
+
+/*
+ * The end of AutoencoderKL.encode: quant_conv (8 x 8 matrix + bias, fp32) on conv_out's fp32 [B, H, W, ldy] (8 real
+ * channels), written NCHW as diffusers' moments [B, 8, H, W] fp32 (DiagonalGaussianDistribution.parameters), and
+ * optionally the sample: given eps fp32 NCHW [B, 4, H, W],
+ *     latents = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps)      (mean = moments[:, :4], logvar = moments[:, 4:])
+ * as fp32 or bf16 NCHW [B, 4, H, W].  Every operation is one explicitly rounded fp32 operation (no FMA contraction), in the
+ * order written, the quant_conv sum in input-channel order; no atomics (deterministic).  scale == 1 gives the plain
+ * sample; the scale multiply is last, so scale * sample(scale 1) in fp32 is bit-identical to the scaled launch.
+ */
+typedef struct {
+  const float* y; int64_t ldy;     /* fp32 [B, H, W, ldy], ldy >= 8 */
+  const float* wq;                 /* fp32 [8][8] (out, in) */
+  const float* bq;                 /* fp32 [8] */
+  float* moments;                  /* fp32 [B, 8, H, W] or NULL */
+  const float* eps;                /* fp32 [B, 4, H, W] or NULL (no sample) */
+  void* latents; int32_t latents_bf16;
+  float scale;
+  int32_t B, H, W;
+} AptpLatentDistParams;
+
+int aptp_latent_dist(const AptpLatentDistParams* p, aptp_stream_t stream);
 
 /* Fused tail of a transformer block on the large-M levels (diffusers BasicTransformerBlock.norm3 -> ff (GEGLUGated +
  * Linear, pdm/models/unet/blocks.py:41-50,121-129,821-823) -> "+ hidden_states", then Transformer2DModel.proj_out and its
