@@ -65,6 +65,15 @@ def _ld(x: torch.Tensor) -> int:
     return max(x.stride(2), C)
 
 
+def _set_views(p, **views):
+    """fill the pointer / batch stride / row stride fields ``<name>``, ``<name>_stride_b``, ``<name>_stride_l`` of a params
+    struct from [B, L, C] views"""
+    for name, t in views.items():
+        setattr(p, name, t.data_ptr())
+        setattr(p, name + "_stride_b", t.stride(0))
+        setattr(p, name + "_stride_l", t.stride(1))
+
+
 @dataclass
 class PackedWeight:
     """bf16 weights in the kernel's [N][taps][cin_pad] layout + fp32 bias (both already gathered/compacted)."""
@@ -869,10 +878,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, sca
         out = torch.empty(B, Lq, heads * 64, dtype=q.dtype, device=q.device)
     p = AttentionParams()
     p.io_f32 = int(q.dtype == torch.float32)      # fp32 parity path (csrc/parity_f32.hip)
-    p.q, p.q_stride_b, p.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
-    p.k, p.k_stride_b, p.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
-    p.v, p.v_stride_b, p.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
-    p.o, p.o_stride_b, p.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
+    _set_views(p, q=q, k=k, v=v, o=out)
     p.B, p.heads, p.Lq, p.Lk = B, heads, Lq, Lk
     p.scale = (1.0 / 8.0) if scale is None else scale
     p.variant = ATTN_VARIANT
@@ -987,6 +993,9 @@ def unet_epilogue(y: torch.Tensor, channels: int, out_dtype: torch.dtype, out: O
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# model-I/O wrappers of the VAE and the text encoder
+# ------------------------------------------------------------------------------------------------------------------
 WIDE_HEAD = 512
 ATTN_WIDE_LAUNCH_LOG = None     # tools/bench_vae.py: the wide-head attention launches of one decode (re-timed on their own)
 
@@ -1012,10 +1021,7 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Opt
         raise ValueError("attention_wide: out must be [B, Lq, 512] of q's dtype with contiguous channels")
     p = AttentionWideParams()
     p.io_f32 = int(q.dtype == torch.float32)
-    p.q, p.q_stride_b, p.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
-    p.k, p.k_stride_b, p.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
-    p.v, p.v_stride_b, p.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
-    p.o, p.o_stride_b, p.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
+    _set_views(p, q=q, k=k, v=v, o=out)
     p.B, p.Lq, p.Lk = B, Lq, Lk
     p.scale = WIDE_HEAD ** -0.5 if scale is None else float(scale)
     if ATTN_WIDE_LAUNCH_LOG is not None and not p.io_f32:
@@ -1112,9 +1118,6 @@ def latent_dist(y: torch.Tensor, wq: torch.Tensor, bq: torch.Tensor, eps: Option
     return mom, lat
 
 
-# ------------------------------------------------------------------------------------------------------------------
-# backward-path wrappers
-# ------------------------------------------------------------------------------------------------------------------
 CAUSAL_MAX_L = 128
 
 
@@ -1134,10 +1137,7 @@ def attention_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
                              f"channels on {q.device}, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
     p = AttentionCausalParams()
     p.io_f32 = int(q.dtype == torch.float32)
-    p.q, p.q_stride_b, p.q_stride_l = q.data_ptr(), q.stride(0), q.stride(1)
-    p.k, p.k_stride_b, p.k_stride_l = k.data_ptr(), k.stride(0), k.stride(1)
-    p.v, p.v_stride_b, p.v_stride_l = v.data_ptr(), v.stride(0), v.stride(1)
-    p.o, p.o_stride_b, p.o_stride_l = out.data_ptr(), out.stride(0), out.stride(1)
+    _set_views(p, q=q, k=k, v=v, o=out)
     p.B, p.heads, p.L = B, heads, L
     p.scale = 0.125 if scale is None else scale
     _lib.check(lib.aptp_attention_causal(ctypes.byref(p), _stream()), "aptp_attention_causal")
@@ -1171,6 +1171,9 @@ def token_embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, out_f32
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# backward-path wrappers
+# ------------------------------------------------------------------------------------------------------------------
 def pack_weight_dgrad(w: torch.Tensor, device=None) -> PackedWeight:
     """Packed weights of the data-gradient contraction: OIHW -> IOHW with the filter rotated by 180 degrees
     (a linear weight [out,in] -> its transpose)."""
@@ -1648,11 +1651,10 @@ def attention_bwd(q, k, v, o, dout, lse, heads: int, dq, dk, dv, scale: Optional
     B, Lq, Lk = q.shape[0], q.shape[1], k.shape[1]
     delta = torch.empty(B, heads, Lq, dtype=torch.float32, device=q.device)
     p = AttentionBwdParams()
-    for name, t in (("q", q), ("k", k), ("v", v), ("o", o), ("dout", dout), ("dq", dq), ("dk", dk), ("dv", dv)):
+    views = dict(q=q, k=k, v=v, o=o, dout=dout, dq=dq, dk=dk, dv=dv)
+    for name, t in views.items():
         assert t.dtype == torch.bfloat16 and t.stride(2) == 1 and t.shape[2] == heads * 64, name
-        setattr(p, name, t.data_ptr())
-        setattr(p, name + "_stride_b", t.stride(0))
-        setattr(p, name + "_stride_l", t.stride(1))
+    _set_views(p, **views)
     p.lse, p.delta = lse.data_ptr(), delta.data_ptr()
     p.B, p.heads, p.Lq, p.Lk = B, heads, Lq, Lk
     p.scale = (1.0 / 8.0) if scale is None else scale

@@ -26,8 +26,6 @@ check below is skipped then), so an encode can be captured with ``torch.cuda.gra
 """
 from __future__ import annotations
 
-import json
-import os
 from dataclasses import dataclass, fields
 from typing import Dict, Optional, Tuple
 
@@ -35,8 +33,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .unet import LinearP, _versions
-from .vae import read_safetensors
+from .loading import load_strict, read_pretrained
+from .unet import LinearP, _PlanCache, _versions
 
 # encodes of at most this many tokens (B * L) fold LN1 / LN2 into the q|k|v and fc1 GEMMs, larger ones launch stand-alone
 # LayerNorms.  Measured (tools/bench_text_encoder.py, graph replays, both forms alternately): folded 1.455 vs 1.503 ms at
@@ -164,7 +162,8 @@ class CLIPTextModel(nn.Module):
             raise NotImplementedError(f"CLIPTextModel: max_position_embeddings {cfg.max_position_embeddings} > {ops.CAUSAL_MAX_L}")
         self.config = cfg
         self.text_model = _TextTransformer(cfg)
-        self._plans = {}
+        # 2 dtypes x 2 LayerNorm forms fit unpinned: an encode of one form never evicts the other form's packs
+        self._plans = _PlanCache(cap=4)
 
     # ---- weights ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -190,36 +189,18 @@ class CLIPTextModel(nn.Module):
         """Strict load of a transformers CLIPTextModel state dict, with or without the ``text_model.`` prefix (transformers
         4.34 writes it); ``embeddings.position_ids`` (a buffer some checkpoints carry) is ignored.  A missing, unexpected
         or mis-shaped key raises."""
-        own = self.state_dict()
-        got = {}
-        for name, t in sd.items():
-            if not name.startswith("text_model."):
-                name = "text_model." + name
-            if name == "text_model.embeddings.position_ids":
-                continue
-            if name not in own:
-                raise KeyError(f"CLIPTextModel: unexpected key {name}")
-            if tuple(t.shape) != tuple(own[name].shape):
-                raise ValueError(f"CLIPTextModel: {name} has shape {tuple(t.shape)}, expected {tuple(own[name].shape)}")
-            got[name] = t
-        missing = sorted(set(own) - set(got))
-        if missing:
-            raise KeyError(f"CLIPTextModel: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
-        self.load_state_dict(got)
-        self.invalidate()
-        return self
+        return load_strict(self, sd, lambda n: n if n.startswith("text_model.") else "text_model." + n,
+                           lambda n: n == "text_model.embeddings.position_ids")
 
     @classmethod
     def from_pretrained(cls, root: str, subfolder: Optional[str] = "text_encoder") -> "CLIPTextModel":
         """Read ``config.json`` and ``model.safetensors`` of a transformers CLIPTextModel folder."""
-        d = os.path.join(root, subfolder) if subfolder else root
-        with open(os.path.join(d, "config.json")) as f:
-            cfg = CLIPTextConfig.from_dict(json.load(f))
-        sd = read_safetensors(os.path.join(d, "model.safetensors"), skip=lambda n: n.endswith("embeddings.position_ids"))
+        cfg, sd = read_pretrained(CLIPTextConfig, root, subfolder, "model.safetensors",
+                                  skip=lambda n: n.endswith("embeddings.position_ids"))
         return cls(cfg).load_text_state_dict(sd)
 
     def invalidate(self):
-        self._plans = {}
+        self._plans.clear()
         self.__dict__.pop("_vparams", None)
 
     def _apply(self, fn, *a, **k):
@@ -228,13 +209,12 @@ class CLIPTextModel(nn.Module):
 
     # ---- packed weights ---------------------------------------------------------------------------------------------
     def plan(self, device, fold: bool = True) -> dict:
-        """packed weights per (device, ACT_DTYPE, LayerNorm form): encodes of either form keep the other form's packs alive,
-        so a graph captured under either stays valid; a weight update (parameter versions) replaces the entry"""
-        key = (str(device), ops.ACT_DTYPE, fold)
-        version = _versions(self)
-        hit = self._plans.get(key)
-        if hit is not None and hit[0] == version:
-            return hit[1]
+        """packed weights per (device, ACT_DTYPE, LayerNorm form) in the _PlanCache: a plan seen during a capture outlives
+        the graph, whichever form or dtype is encoded afterwards; a weight update (parameter versions) replaces the entry"""
+        key, version = (str(device), ops.ACT_DTYPE, fold), _versions(self)
+        pl = self._plans.get(key, version)
+        if pl is not None:
+            return pl
         f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
         tm = self.text_model
         layers = []
@@ -258,8 +238,7 @@ class CLIPTextModel(nn.Module):
             layers.append(e)
         pl = {"tok": f32(tm.embeddings.token_embedding.weight), "pos": f32(tm.embeddings.position_embedding.weight),
               "final": (f32(tm.final_layer_norm.weight), f32(tm.final_layer_norm.bias)), "layers": layers}
-        self._plans[key] = (version, pl)
-        return pl
+        return self._plans.put(key, version, pl)
 
     # ---- forward ----------------------------------------------------------------------------------------------------
     def _ln_linear(self, x, st, e, idx, name, **kw):

@@ -191,7 +191,8 @@ def _versions(mod: nn.Module) -> tuple:
 
 
 class _PlanCache:
-    """Packed-weight plans of one module, keyed by (mask, semantics, device).
+    """Packed-weight plans of one module, keyed by whatever the packs depend on besides the parameters (mask, semantics,
+    device, activation dtype, ...).  Every module of the package that packs weights keeps them here.
 
     * At most ``cap`` UNPINNED entries; the oldest is evicted.  A plan that is created or looked up while a stream is
       capturing is PINNED: a HIP graph bakes raw pointers to its packs, so it must outlive the graph and is only released
@@ -222,6 +223,11 @@ class _PlanCache:
             del self.entries[unpinned[0]]
         self.entries[key] = [version, plan, _capturing()]
         return plan
+
+    def lookup(self, key, version, make):
+        """the current plan under ``key``, made by ``make()`` on a miss"""
+        plan = self.get(key, version)
+        return plan if plan is not None else self.put(key, version, make())
 
     def clear(self):
         self.entries.clear()
@@ -1016,87 +1022,68 @@ class UNet2DConditionOutput:
     sample: torch.Tensor
 
 
-class Downsample2D(nn.Module):
-    """diffusers Downsample2D(use_conv=True, padding=1): conv 3x3 stride 2 (SURVEY App. E)."""
+class _Resample2D(nn.Module):
+    """One 3x3 convolution that changes the resolution.  A subclass names the conv_gemm arguments (``conv_kw``) and the
+    output size; packing (the dgrad pack is made on first use and lives in the same plan), staleness and the lifetime of
+    packs a captured graph points to are the _PlanCache's."""
+    conv_kw: dict = {}
 
     def __init__(self, channels: int):
         super().__init__()
         self.conv = Conv2dP(channels, channels, 3)
-        self._pw, self._pw_ver, self._pinned, self._parked = None, None, False, []
+        self._plans = _PlanCache(cap=1)
 
     def invalidate(self):
-        self._pw, self._pinned = None, False
-        self._parked.clear()
+        self._plans.clear()
         self.__dict__.pop("_vparams", None)
+
+    def plan(self, device) -> dict:
+        return self._plans.lookup(str(device), _versions(self), lambda: {
+            "pw": ops.pack_weight(self.conv.weight.detach(), self.conv.bias.detach(), device=device)})
+
+    def _out_hw(self, H: int, W: int) -> Tuple[int, int]:
+        raise NotImplementedError
+
+    def _resample(self, hidden_states):
+        x = _nhwc(hidden_states)
+        if _ft_mode(self):
+            self.__dict__.pop("_out_dst", None)
+        pl = self.plan(x.device)
+        pw = pl["pw"]
+
+        def get_bwd():
+            if "pwb" not in pl:
+                pl["pwb"] = ops.pack_weight_dgrad(self.conv.weight.detach(), device=x.device)
+            return pl["pwb"]
+        if _ft_mode(self) and self.conv.weight.requires_grad:
+            return _nchw(_cw(self, x, self.conv.weight, self.conv.bias, pw, get_bwd, **self.conv_kw))
+        if torch.is_grad_enabled() and x.requires_grad:
+            from . import autograd as AG
+            return _nchw(AG.conv(x, pw, get_bwd, **self.conv_kw))
+        dst = _take_dst(self, x.shape[0], *self._out_hw(x.shape[1], x.shape[2]), pw.N, x.device)
+        return _nchw(ops.conv_gemm(x, pw, out=dst, colstats=True, **self.conv_kw))
+
+
+class Downsample2D(_Resample2D):
+    """diffusers Downsample2D(use_conv=True, padding=1): conv 3x3 stride 2 (SURVEY App. E)."""
+    conv_kw = {"stride": 2, "pad": 1}
+
+    def _out_hw(self, H, W):
+        return (H - 1) // 2 + 1, (W - 1) // 2 + 1
 
     def forward(self, hidden_states, scale: float = 1.0):
-        x = _nhwc(hidden_states)
-        if _ft_mode(self):
-            self.__dict__.pop("_out_dst", None)
-        ver = _versions(self)
-        if self._pw is None or self._pw.w.device != x.device or self._pw_ver != ver:
-            if self._pw is not None and self._pinned:
-                self._parked.append((self._pw, getattr(self, "_pwb", None)))      # a captured graph still points to it
-            self._pw = ops.pack_weight(self.conv.weight.detach(), self.conv.bias.detach(), device=x.device)
-            self._pwb, self._pw_ver, self._pinned = None, ver, False
-        self._pinned = self._pinned or _capturing()
-        if _ft_mode(self) and self.conv.weight.requires_grad:
-            from . import autograd as AG
-            return _nchw(_cw(self, x, self.conv.weight, self.conv.bias, self._pw, self._get_bwd(x.device), stride=2, pad=1))
-        if torch.is_grad_enabled() and x.requires_grad:
-            from . import autograd as AG
-            return _nchw(AG.conv(x, self._pw, self._get_bwd(x.device), stride=2, pad=1))
-        Ho, Wo = (x.shape[1] - 1) // 2 + 1, (x.shape[2] - 1) // 2 + 1
-        dst = _take_dst(self, x.shape[0], Ho, Wo, self._pw.N, x.device)
-        return _nchw(ops.conv_gemm(x, self._pw, stride=2, pad=1, out=dst, colstats=True))
-
-    def _get_bwd(self, dev):
-        def get():
-            if getattr(self, "_pwb", None) is None:
-                self._pwb = ops.pack_weight_dgrad(self.conv.weight.detach(), device=dev)
-            return self._pwb
-        return get
+        return self._resample(hidden_states)
 
 
-class Upsample2D(nn.Module):
+class Upsample2D(_Resample2D):
     """diffusers Upsample2D(use_conv=True): nearest x2 then conv 3x3 — the upsample is folded into the conv's gather."""
+    conv_kw = {"ups": 1}
 
-    def __init__(self, channels: int):
-        super().__init__()
-        self.conv = Conv2dP(channels, channels, 3)
-        self._pw, self._pw_ver, self._pinned, self._parked = None, None, False, []
-
-    def invalidate(self):
-        self._pw, self._pinned = None, False
-        self._parked.clear()
-        self.__dict__.pop("_vparams", None)
+    def _out_hw(self, H, W):
+        return 2 * H, 2 * W
 
     def forward(self, hidden_states, output_size=None, scale: float = 1.0):
-        x = _nhwc(hidden_states)
-        if _ft_mode(self):
-            self.__dict__.pop("_out_dst", None)
-        ver = _versions(self)
-        if self._pw is None or self._pw.w.device != x.device or self._pw_ver != ver:
-            if self._pw is not None and self._pinned:
-                self._parked.append((self._pw, getattr(self, "_pwb", None)))      # a captured graph still points to it
-            self._pw = ops.pack_weight(self.conv.weight.detach(), self.conv.bias.detach(), device=x.device)
-            self._pwb, self._pw_ver, self._pinned = None, ver, False
-        self._pinned = self._pinned or _capturing()
-        if _ft_mode(self) and self.conv.weight.requires_grad:
-            from . import autograd as AG
-            return _nchw(_cw(self, x, self.conv.weight, self.conv.bias, self._pw, self._get_bwd(x.device), ups=1))
-        if torch.is_grad_enabled() and x.requires_grad:
-            from . import autograd as AG
-            return _nchw(AG.conv(x, self._pw, self._get_bwd(x.device), ups=1))
-        dst = _take_dst(self, x.shape[0], 2 * x.shape[1], 2 * x.shape[2], self._pw.N, x.device)
-        return _nchw(ops.conv_gemm(x, self._pw, ups=1, out=dst, colstats=True))
-
-    def _get_bwd(self, dev):
-        def get():
-            if getattr(self, "_pwb", None) is None:
-                self._pwb = ops.pack_weight_dgrad(self.conv.weight.detach(), device=dev)
-            return self._pwb
-        return get
+        return self._resample(hidden_states)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -1358,8 +1345,7 @@ class UNet2DConditionModelGated(nn.Module):
         self.prunable_macs_list = None
         self.resource_info_dict = None
         self.semantics = "gated"
-        self._misc = None       # packed conv_in / time MLP / conv_out
-        self._misc_parked = []  # superseded _misc packs a captured graph may still point to
+        self._misc = _PlanCache(cap=1)    # device -> packed conv_in / time MLP / conv_out
         self._batched = _PlanCache()      # structure-key -> batched temb / ctx-kv packs
 
     # ---- construction helpers -------------------------------------------------------------------------------------
@@ -1390,8 +1376,7 @@ class UNet2DConditionModelGated(nn.Module):
 
     def invalidate_plans(self):
         """Drop every packed-weight cache (call after changing parameters)."""
-        self._misc = None
-        self._misc_parked = []
+        self._misc.clear()
         self._batched.clear()
         for m in self.modules():
             if m is not self and hasattr(m, "invalidate"):
@@ -1537,13 +1522,10 @@ class UNet2DConditionModelGated(nn.Module):
     def _misc_packs(self, dev):
         ver = () if self.__dict__.get("_pk") is not None else \
             tuple(p._version for mod in (self.conv_in, self.time_embedding, self.conv_norm_out, self.conv_out) for p in mod.parameters())
-        if self._misc is not None and self._misc["dev"] == str(dev) and self._misc["ver"] == ver:
-            self._misc["pinned"] = self._misc["pinned"] or _capturing()
-        if self._misc is None or self._misc["dev"] != str(dev) or self._misc["ver"] != ver:
-            if self._misc is not None and self._misc["pinned"]:
-                self._misc_parked.append(self._misc)
+        m = self._misc.get(str(dev), ver)
+        if m is None:
             cin_pad = ops.round_up(self.in_channels, 8)
-            m = {"dev": str(dev), "cin_pad": cin_pad, "ver": ver, "pinned": _capturing()}
+            m = {"cin_pad": cin_pad}
             m["conv_in"] = ops.pack_weight(self.conv_in.weight.detach(), self.conv_in.bias.detach(), device=dev)
             te = self.time_embedding
             m["t1"] = ops.pack_weight(te.linear_1.weight.detach(), te.linear_1.bias.detach(), device=dev)
@@ -1552,8 +1534,8 @@ class UNet2DConditionModelGated(nn.Module):
             m["conv_out"] = ops.pack_weight(self.conv_out.weight.detach(), self.conv_out.bias.detach(), device=dev)
             half = self.conv_in.out_channels // 2
             m["freqs"] = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32, device=dev) / half)
-            self._misc = m
-        return self._misc
+            self._misc.put(str(dev), ver, m)
+        return m
 
     def _batched_packs(self, dev):
         """One GEMM for all 22 time_emb_proj, one for all 16 cross-attention K/V projections."""

@@ -28,9 +28,6 @@ that no activation of one slice reaches ``MAX_TENSOR_BYTES`` -- diffusers' VAE s
 """
 from __future__ import annotations
 
-import json
-import os
-import struct
 from dataclasses import dataclass, fields
 from typing import Dict, List, Optional, Tuple
 
@@ -39,7 +36,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .unet import Conv2dP, LinearP, NormP, _versions
+from .loading import load_strict, read_pretrained, read_safetensors  # noqa: F401  (vae.read_safetensors: the old home)
+from .unet import Conv2dP, LinearP, NormP, _PlanCache, _versions
 
 
 @dataclass(frozen=True)
@@ -68,97 +66,58 @@ GN_EPS = 1e-6
 MAX_TENSOR_BYTES = (1 << 31) - (1 << 20)
 
 
-def largest_activation_elements(cfg: VAEConfig, h: int, w: int) -> int:
-    """elements of the largest activation of ONE image (the input of the last level's first resnet for SD-2.1:
-    8h x 8w x 256)"""
-    ch = list(reversed(cfg.block_out_channels))
-    H, W = h, w
-    big = H * W * max(ch[0], cfg.latent_channels)
+def _largest(ch: List[int], H: int, W: int, first: int, up: bool) -> int:
+    """largest H x W x channels product along the levels ``ch``, starting from ``first`` channels at H x W"""
+    big = H * W * first
     prev = ch[0]
     for i, c in enumerate(ch):
         big = max(big, H * W * max(prev, c))
         prev = c
         if i < len(ch) - 1:
-            H, W = 2 * H, 2 * W
+            H, W = (2 * H, 2 * W) if up else (H // 2, W // 2)
             big = max(big, H * W * c)
     return big
 
 
-def slice_plan(cfg: VAEConfig, batch: int, h: int, w: int, elem_bytes: int = 2) -> List[int]:
-    """batch sizes of the decode slices: as few as possible, each below MAX_TENSOR_BYTES in every activation"""
-    per = largest_activation_elements(cfg, h, w) * elem_bytes
-    if per >= MAX_TENSOR_BYTES:
-        raise ValueError(f"decode: one {8 * h}x{8 * w} image needs a {per} B activation, above the verified {MAX_TENSOR_BYTES} B")
-    n = max(1, MAX_TENSOR_BYTES // per)
-    return [min(n, batch - s) for s in range(0, batch, n)]
-
-
-def vae_decoder_macs(cfg: VAEConfig, h: int, w: int) -> Tuple[int, int]:
-    """(MACs per image, attention MACs per image) of the decoder at an h x w latent: the layer table (one MAC = one
-    multiply-add; the two attention contractions are 2 (hw)^2 512)"""
-    macs = 0
+def largest_activation_elements(cfg: VAEConfig, h: int, w: int) -> int:
+    """elements of the largest activation of ONE image (the input of the last level's first resnet for SD-2.1:
+    8h x 8w x 256)"""
     ch = list(reversed(cfg.block_out_channels))
-    H, W = h, w
-
-    def conv(ci, co, k):
-        nonlocal macs
-        macs += H * W * ci * co * k * k
-
-    def res(ci, co):
-        conv(ci, co, 3)
-        conv(co, co, 3)
-        if ci != co:
-            conv(ci, co, 1)
-    lc = cfg.latent_channels
-    conv(lc, lc, 1)
-    conv(lc, ch[0], 3)
-    res(ch[0], ch[0])
-    for _ in range(4):
-        conv(ch[0], ch[0], 1)
-    attn = 2 * (H * W) ** 2 * ch[0]
-    macs += attn
-    res(ch[0], ch[0])
-    prev = ch[0]
-    for i, c in enumerate(ch):
-        for j in range(cfg.layers_per_block + 1):
-            res(prev if j == 0 else c, c)
-        prev = c
-        if i < len(ch) - 1:
-            H, W = 2 * H, 2 * W
-            conv(c, c, 3)
-    conv(ch[-1], cfg.out_channels, 3)
-    return macs, attn
+    return _largest(ch, h, w, max(ch[0], cfg.latent_channels), True)
 
 
 def encoder_largest_activation_elements(cfg: VAEConfig, H: int, W: int) -> int:
     """elements of the largest activation of ONE H x W image in the encoder (image_in's 32 columns or conv_in's output at
     full resolution for SD-2.1: H x W x 128)"""
     ch = list(cfg.block_out_channels)
-    big = H * W * max(32, ch[0])
-    prev = ch[0]
-    for i, c in enumerate(ch):
-        big = max(big, H * W * max(prev, c))
-        prev = c
-        if i < len(ch) - 1:
-            H, W = H // 2, W // 2
-            big = max(big, H * W * c)
-    return big
+    return _largest(ch, H, W, max(32, ch[0]), False)
 
 
-def encoder_slice_plan(cfg: VAEConfig, batch: int, H: int, W: int, elem_bytes: int = 2) -> List[int]:
-    """batch sizes of the encode slices: as few as possible, each below MAX_TENSOR_BYTES in every activation"""
-    per = encoder_largest_activation_elements(cfg, H, W) * elem_bytes
+def _slices(per: int, batch: int, what: str) -> List[int]:
+    """batch sizes of the slices of a pass whose largest activation is ``per`` bytes per image: as few as possible, each
+    below MAX_TENSOR_BYTES in every activation"""
     if per >= MAX_TENSOR_BYTES:
-        raise ValueError(f"encode: one {H}x{W} image needs a {per} B activation, above the verified {MAX_TENSOR_BYTES} B")
+        raise ValueError(f"{what} image needs a {per} B activation, above the verified {MAX_TENSOR_BYTES} B")
     n = max(1, MAX_TENSOR_BYTES // per)
     return [min(n, batch - s) for s in range(0, batch, n)]
 
 
-def vae_encoder_macs(cfg: VAEConfig, H: int, W: int) -> Tuple[int, int]:
-    """(MACs per image, attention MACs per image) of the encoder plus quant_conv on an H x W image: the layer table (conv_in
-    counted with its 3 real input channels; the two attention contractions are 2 (hw)^2 C)"""
+def slice_plan(cfg: VAEConfig, batch: int, h: int, w: int, elem_bytes: int = 2) -> List[int]:
+    """batch sizes of the decode slices"""
+    return _slices(largest_activation_elements(cfg, h, w) * elem_bytes, batch, f"decode: one {8 * h}x{8 * w}")
+
+
+def encoder_slice_plan(cfg: VAEConfig, batch: int, H: int, W: int, elem_bytes: int = 2) -> List[int]:
+    """batch sizes of the encode slices"""
+    return _slices(encoder_largest_activation_elements(cfg, H, W) * elem_bytes, batch, f"encode: one {H}x{W}")
+
+
+def _vae_macs(cfg: VAEConfig, H: int, W: int, encoder: bool) -> Tuple[int, int]:
+    """the layer table of one half at H x W (the decoder's latent, the encoder's image): one MAC = one multiply-add; the
+    two attention contractions are 2 (hw)^2 C"""
     macs = 0
-    ch = list(cfg.block_out_channels)
+    ch = list(cfg.block_out_channels) if encoder else list(reversed(cfg.block_out_channels))
+    lc = cfg.latent_channels
 
     def conv(ci, co, k):
         nonlocal macs
@@ -169,26 +128,51 @@ def vae_encoder_macs(cfg: VAEConfig, H: int, W: int) -> Tuple[int, int]:
         conv(co, co, 3)
         if ci != co:
             conv(ci, co, 1)
-    conv(cfg.in_channels, ch[0], 3)
-    prev = ch[0]
-    for i, c in enumerate(ch):
-        for j in range(cfg.layers_per_block):
-            res(prev if j == 0 else c, c)
-        prev = c
-        if i < len(ch) - 1:
-            H, W = H // 2, W // 2               # Downsample2D: pad (0, 1, 0, 1), 3x3 stride 2 -> H / 2 for even H
-            conv(c, c, 3)
-    c = ch[-1]
-    res(c, c)
-    for _ in range(4):
-        conv(c, c, 1)
-    attn = 2 * (H * W) ** 2 * c
-    macs += attn
-    res(c, c)
-    z2 = 2 * cfg.latent_channels
-    conv(c, z2, 3)
-    conv(z2, z2, 1)
+
+    def mid(c):
+        nonlocal macs
+        res(c, c)
+        for _ in range(4):
+            conv(c, c, 1)
+        attn = 2 * (H * W) ** 2 * c
+        macs += attn
+        res(c, c)
+        return attn
+
+    def levels(layers):
+        nonlocal H, W
+        prev = ch[0]
+        for i, c in enumerate(ch):
+            for j in range(layers):
+                res(prev if j == 0 else c, c)
+            prev = c
+            if i < len(ch) - 1:               # Downsample2D: pad (0, 1, 0, 1), 3x3 stride 2 -> H / 2 for even H
+                H, W = (H // 2, W // 2) if encoder else (2 * H, 2 * W)
+                conv(c, c, 3)
+    if encoder:
+        conv(cfg.in_channels, ch[0], 3)
+        levels(cfg.layers_per_block)
+        attn = mid(ch[-1])
+        conv(ch[-1], 2 * lc, 3)
+        conv(2 * lc, 2 * lc, 1)
+    else:
+        conv(lc, lc, 1)
+        conv(lc, ch[0], 3)
+        attn = mid(ch[0])
+        levels(cfg.layers_per_block + 1)
+        conv(ch[-1], cfg.out_channels, 3)
     return macs, attn
+
+
+def vae_decoder_macs(cfg: VAEConfig, h: int, w: int) -> Tuple[int, int]:
+    """(MACs per image, attention MACs per image) of the decoder at an h x w latent"""
+    return _vae_macs(cfg, h, w, False)
+
+
+def vae_encoder_macs(cfg: VAEConfig, H: int, W: int) -> Tuple[int, int]:
+    """(MACs per image, attention MACs per image) of the encoder plus quant_conv on an H x W image (conv_in counted with
+    its 3 real input channels)"""
+    return _vae_macs(cfg, H, W, True)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -349,37 +333,6 @@ class AutoencoderKLOutput:
     latent_dist: DiagonalGaussianDistribution
 
 
-# ----------------------------------------------------------------------------------------------------------------
-# safetensors (the format is an 8-byte little-endian header length, a JSON header, then the raw tensor bytes)
-# ----------------------------------------------------------------------------------------------------------------
-_ST_DTYPES = {"F32": (np.float32, torch.float32), "F16": (np.float16, torch.float16), "F64": (np.float64, torch.float64)}
-
-
-def read_safetensors(path: str, skip=None) -> Dict[str, torch.Tensor]:
-    """every tensor of a safetensors file as fp32; names for which skip(name) is true are not read"""
-    with open(path, "rb") as f:
-        raw = f.read()
-    (n,) = struct.unpack("<Q", raw[:8])
-    header = json.loads(raw[8:8 + n].decode("utf-8"))
-    base = 8 + n
-    out = {}
-    for name, info in header.items():
-        if name == "__metadata__" or (skip is not None and skip(name)):
-            continue
-        b0, b1 = info["data_offsets"]
-        dt = info["dtype"]
-        if dt == "BF16":
-            a = np.frombuffer(raw, dtype=np.uint16, count=(b1 - b0) // 2, offset=base + b0).astype(np.uint32) << 16
-            t = torch.from_numpy(a.view(np.float32).copy())
-        elif dt in _ST_DTYPES:
-            npd, _ = _ST_DTYPES[dt]
-            t = torch.from_numpy(np.frombuffer(raw, dtype=npd, count=(b1 - b0) // np.dtype(npd).itemsize, offset=base + b0).copy())
-        else:
-            raise ValueError(f"{path}: tensor {name} has unsupported dtype {dt}")
-        out[name] = t.reshape(info["shape"]).float()
-    return out
-
-
 _DEPRECATED_ATTN = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
 
 
@@ -389,6 +342,69 @@ def _rename_deprecated(name: str) -> str:
     if mod in _DEPRECATED_ATTN and ".attentions." in name:
         return f"{mod_path}.{_DEPRECATED_ATTN[mod]}.{leaf}"
     return name
+
+
+def _flatten_1x1(name: str, t: torch.Tensor) -> torch.Tensor:
+    """attention weights some checkpoints keep as 1x1 convolutions -> linear weights"""
+    if ".attentions." in name and name.endswith("weight") and t.dim() == 4 and t.shape[2:] == (1, 1):
+        return t[:, :, 0, 0]
+    return t
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# packed weights of the layers both halves are made of
+# ----------------------------------------------------------------------------------------------------------------
+def _f32(t: torch.Tensor, dev) -> torch.Tensor:
+    return t.detach().float().to(dev).contiguous()
+
+
+def _pack_conv(m, dev) -> ops.PackedWeight:
+    return ops.pack_weight(m.weight.detach(), m.bias.detach(), device=dev)
+
+
+def _pack_gn(m, dev):
+    return _f32(m.weight, dev), _f32(m.bias, dev)
+
+
+def _pack_res(r, dev) -> dict:
+    e = {"g1": _pack_gn(r.norm1, dev), "g2": _pack_gn(r.norm2, dev), "w1": _pack_conv(r.conv1, dev)}
+    w2 = _pack_conv(r.conv2, dev)
+    if r.conv_shortcut is not None:
+        w2 = ops.pack_weight_cat(w2, r.conv_shortcut.weight.detach(), r.conv_shortcut.bias.detach())
+    e["w2"], e["shortcut"] = w2, r.conv_shortcut is not None
+    return e
+
+
+def _pack_mid(mid, dev) -> dict:
+    """the mid-block's entries of a plan: resnet, attention (q|k|v as one linear), resnet"""
+    a = mid.attentions[0]
+    wqkv = torch.cat([a.to_q.weight, a.to_k.weight, a.to_v.weight], 0).detach()
+    bqkv = torch.cat([a.to_q.bias, a.to_k.bias, a.to_v.bias], 0).detach()
+    return {"mid0": _pack_res(mid.resnets[0], dev),
+            "attn": {"g": _pack_gn(a.group_norm, dev), "qkv": ops.pack_weight(wqkv, bqkv, device=dev),
+                     "out": _pack_conv(a.to_out[0], dev)},
+            "mid1": _pack_res(mid.resnets[1], dev)}
+
+
+def _act_bytes() -> int:
+    return torch.tensor([], dtype=ops.ACT_DTYPE).element_size()
+
+
+def _sliced(domain: str, sizes: List[int], one):
+    """one(b0, b1) for every batch slice, under the scratch domain ``domain``"""
+    with ops.scratch_domain(domain):
+        b0 = 0
+        for n in sizes:
+            one(b0, b0 + n)
+            b0 += n
+
+
+def _nhwc_padded(x: torch.Tensor, cin: int) -> torch.Tensor:
+    """NCHW [B, C, H, W] -> ops.ACT_DTYPE NHWC [B, H, W, cin] with zero padding channels"""
+    B, C, H, W = x.shape
+    y = torch.zeros(B, H, W, cin, dtype=ops.ACT_DTYPE, device=x.device)
+    y[..., :C] = x.permute(0, 2, 3, 1)
+    return y
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -415,10 +431,8 @@ class AutoencoderKL(nn.Module):
         # encoder.conv_in as a 1x1 contraction over ops.image_in's im2col columns (False: a 3x3 convolution over the image
         # zero padded to 8 channels -- the A/B form of tools/bench_vae_encode.py)
         self.conv_in_im2col = True
-        self._plan = None
-        self._plan_key = None
-        self._eplan = None
-        self._eplan_key = None
+        # both halves' plans; 2 dtypes x (decoder + 2 conv_in forms of the encoder) fit unpinned
+        self._plans = _PlanCache(cap=8)
 
     # ---- weights ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -445,67 +459,24 @@ class AutoencoderKL(nn.Module):
         """Load diffusers VAE weights: ``encoder.*`` / ``quant_conv.*`` are ignored, the deprecated attention names
         (query / key / value / proj_attn) are accepted, 1x1-conv-shaped attention weights are flattened.  Missing or
         mis-shaped keys raise."""
-        own = self.state_dict()
-        got = {}
-        for name, t in sd.items():
-            if name.startswith("encoder.") or name.startswith("quant_conv."):
-                continue
-            name = _rename_deprecated(name)
-            if name not in own:
-                raise KeyError(f"AutoencoderKL: unexpected key {name}")
-            if ".attentions." in name and name.endswith("weight") and t.dim() == 4 and t.shape[2:] == (1, 1):
-                t = t[:, :, 0, 0]
-            if tuple(t.shape) != tuple(own[name].shape):
-                raise ValueError(f"AutoencoderKL: {name} has shape {tuple(t.shape)}, expected {tuple(own[name].shape)}")
-            got[name] = t
-        missing = sorted(set(own) - set(got))
-        if missing:
-            raise KeyError(f"AutoencoderKL: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
-        self.load_state_dict(got)
-        self.invalidate()
-        return self
+        return load_strict(self, sd, _rename_deprecated, lambda n: n.startswith(("encoder.", "quant_conv.")), _flatten_1x1)
 
     def load_vae_state_dict(self, sd: Dict[str, torch.Tensor]):
         """Load a whole diffusers VAE state dict (encoder, quant_conv, post_quant_conv, decoder) strictly: every key of this
         module must be present with its shape and no other key may be; the deprecated attention names (query / key / value /
         proj_attn) are accepted in both mid-blocks, 1x1-conv-shaped attention weights are flattened."""
-        own = self.state_dict()
-        got = {}
-        for name, t in sd.items():
-            name = _rename_deprecated(name)
-            if name not in own:
-                raise KeyError(f"AutoencoderKL: unexpected key {name}")
-            if ".attentions." in name and name.endswith("weight") and t.dim() == 4 and t.shape[2:] == (1, 1):
-                t = t[:, :, 0, 0]
-            if tuple(t.shape) != tuple(own[name].shape):
-                raise ValueError(f"AutoencoderKL: {name} has shape {tuple(t.shape)}, expected {tuple(own[name].shape)}")
-            got[name] = t
-        missing = sorted(set(own) - set(got))
-        if missing:
-            raise KeyError(f"AutoencoderKL: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
-        self.load_state_dict(got)
-        self.invalidate()
-        return self
+        return load_strict(self, sd, _rename_deprecated, fixup=_flatten_1x1)
 
     @classmethod
     def from_pretrained(cls, root: str, subfolder: Optional[str] = "vae", with_encoder: bool = False) -> "AutoencoderKL":
         """Read ``config.json`` and ``diffusion_pytorch_model.safetensors`` of a diffusers VAE folder (with_encoder: the
         encoder and quant_conv too, strictly)."""
-        d = os.path.join(root, subfolder) if subfolder else root
-        with open(os.path.join(d, "config.json")) as f:
-            cfg = VAEConfig.from_dict(json.load(f))
-        sd = read_safetensors(os.path.join(d, "diffusion_pytorch_model.safetensors"))
-        if with_encoder:
-            return cls(cfg, with_encoder=True).load_vae_state_dict(sd)
-        m = cls(cfg)
-        m.load_decoder_state_dict(sd)
-        return m
+        cfg, sd = read_pretrained(VAEConfig, root, subfolder, "diffusion_pytorch_model.safetensors")
+        m = cls(cfg, with_encoder=with_encoder)
+        return m.load_vae_state_dict(sd) if with_encoder else m.load_decoder_state_dict(sd)
 
     def invalidate(self):
-        self._plan = None
-        self._plan_key = None
-        self._eplan = None
-        self._eplan_key = None
+        self._plans.clear()
         self.__dict__.pop("_vparams", None)
 
     def _apply(self, fn, *a, **k):
@@ -514,89 +485,39 @@ class AutoencoderKL(nn.Module):
 
     # ---- packed weights ---------------------------------------------------------------------------------------------
     def plan(self, device) -> dict:
-        key = (str(device), ops.ACT_DTYPE, _versions(self))
-        if self._plan is not None and self._plan_key == key:
-            return self._plan
-        dev = device
-        f32 = lambda t: t.detach().float().to(dev).contiguous()      # noqa: E731
-
-        def conv(m):
-            return ops.pack_weight(m.weight.detach(), m.bias.detach(), device=dev)
-
-        def gn(m):
-            return f32(m.weight), f32(m.bias)
-
-        def res(r):
-            e = {"g1": gn(r.norm1), "g2": gn(r.norm2), "w1": conv(r.conv1)}
-            w2 = conv(r.conv2)
-            if r.conv_shortcut is not None:
-                w2 = ops.pack_weight_cat(w2, r.conv_shortcut.weight.detach(), r.conv_shortcut.bias.detach())
-            e["w2"], e["shortcut"] = w2, r.conv_shortcut is not None
-            return e
-        dec = self.decoder
-        a = dec.mid_block.attentions[0]
-        wqkv = torch.cat([a.to_q.weight, a.to_k.weight, a.to_v.weight], 0).detach()
-        bqkv = torch.cat([a.to_q.bias, a.to_k.bias, a.to_v.bias], 0).detach()
-        pl = {
-            "pq": conv(self.post_quant_conv),
-            "conv_in": conv(dec.conv_in),
-            "mid0": res(dec.mid_block.resnets[0]),
-            "attn": {"g": gn(a.group_norm), "qkv": ops.pack_weight(wqkv, bqkv, device=dev),
-                     "out": ops.pack_weight(a.to_out[0].weight.detach(), a.to_out[0].bias.detach(), device=dev)},
-            "mid1": res(dec.mid_block.resnets[1]),
-            "up": [{"res": [res(r) for r in blk.resnets],
-                    "ups": conv(blk.upsamplers[0].conv) if blk.upsamplers is not None else None} for blk in dec.up_blocks],
-            "gn_out": gn(dec.conv_norm_out),
-            "conv_out": conv(dec.conv_out),
-        }
-        self._plan, self._plan_key = pl, key
-        return pl
+        """packed decoder weights, cached per (device, ops.ACT_DTYPE) in the _PlanCache"""
+        def make():
+            dec, dev = self.decoder, device
+            return {"pq": _pack_conv(self.post_quant_conv, dev),
+                    "conv_in": _pack_conv(dec.conv_in, dev),
+                    **_pack_mid(dec.mid_block, dev),
+                    "up": [{"res": [_pack_res(r, dev) for r in blk.resnets],
+                            "ups": _pack_conv(blk.upsamplers[0].conv, dev) if blk.upsamplers is not None else None}
+                           for blk in dec.up_blocks],
+                    "gn_out": _pack_gn(dec.conv_norm_out, dev),
+                    "conv_out": _pack_conv(dec.conv_out, dev)}
+        return self._plans.lookup(("decoder", str(device), ops.ACT_DTYPE), _versions(self), make)
 
     def encoder_plan(self, device) -> dict:
-        """packed encoder weights (cached like plan())"""
+        """packed encoder weights (cached like plan(), per conv_in form too)"""
         if not self.with_encoder:
             raise NotImplementedError("AutoencoderKL.encode: this instance holds the decoder only "
                                       "(AutoencoderKL(with_encoder=True) / from_pretrained(..., with_encoder=True))")
-        key = (str(device), ops.ACT_DTYPE, self.conv_in_im2col, _versions(self))
-        if self._eplan is not None and self._eplan_key == key:
-            return self._eplan
-        dev = device
-        f32 = lambda t: t.detach().float().to(dev).contiguous()      # noqa: E731
 
-        def conv(m):
-            return ops.pack_weight(m.weight.detach(), m.bias.detach(), device=dev)
-
-        def gn(m):
-            return f32(m.weight), f32(m.bias)
-
-        def res(r):
-            e = {"g1": gn(r.norm1), "g2": gn(r.norm2), "w1": conv(r.conv1)}
-            w2 = conv(r.conv2)
-            if r.conv_shortcut is not None:
-                w2 = ops.pack_weight_cat(w2, r.conv_shortcut.weight.detach(), r.conv_shortcut.bias.detach())
-            e["w2"], e["shortcut"] = w2, r.conv_shortcut is not None
-            return e
-        enc = self.encoder
-        a = enc.mid_block.attentions[0]
-        wqkv = torch.cat([a.to_q.weight, a.to_k.weight, a.to_v.weight], 0).detach()
-        bqkv = torch.cat([a.to_q.bias, a.to_k.bias, a.to_v.bias], 0).detach()
-        ci = enc.conv_in
-        pl = {
-            "conv_in": (ops.pack_conv_in_im2col(ci.weight, ci.bias, device=dev) if self.conv_in_im2col else conv(ci)),
-            "down": [{"res": [res(r) for r in blk.resnets],
-                      "down": conv(blk.downsamplers[0].conv) if blk.downsamplers is not None else None}
-                     for blk in enc.down_blocks],
-            "mid0": res(enc.mid_block.resnets[0]),
-            "attn": {"g": gn(a.group_norm), "qkv": ops.pack_weight(wqkv, bqkv, device=dev),
-                     "out": ops.pack_weight(a.to_out[0].weight.detach(), a.to_out[0].bias.detach(), device=dev)},
-            "mid1": res(enc.mid_block.resnets[1]),
-            "gn_out": gn(enc.conv_norm_out),
-            "conv_out": conv(enc.conv_out),
-            "wq": f32(self.quant_conv.weight[:, :, 0, 0]),
-            "bq": f32(self.quant_conv.bias),
-        }
-        self._eplan, self._eplan_key = pl, key
-        return pl
+        def make():
+            enc, dev = self.encoder, device
+            ci = enc.conv_in
+            return {"conv_in": (ops.pack_conv_in_im2col(ci.weight, ci.bias, device=dev) if self.conv_in_im2col
+                                else _pack_conv(ci, dev)),
+                    "down": [{"res": [_pack_res(r, dev) for r in blk.resnets],
+                              "down": _pack_conv(blk.downsamplers[0].conv, dev) if blk.downsamplers is not None else None}
+                             for blk in enc.down_blocks],
+                    **_pack_mid(enc.mid_block, dev),
+                    "gn_out": _pack_gn(enc.conv_norm_out, dev),
+                    "conv_out": _pack_conv(enc.conv_out, dev),
+                    "wq": _f32(self.quant_conv.weight[:, :, 0, 0], dev),
+                    "bq": _f32(self.quant_conv.bias, dev)}
+        return self._plans.lookup(("encoder", str(device), ops.ACT_DTYPE, self.conv_in_im2col), _versions(self), make)
 
     # ---- forward ----------------------------------------------------------------------------------------------------
     def _resnet(self, x, e):
@@ -619,9 +540,7 @@ class AutoencoderKL(nn.Module):
     def _decode_nhwc(self, z: torch.Tensor) -> torch.Tensor:
         """z [B, 4, h, w] -> conv_out's fp32 [B, 8h, 8w, 8] (3 real channels)"""
         pl = self.plan(z.device)
-        B, C, h, w = z.shape
-        x = torch.zeros(B, h, w, pl["pq"].Cin, dtype=ops.ACT_DTYPE, device=z.device)
-        x[..., :C] = z.permute(0, 2, 3, 1)                                       # the 4-channel layout change
+        x = _nhwc_padded(z, pl["pq"].Cin)                                         # the 4-channel layout change
         x = ops.conv_gemm(x, pl["pq"], pad=0)                                     # post_quant_conv (bias: not folded
         x = ops.conv_gemm(x, pl["conv_in"], colstats=True)                        #  across conv_in's zero border)
         x = self._resnet(x, pl["mid0"])
@@ -642,10 +561,7 @@ class AutoencoderKL(nn.Module):
         if self.conv_in_im2col:
             h = ops.conv_gemm(ops.image_in(x, out_f32=f32), pl["conv_in"], pad=0, colstats=True)   # conv_in: 1x1 over the im2col
         else:
-            B, C, H, W = x.shape
-            xp = torch.zeros(B, H, W, pl["conv_in"].Cin, dtype=ops.ACT_DTYPE, device=x.device)
-            xp[..., :C] = x.permute(0, 2, 3, 1)
-            h = ops.conv_gemm(xp, pl["conv_in"], colstats=True)
+            h = ops.conv_gemm(_nhwc_padded(x, pl["conv_in"].Cin), pl["conv_in"], colstats=True)
         for blk in pl["down"]:
             for e in blk["res"]:
                 h = self._resnet(h, e)
@@ -683,16 +599,13 @@ class AutoencoderKL(nn.Module):
                 raise ValueError(f"AutoencoderKL.encode: eps shape {tuple(eps.shape)} != {(B, z2 // 2, h, w)}")
             eps = eps.to(device=x.device, dtype=torch.float32).contiguous()
             lat = torch.empty(B, z2 // 2, h, w, dtype=latents_dtype, device=x.device)
-        esz = torch.tensor([], dtype=ops.ACT_DTYPE).element_size()
-        with ops.scratch_domain("vae_encoder"):          # never shares a GroupNorm arena with a captured decode
-            b0 = 0
-            for n in encoder_slice_plan(self.config, B, H, W, esz):
-                y = self._encode_nhwc(x[b0:b0 + n], pl)
-                ops.latent_dist(y, pl["wq"], pl["bq"], eps=None if eps is None else eps[b0:b0 + n], scale=scale,
-                                moments=moments, latents_dtype=latents_dtype,
-                                moments_out=None if mom is None else mom[b0:b0 + n],
-                                latents_out=None if lat is None else lat[b0:b0 + n])
-                b0 += n
+
+        def one(b0, b1):
+            ops.latent_dist(self._encode_nhwc(x[b0:b1], pl), pl["wq"], pl["bq"], eps=None if eps is None else eps[b0:b1],
+                            scale=scale, moments=moments, latents_dtype=latents_dtype,
+                            moments_out=None if mom is None else mom[b0:b1], latents_out=None if lat is None else lat[b0:b1])
+        # its own scratch domain: never shares a GroupNorm arena with a captured decode
+        _sliced("vae_encoder", encoder_slice_plan(self.config, B, H, W, _act_bytes()), one)
         return mom, lat
 
     def encode(self, x: torch.Tensor, return_dict: bool = True):
@@ -722,12 +635,7 @@ class AutoencoderKL(nn.Module):
         """decode slice by slice (slice_plan); finish(y_slice, b0, b1) writes the slice's result"""
         self._check_latents(z)
         B, _, h, w = z.shape
-        esz = torch.tensor([], dtype=ops.ACT_DTYPE).element_size()
-        with ops.scratch_domain("vae"):
-            b0 = 0
-            for n in slice_plan(self.config, B, h, w, esz):
-                finish(self._decode_nhwc(z[b0:b0 + n]), b0, b0 + n)
-                b0 += n
+        _sliced("vae", slice_plan(self.config, B, h, w, _act_bytes()), lambda b0, b1: finish(self._decode_nhwc(z[b0:b1]), b0, b1))
 
     def decode(self, z: torch.Tensor, return_dict: bool = True):
         """diffusers AutoencoderKL.decode: z = latents / scaling_factor -> DecoderOutput(sample fp32 [B, 3, 8h, 8w])"""

@@ -232,6 +232,62 @@ def test_plan_cache_pins_plans_seen_during_capture_and_drops_stale_ones(monkeypa
     assert len(c) == 0 and not c.parked
 
 
+def _captured_plan_outlives_updates(monkeypatch, mod, lookup, param):
+    """a plan looked up "during capture" stays referenced by ``mod._plans`` (served or parked) through a lookup under the
+    other ops.ACT_DTYPE and through an in-place weight update: a captured graph holds raw pointers to its packs.  Before
+    these caches were _PlanCaches, AutoencoderKL's single slot per half and CLIPTextModel's dict released such a plan."""
+    from diffusion_pruning_amd import ops, unet as U
+    capturing = {"on": True}
+    monkeypatch.setattr(U, "_capturing", lambda: capturing["on"])
+    held = lambda: [id(e[1]) for e in mod._plans.entries.values()] + [id(q) for q in mod._plans.parked]      # noqa: E731
+    pl = lookup()
+    capturing["on"] = False
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "ACT_DTYPE", torch.float32)
+        lookup()
+        assert id(pl) in held()
+    assert lookup() is pl                           # still the plan of its own key
+    with torch.no_grad():
+        param.mul_(1.0)                             # bumps the version counter
+    assert lookup() is not pl and id(pl) in held()  # stale: never served again, but not released
+    mod.invalidate()
+    assert id(pl) not in held() and len(mod._plans) == 0
+
+
+@pytest.mark.parametrize("half", ["decoder", "encoder"])
+def test_vae_plan_seen_during_capture_outlives_dtype_switch_and_weight_update(monkeypatch, half):
+    from diffusion_pruning_amd.vae import AutoencoderKL, VAEConfig
+    vae = AutoencoderKL(VAEConfig(block_out_channels=(32, 64), layers_per_block=1), with_encoder=True).init_synthetic(0)
+    cpu = torch.device("cpu")
+    if half == "decoder":
+        _captured_plan_outlives_updates(monkeypatch, vae, lambda: vae.plan(cpu), vae.decoder.conv_in.weight)
+    else:
+        _captured_plan_outlives_updates(monkeypatch, vae, lambda: vae.encoder_plan(cpu), vae.encoder.conv_in.weight)
+
+
+@pytest.mark.parametrize("fold", [True, False])
+def test_text_encoder_plan_seen_during_capture_outlives_dtype_switch_and_weight_update(monkeypatch, fold):
+    from diffusion_pruning_amd.text_encoder import CLIPTextModel
+    te = CLIPTextModel(vocab_size=256, hidden_size=128, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2,
+                       max_position_embeddings=77).init_synthetic(0)
+    _captured_plan_outlives_updates(monkeypatch, te, lambda: te.plan(torch.device("cpu"), fold),
+                                    te.text_model.final_layer_norm.weight)
+    # and a plan of the other form does not displace it: 2 dtypes x 2 forms fit unpinned
+    pl = te.plan(torch.device("cpu"), fold)
+    te.plan(torch.device("cpu"), not fold)
+    assert te.plan(torch.device("cpu"), fold) is pl
+
+
+@pytest.mark.parametrize("cls", ["Downsample2D", "Upsample2D"])
+def test_resample_plan_seen_during_capture_outlives_dtype_switch_and_weight_update(monkeypatch, cls):
+    from diffusion_pruning_amd import unet as U
+    m = getattr(U, cls)(32)
+    with torch.no_grad():
+        m.conv.weight.normal_()
+        m.conv.bias.zero_()
+    _captured_plan_outlives_updates(monkeypatch, m, lambda: m.plan(torch.device("cpu")), m.conv.weight)
+
+
 def test_resnet_plan_follows_in_place_parameter_updates(tiny):
     """a fine-tuning loop that never calls invalidate_plans() must still compute with the current weights"""
     cfg, model, params = tiny

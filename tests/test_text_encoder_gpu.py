@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.clip_text_oracle import clip_text_forward
+from tests.helpers import rel_l2
 from tests.margins import check
 
 pytestmark = pytest.mark.gpu
@@ -17,11 +18,6 @@ LIN_BF16_TOL = 4e-3
 LIN_F32_TOL = 1e-5
 ENC_BF16_TOL = 2e-2
 ENC_F32_TOL = 1e-4
-
-
-def rel_l2(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,6 @@ the configuration, strict loading, rejected arguments, the pipeline's argument c
 import ctypes
 import json
 import os
-import struct
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 from diffusion_pruning_amd.pipeline import PruningDenoiseLoop
 from diffusion_pruning_amd.text_encoder import CLIPTextConfig, CLIPTextModel, CLIPTextModelOutput, text_encoder_flops
 from tests.clip_text_oracle import clip_text_forward
+from tests.helpers import write_safetensors
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_text_tiny.npz")
 TINY = dict(vocab_size=256, hidden_size=128, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2,
@@ -95,25 +95,11 @@ def test_output_indexing_follows_transformers():
     assert o[0] is h and o[1] is p and o["pooler_output"] is p and o.to_tuple() == (h, p)
 
 
-def _write_safetensors(path, tensors):
-    header, blobs, off = {}, [], 0
-    for name, t in tensors.items():
-        a = t.detach().cpu().contiguous().numpy()
-        dt = {np.dtype(np.float32): "F32", np.dtype(np.int64): "I64"}[a.dtype]
-        b = a.tobytes()
-        header[name] = {"dtype": dt, "shape": list(a.shape), "data_offsets": [off, off + len(b)]}
-        blobs.append(b)
-        off += len(b)
-    h = json.dumps(header).encode()
-    with open(path, "wb") as f:
-        f.write(struct.pack("<Q", len(h)) + h + b"".join(blobs))
-
-
 def _folder(tmp_path, sd):
     d = tmp_path / "text_encoder"
     d.mkdir()
     (d / "config.json").write_text(json.dumps({**TINY, "hidden_act": "gelu", "eos_token_id": 2, "model_type": "clip_text_model"}))
-    _write_safetensors(str(d / "model.safetensors"), sd)
+    write_safetensors(str(d / "model.safetensors"), sd)
     return str(tmp_path)
 
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from tests import vae_oracle as V
+from tests.helpers import rel_l2
 from tests.margins import check
 
 pytestmark = pytest.mark.gpu
@@ -14,11 +15,6 @@ ATTN_BF16_TOL = 4e-3
 ATTN_F32_TOL = 1e-5
 DEC_BF16_TOL = 2e-2
 DEC_F32_TOL = 1e-4
-
-
-def rel_l2(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 def _qkv(B, L, dtype, dev, seed):

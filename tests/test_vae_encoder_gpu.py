@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import vae_encoder_oracle as E
+from tests.helpers import rel_l2
 from tests.margins import check
 
 pytestmark = pytest.mark.gpu
@@ -16,11 +17,6 @@ CONV_BF16_TOL = 4e-3
 CONV_F32_TOL = 1e-5
 ENC_BF16_TOL = 2e-2
 ENC_F32_TOL = 1e-4
-
-
-def rel_l2(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).norm() / (b.norm() + 1e-30))
 
 
 def max_ulps(a, b, mag=None):

@@ -13,7 +13,7 @@ import torch
 
 from tests import vae_encoder_oracle as E
 from tests import vae_oracle as V
-from tests.test_vae_host import _write_safetensors
+from tests.helpers import write_safetensors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "aptp_hip.h")
@@ -52,7 +52,7 @@ def _vae_dir(tmp_path, disk):
     (d / "config.json").write_text(json.dumps({"_class_name": "AutoencoderKL", "block_out_channels": [128, 256, 512, 512],
                                                "latent_channels": 4, "layers_per_block": 2, "norm_num_groups": 32,
                                                "scaling_factor": 0.18215, "sample_size": 768}))
-    _write_safetensors(str(d / "diffusion_pytorch_model.safetensors"), disk)
+    write_safetensors(str(d / "diffusion_pytorch_model.safetensors"), disk)
     return str(tmp_path)
 
 

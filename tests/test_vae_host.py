@@ -3,15 +3,14 @@ loader, the oracle, the slicing plan, the new ABI structs and the pipeline's def
 import ctypes
 import json
 import os
-import struct
 import subprocess
 import tempfile
 
-import numpy as np
 import pytest
 import torch
 
 from tests import vae_oracle as V
+from tests.helpers import write_safetensors
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "aptp_hip.h")
@@ -52,18 +51,6 @@ def test_flop_table_equals_hook_count_of_the_oracle(h, w):
         assert macs == 1_257_259_466_752
 
 
-def _write_safetensors(path, tensors):
-    header, blobs, off = {}, [], 0
-    for name, t in tensors.items():
-        b = t.detach().float().contiguous().numpy().astype(np.float32).tobytes()
-        header[name] = {"dtype": "F32", "shape": list(t.shape), "data_offsets": [off, off + len(b)]}
-        blobs.append(b)
-        off += len(b)
-    hb = json.dumps(header).encode()
-    with open(path, "wb") as f:
-        f.write(struct.pack("<Q", len(hb)) + hb + b"".join(blobs))
-
-
 def _small_sd(seed=0):
     g = torch.Generator().manual_seed(seed)
     ref = V.DecoderOracle().state_dict()
@@ -87,7 +74,7 @@ def test_loader_reads_both_attention_namings_and_ignores_the_encoder(naming, tmp
     (d / "config.json").write_text(json.dumps({"_class_name": "AutoencoderKL", "block_out_channels": [128, 256, 512, 512],
                                                "latent_channels": 4, "layers_per_block": 2, "norm_num_groups": 32,
                                                "scaling_factor": 0.18215, "sample_size": 768}))
-    _write_safetensors(str(d / "diffusion_pytorch_model.safetensors"), disk)
+    write_safetensors(str(d / "diffusion_pytorch_model.safetensors"), disk)
     m = AutoencoderKL.from_pretrained(str(tmp_path), subfolder="vae")
     got = m.state_dict()
     for k, v in sd.items():
