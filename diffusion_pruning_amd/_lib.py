@@ -18,6 +18,12 @@ ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU = 0, 1, 2, 3
 TILE_AUTO, TILE_128x128, TILE_128x160, TILE_64x128, TILE_64x160, TILE_128x64, TILE_64x64 = range(7)
 (TILE_DMA_128x128, TILE_DMA_128x160, TILE_DMA_64x128, TILE_DMA_64x160, TILE_DMA_128x64, TILE_DMA_64x64) = range(7, 13)
 (TILE_DMA3_128x128, TILE_DMA3_128x160, TILE_DMA3_64x128, TILE_DMA3_64x160, TILE_DMA3_128x64, TILE_DMA3_64x64) = range(13, 19)
+# (past 18 only the ids host code names: launch_policy.py's lean set, the halo-in-LDS pair, the stream-K tiles it picks)
+TILE_DMA4_64x128, TILE_DMA4_64x64, TILE_DMA4_128x64 = 24, 25, 26
+TILE_HALO_128x160, TILE_HALO_128x128 = 43, 44
+(TILE_DMA6_64x64, TILE_DMA8S_64x64, TILE_DMA6_64x128, TILE_DMA6_128x64, TILE_KU2S4_64x64, TILE_KU2S6_64x64, TILE_KU2S4_64x128,
+ TILE_KU2S6_64x128, TILE_KU2S4_128x64) = range(45, 54)
+TILE_SK_256x160, TILE_SK_256x128 = 64, 65
 
 
 class ConvGemmParams(Structure):

@@ -21,8 +21,12 @@ from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F40
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
+# The tuning table and the rules that pick a launch's tile / split-K depth / order live in launch_policy.py (pure host logic).
+# The names are re-exported for readers (tests, bench.py, tools); TUNING is the very dict the lookup reads.  Change the table
+# through set_tuning / set_entry, and the policy's switches on the launch_policy module itself.
+from .launch_policy import (BK, SK_AUTO, SK_TILE_FIRST, TUNING, _HALO_TILES, choose_launch, key_of, parse_key,  # noqa: F401
+                            set_entry, set_tuning, splitk_in_kernel, tuning_key, tuning_lookup)
 
-BK = 64
 # Storage type of activations and packed weights.  The HIP kernels exist for bf16 only (MFMA operands); the test-only CPU
 # emulator (tests/hip_emulator.py) can switch both to fp32 to run the SAME host logic -- compaction, GroupNorm-beta
 # correction, gate plumbing, batched time / text projections, in-place skip-concats, depth lerp -- without any rounding and
@@ -201,87 +205,6 @@ def pack_weight_cat(pw: PackedWeight, w2: torch.Tensor, bias2: Optional[torch.Te
 _ws_cache = {}
 _ws_capture_keep = []      # see _workspace
 
-def tuning_key(M, N, Cin, taps, stride, ups, geglu, Cin2: int = 0) -> str:
-    return f"M{M}_N{N}_C{Cin}_T{taps}_s{stride}u{ups}g{int(bool(geglu))}" + (f"x{Cin2}" if Cin2 else "")
-
-
-def _load_tuning():
-    import json
-    import os
-    # (APTP_TUNING=<file> substitutes another table: A/B timing of tuning runs)
-    path = os.environ.get("APTP_TUNING") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuning_gfx950.json")
-    if os.path.exists(path):
-        with open(path) as f:
-            return json.load(f)
-    return {}
-
-
-# (tile, split_k) per GEMM shape measured on MI355X by tools/tune_convs.py.  The table holds the shapes of the headline
-# mask, the dense model and the pruning step; every OTHER architecture code (config 5's experts, real APTP experts with
-# irregular widths) produces shapes that are not in it.  Those take the entry of the NEAREST tuned shape of the same class
-# (taps, stride, upsampling, GEGLU, second operand) in log-space distance over (M, N, K) -- the tile engine's behaviour
-# changes smoothly with the extents, while the library heuristic only knows the generic non-DMA tiles (measured on a
-# 55 %-keep expert: 29 us per launch on conv_gemm_kernel<64,128> where the neighbours' DMA tiles take ~20).  Beyond
-# TUNING_MAX_DIST the heuristic (aptp_conv_gemm_suggest_split_k / pick_tile) decides.  APTP_TUNING_NEAREST=0 disables.
-TUNING = _load_tuning()
-TUNING_NEAREST = os.environ.get("APTP_TUNING_NEAREST", "1") != "0"
-TUNING_MAX_DIST = 2.0
-_HALO_TILES = (43, 44)
-_LEAN_TILES = (9, 11, 12, 15, 17, 18, 24, 25, 26, 45, 46, 47, 48, 49, 50, 51, 52, 53)     # tiles csrc/lin_gemm.hip instantiates (aptp_lin_eligible)
-LEAN_REMAP = os.environ.get("APTP_LEAN_REMAP", "1") != "0"
-SK_TILE_FIRST = 64          # APTP_TILE_SK_*: persistent stream-K macro-tiles (csrc/conv_gemm_sk.hip)
-SK_AUTO = os.environ.get("APTP_SK_AUTO", "1") == "1"
-SK_AUTO_MIN_OUTPUTS = 256 * 256 * 160
-_tuning_index = None
-_tuning_near_cache = {}
-
-
-def _tuning_classes():
-    global _tuning_index
-    if _tuning_index is None:
-        import re
-        idx = {}
-        pat = re.compile(r"M(\d+)_N(\d+)_C(\d+)_T(\d+)_s(\d+)u(\d+)g(\d+)(?:x(\d+))?$")
-        for k, v in TUNING.items():
-            m = pat.match(k)
-            if not m:
-                continue
-            M, N, C, T, s_, u, g, x2 = (int(t) if t else 0 for t in m.groups())
-            idx.setdefault((T, s_, u, g, x2 > 0), []).append((M, N, T * C + x2, v))
-        _tuning_index = idx
-    return _tuning_index
-
-
-def tuning_lookup(M, N, Cin, taps, stride, ups, geglu, Cin2: int = 0):
-    """exact table entry, else the nearest tuned shape of the same class (None when there is none close enough)"""
-    key = tuning_key(M, N, Cin, taps, stride, ups, geglu, Cin2)
-    hit = TUNING.get(key)
-    if hit is not None or not TUNING_NEAREST:
-        return hit
-    if key in _tuning_near_cache:
-        return _tuning_near_cache[key]
-    import math
-    K = taps * Cin + Cin2
-    best, bd = None, TUNING_MAX_DIST
-    for (M2, N2, K2, v) in _tuning_classes().get((taps, stride, ups, int(bool(geglu)), Cin2 > 0), ()):
-        if v["tile"] in _HALO_TILES and M2 != M:
-            continue                      # the halo-in-LDS tiles are tied to the map width
-        if v["tile"] > 6 and max(Cin, Cin2) > 4032:
-            continue                      # every tile past the six register-staged ones is an LDS-DMA tile: channel steps <= 4032 (csrc)
-        # (more rows than the tuned shape is the benign direction -- the same tile, more of them: a U-Net batch of 16 takes the
-        #  entries tuned at batch 4 instead of falling back to the register-staged heuristic tiles, which bench.py's infer_bs16 leg
-        #  measured at 0.08 of the MFMA peak on 48 launches)
-        dm = math.log2(M / M2)
-        d = (0.5 * dm if dm > 0 else -1.5 * dm) + abs(math.log2(N / N2)) + abs(math.log2(K / K2))
-        if d < bd:
-            best, bd = v, d
-    if best is not None:
-        nK = (K + BK - 1) // BK
-        best = dict(best)
-        best["split_k"] = max(1, min(int(best["split_k"]), nK // 4 if nK >= 8 else 1))
-    _tuning_near_cache[key] = best
-    return best
-
 # Optional launch recorder used by bench.py's roofline leg: when a list, every aptp_conv_gemm launch appends
 # {"params": ConvGemmParams, "flops": algorithmic FLOPs, "keep": tensors referenced by the params}.
 LAUNCH_LOG = None
@@ -292,7 +215,6 @@ ATTN_LAUNCH_LOG = None      # bench.py: the attention launches of ONE forward (r
 # Split-K launches combine their K-slices inside the kernel (AptpConvGemmParams.tile_counters) instead of launching
 # splitk_reduce_kernel; False restores the two-launch form (A/B timing, tests of both forms)
 SPLITK_IN_KERNEL = True
-SPLITK_FORCE_IN_KERNEL = os.environ.get("APTP_SPLITK_FORCE_INKERNEL", "0") == "1"
 _counters = {}
 _N_COUNTERS = 1 << 16
 
@@ -415,8 +337,6 @@ def _root(t: torch.Tensor) -> torch.Tensor:
 # inside a captured graph) and ustat_end() at the end; outside such a bracket nothing is emitted.  USTAT_UNIT = channels per unit:
 # it must divide every GroupNorm group size of the model (SD-2.1: 320 / 32 = 10); 0 = off.
 USTAT = os.environ.get("APTP_USTAT", "1") != "0"
-# a split-K launch whose output feeds a GroupNorm combines its slices in-kernel (and emits the statistics) up to this many slices
-COLS_SPLIT_MAX = int(os.environ.get("APTP_COLS_SPLIT_MAX", "2"))
 USTAT_NREP = int(os.environ.get("APTP_USTAT_NREP", "8"))
 _USTAT_WORDS = 1 << 17            # int64 words per arena (1 MiB): ~35 producers x 8 replicas x 4 samples x <= 128 units x 2
 _ustat_arenas = {}
@@ -642,8 +562,6 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
         p.depth, p.depth_B = depth.data_ptr(), depth.shape[0]
         p.depth_in, p.lddin = depth_in.data_ptr(), _ld(depth_in)
     p.y, p.ldy, p.out_f32 = out.data_ptr(), _ld(out), int(out_f32)
-    p.tile = tile
-    p.order = order
     p.epilogue = EPILOGUE
     p.io_f32 = int(f32)
     if f32:
@@ -658,74 +576,26 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
             prefetch = plan.step(pw.w)
     if prefetch is not None:
         p.prefetch, p.prefetch_bytes = prefetch.data_ptr(), prefetch.numel() * prefetch.element_size()
+    # a plain linear layer the lean kernel can take (csrc/lin_gemm.hip, aptp_lin_eligible)
+    plain_linear = pw.KH == 1 and pw.KW == 1 and stride == 1 and not ups and x2 is None and colgate is None and corr is None \
+        and rowbias is None and depth is None and not out_f32 and gn is None and (act != ACT_GEGLU or (residual is None and not rowstats))
     p.split_k = 1
-    in_kernel = None                 # split-K form: tuned per shape; untuned shapes combine in-kernel up to 4 slices
-    explicit_split = split_k is not None
-    if split_k is None and tile == 0 and not f32:
-        tuned = tuning_lookup(B * Hout * Wout, pw.N, Cx, pw.KH * pw.KW, stride, ups, act == ACT_GEGLU, pw.Cin2)
-        if tuned is not None and SK_AUTO and B * Hout * Wout * pw.N >= SK_AUTO_MIN_OUTPUTS \
-                and pw.KH * pw.KW * (pw.cin_pad // BK) + pw.cin2_pad // BK >= 16 \
-                and tuning_key(B * Hout * Wout, pw.N, Cx, pw.KH * pw.KW, stride, ups, act == ACT_GEGLU, pw.Cin2) not in TUNING:
-            tuned = None                   # only a NEIGHBOUR's entry, and the shape is in the stream-K macro-tiles' range (below)
-        if tuned is not None and tuned["tile"] >= 7 and max(pw.cin_pad, pw.cin2_pad) > (32704 if tuned["tile"] >= SK_TILE_FIRST else 4032):
-            tuned = None                   # the LDS-DMA tiles address at most 4032 channels per tap (a neighbour's tile may be one)
-        if tuned is not None:
-            p.tile, split_k = tuned["tile"], tuned["split_k"]
-            in_kernel = bool(tuned.get("in_kernel", 0))
-            if LEAN_REMAP and p.tile not in _LEAN_TILES and split_k == 1 and "insitu" not in tuned and pw.KH == 1 and pw.KW == 1 and pw.cin_pad <= 4032 \
-                    and stride == 1 and not ups and x2 is None and colgate is None and corr is None and rowbias is None \
-                    and depth is None and not out_f32 and gn is None and (act != ACT_GEGLU or (residual is None and not rowstats)):
-                # a plain linear layer whose table entry (tuned before csrc/lin_gemm.hip existed: the training steps' shapes) names a
-                # tile the lean kernel has no instantiation of -- the 160-wide and the intra-workgroup K-split tiles: take the lean
-                # tile the in-situ pass over the inference forward preferred at this row count (profiles/r4_tune_insitu_lean.txt)
-                M_ = B * Hout * Wout
-                p.tile = 11 if M_ >= 8192 else (18 if M_ >= 2048 else 49)
-            if order == 0:
-                p.order = tuned.get("order", 1)     # tables tuned before the XCD-aware orders existed mean the legacy order
-    if split_k is None and tile == 0 and p.tile == 0 and LEAN_REMAP and not f32 and pw.KH == 1 and pw.KW == 1 and stride == 1 and not ups \
-            and x2 is None and colgate is None and corr is None and rowbias is None and depth is None and not out_f32 and gn is None \
-            and (act != ACT_GEGLU or (residual is None and not rowstats)) and pw.cin_pad <= 4032:
-        # an untuned plain linear layer: a lean tile by row count (csrc/lin_gemm.hip) instead of the library's register-staged pick
-        M_ = B * Hout * Wout
-        p.tile, split_k = (11 if M_ >= 8192 else (18 if M_ >= 2048 else 49)), 1
-        if M_ <= 512 and pw.cin_pad >= 1280:
-            p.tile, split_k = 0, None          # (tiny M with a long K wants a K split: the library heuristic decides)
-    if split_k is None and tile == 0 and p.tile == 0 and SK_AUTO and not f32:
-        # no table entry: contractions with >= SK_AUTO_MIN_OUTPUTS outputs (a chip-filling number of 256 x 160 macro-tiles) and
-        # a long K take the persistent stream-K macro-tiles -- measured 1.28-1.42x the best per-tile launch on such shapes
-        # (tools/bench_sk.py: 16384 x 1280 x 11520 at 1,093 TFLOP/s; 8192^3 at 995 against 744) -- and nothing below that
-        # size does (0.5-0.98x on every launch of the bs=4 forward, which is why the table holds none)
-        nK = pw.KH * pw.KW * (pw.cin_pad // BK) + pw.cin2_pad // BK
-        if B * Hout * Wout * pw.N >= SK_AUTO_MIN_OUTPUTS and nK >= 16 and max(pw.cin_pad, pw.cin2_pad) <= 32704:
-            p.tile = SK_TILE_FIRST + 1 if act == ACT_GEGLU else SK_TILE_FIRST      # 256 x 128 for GEGLU's (h, g) column pairs
-            split_k, in_kernel = 2, True
-            if order == 0:
-                p.order = 3
-    if split_k is None:
-        split_k = lib.aptp_conv_gemm_suggest_split_k(ctypes.byref(p))
-    p.split_k = max(1, int(split_k))
+    p.tile, sk, in_kernel, p.order = choose_launch(B * Hout * Wout, pw.N, Cx, pw.cin_pad, pw.KH, pw.KW, stride, ups, act, pw.Cin2, pw.cin2_pad,
+                                                   plain_linear=plain_linear, f32=f32, tile=tile, split_k=split_k, order=order)
+    p.split_k = max(1, int(lib.aptp_conv_gemm_suggest_split_k(ctypes.byref(p)) if sk is None else sk))
     ws = cnt = None
     gn_fused = False
     if gn is not None and FUSE_GN_REDUCE and p.split_k > 1 and Hout * Wout <= GN_REDUCE_MAX_HW:
         gamma, beta, groups, eps_, silu_, Cn = gn
         cgn = Cn // groups
         gn_fused = Cn % 8 == 0 and Cn % groups == 0 and cgn % 4 == 0 and Hout * Wout * cgn <= 4 * 24 * 256 and Cn <= nout
-    if gn_fused:
-        in_kernel = False                  # the K-slices are combined by the reduce launch, which also normalises
+    if gn_fused:                           # the K-slices are combined by the reduce launch, which also normalises
         colstats = False
         p.gn_gamma, p.gn_beta, p.gn_groups, p.gn_C, p.gn_silu, p.gn_eps = gamma.data_ptr(), beta.data_ptr(), groups, Cn, int(silu_), eps_
+    # column statistics this launch would want to emit (whether it can is decided below, once the split-K form is known)
+    want_cols = colstats and COLSTATS and Hout * Wout >= COLSTATS_MIN_HW and act != ACT_GEGLU and not out_f32
     if p.split_k > 1:
-        if SPLITK_FORCE_IN_KERNEL and not gn_fused:
-            in_kernel = True               # (A/B switch: every split launch combines its slices itself, no reduce launches)
-        if in_kernel is None:
-            in_kernel = p.split_k <= 4 or explicit_split
-        # only the workgroup that combines the slices can emit row / column statistics.  Column statistics are worth the
-        # in-kernel form up to 2 slices (beyond that it loses more than the GroupNorm statistics pass it saves: measured
-        # +8 us on the 4-slice level-32 convs against a 6.5 us pass + a kernel boundary)
-        want_cols = colstats and COLSTATS and Hout * Wout >= COLSTATS_MIN_HW and act != ACT_GEGLU and not out_f32 \
-            and (in_kernel or p.split_k <= COLS_SPLIT_MAX)
-        if rowstats or want_cols:
-            in_kernel = True
+        in_kernel = splitk_in_kernel(p.split_k, in_kernel, explicit=split_k is not None, reduce_launch=gn_fused, rowstats=rowstats, colstats=want_cols)
         sk_tile = p.tile >= SK_TILE_FIRST     # persistent stream-K tiles: partial tiles are always combined in-kernel
         if (SPLITK_IN_KERNEL or sk_tile) and (in_kernel or sk_tile) and lib.aptp_conv_gemm_tiles(ctypes.byref(p)) <= _N_COUNTERS:
             cnt = _tile_counters(x.device)
@@ -743,8 +613,7 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
         stats = torch.empty(slots // 2, B * Hout * Wout, 4, dtype=torch.float32, device=x.device)
         p.rowstat_out, p.rowstat_slots = stats.data_ptr(), slots
     cstats = ustat = None
-    if colstats and COLSTATS and Hout * Wout >= COLSTATS_MIN_HW and act != ACT_GEGLU and not out_f32 \
-            and (p.split_k == 1 or cnt is not None) and _ld(out) % 8 == 0 and out.data_ptr() % 16 == 0 and nout % 8 == 0 \
+    if want_cols and (p.split_k == 1 or cnt is not None) and _ld(out) % 8 == 0 and out.data_ptr() % 16 == 0 and nout % 8 == 0 \
             and (residual is None or (_ld(residual) % 8 == 0 and residual.data_ptr() % 16 == 0)) \
             and (depth_in is None or (_ld(depth_in) % 8 == 0 and depth_in.data_ptr() % 16 == 0)) and p.epilogue == 0:
         rpb = lib.aptp_conv_gemm_colstat_rows(ctypes.byref(p))

@@ -350,6 +350,229 @@ def test_tuning_lookup_falls_back_to_the_nearest_tuned_shape_of_the_same_class()
         assert wide is None or wide["tile"] <= 6, wide
 
 
+# ---- ops.conv_gemm's launch choice (diffusion_pruning_amd/launch_policy.py), rule by rule; shapes from the committed table -------
+LIBRARY = (0, None, None)          # tile 0 = the library's pick_tile, split_k None = aptp_conv_gemm_suggest_split_k
+
+
+@pytest.fixture()
+def policy(monkeypatch):
+    """the policy module; table and switches are put back afterwards (the entries keep their identity)"""
+    from diffusion_pruning_amd import launch_policy as lp
+    saved = dict(lp.TUNING)
+    for sw in ("TUNING_NEAREST", "LEAN_REMAP", "SK_AUTO"):
+        monkeypatch.setattr(lp, sw, True)
+    yield lp
+    lp.set_tuning(saved)
+
+
+def choose(lp, M, N, Cin, taps=1, *, geglu=False, Cin2=0, plain=False, f32=False, tile=0, split_k=None, order=0, stride=1, ups=0):
+    k = {1: 1, 9: 3}[taps]
+    pad = lambda c: (c + 63) // 64 * 64
+    return lp.choose_launch(M, N, Cin, pad(Cin), k, k, stride, ups, 2 if geglu else 0, Cin2, pad(Cin2),      # (2 = ACT_GEGLU)
+                            plain_linear=plain, f32=f32, tile=tile, split_k=split_k, order=order)
+
+
+def test_launch_policy_imports_without_torch_or_the_library():
+    import os
+    import subprocess
+    import sys
+    code = ("import sys; import diffusion_pruning_amd.launch_policy as lp; assert 'torch' not in sys.modules; "
+            "assert lp.choose_launch(24, 40, 72, 128, 1, 1, 1, 0, 0, 0, 0, plain_linear=False, f32=False, tile=0, split_k=None, order=0) == (0, None, None, 0)")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run([sys.executable, "-c", code], check=True, cwd=root)
+
+
+def test_rule1_caller_given_tile_split_k_and_the_fp32_path_bypass_table_and_heuristics(policy):
+    assert policy.tuning_lookup(16384, 320, 320, 1, 1, 0, False) is not None           # an exact entry that would otherwise decide
+    assert choose(policy, 16384, 320, 320, plain=True, tile=3, order=2) == (3, None, None, 2)
+    assert choose(policy, 16384, 320, 320, plain=True, split_k=2) == (0, 2, None, 0)
+    assert choose(policy, 16384, 320, 320, plain=True, f32=True) == LIBRARY + (0,)
+    assert choose(policy, 65536, 1280, 1280, 9, f32=True) == LIBRARY + (0,)             # (stream-K sized: still the library's tiles 1..6)
+
+
+def test_rule2_the_table_entry_gives_tile_split_k_form_and_order(policy):
+    e = policy.TUNING["M16384_N320_C320_T1_s1u0g0"]                                    # a lean tile, tuned in situ, order 3
+    assert (e["tile"], e["split_k"], e["in_kernel"], e["order"]) == (11, 1, 0, 3)
+    assert choose(policy, 16384, 320, 320, plain=True) == (11, 1, False, 3)
+    assert choose(policy, 16384, 320, 320, plain=True, order=2) == (11, 1, False, 2)   # a caller-given order survives
+    e = policy.TUNING["M256_N640_C1280_T1_s1u0g0"]                                     # split along K, combined in-kernel
+    assert choose(policy, 256, 640, 1280, plain=True) == (e["tile"], 4, True, e["order"])
+    e = policy.TUNING["M16384_N320_C960_T1_s1u0g0"]                                    # no "in_kernel" in the entry: false
+    assert "in_kernel" not in e and choose(policy, 16384, 320, 960) == (e["tile"], e["split_k"], False, e["order"])
+    assert policy.TUNING["M1024_N10240_C1280_T1_s1u0g0"]["order"] == 0                 # the entry's own 0 is passed on as it is
+    assert choose(policy, 1024, 10240, 1280, plain=True)[3] == 0
+    policy.set_entry("M24_N40_C72_T1_s1u0g0", {"tile": 12, "split_k": 1})              # an entry without "order": the legacy order
+    assert choose(policy, 24, 40, 72) == (12, 1, False, 1)
+    assert choose(policy, 24, 40, 72, order=3) == (12, 1, False, 3)
+    # the nearest tuned shape of the same class stands in (a 41-group expert width)
+    assert "M16384_N328_C320_T1_s1u0g0" not in policy.TUNING
+    assert choose(policy, 16384, 328, 320, plain=True) == (11, 1, False, 3)
+    policy.TUNING_NEAREST = False
+    assert choose(policy, 16384, 328, 320) == LIBRARY + (0,)
+    assert choose(policy, 16384, 320, 320, plain=True) == (11, 1, False, 3)            # (exact entries are not affected)
+
+
+def test_rule3_entries_that_do_not_apply_are_dropped(policy):
+    # only a neighbour's entry, and the shape is in the stream-K range of rule 6: stream-K wins
+    near = policy.tuning_lookup(65536, 328, 1280, 1, 1, 0, False)
+    assert "M65536_N328_C1280_T1_s1u0g0" not in policy.TUNING and near is not None and near["tile"] == 19
+    assert 65536 * 328 >= policy.SK_AUTO_MIN_OUTPUTS and 1280 // 64 >= 16
+    assert choose(policy, 65536, 328, 1280) == (64, 2, True, 3)
+    assert choose(policy, 65536, 320, 1280) == (19, 1, False, 0)                       # the exact entry of the same range is kept
+    assert choose(policy, 65536, 328, 640)[0] == policy.tuning_lookup(65536, 328, 640, 1, 1, 0, False)["tile"]     # 10 K-steps: kept
+    policy.SK_AUTO = False
+    assert choose(policy, 65536, 328, 1280) == (19, 1, False, 0)
+    # an LDS-DMA tile (id >= 7) addresses 4032 channels per tap, a stream-K tile 32704
+    policy.set_tuning({"M64_N64_C4096_T1_s1u0g0": {"tile": 9, "split_k": 1, "order": 1},
+                       "M64_N64_C4032_T1_s1u0g0": {"tile": 9, "split_k": 1, "order": 1},
+                       "M128_N64_C4096_T1_s1u0g0": {"tile": 6, "split_k": 2, "order": 1},
+                       "M64_N64_C64_T9_s1u0g0x4096": {"tile": 13, "split_k": 1, "order": 1},
+                       "M256_N64_C4096_T1_s1u0g0": {"tile": 64, "split_k": 2, "in_kernel": 1, "order": 3},
+                       "M256_N64_C32768_T1_s1u0g0": {"tile": 64, "split_k": 2, "in_kernel": 1, "order": 3}})
+    assert choose(policy, 64, 64, 4096) == LIBRARY + (0,)
+    assert choose(policy, 64, 64, 4032) == (9, 1, False, 1)
+    assert choose(policy, 128, 64, 4096) == (6, 2, False, 1)                           # register-staged: no limit
+    assert choose(policy, 64, 64, 64, 9, Cin2=4096) == LIBRARY + (0,)                  # the second operand's channels count too
+    assert choose(policy, 256, 64, 4096) == (64, 2, True, 3)
+    assert choose(policy, 256, 64, 32768) == LIBRARY + (0,)
+
+
+def test_rule4_a_tuned_plain_linear_layer_on_a_tile_without_lean_instantiation_is_remapped(policy):
+    for M, N, C, was, now in ((16384, 640, 320, 19, 11), (4096, 5120, 640, 19, 18), (256, 1280, 640, 59, 49)):
+        e = policy.TUNING[policy.tuning_key(M, N, C, 1, 1, 0, False)]
+        assert e["tile"] == was and was not in policy._LEAN_TILES and e["split_k"] == 1 and "insitu" not in e
+        assert choose(policy, M, N, C, plain=True) == (now, 1, False, e["order"])
+        assert choose(policy, M, N, C, plain=False) == (was, 1, False, e["order"])     # some epilogue the lean kernel does not have
+    e = policy.TUNING["M1024_N7680_C1280_T1_s1u0g1"]                                   # chosen in situ with the lean kernel present: kept
+    assert e["tile"] == 21 and "insitu" in e
+    assert choose(policy, 1024, 7680, 1280, geglu=True, plain=True)[0] == 21
+    e = policy.TUNING["M256_N1280_C3840_T1_s1u0g0"]                                    # split along K: not the lean kernel's
+    assert e["tile"] == 40 and e["split_k"] == 6
+    assert choose(policy, 256, 1280, 3840, plain=True)[:2] == (40, 6)
+    assert choose(policy, 16384, 320, 320, plain=True)[0] == 11                        # already a lean tile: as tuned
+    assert policy.TUNING["M4096_N1280_C1280_T1_s1u0g0"]["tile"] == 9 and choose(policy, 4096, 1280, 1280, plain=True)[0] == 9
+    # only a key named exactly "insitu" exempts an entry
+    policy.set_entry("M24_N40_C72_T1_s1u0g0", {"tile": 19, "split_k": 1, "order": 1, "insitu_train": 1.0})
+    assert choose(policy, 24, 40, 72, plain=True) == (49, 1, False, 1)
+    policy.set_entry("M24_N40_C72_T1_s1u0g0", {"tile": 19, "split_k": 1, "order": 1, "insitu": 1.0})
+    assert choose(policy, 24, 40, 72, plain=True) == (19, 1, False, 1)
+    policy.LEAN_REMAP = False
+    assert choose(policy, 16384, 640, 320, plain=True)[0] == 19
+
+
+def test_rule5_an_untuned_plain_linear_layer_takes_a_lean_tile_by_row_count(policy):
+    assert policy.tuning_lookup(24, 40, 72, 1, 1, 0, False) is None                    # nothing within reach in the committed table
+    assert choose(policy, 24, 40, 72, plain=True, order=2) == (49, 1, None, 2)
+    policy.set_tuning({})                                                              # no neighbour interferes below
+    assert choose(policy, 8192, 320, 320, plain=True) == (11, 1, None, 0)
+    assert choose(policy, 8191, 320, 320, plain=True) == (18, 1, None, 0)
+    assert choose(policy, 2048, 320, 320, plain=True) == (18, 1, None, 0)
+    assert choose(policy, 2047, 320, 320, plain=True) == (49, 1, None, 0)
+    assert choose(policy, 4096, 5120, 640, geglu=True, plain=True) == (18, 1, None, 0)
+    # tiny M with a long K wants a K split: back to the library
+    assert choose(policy, 512, 1280, 1280, plain=True) == LIBRARY + (0,)
+    assert choose(policy, 513, 1280, 1280, plain=True) == (49, 1, None, 0)
+    assert choose(policy, 512, 1280, 1216, plain=True) == (49, 1, None, 0)
+    assert choose(policy, 4096, 1280, 4032, plain=True) == (18, 1, None, 0)
+    assert choose(policy, 4096, 1280, 4040, plain=True) == LIBRARY + (0,)              # past the LDS-DMA tiles' channel range
+    assert choose(policy, 4096, 320, 320, plain=False) == LIBRARY + (0,)
+    assert choose(policy, 65536, 1280, 1280, plain=True) == (11, 1, None, 0)           # (before the stream-K take-over)
+    policy.LEAN_REMAP = False
+    assert choose(policy, 4096, 320, 320, plain=True) == LIBRARY + (0,)
+
+
+def test_rule6_large_untuned_contractions_take_the_stream_k_tiles(policy):
+    policy.set_tuning({})
+    assert policy.SK_AUTO_MIN_OUTPUTS == 256 * 256 * 160 == 8192 * 1280
+    assert choose(policy, 8192, 1280, 1280, 9) == (64, 2, True, 3)
+    assert choose(policy, 8192, 1280, 1280, 9, order=2) == (64, 2, True, 2)            # a caller-given order survives
+    assert choose(policy, 8192, 2560, 1280, geglu=True) == (65, 2, True, 3)            # 256 x 128 for GEGLU's column pairs
+    assert choose(policy, 8192, 1272, 1280, 9) == LIBRARY + (0,)                       # too few outputs
+    assert choose(policy, 8192, 1280, 1024) == (64, 2, True, 3)                        # 16 K-steps
+    assert choose(policy, 8192, 1280, 960) == LIBRARY + (0,)                           # 15
+    assert choose(policy, 8192, 1280, 64, 9, Cin2=448) == (64, 2, True, 3)             # 9 + 7 K-steps with the second operand's
+    assert choose(policy, 8192, 1280, 32704) == (64, 2, True, 3)
+    assert choose(policy, 8192, 1280, 32768) == LIBRARY + (0,)                         # past the stream-K tiles' channel range
+    policy.SK_AUTO = False
+    assert choose(policy, 8192, 1280, 1280, 9) == LIBRARY + (0,)
+
+
+def test_rule7_otherwise_the_library_decides(policy):
+    assert choose(policy, 24, 40, 72) == LIBRARY + (0,)
+    assert choose(policy, 24, 40, 72, 9, order=3) == LIBRARY + (3,)
+
+
+def test_split_k_form(policy):
+    f = policy.splitk_in_kernel
+    kw = dict(explicit=False, reduce_launch=False, rowstats=False, colstats=False)
+    assert [f(s, None, **kw) for s in (2, 4, 5, 8)] == [True, True, False, False]      # untuned: in-kernel up to 4 slices
+    assert f(8, None, **dict(kw, explicit=True))                                       # ... or when the caller chose the depth
+    assert not f(2, False, **kw) and f(8, True, **kw)                                  # tuned per shape
+    assert f(8, False, **dict(kw, rowstats=True))                                      # only the combining workgroup can emit statistics
+    assert policy.COLS_SPLIT_MAX == 2
+    assert f(2, False, **dict(kw, colstats=True)) and not f(3, False, **dict(kw, colstats=True))
+    assert not f(2, True, **dict(kw, reduce_launch=True))                              # the reduce launch applies the fused GroupNorm
+
+
+def test_editing_the_table_drops_the_cached_nearest_shape_answers(policy):
+    from diffusion_pruning_amd import ops
+    assert ops.TUNING is policy.TUNING
+    key = "M16384_N320_C320_T1_s1u0g0"
+    near = ops.tuning_lookup(16384, 328, 320, 1, 1, 0, False)
+    assert near["tile"] == policy.TUNING[key]["tile"] == 11
+    tuned = policy.TUNING[key]
+    ops.set_entry(key, dict(tuned, tile=12))                                           # (no other entry of the class within reach has tile 12)
+    assert ops.tuning_lookup(16384, 328, 320, 1, 1, 0, False)["tile"] == 12
+    ops.set_entry(key, None)                                                           # removed: some other neighbour, or none
+    assert key not in ops.TUNING and (ops.tuning_lookup(16384, 328, 320, 1, 1, 0, False) or {"tile": 0})["tile"] != 12
+    ops.set_entry(key, tuned)
+    assert ops.tuning_lookup(16384, 320, 320, 1, 1, 0, False) is tuned and ops.tuning_lookup(16384, 328, 320, 1, 1, 0, False) == near
+    ops.set_tuning({})
+    assert ops.TUNING is policy.TUNING and not ops.TUNING
+    assert ops.tuning_lookup(16384, 328, 320, 1, 1, 0, False) is None and ops.tuning_lookup(16384, 320, 320, 1, 1, 0, False) is None
+    ops.set_tuning({key: {"tile": 25, "split_k": 1, "order": 1}})
+    assert ops.tuning_lookup(16384, 328, 320, 1, 1, 0, False)["tile"] == 25
+
+
+def test_tuning_keys_round_trip():
+    from types import SimpleNamespace
+    from diffusion_pruning_amd import _lib, launch_policy as lp
+    for k in lp.TUNING:
+        assert lp.tuning_key(*lp.parse_key(k)) == k
+    assert lp.parse_key("M4096_N640_C320_T9_s1u0g0x640") == (4096, 640, 320, 9, 1, 0, False, 640)
+    assert lp.parse_key("M4_N8_C8_T1_s1u0g1") == (4, 8, 8, 1, 1, 0, True, 0) and lp.parse_key("us") is None
+    p = SimpleNamespace(B=4, Hout=32, Wout=32, N=640, Cin=320, KH=3, KW=3, stride=1, ups=0, act=_lib.ACT_GEGLU, Cin2=640, x2=None)
+    assert lp.key_of(p) == "M4096_N640_C320_T9_s1u0g1"                                 # Cin2 counts only with an x2 operand
+    p.x2, p.act = 1234, 0
+    assert lp.key_of(p) == "M4096_N640_C320_T9_s1u0g0x640"
+
+
+def test_the_tile_ids_of_the_policy_are_the_library_s():
+    import os
+    import re
+    from diffusion_pruning_amd import _lib, launch_policy as lp
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "aptp_hip.h")).read()
+    enum = {n: int(v) for n, v in re.findall(r"APTP_TILE_(\w+)\s*=\s*(\d+)", header)}
+    assert enum["AUTO"] == 0 and len(set(enum.values())) == len(enum)
+    n_tiles = int(re.search(r"constexpr int kNumTiles = (\d+);", open(os.path.join(root, "diffusion_pruning_amd", "csrc", "conv_gemm.hip")).read()).group(1))
+    assert sorted(enum.values()) == list(range(n_tiles))
+    named = {n[5:]: v for n, v in vars(_lib).items() if n.startswith("TILE_")}
+    assert named and all(enum[n] == v for n, v in named.items())                       # no second numbering
+    lin = open(os.path.join(root, "diffusion_pruning_amd", "csrc", "lin_gemm.hip")).read()
+    body = lin[lin.index("bool aptp_lin_eligible("):]
+    body = body[:body.index("default:")]
+    cases = {enum[n] for n in re.findall(r"case APTP_TILE_(\w+):", body)}
+    assert cases == set(lp._LEAN_TILES) == {9, 11, 12, 15, 17, 18, 24, 25, 26} | set(range(45, 54))
+    assert set(lp._HALO_TILES) == {enum["HALO_128x160"], enum["HALO_128x128"]}
+    assert lp.DMA_TILE_FIRST == enum["DMA_128x128"] == enum["64x64"] + 1 and lp.SK_TILE_FIRST == enum["SK_256x160"]
+    policy_tiles = set(lp._LEAN_TILES) | set(lp._HALO_TILES) | {lp.DMA_TILE_FIRST, lp.SK_TILE_FIRST, _lib.TILE_SK_256x160, _lib.TILE_SK_256x128}
+    policy_tiles |= {lp._lean_tile(M) for M in (1, 2048, 8192)}
+    assert {lp._lean_tile(M) for M in (1, 2048, 8192)} <= set(lp._LEAN_TILES)
+    assert all(0 < t < n_tiles for t in policy_tiles)
+    assert all(0 < e["tile"] < n_tiles for e in lp.TUNING.values())
+
+
 # ---- the same host logic without any rounding: fp32 storage end to end (emulator exact mode) vs the fp32 oracle -------------
 EXACT_TOL = 1e-5
 

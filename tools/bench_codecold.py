@@ -30,7 +30,7 @@ s = torch.cuda.current_stream().cuda_stream
 seen = {}
 for rec in log:
     p = rec["params"]
-    key = ops.tuning_key(p.B * p.Hout * p.Wout, p.N, p.Cin, p.KH * p.KW, p.stride, p.ups, p.act == ops.ACT_GEGLU, p.Cin2 if p.x2 else 0)
+    key = ops.key_of(p)
     seen.setdefault(key, [rec, 0])[1] += 1
 tot = [0.0, 0.0, 0.0]
 for key, (rec, cnt) in seen.items():

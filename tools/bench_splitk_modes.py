@@ -1,6 +1,6 @@
 """A/B of the two split-K forms (in-kernel reduction vs reduce launch) on every split shape of the tuning table, at the
 tuned (tile, order) and a range of split factors.  Usage: python tools/bench_splitk_modes.py"""
-import os, re, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from diffusion_pruning_amd import ops
@@ -29,8 +29,7 @@ ops._tile_counters(dev)
 for key, t in sorted(ops.TUNING.items()):
     if t["split_k"] <= 1:
         continue
-    m = re.match(r"M(\d+)_N(\d+)_C(\d+)_T(\d+)_s(\d)u(\d)g(\d)", key)
-    M, N, C, T, st, up, gg = (int(v) for v in m.groups())
+    M, N, C, T, st, up, gg, x2 = ops.parse_key(key)
     if gg or st != 1 or up or M % 4:
         continue
     k = 3 if T == 9 else 1

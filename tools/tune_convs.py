@@ -105,7 +105,7 @@ def main():
     ehs = torch.randn(B, 77, 1024, device=dev)
     t = torch.full((B,), 500, dtype=torch.int64, device=dev)
     if not args.refine:
-        ops.TUNING = {}      # record with heuristics only
+        ops.set_tuning({})      # record with heuristics only
     with torch.no_grad():
         model(sample, t, ehs)
         ops.LAUNCH_LOG = []
@@ -134,7 +134,7 @@ def record_train_step(args):
     opt = torch.optim.AdamW(step.trainable_parameters(), lr=2e-4)
     batch = synthetic_batch(args.batch, args.latent, dev)
     if not args.refine:
-        ops.TUNING = {}
+        ops.set_tuning({})
     step.train_step(opt, batch)
     ops.LAUNCH_LOG = []
     step.train_step(opt, batch)
@@ -151,7 +151,7 @@ def tune(args, lib, log):
         if "fn" in rec:                   # aptp_ff_tail etc.: not a conv_gemm launch
             continue
         p = rec["params"]
-        key = ops.tuning_key(p.B * p.Hout * p.Wout, p.N, p.Cin, p.KH * p.KW, p.stride, p.ups, p.act == ACT_GEGLU, p.Cin2 if p.x2 else 0)
+        key = ops.key_of(p)
         u = uniq.setdefault(key, {"rec": rec, "count": 0})
         u["count"] += 1
     print(f"{len(log)} launches, {len(uniq)} distinct", flush=True)

@@ -16,7 +16,6 @@ import argparse
 import ctypes
 import json
 import os
-import re
 import sys
 import time
 
@@ -26,10 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bench import expert_mask  # noqa: E402
 from diffusion_pruning_amd import ops  # noqa: E402
-from diffusion_pruning_amd._lib import ACT_GEGLU  # noqa: E402
 
 dev = torch.device("cuda:0")
-KEY = re.compile(r"M(\d+)_N(\d+)_C(\d+)_T(\d+)_s(\d+)u(\d+)g(\d+)(?:x(\d+))?$")
 
 
 def main():
@@ -114,7 +111,7 @@ def main():
     for rec in hl_log:
         if "fn" not in rec:
             p = rec["params"]
-            headline_keys.add(ops.tuning_key(p.B * p.Hout * p.Wout, p.N, p.Cin, p.KH * p.KW, p.stride, p.ups, p.act == ACT_GEGLU, p.Cin2 if p.x2 else 0))
+            headline_keys.add(ops.key_of(p))
     unet.set_structure(ones_mask(st0, dev))
     del hl_log
 
@@ -149,18 +146,18 @@ def main():
         if "fn" in rec:
             continue
         p = rec["params"]
-        key = ops.tuning_key(p.B * p.Hout * p.Wout, p.N, p.Cin, p.KH * p.KW, p.stride, p.ups, p.act == ACT_GEGLU, p.Cin2 if p.x2 else 0)
+        key = ops.key_of(p)
         s = shapes.setdefault(key, {"count": 0, "flops": rec["flops"], "params": p})
         s["count"] += 1
     order = sorted(shapes, key=lambda k: -shapes[k]["flops"] * shapes[k]["count"])[args.skip:args.skip + args.top]
 
     def cls(key):
-        M, N, C, T, s_, u, g_, x2 = (int(v) if v else 0 for v in KEY.match(key).groups())
-        return (T, s_, u, g_, x2 > 0), M, N, T * C + x2
+        M, N, C, T, s_, u, g_, x2 = ops.parse_key(key)
+        return (T, s_, u, int(g_), x2 > 0), M, N, T * C + x2
 
     by_class = {}
     for k, v in ops.TUNING.items():
-        if KEY.match(k):
+        if ops.parse_key(k):
             by_class.setdefault(cls(k)[0], set()).add((v["tile"], v["split_k"], v.get("order", 1), int(v.get("in_kernel", 0))))
 
     from tools.tune_convs import clone_params
@@ -198,8 +195,7 @@ def main():
             continue
         c, M, N, K = cls(key)
         nK = (K + 63) // 64
-        g = [int(v) if v else 0 for v in KEY.match(key).groups()]
-        cur = ops.tuning_lookup(*g[:7], g[7])
+        cur = ops.tuning_lookup(*ops.parse_key(key))
         if cur is None:
             continue
         inc = (cur["tile"], cur["split_k"], cur.get("order", 1), int(cur.get("in_kernel", 0)))
@@ -219,8 +215,7 @@ def main():
                 break
             if not runnable(key, cd):
                 continue
-            ops.TUNING[key] = {"tile": cd[0], "split_k": cd[1], "order": cd[2], "in_kernel": cd[3]}
-            ops._tuning_near_cache.clear()
+            ops.set_entry(key, {"tile": cd[0], "split_k": cd[1], "order": cd[2], "in_kernel": cd[3]})
             try:
                 v = measure()
             except Exception:  # noqa: BLE001    (a tile that cannot run this shape under the step's epilogue)
@@ -231,17 +226,13 @@ def main():
                 if min(v, v2) > best_v * (1 + args.margin):
                     best, best_v = cd, min(v, v2)
         if best != inc:
-            ops.TUNING[key] = {"tile": best[0], "split_k": best[1], "order": best[2], "in_kernel": best[3], "insitu_" + args.step: round(best_v, 3)}
-            changed[key] = ops.TUNING[key]
+            changed[key] = {"tile": best[0], "split_k": best[1], "order": best[2], "in_kernel": best[3], "insitu_" + args.step: round(best_v, 3)}
+            ops.set_entry(key, changed[key])
             out(f"{key:42s} x{shapes[key]['count']:3d}  {inc} -> {best}   {base:.3f} -> {best_v:.3f} steps/s")
             base = best_v
         else:
-            if saved is None:
-                ops.TUNING.pop(key, None)
-            else:
-                ops.TUNING[key] = saved
+            ops.set_entry(key, saved)
             out(f"{key:42s} x{shapes[key]['count']:3d}  keeps {inc}")
-        ops._tuning_near_cache.clear()
     del base_step
     final = max(measure(), measure())
     out(f"final {final:.3f} steps/s with {len(changed)} entries changed")
