@@ -272,6 +272,35 @@ class TokenEmbedParams(Structure):
     ]
 
 
+class AttentionBiasParams(Structure):
+    _fields_ = [
+        ("q", c_void_p), ("q_stride_b", c_int64), ("q_stride_l", c_int64),
+        ("k", c_void_p), ("k_stride_b", c_int64), ("k_stride_l", c_int64),
+        ("v", c_void_p), ("v_stride_b", c_int64), ("v_stride_l", c_int64),
+        ("o", c_void_p), ("o_stride_b", c_int64), ("o_stride_l", c_int64),
+        ("relbias", c_void_p), ("key_mask", c_void_p),
+        ("B", c_int32), ("heads", c_int32), ("L", c_int32),
+        ("scale", c_float),
+        ("io_f32", c_int32),
+    ]
+
+
+class EmbedLnParams(Structure):
+    _fields_ = [
+        ("ids", c_void_p), ("word", c_void_p), ("pos", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
+        ("out", c_void_p), ("ldo", c_int64),
+        ("B", c_int32), ("L", c_int32), ("C", c_int32), ("vocab", c_int32), ("pos_rows", c_int32), ("pad_id", c_int32),
+        ("out_f32", c_int32), ("eps", c_float),
+    ]
+
+
+class MaskedMeanParams(Structure):
+    _fields_ = [
+        ("x", c_void_p), ("x_stride_b", c_int64), ("x_stride_l", c_int64), ("mask", c_void_p), ("out", c_void_p),
+        ("B", c_int32), ("L", c_int32), ("C", c_int32), ("x_f32", c_int32),
+    ]
+
+
 class ColsumParams(Structure):
     _fields_ = [("x", c_void_p), ("ldx", c_int64), ("rows", c_int32), ("C", c_int32), ("partial", c_void_p), ("batch", c_int32)]
 
@@ -360,6 +389,9 @@ EXPORTS = [
     ("aptp_latent_dist", c_int, [POINTER(LatentDistParams), c_void_p]),
     ("aptp_attention_causal", c_int, [POINTER(AttentionCausalParams), c_void_p]),
     ("aptp_token_embed", c_int, [POINTER(TokenEmbedParams), c_void_p]),
+    ("aptp_attention_bias", c_int, [POINTER(AttentionBiasParams), c_void_p]),
+    ("aptp_embed_ln", c_int, [POINTER(EmbedLnParams), c_void_p]),
+    ("aptp_masked_mean", c_int, [POINTER(MaskedMeanParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from ._lib import ImageInParams, LatentDistParams, UnetEpilogueParams, UnetPrologueParams
 from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F401
+from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1037,6 +1038,96 @@ def token_embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, out_f32
     p.ids, p.tok, p.pos, p.out, p.ldo = ids.data_ptr(), tok.data_ptr(), pos.data_ptr(), out.data_ptr(), C
     p.B, p.L, p.C, p.vocab, p.out_f32, p.pos_rows = B, L, C, V, int(out_f32), pos.shape[0]
     _lib.check(lib.aptp_token_embed(ctypes.byref(p), _stream()), "aptp_token_embed")
+    return out
+
+
+BIAS_MAX_L = 512
+
+
+def _check_mask(mask: Optional[torch.Tensor], B: int, L: int, device, name: str):
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, L) or not mask.is_contiguous()
+                             or mask.device != device):
+        raise ValueError(f"{name}: the mask must be a contiguous fp32 [{B}, {L}] tensor on {device}, got {mask.dtype} "
+                         f"{tuple(mask.shape)} on {mask.device}")
+
+
+def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, relbias: torch.Tensor,
+                   key_mask: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T * scale + relbias[h, j - i + L - 1] + key mask) v with head_dim 64 and 1 <= L <= 512 (MPNet's
+    self-attention).  q, k, v and out [B, L, heads*64] are views with a contiguous last dim on one device (e.g. column slices
+    of a fused q|k|v buffer); bf16, or fp32 for the parity path.  relbias fp32 [heads, 2L-1]; key_mask fp32 [B, L] (0 = masked,
+    any pattern) or None for all valid: a masked key gets weight exactly 0.  Default scale 64^-0.5."""
+    lib = _lib.load()
+    B, L = q.shape[0], q.shape[1]
+    if out is None:
+        out = torch.empty(B, L, heads * 64, dtype=q.dtype, device=q.device)
+    for t in (q, k, v, out):
+        if t.dtype != q.dtype or t.dtype not in (torch.bfloat16, torch.float32) or t.dim() != 3 or t.stride(2) != 1 \
+                or tuple(t.shape) != (B, L, heads * 64) or not t.is_cuda or t.device != q.device:
+            raise ValueError(f"attention_bias: q, k, v and out must be {q.dtype} [B, L, {heads * 64}] views with contiguous "
+                             f"channels on {q.device}, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    if relbias.dtype != torch.float32 or tuple(relbias.shape) != (heads, 2 * L - 1) or not relbias.is_contiguous() \
+            or relbias.device != q.device:
+        raise ValueError(f"attention_bias: relbias must be a contiguous fp32 [{heads}, {2 * L - 1}] tensor on {q.device}, got "
+                         f"{relbias.dtype} {tuple(relbias.shape)} on {relbias.device}")
+    _check_mask(key_mask, B, L, q.device, "attention_bias")
+    p = AttentionBiasParams()
+    p.io_f32 = int(q.dtype == torch.float32)
+    _set_views(p, q=q, k=k, v=v, o=out)
+    p.relbias, p.key_mask = relbias.data_ptr(), (None if key_mask is None else key_mask.data_ptr())
+    p.B, p.heads, p.L = B, heads, L
+    p.scale = 0.125 if scale is None else scale
+    _lib.check(lib.aptp_attention_bias(ctypes.byref(p), _stream()), "aptp_attention_bias")
+    return out
+
+
+def embed_ln(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+             eps: float = 1e-5, pad_id: int = 1, out_f32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[B, L] int64 ids -> bf16 (fp32 when out_f32) [B, L, C] = LayerNorm(word[ids] + pos[pos_id]) (MPNetEmbeddings), where
+    pos_id counts the non-pad ids up to and including the token, plus pad_id (a pad token: pad_id).  word fp32 [vocab, C], pos
+    fp32 [> L + pad_id, C], gamma / beta fp32 [C].  An id outside [0, vocab) is not read: its row comes out NaN."""
+    lib = _lib.load()
+    if ids.dtype != torch.int64 or ids.dim() != 2 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError(f"embed_ln: ids must be a contiguous CUDA int64 [B, L] tensor, got {ids.dtype} {tuple(ids.shape)}")
+    B, L = ids.shape
+    V, C = word.shape
+    for t, nm, shp in ((word, "word", (V, C)), (pos, "pos", (pos.shape[0], C)), (gamma, "gamma", (C,)), (beta, "beta", (C,))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous() or t.device != ids.device:
+            raise ValueError(f"embed_ln: {nm} must be a contiguous fp32 {shp} tensor on the ids' device")
+    if pos.shape[0] <= L + pad_id:
+        raise ValueError(f"embed_ln: {L} tokens with pad id {pad_id} need {L + pad_id + 1} positions, have {pos.shape[0]}")
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty(B, L, C, dtype=odt, device=ids.device)
+    elif tuple(out.shape) != (B, L, C) or out.dtype != odt or not out.is_contiguous():
+        raise ValueError(f"embed_ln: out must be a contiguous {odt} [{B}, {L}, {C}] tensor")
+    p = EmbedLnParams()
+    p.ids, p.word, p.pos, p.gamma, p.beta = ids.data_ptr(), word.data_ptr(), pos.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+    p.out, p.ldo = out.data_ptr(), C
+    p.B, p.L, p.C, p.vocab, p.pos_rows, p.pad_id, p.out_f32, p.eps = B, L, C, V, pos.shape[0], pad_id, int(out_f32), eps
+    _lib.check(lib.aptp_embed_ln(ctypes.byref(p), _stream()), "aptp_embed_ln")
+    return out
+
+
+def masked_mean(x: torch.Tensor, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 or fp32 [B, L, C] -> fp32 [B, C] = sum_l x * mask / max(sum_l mask, 1e-9); mask fp32 [B, L] or None (all ones).
+    fp32 sums in a fixed order: bit-identical from run to run."""
+    lib = _lib.load()
+    if x.dtype not in (torch.bfloat16, torch.float32) or x.dim() != 3 or x.stride(2) != 1 or not x.is_cuda:
+        raise ValueError(f"masked_mean: x must be a CUDA bf16 or fp32 [B, L, C] tensor with contiguous channels, got {x.dtype} "
+                         f"{tuple(x.shape)}")
+    B, L, C = x.shape
+    _check_mask(mask, B, L, x.device, "masked_mean")
+    if out is None:
+        out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (B, C) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"masked_mean: out must be a contiguous fp32 [{B}, {C}] tensor on {x.device}")
+    p = MaskedMeanParams()
+    p.x, p.x_stride_b, p.x_stride_l = x.data_ptr(), x.stride(0), (x.stride(1) if L > 1 else max(x.stride(1), C))
+    p.mask, p.out = (None if mask is None else mask.data_ptr()), out.data_ptr()
+    p.B, p.L, p.C, p.x_f32 = B, L, C, int(x.dtype == torch.float32)
+    _lib.check(lib.aptp_masked_mean(ctypes.byref(p), _stream()), "aptp_masked_mean")
     return out
 
 

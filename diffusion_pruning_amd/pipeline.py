@@ -1,7 +1,8 @@
 """Denoise-loop glue of StableDiffusionPruningPipeline (pdm/pipelines/pruning_pipelines.py:746-759, 787-824), SURVEY §8
 row a21 / f.2: route the prompt batch once -> ``unet.set_structure`` -> per step: CFG batch doubling -> U-Net ->
 ``uncond + s*(text - uncond)`` -> scheduler step.  Token ids are encoded by the HIP CLIP text encoder (``text_encoder=``,
-``prompt_ids=``) and latents decoded by the HIP VAE (``vae=``); the safety checker is not reproduced.
+``prompt_ids=``), the router's MPNet token ids by the HIP prompt encoder (``prompt_encoder=``, ``router_ids=``) and latents
+decoded by the HIP VAE (``vae=``); the safety checker is not reproduced.
 
 MI355X-first differences:
   * the cross-attention K/V projections depend only on the text states, so they are computed ONCE per prompt batch
@@ -182,10 +183,12 @@ class PipelineOutput:
 
 
 class PruningDenoiseLoop:
-    def __init__(self, unet, hyper_net=None, quantizer=None, scheduler=None, vae=None, text_encoder=None):
+    def __init__(self, unet, hyper_net=None, quantizer=None, scheduler=None, vae=None, text_encoder=None,
+                 prompt_encoder=None):
         self.unet, self.hyper_net, self.quantizer = unet, hyper_net, quantizer
         self.vae = vae                   # diffusion_pruning_amd.vae.AutoencoderKL: decodes for output_type != "latent"
         self.text_encoder = text_encoder  # diffusion_pruning_amd.text_encoder.CLIPTextModel: encodes prompt_ids
+        self.prompt_encoder = prompt_encoder  # diffusion_pruning_amd.prompt_encoder.MPNetModel: encodes router_ids
         self.scheduler = scheduler or DDIMSchedulerLite()
         self._graph = None
         self._graph_key = None
@@ -214,14 +217,24 @@ class PruningDenoiseLoop:
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, hyper_net_input: Optional[torch.Tensor] = None,
                  negative_prompt_embeds: Optional[torch.Tensor] = None, use_graph: bool = True,
                  output_type: str = "latent", *, prompt_ids: Optional[torch.Tensor] = None,
-                 negative_prompt_ids: Optional[torch.Tensor] = None) -> PipelineOutput:
+                 negative_prompt_ids: Optional[torch.Tensor] = None, router_ids: Optional[torch.Tensor] = None,
+                 router_attention_mask: Optional[torch.Tensor] = None) -> PipelineOutput:
         """prompt_embeds [B,77,X] (+ negative_prompt_embeds for CFG, concatenated as [uncond, cond] like the
         reference, :765); latents [B,4,h,w] ~ N(0,1) on the device.  output_type "latent" returns the latents only;
         "pt" (fp32 [B,3,H,W] in [0, 1]), "np" (fp32 [B,H,W,3] numpy) and "pil" (list of PIL images) also decode them
         through ``vae`` and postprocess like the reference (:826-839, do_denormalize always true).
         prompt_ids / negative_prompt_ids (int64 [B, L] token ids) instead of the embeddings: encode_prompt (:735-744) on
         ``text_encoder`` -- [negative_prompt_ids; prompt_ids] in ONE encoder call with CFG, prompt_ids alone without --
-        then the same loop as with the embeddings."""
+        then the same loop as with the embeddings.
+        router_ids (+ router_attention_mask): the MPNet token ids of the prompts instead of hyper_net_input, which is then
+        ``prompt_encoder.encode(router_ids, router_attention_mask)`` (get_mpnet_embeddings, pdm/utils/data_utils.py:130-155)."""
+        if router_ids is not None or router_attention_mask is not None:
+            if hyper_net_input is not None:
+                raise ValueError("give either hyper_net_input or router_ids / router_attention_mask, not both")
+            if router_ids is None:
+                raise ValueError("router_attention_mask needs router_ids")
+            if self.prompt_encoder is None:
+                raise ValueError("router_ids need a prompt_encoder (PruningDenoiseLoop(..., prompt_encoder=MPNetModel))")
         if prompt_ids is not None or negative_prompt_ids is not None:
             if prompt_embeds is not None or negative_prompt_embeds is not None:
                 raise ValueError("give either prompt_embeds / negative_prompt_embeds or prompt_ids / negative_prompt_ids, not both")
@@ -247,6 +260,8 @@ class PruningDenoiseLoop:
         if output_type != "latent" and self.vae is None:
             raise ValueError(f"output_type {output_type!r} needs a vae (PruningDenoiseLoop(..., vae=AutoencoderKL))")
         dev = latents.device
+        if router_ids is not None:
+            hyper_net_input = self.prompt_encoder.encode(router_ids, router_attention_mask)
         arch_q = idx = None
         if self.hyper_net is not None and hyper_net_input is not None:
             arch_q, idx = self.route(hyper_net_input.to(dev))

@@ -878,12 +878,31 @@ def noisy_latents_and_target(latents: torch.Tensor, noise: torch.Tensor, timeste
     return noisy, target
 
 
-def batch_from_images(vae, pixel_values: torch.Tensor, encoder_hidden_states: torch.Tensor, mpnet_embeddings: torch.Tensor,
-                      schedule: Optional[NoiseSchedule] = None, prediction_type: str = "v_prediction", generator=None):
+def router_embeddings(prompt_encoder, router_ids: torch.Tensor, router_attention_mask: Optional[torch.Tensor] = None):
+    """batch["mpnet_embeddings"] from the router's token ids (pdm/utils/data_utils.py:158-172): fp32 [B, 768] =
+    prompt_encoder.encode(router_ids, router_attention_mask) on the HIP MPNet encoder (prompt_encoder.MPNetModel)"""
+    if prompt_encoder is None:
+        raise ValueError("router_ids need a prompt_encoder (diffusion_pruning_amd.prompt_encoder.MPNetModel)")
+    return prompt_encoder.encode(router_ids, router_attention_mask)
+
+
+def batch_from_images(vae, pixel_values: torch.Tensor, encoder_hidden_states: torch.Tensor,
+                      mpnet_embeddings: Optional[torch.Tensor] = None,
+                      schedule: Optional[NoiseSchedule] = None, prediction_type: str = "v_prediction", generator=None, *,
+                      router_ids: Optional[torch.Tensor] = None, router_attention_mask: Optional[torch.Tensor] = None,
+                      prompt_encoder=None):
     """A training batch (synthetic_batch's keys) from images, as the reference's training steps build it
     (trainer.py:1097-1122): latents = vae.encode(pixel_values).latent_dist.sample() * scaling_factor (vae.encode_latents, one
     pass on the HIP encoder), then noise and timesteps, drawn in that order from ``generator``, add_noise and the target.
-    pixel_values: NCHW [B, 3, H, W] in [-1, 1] on the GPU; H and W multiples of 8."""
+    pixel_values: NCHW [B, 3, H, W] in [-1, 1] on the GPU; H and W multiples of 8.
+    The router's input is either ``mpnet_embeddings`` [B, 768] or ``router_ids`` (+ ``router_attention_mask``), the MPNet token
+    ids, which ``prompt_encoder`` encodes (router_embeddings); exactly one of the two."""
+    if (mpnet_embeddings is None) == (router_ids is None):
+        raise ValueError("give exactly one of mpnet_embeddings and router_ids")
+    if router_ids is None and router_attention_mask is not None:
+        raise ValueError("router_attention_mask needs router_ids")
+    if router_ids is not None:
+        mpnet_embeddings = router_embeddings(prompt_encoder, router_ids, router_attention_mask)
     from .vae import randn_tensor
     schedule = schedule or NoiseSchedule()
     latents = vae.encode_latents(pixel_values, generator=generator)

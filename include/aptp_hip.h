@@ -460,6 +460,74 @@ typedef struct {
 
 int aptp_token_embed(const AptpTokenEmbedParams* p, aptp_stream_t stream);
 
+/*
+ * Bidirectional self-attention with a relative-position bias and a key padding mask, head_dim 64 (transformers
+ * MPNetSelfAttention with the position_bias of MPNetEncoder.compute_position_bias and the extended attention mask), the
+ * self-attention of the router's prompt encoder (sentence-transformers/all-mpnet-base-v2, pdm/utils/data_utils.py:130-155):
+ *     o[b, i, h] = softmax_j(q[b, i, h] . k[b, j, h] * scale + relbias[h, j - i + L - 1] + (key_mask[b, j] ? 0 : -inf)) v[b, j, h]
+ * relbias fp32 [heads, 2L - 1] contiguous (the bias depends on j - i only); key_mask fp32 [B, L] contiguous, any 0 / non-zero
+ * pattern (not only a prefix), or NULL for "all valid".  A masked key gets weight exactly 0 whenever the row has a valid key
+ * (its K and V are not even read into the contraction).  Query rows at or past the sample's last valid key are padding and are
+ * written as zeros (a sample whose mask is all zero: every row zero); other masked query rows get finite values nobody reads.
+ * Same strided layout as aptp_attention_causal: element (b, l, h, d) at ptr + b*stride_b + l*stride_l + h*64 + d (a fused
+ * q|k|v linear output is read in place).  1 <= L <= 512 (else APTP_EINVAL); row strides >= heads*64; strides multiples of 8
+ * elements (4 for io_f32), pointers 16-byte aligned.  bf16 MFMA contractions, fp32 softmax statistics.
+ */
+typedef struct {
+  const void* q; int64_t q_stride_b, q_stride_l;
+  const void* k; int64_t k_stride_b, k_stride_l;
+  const void* v; int64_t v_stride_b, v_stride_l;
+  void* o; int64_t o_stride_b, o_stride_l;
+  const float* relbias;    /* fp32 [heads, 2L - 1] */
+  const float* key_mask;   /* fp32 [B, L] or NULL */
+  int32_t B, heads, L;
+  float scale;       /* > 0 */
+  int32_t io_f32;    /* fp32 PARITY path: q, k, v, o are fp32, exact-fp32 arithmetic; never benchmarked */
+} AptpAttentionBiasParams;
+
+int aptp_attention_bias(const AptpAttentionBiasParams* p, aptp_stream_t stream);
+
+/*
+ * MPNet embeddings (transformers MPNetEmbeddings in eval mode) in one launch, per token row (b, l):
+ *     pos_id = (ids[b, l] != pad_id ? #{j <= l : ids[b, j] != pad_id} : 0) + pad_id        (create_position_ids_from_input_ids)
+ *     out    = LayerNorm(word[ids[b, l]] + pos[pos_id]) * gamma + beta                      (fp32 sum, fp32 two-pass statistics)
+ * rounded once to bf16 (fp32 out when out_f32).  ids int64 [B, L] contiguous; word fp32 [vocab, C], pos fp32 [pos_rows, C],
+ * gamma / beta fp32 [C], all contiguous; C a multiple of 8, <= 2048; L + pad_id < pos_rows (else APTP_EINVAL).  An id outside
+ * [0, vocab) is never used as an index: its row is written as NaN.
+ */
+typedef struct {
+  const int64_t* ids;
+  const float* word;
+  const float* pos;
+  const float* gamma;
+  const float* beta;
+  void* out; int64_t ldo;     /* [B*L, ldo], ldo >= C, a multiple of 8 */
+  int32_t B, L, C, vocab;
+  int32_t pos_rows;           /* rows of pos (max_position_embeddings) */
+  int32_t pad_id;
+  int32_t out_f32;
+  float eps;
+} AptpEmbedLnParams;
+
+int aptp_embed_ln(const AptpEmbedLnParams* p, aptp_stream_t stream);
+
+/*
+ * Masked mean over the tokens (get_mpnet_embeddings, pdm/utils/data_utils.py:130-155; NOT L2-normalised):
+ *     out[b, c] = sum_l x[b, l, c] * mask[b, l] / max(sum_l mask[b, l], 1e-9)
+ * x bf16 (fp32 when x_f32) at x + b*x_stride_b + l*x_stride_l + c; mask fp32 [B, L] contiguous or NULL (all ones); out fp32
+ * [B, C] contiguous.  fp32 sums in one fixed order (no atomics): repeated runs are bit-identical.  Rows whose mask is 0 are
+ * not read.  C a multiple of 4, strides multiples of 4 elements.
+ */
+typedef struct {
+  const void* x; int64_t x_stride_b, x_stride_l;
+  const float* mask;
+  float* out;
+  int32_t B, L, C;
+  int32_t x_f32;
+} AptpMaskedMeanParams;
+
+int aptp_masked_mean(const AptpMaskedMeanParams* p, aptp_stream_t stream);
+
 /* Fused tail of a transformer block on the large-M levels (diffusers BasicTransformerBlock.norm3 -> ff (GEGLUGated +
  * Linear, pdm/models/unet/blocks.py:41-50,121-129,821-823) -> "+ hidden_states", then Transformer2DModel.proj_out and its
  * "+ residual", blocks.py:1294-1308) as ONE kernel per 64-token tile:
