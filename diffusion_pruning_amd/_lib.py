@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("APTP_LIB") or os.path.join(_HERE, "csrc", "libaptp_hip.so")
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_GELU = 0, 1, 2, 3
+ACT_QUICK_GELU = 5          # (4 is reserved: include/aptp_hip.h)
 TILE_AUTO, TILE_128x128, TILE_128x160, TILE_64x128, TILE_64x160, TILE_128x64, TILE_64x64 = range(7)
 (TILE_DMA_128x128, TILE_DMA_128x160, TILE_DMA_64x128, TILE_DMA_64x160, TILE_DMA_128x64, TILE_DMA_64x64) = range(7, 13)
 (TILE_DMA3_128x128, TILE_DMA3_128x160, TILE_DMA3_64x128, TILE_DMA3_64x160, TILE_DMA3_128x64, TILE_DMA3_64x64) = range(13, 19)
@@ -338,6 +339,44 @@ class AttentionBwdParams(Structure):
     ]
 
 
+class ImagePatchesParams(Structure):
+    _fields_ = [
+        ("x", c_void_p), ("nchw", c_int32),
+        ("B", c_int32), ("H", c_int32), ("W", c_int32),
+        ("S", c_int32), ("P", c_int32),
+        ("resize", c_int32),
+        ("mean", c_float * 3), ("std", c_float * 3),
+        ("out", c_void_p), ("ldo", c_int64),
+        ("out_f32", c_int32),
+    ]
+
+
+class VitEmbedLnParams(Structure):
+    _fields_ = [
+        ("patches", c_void_p), ("ldp", c_int64),
+        ("cls", c_void_p), ("pos", c_void_p), ("gamma", c_void_p), ("beta", c_void_p),
+        ("out", c_void_p), ("ldo", c_int64),
+        ("B", c_int32), ("T", c_int32), ("C", c_int32),
+        ("out_f32", c_int32),
+        ("eps", c_float),
+    ]
+
+
+class L2NormalizeParams(Structure):
+    _fields_ = [("x", c_void_p), ("ldx", c_int64), ("out", c_void_p), ("ldo", c_int64), ("n", c_int32), ("D", c_int32)]
+
+
+class MmdRbfParams(Structure):
+    _fields_ = [
+        ("x", c_void_p), ("ldx", c_int64),
+        ("y", c_void_p), ("ldy", c_int64),
+        ("n", c_int32), ("m", c_int32), ("D", c_int32),
+        ("sigma", c_float), ("scale", c_float),
+        ("workspace", c_void_p),
+        ("out", c_void_p),
+    ]
+
+
 # every symbol include/aptp_hip.h declares: (name, restype, argtypes)
 EXPORTS = [
     ("aptp_conv_gemm", c_int, [POINTER(ConvGemmParams), c_void_p]),
@@ -392,6 +431,11 @@ EXPORTS = [
     ("aptp_attention_bias", c_int, [POINTER(AttentionBiasParams), c_void_p]),
     ("aptp_embed_ln", c_int, [POINTER(EmbedLnParams), c_void_p]),
     ("aptp_masked_mean", c_int, [POINTER(MaskedMeanParams), c_void_p]),
+    ("aptp_image_patches", c_int, [POINTER(ImagePatchesParams), c_void_p]),
+    ("aptp_vit_embed_ln", c_int, [POINTER(VitEmbedLnParams), c_void_p]),
+    ("aptp_l2_normalize", c_int, [POINTER(L2NormalizeParams), c_void_p]),
+    ("aptp_mmd_rbf_workspace_bytes", c_int64, [c_int32, c_int32]),
+    ("aptp_mmd_rbf", c_int, [POINTER(MmdRbfParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

@@ -81,6 +81,8 @@ __device__ __forceinline__ float norm_cdf_f(float x, float* exp_mhx2) {
   return x >= 0.f ? 1.0f - half_erfc : half_erfc;
 }
 __device__ __forceinline__ float gelu_erf_f(float x) { return x * norm_cdf_f(x, nullptr); }
+// QuickGELU of OpenAI's CLIP checkpoints: x * sigmoid(1.702 x)
+__device__ __forceinline__ float quick_gelu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x)); }
 
 // Next-launch weight prefetch (AptpConvGemmParams.prefetch / AptpGroupNormParams.prefetch): touch one dword per 64-byte line
 // of slice j of nper of the xcd-th eighth of [ptr, ptr + bytes) by LDS-DMA into a 256-byte scratch row (no VGPRs; results

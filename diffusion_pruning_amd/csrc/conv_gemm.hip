@@ -1060,7 +1060,7 @@ int fill_kparams(const AptpConvGemmParams* p, KParams& k) {
   APTP_CHECK(p->cin_pad % BK == 0 && p->cin_pad >= p->Cin && p->cin_pad < p->Cin + BK, "conv_gemm: cin_pad (%d) != ceil(Cin/64)*64", p->cin_pad);
   APTP_CHECK(p->KH >= 1 && p->KW >= 1 && p->stride >= 1 && p->pad >= 0 && p->ups >= 0 && p->ups <= 2, "conv_gemm: bad filter geometry");
   APTP_CHECK(((uintptr_t)p->x % 16) == 0 && ((uintptr_t)p->w % 16) == 0 && ((uintptr_t)p->y % 8) == 0, "conv_gemm: pointer alignment");
-  APTP_CHECK(p->act >= APTP_ACT_NONE && p->act <= APTP_ACT_GELU, "conv_gemm: unknown act %d", p->act);
+  APTP_CHECK((p->act >= APTP_ACT_NONE && p->act <= APTP_ACT_GELU) || p->act == APTP_ACT_QUICK_GELU, "conv_gemm: unknown act %d", p->act);
   const int geglu = p->act == APTP_ACT_GEGLU;
   APTP_CHECK(!geglu || p->N % 32 == 0, "conv_gemm: GEGLU needs N %% 32 == 0");
   const int nout = geglu ? p->N / 2 : p->N;

@@ -162,6 +162,9 @@ __device__ __forceinline__ void epilogue_pre(const KParams& p, const RowCtx& rc,
   } else if (p.act == APTP_ACT_GELU) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = gelu_erf_f(h[r]);
+  } else if (p.act == APTP_ACT_QUICK_GELU) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = quick_gelu_f(h[r]);
   } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = h[r];

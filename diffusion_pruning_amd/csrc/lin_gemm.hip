@@ -31,8 +31,8 @@ typedef __attribute__((address_space(3))) void* lds_ptr;
 typedef const __attribute__((address_space(1))) void* gbl_ptr;
 
 // GELU: the fc1 + GELU launches of the CLIP text encoder get their own instantiation, so the code of every other launch is
-// the code it was before APTP_ACT_GELU existed
-template <int BM, int BN, int WM, int WN, int STAGES, int KU, bool GEGLU = false, bool GELU = false>
+// the code it was before APTP_ACT_GELU existed; GELU == 2 is the QuickGELU instantiation of the CLIP image encoder's fc1
+template <int BM, int BN, int WM, int WN, int STAGES, int KU, bool GEGLU = false, int GELU = 0>
 __global__ __launch_bounds__(WM * WN * 64) void lin_gemm_kernel(const KParams p) {
   constexpr int NW = WM * WN, NT = NW * 64, RPP = NT / 8;      // RPP: tile rows one LDS-DMA pass of the workgroup covers
   constexpr int WTM = BM / WM, WTN = BN / WN, MF = WTM / 16, NF = WTN / 16;
@@ -321,9 +321,13 @@ __global__ __launch_bounds__(WM * WN * 64) void lin_gemm_kernel(const KParams p)
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = v[e] * gelu_erf_f(gt[e] + cbg[e]);
     } else
-    if constexpr (GELU) {
+    if constexpr (GELU == 1) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = gelu_erf_f(v[e]);
+    } else
+    if constexpr (GELU == 2) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = quick_gelu_f(v[e]);
     } else
     if (p.act == APTP_ACT_SILU) {
 #pragma unroll
@@ -417,7 +421,8 @@ void launch_lin(KParams k, hipStream_t s) {
     if (k.pf_per < 1) k.pf_per = 1;
   }
   if (geglu) hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, true>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
-  else if (k.act == APTP_ACT_GELU) hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, false, true>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
+  else if (k.act == APTP_ACT_GELU) hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, false, 1>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
+  else if (k.act == APTP_ACT_QUICK_GELU) hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, false, 2>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
   else hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, false>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
 }
 

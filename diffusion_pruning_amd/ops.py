@@ -19,6 +19,7 @@ from . import _lib
 from ._lib import ImageInParams, LatentDistParams, UnetEpilogueParams, UnetPrologueParams
 from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F401
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
+from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1129,6 +1130,117 @@ def masked_mean(x: torch.Tensor, mask: Optional[torch.Tensor] = None, out: Optio
     p.B, p.L, p.C, p.x_f32 = B, L, C, int(x.dtype == torch.float32)
     _lib.check(lib.aptp_masked_mean(ctypes.byref(p), _stream()), "aptp_masked_mean")
     return out
+
+
+# OpenAI CLIP's image normalisation (transformers OPENAI_CLIP_MEAN / OPENAI_CLIP_STD, the CLIPImageProcessor defaults)
+CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def image_patches(x: torch.Tensor, size: int, patch: int, *, resize: bool = True, mean=CLIP_IMAGE_MEAN, std=CLIP_IMAGE_STD,
+                  out_f32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Image front end of the CLIP image encoder.  resize=True: fp32 images in [0, 1], [B, H, W, 3] or [B, 3, H, W] (told apart
+    by which of the two dims is 3; [B, 3, H, 3] is refused) -> bicubic resize to size x size (F.interpolate semantics),
+    (v - mean) / std, patchify.  resize=False: x is pixel_values [B, 3, size, size], only patchified.  Returns bf16 (fp32 when
+    out_f32) [B * (size / patch)^2, Kpad], Kpad = roundup64(3 patch^2), row element order (c, py, px), zero tail."""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError(f"image_patches: x must be a contiguous CUDA fp32 4-D tensor, got {x.dtype} {tuple(x.shape)}")
+    if size < 1 or patch < 1 or size % patch != 0:
+        raise ValueError(f"image_patches: size {size} must be a positive multiple of patch {patch}")
+    first, last = x.shape[1] == 3, x.shape[3] == 3
+    if first == last:
+        raise ValueError(f"image_patches: cannot tell [B, H, W, 3] from [B, 3, H, W] in shape {tuple(x.shape)}")
+    nchw = first
+    B = x.shape[0]
+    H, W = (x.shape[2], x.shape[3]) if nchw else (x.shape[1], x.shape[2])
+    if not resize and not (nchw and H == size and W == size):
+        raise ValueError(f"image_patches: resize=False takes pixel_values [B, 3, {size}, {size}], got {tuple(x.shape)}")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError("image_patches: empty input")
+    G = size // patch
+    kpad = round_up(3 * patch * patch, 64)
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty(B * G * G, kpad, dtype=odt, device=x.device)
+    elif tuple(out.shape) != (B * G * G, kpad) or out.dtype != odt or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"image_patches: out must be a contiguous {odt} [{B * G * G}, {kpad}] tensor on {x.device}")
+    p = ImagePatchesParams()
+    p.x, p.nchw, p.B, p.H, p.W, p.S, p.P, p.resize = x.data_ptr(), int(nchw), B, H, W, size, patch, int(resize)
+    for c in range(3):
+        p.mean[c], p.std[c] = float(mean[c]), float(std[c])
+    p.out, p.ldo, p.out_f32 = out.data_ptr(), kpad, int(out_f32)
+    _lib.check(lib.aptp_image_patches(ctypes.byref(p), _stream()), "aptp_image_patches")
+    return out
+
+
+def vit_embed_ln(patches: torch.Tensor, B: int, cls: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                 eps: float = 1e-5, out_f32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 patch GEMM output [B * (T - 1), C] -> bf16 (fp32 when out_f32) [B, T, C] = LayerNorm([cls | patches] + pos)
+    (transformers CLIPVisionEmbeddings + pre_layrnorm): fp32 sum and statistics, one rounding.  cls fp32 [C], pos fp32 [T, C]."""
+    lib = _lib.load()
+    if patches.dtype != torch.float32 or patches.dim() != 2 or patches.stride(1) != 1 or not patches.is_cuda:
+        raise ValueError(f"vit_embed_ln: patches must be a CUDA fp32 [rows, C] tensor, got {patches.dtype} {tuple(patches.shape)}")
+    rows, C = patches.shape
+    T = pos.shape[0]
+    if B < 1 or T < 2 or rows != B * (T - 1):
+        raise ValueError(f"vit_embed_ln: {rows} patch rows do not make {B} samples of {T} - 1 tokens")
+    for t, nm, shp in ((cls, "cls", (C,)), (pos, "pos", (T, C)), (gamma, "gamma", (C,)), (beta, "beta", (C,))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shp or not t.is_contiguous() or t.device != patches.device:
+            raise ValueError(f"vit_embed_ln: {nm} must be a contiguous fp32 {shp} tensor on the patches' device")
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty(B, T, C, dtype=odt, device=patches.device)
+    elif tuple(out.shape) != (B, T, C) or out.dtype != odt or not out.is_contiguous():
+        raise ValueError(f"vit_embed_ln: out must be a contiguous {odt} [{B}, {T}, {C}] tensor")
+    p = VitEmbedLnParams()
+    p.patches, p.ldp = patches.data_ptr(), patches.stride(0) if rows > 1 else max(patches.stride(0), C)
+    p.cls, p.pos, p.gamma, p.beta = cls.data_ptr(), pos.data_ptr(), gamma.data_ptr(), beta.data_ptr()
+    p.out, p.ldo, p.B, p.T, p.C, p.out_f32, p.eps = out.data_ptr(), C, B, T, C, int(out_f32), eps
+    _lib.check(lib.aptp_vit_embed_ln(ctypes.byref(p), _stream()), "aptp_vit_embed_ln")
+    return out
+
+
+def l2_normalize(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [n, D] -> rows divided by their Euclidean norm (no epsilon, as the reference); out may be x itself"""
+    lib = _lib.load()
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous() or not x.is_cuda or x.shape[0] < 1:
+        raise ValueError(f"l2_normalize: x must be a contiguous CUDA fp32 [n, D] tensor, got {x.dtype} {tuple(x.shape)}")
+    n, D = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != (n, D) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"l2_normalize: out must be a contiguous fp32 [{n}, {D}] tensor on {x.device}")
+    p = L2NormalizeParams()
+    p.x, p.ldx, p.out, p.ldo, p.n, p.D = x.data_ptr(), D, out.data_ptr(), D, n, D
+    _lib.check(lib.aptp_l2_normalize(ctypes.byref(p), _stream()), "aptp_l2_normalize")
+    return out
+
+
+MMD_SIGMA = 10.0          # bandwidth of CMMD's Gaussian kernel and its readability scale (cmmd-pytorch/distance.py:20-25)
+MMD_SCALE = 1000.0
+
+
+def mmd_rbf(x: torch.Tensor, y: torch.Tensor, sigma: float = MMD_SIGMA, scale: float = MMD_SCALE, parts: bool = False) -> torch.Tensor:
+    """scale * (mean k(x, x) + mean k(y, y) - 2 mean k(x, y)), k(a, b) = exp(-|a - b|^2 / (2 sigma^2)), for fp32 x [n, D] and
+    y [m, D] on the device: an fp64 scalar tensor (parts: the fp64 [4] the kernel writes, include/aptp_hip.h).  The kernel
+    matrices are never stored; the only allocation is the workspace of 4 (n + m) bytes and 4 bytes per 128 x 128 tile."""
+    lib = _lib.load()
+    for t, nm in ((x, "x"), (y, "y")):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda or t.shape[0] < 1:
+            raise ValueError(f"mmd_rbf: {nm} must be a contiguous CUDA fp32 [rows, D] tensor, got {t.dtype} {tuple(t.shape)}")
+    if x.shape[1] != y.shape[1] or x.shape[1] % 4 != 0 or x.shape[1] < 4 or x.device != y.device:
+        raise ValueError(f"mmd_rbf: x and y need the same width, a multiple of 4, on one device; got {tuple(x.shape)} and {tuple(y.shape)}")
+    if not sigma > 0:
+        raise ValueError("mmd_rbf: sigma must be positive")
+    n, m, D = x.shape[0], y.shape[0], x.shape[1]
+    ws = torch.empty(lib.aptp_mmd_rbf_workspace_bytes(n, m) // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty(4, dtype=torch.float64, device=x.device)
+    p = MmdRbfParams()
+    p.x, p.ldx, p.y, p.ldy, p.n, p.m, p.D = x.data_ptr(), D, y.data_ptr(), D, n, m, D
+    p.sigma, p.scale, p.workspace, p.out = sigma, scale, ws.data_ptr(), out.data_ptr()
+    _lib.check(lib.aptp_mmd_rbf(ctypes.byref(p), _stream()), "aptp_mmd_rbf")
+    return out if parts else out[0]
 
 
 # ------------------------------------------------------------------------------------------------------------------

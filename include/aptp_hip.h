@@ -34,8 +34,10 @@ enum {
 };
 
 /* APTP_ACT_GELU: exact (erf) GELU of the biased value, the hidden_act "gelu" of CLIP's text encoder (transformers CLIPMLP:
- * fc1 -> GELU -> fc2).  aptp_conv_gemm refuses any other value with APTP_EINVAL. */
-enum { APTP_ACT_NONE = 0, APTP_ACT_SILU = 1, APTP_ACT_GEGLU = 2, APTP_ACT_GELU = 3 };
+ * fc1 -> GELU -> fc2).  APTP_ACT_QUICK_GELU: v * sigmoid(1.702 v) of the biased value, the hidden_act "quick_gelu" of OpenAI's
+ * CLIP checkpoints (transformers QuickGELUActivation; the vision tower CMMD embeds with, cmmd-pytorch/embedding.py:38).  Its value
+ * is 5: 4 is reserved and, like any other value, refused by aptp_conv_gemm with APTP_EINVAL. */
+enum { APTP_ACT_NONE = 0, APTP_ACT_SILU = 1, APTP_ACT_GEGLU = 2, APTP_ACT_GELU = 3, APTP_ACT_QUICK_GELU = 5 };
 
 /*
  * Implicit-GEMM convolution / linear:  y[m, n] = epilogue( sum_{tap,c} x[pix(m,tap), c] * w[n, tap, c] )
@@ -52,7 +54,8 @@ enum { APTP_ACT_NONE = 0, APTP_ACT_SILU = 1, APTP_ACT_GEGLU = 2, APTP_ACT_GELU =
  *   v += bias[n]; v += rowbias[b, n]                      (conv bias; + time_emb_proj(SiLU(temb)), blocks.py:342-343)
  *   v *= colgate[b % gate_B, n / gate_group]              (WidthGate, gates.py:15-21; blocks.py:345-348, 250-255)
  *   act: SiLU, or GEGLU on (h,g) column pairs: h * gelu_erf(g)   (blocks.py:41-50; gate applied to both halves),
- *        or GELU: gelu_erf(v)    (CLIPMLP.fc1 + activation_fn; split-K: applied by whichever launch sums the K-slices)
+ *        or GELU: gelu_erf(v), or QUICK_GELU: v * sigmoid(1.702 v)    (CLIPMLP.fc1 + activation_fn; split-K: applied by
+ *        whichever launch sums the K-slices)
  *   v += corr[(b % corr_B), border_class(oy,ox), n]       (gated-vs-pruned GroupNorm-beta term)
  *   v += residual[m, n]                                   (blocks.py:369, 799, 818, 849, 1308)
  *   v = (1-d[b % depth_B]) * depth_in[m, n] + d * v       (DepthGate, gates.py:36-42; blocks.py:577-582,1345-1348)
@@ -782,6 +785,66 @@ typedef struct {
 int aptp_attention_bwd_q_split(const AptpAttentionBwdParams* p);
 size_t aptp_attention_bwd_workspace_bytes(const AptpAttentionBwdParams* p, int32_t q_split);
 int aptp_attention_bwd(const AptpAttentionBwdParams* p, aptp_stream_t stream);
+
+/* Image front end of the CLIP image encoder: what cmmd-pytorch/embedding.py:26-30 (_resize_bicubic) and :57-65 (the
+ * CLIPImageProcessor call with do_normalize only) do on the host, and the unfold the patch convolution of transformers'
+ * CLIPVisionEmbeddings implies, in one launch.  x: fp32 images in [0, 1], [B, H, W, 3] (nchw = 0, CMMD's array format) or
+ * [B, 3, H, W] (nchw = 1, the pipeline's "pt" output), any H and W.
+ *   resize = 1: bicubic resize to S x S with F.interpolate(mode="bicubic") semantics (A = -0.75, align_corners = False, no
+ *               antialiasing, border indices clamped, overshoot not clamped), then (v - mean[c]) / std[c];
+ *   resize = 0: x is already preprocessed pixel_values [B, 3, S, S] (nchw = 1, H = W = S) and is only patchified.
+ * out: [B * (S/P)^2, ldo] with ldo = ceil(3 P^2 / 64) * 64; row (b, gy, gx) holds patch (gy, gx) of image b in the element order
+ * of patch_embedding.weight.flatten(1) (c, py, px), columns [3 P^2, ldo) are written as zeros: the patch convolution is a plain
+ * linear layer without bias on these rows.  bf16, or fp32 when out_f32. */
+typedef struct {
+  const float* x; int32_t nchw;
+  int32_t B, H, W;
+  int32_t S, P;
+  int32_t resize;
+  float mean[3], std[3];
+  void* out; int64_t ldo;
+  int32_t out_f32;
+} AptpImagePatchesParams;
+int aptp_image_patches(const AptpImagePatchesParams* p, aptp_stream_t stream);
+
+/* CLIPVisionEmbeddings + pre_layrnorm (transformers modeling_clip.py, CLIPVisionTransformer.forward): row 0 of every sample is
+ * class_embedding, row 1 + t is row t of the patch GEMM's fp32 output; position_embedding is added and the LayerNorm applied in
+ * fp32, with one rounding to the residual stream (bf16, or fp32 when out_f32).  The counterpart of aptp_embed_ln.
+ * patches fp32 [B * (T - 1), >= C] (row stride ldp), cls fp32 [C], pos fp32 [T, C], out [B, T, C] (row stride ldo).
+ * C a multiple of 8, at most 2048. */
+typedef struct {
+  const float* patches; int64_t ldp;
+  const float* cls; const float* pos; const float* gamma; const float* beta;
+  void* out; int64_t ldo;
+  int32_t B, T, C;
+  int32_t out_f32;
+  float eps;
+} AptpVitEmbedLnParams;
+int aptp_vit_embed_ln(const AptpVitEmbedLnParams* p, aptp_stream_t stream);
+
+/* Rows of an fp32 [n, D] matrix divided by their Euclidean norm (cmmd-pytorch/embedding.py:70, pdm/utils/clip_utils.py:160-161;
+ * no epsilon, as there).  D a multiple of 4; x and out may be the same memory. */
+typedef struct { const float* x; int64_t ldx; float* out; int64_t ldo; int32_t n, D; } AptpL2NormalizeParams;
+int aptp_l2_normalize(const AptpL2NormalizeParams* p, aptp_stream_t stream);
+
+/* The MMD statistic of cmmd-pytorch/distance.py:28-64 with the Gaussian kernel k(a, b) = exp(-|a - b|^2 / (2 sigma^2)):
+ *   out[0] = scale * (mean k(x, x) + mean k(y, y) - 2 mean k(x, y))
+ * for fp32 x [n, D] and y [m, D].  The Gram tiles (v_mfma_f32_16x16x4_f32: fp32 operands), the squared distances and 1 - k =
+ * -expm1(-d^2 / (2 sigma^2)) are formed and summed inside 128 x 128 tiles; no n x n, n x m or m x m matrix is stored.  Every
+ * tile writes one fp32 partial to the workspace; one workgroup then adds them in a fixed order in fp64: bit-identical from run to
+ * run.  (1 - k is summed rather than k: the result is about 1e-4 of its three terms.)
+ * out: fp64 [4] = the statistic, mean(1 - k_xx), mean(1 - k_yy), mean(1 - k_xy).
+ * workspace: aptp_mmd_rbf_workspace_bytes(n, m) bytes, 16-byte aligned.  n, m >= 1; D a multiple of 4; ldx, ldy multiples of 4. */
+typedef struct {
+  const float* x; int64_t ldx;
+  const float* y; int64_t ldy;
+  int32_t n, m, D;
+  float sigma, scale;
+  void* workspace;
+  double* out;
+} AptpMmdRbfParams;
+int64_t aptp_mmd_rbf_workspace_bytes(int32_t n, int32_t m);
+int aptp_mmd_rbf(const AptpMmdRbfParams* p, aptp_stream_t stream);
 
 const char* aptp_last_error(void);
 int aptp_version(void);

@@ -1,0 +1,375 @@
+"""The HIP CLIP image encoder and the image metrics on the GPU: the QuickGELU epilogue on every tile the linear path accepts
+(and split-K), the image front end against F.interpolate + normalise + unfold, the class / position embedding + pre_layrnorm
+kernel, ops.attention at the ragged sequence lengths of the ViTs, the tiny fixture and the full-size encoders against the CPU
+oracle (tests/clip_vision_oracle.py) in bf16 and on the fp32 parity path, graph replay, determinism, aptp_mmd_rbf against the fp64
+oracle (value, memory, determinism), the CLIP score and CMMD end to end.  Margins go through tests.margins.check."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import clip_vision_oracle as O
+from tests.helpers import rel_l2
+from tests.margins import check
+
+pytestmark = pytest.mark.gpu
+
+LIN_BF16_TOL = 4e-3
+LIN_F32_TOL = 1e-5
+ATTN_BF16_TOL = 6e-3
+ATTN_F32_TOL = 1e-5
+ENC_BF16_TOL = 2e-2
+ENC_F32_TOL = 1e-4
+# absolute bound of the MMD statistic: the granularity of the reference's own fp32 result -- three fp32 means of values just
+# under 1 (ulp 2^-24 below 1, so 2^-23 after the subtraction), weighted 1, 1, 2 and scaled by 1000
+MMD_BOUND = 1000 * 4 * 2.0 ** -23
+HALO_TILES = (43, 44)
+TINY = dict(hidden_size=128, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2, patch_size=14, image_size=56,
+            projection_dim=64)
+VISION_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_vision_tiny.npz")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# QuickGELU epilogue (APTP_ACT_QUICK_GELU)
+# ---------------------------------------------------------------------------------------------------------------------
+def _qgelu_case(cuda, dtype, seed, M=154, K=256, N=512):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(2, M // 2, K, generator=g)
+    w = torch.randn(N, K, generator=g) * K ** -0.5
+    b = torch.randn(N, generator=g) * 0.3
+    res = torch.randn(2, M // 2, N, generator=g)
+    if dtype == torch.bfloat16:
+        x, w, res = x.to(torch.bfloat16).float(), w.to(torch.bfloat16).float(), res.to(torch.bfloat16).float()
+    v = x.double() @ w.double().t() + b.double()
+    ref = v * torch.sigmoid(1.702 * v) + res.double()
+    return x.to(dtype).to(cuda), w, b, res.to(dtype).to(cuda), ref
+
+
+@pytest.mark.parametrize("general", [False, True])
+def test_quick_gelu_linear_every_tile_bf16(cuda, monkeypatch, general):
+    """every tile: the lean linear kernel where it takes the launch, and (general=True) the general register-staged / LDS-DMA /
+    stream-K kernels; the halo tiles refuse a linear layer"""
+    from diffusion_pruning_amd import ops
+    from diffusion_pruning_amd._lib import AptpError
+    assert ops.ACT_QUICK_GELU == 5
+    monkeypatch.setattr(ops, "EPILOGUE", 2 if general else 0)
+    x, w, b, res, ref = _qgelu_case(cuda, torch.bfloat16, 21)
+    pw = ops.pack_weight(w, b, device=cuda)
+    for tile in range(1, 74):
+        if tile in HALO_TILES:
+            with pytest.raises(AptpError):
+                ops.linear(x, pw, act=ops.ACT_QUICK_GELU, residual=res, tile=tile)
+            continue
+        y = ops.linear(x, pw, act=ops.ACT_QUICK_GELU, residual=res, tile=tile)
+        torch.cuda.synchronize()
+        check(rel_l2(y, ref), LIN_BF16_TOL, f"QuickGELU linear bf16 tile {tile}{' general' if general else ''}")
+    y = ops.linear(x, pw, act=ops.ACT_QUICK_GELU, residual=res)
+    check(rel_l2(y, ref), LIN_BF16_TOL, "QuickGELU linear bf16 auto tile")
+    # and it is not the erf GELU, which misses this reference by more than the tolerance
+    assert rel_l2(ops.linear(x, pw, act=ops.ACT_GELU, residual=res), ref) > LIN_BF16_TOL
+
+
+@pytest.mark.parametrize("split_k", [2, 4, 8])
+@pytest.mark.parametrize("in_kernel", [True, False])
+def test_quick_gelu_linear_split_k_bf16(cuda, monkeypatch, split_k, in_kernel):
+    """QuickGELU after the K-slices are summed, on every tile that takes a linear layer: by the last-arriving workgroup or by
+    the reduce launch"""
+    from diffusion_pruning_amd import ops
+    monkeypatch.setattr(ops, "SPLITK_IN_KERNEL", in_kernel)
+    x, w, b, res, ref = _qgelu_case(cuda, torch.bfloat16, 22, K=1024)
+    pw = ops.pack_weight(w, b, device=cuda)
+    for tile in (t for t in range(1, 74) if t not in HALO_TILES):
+        y = ops.linear(x, pw, act=ops.ACT_QUICK_GELU, residual=res, tile=tile, split_k=split_k)
+        torch.cuda.synchronize()
+        check(rel_l2(y, ref), LIN_BF16_TOL, f"QuickGELU linear bf16 tile {tile} split_k {split_k} in_kernel {in_kernel}")
+
+
+@pytest.mark.parametrize("split_k", [1, 2, 8])
+def test_quick_gelu_linear_fp32_parity(cuda, monkeypatch, split_k):
+    from diffusion_pruning_amd import ops
+    monkeypatch.setattr(ops, "ACT_DTYPE", torch.float32)
+    x, w, b, res, ref = _qgelu_case(cuda, torch.float32, 23, K=512)
+    pw = ops.pack_weight(w, b, device=cuda)
+    for tile in range(0, 7):
+        y = ops.linear(x, pw, act=ops.ACT_QUICK_GELU, residual=res, tile=tile, split_k=split_k)
+        torch.cuda.synchronize()
+        check(rel_l2(y, ref), LIN_F32_TOL, f"QuickGELU linear fp32 tile {tile} split_k {split_k}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# aptp_image_patches
+# ---------------------------------------------------------------------------------------------------------------------
+def _patch_ref(img_nhwc, size, patch):
+    """the oracle: F.interpolate + normalise + unfold, fp32 as the reference runs it"""
+    return O.patch_rows(O.preprocess(img_nhwc, size, dtype=torch.float32), patch)
+
+
+@pytest.mark.parametrize("H,W,size,patch", [(512, 512, 336, 14), (256, 256, 336, 14), (336, 336, 336, 14), (192, 320, 224, 32)])
+@pytest.mark.parametrize("nchw", [False, True])
+def test_image_patches_against_interpolate_normalise_unfold(cuda, H, W, size, patch, nchw):
+    from diffusion_pruning_amd import ops
+    g = torch.Generator().manual_seed(H + W + size)
+    img = torch.rand(2, H, W, 3, generator=g)
+    ref = _patch_ref(img, size, patch)
+    K = 3 * patch * patch
+    x = (img.permute(0, 3, 1, 2) if nchw else img).contiguous().to(cuda)
+    y32 = ops.image_patches(x, size, patch, out_f32=True)
+    y16 = ops.image_patches(x, size, patch)
+    torch.cuda.synchronize()
+    kpad = (K + 63) // 64 * 64
+    assert tuple(y32.shape) == tuple(y16.shape) == (2 * (size // patch) ** 2, kpad) and y32.dtype == torch.float32 and y16.dtype == torch.bfloat16
+    check(rel_l2(y32[:, :K], ref), LIN_F32_TOL, f"image_patches fp32 {H}x{W}->{size} nchw={nchw}")
+    check(rel_l2(y16[:, :K], ref), LIN_BF16_TOL, f"image_patches bf16 {H}x{W}->{size} nchw={nchw}")
+    if kpad > K:
+        assert torch.count_nonzero(y32[:, K:]) == 0 and torch.count_nonzero(y16[:, K:]) == 0      # exact zeros in the padding
+    assert torch.equal(ops.image_patches(x, size, patch, out_f32=True), y32)
+
+
+@pytest.mark.parametrize("size,patch", [(56, 14), (336, 14), (224, 32)])
+def test_image_patches_without_resize_is_unfold_bit_for_bit(cuda, size, patch):
+    from diffusion_pruning_amd import ops
+    px = torch.randn(2, 3, size, size, generator=torch.Generator().manual_seed(size))
+    ref = O.patch_rows(px, patch)
+    K = 3 * patch * patch
+    y32 = ops.image_patches(px.to(cuda), size, patch, resize=False, out_f32=True)
+    y16 = ops.image_patches(px.to(cuda), size, patch, resize=False)
+    torch.cuda.synchronize()
+    assert torch.equal(y32[:, :K].cpu(), ref) and torch.equal(y16[:, :K].cpu(), ref.to(torch.bfloat16))
+    assert torch.count_nonzero(y32[:, K:]) == 0 and torch.count_nonzero(y16[:, K:]) == 0
+
+
+def test_image_patches_argument_checks(cuda):
+    from diffusion_pruning_amd import ops
+    x = torch.zeros(1, 20, 20, 3, device=cuda)
+    for bad in (lambda: ops.image_patches(x, 30, 14), lambda: ops.image_patches(x.cpu(), 28, 14), lambda: ops.image_patches(x.half(), 28, 14),
+                lambda: ops.image_patches(torch.zeros(1, 3, 20, 3, device=cuda), 28, 14), lambda: ops.image_patches(x, 28, 14, resize=False),
+                lambda: ops.image_patches(x, 28, 14, out=torch.zeros(4, 588, device=cuda))):
+        with pytest.raises(ValueError):
+            bad()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# aptp_vit_embed_ln, aptp_l2_normalize
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B,T,C", [(2, 17, 128), (2, 577, 1024), (3, 50, 768)])
+def test_vit_embed_ln_against_torch(cuda, B, T, C):
+    from diffusion_pruning_amd import ops
+    g = torch.Generator().manual_seed(B + T + C)
+    pe, cls, pos = torch.randn(B * (T - 1), C, generator=g), torch.randn(C, generator=g), torch.randn(T, C, generator=g)
+    gamma, beta = 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    x = torch.cat([cls.expand(B, 1, C), pe.view(B, T - 1, C)], 1) + pos
+    ref = F.layer_norm(x.double(), (C,), gamma.double(), beta.double(), 1e-5)
+    a = [t.to(cuda) for t in (pe, cls, pos, gamma, beta)]
+    y32 = ops.vit_embed_ln(a[0], B, *a[1:], out_f32=True)
+    y16 = ops.vit_embed_ln(a[0], B, *a[1:])
+    torch.cuda.synchronize()
+    check(rel_l2(y32, ref), LIN_F32_TOL, f"vit_embed_ln fp32 {B}x{T}x{C}")
+    check(rel_l2(y16, ref), LIN_BF16_TOL, f"vit_embed_ln bf16 {B}x{T}x{C}")
+    assert torch.equal(y16, y32.to(torch.bfloat16))                # one rounding: the bf16 output is the rounded fp32 one
+
+
+def test_l2_normalize(cuda):
+    from diffusion_pruning_amd import ops
+    x = torch.randn(37, 768, generator=torch.Generator().manual_seed(1)) * 3
+    y = ops.l2_normalize(x.to(cuda))
+    check(rel_l2(y, x.double() / x.double().norm(dim=1, keepdim=True)), LIN_F32_TOL, "l2_normalize")
+    z = x.to(cuda)
+    assert ops.l2_normalize(z, out=z) is z and torch.equal(z, y)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# ops.attention at the ViTs' sequence lengths (not multiples of 64)
+# ---------------------------------------------------------------------------------------------------------------------
+def _attn_ref(q, k, v, heads):
+    B, L, _ = q.shape
+    sh = lambda t: t.float().cpu().reshape(B, L, heads, 64).transpose(1, 2)      # noqa: E731
+    s = (sh(q) @ sh(k).transpose(-1, -2)) * 0.125
+    return (torch.softmax(s, dim=-1) @ sh(v)).transpose(1, 2).reshape(B, L, heads * 64)
+
+
+@pytest.mark.parametrize("L", [50, 577])
+@pytest.mark.parametrize("heads", [12, 16])
+@pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, ATTN_BF16_TOL), (torch.float32, ATTN_F32_TOL)])
+def test_attention_at_ragged_lengths(cuda, L, heads, dtype, tol):
+    from diffusion_pruning_amd import ops
+    g = torch.Generator().manual_seed(L * 100 + heads)
+    C = heads * 64
+    qkv = (torch.randn(2, L, 3 * C, generator=g) * 1.5).to(dtype).to(cuda)       # the fused q|k|v layout, read in place
+    q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+    o = ops.attention(q, k, v, heads)
+    torch.cuda.synchronize()
+    check(rel_l2(o, _attn_ref(q, k, v, heads)), tol, f"attention {dtype} L={L} heads={heads}")
+    assert torch.equal(ops.attention(q, k, v, heads), o)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the encoder
+# ---------------------------------------------------------------------------------------------------------------------
+def _tiny_model(cuda, act):
+    from diffusion_pruning_amd.image_encoder import CLIPVisionConfig, CLIPVisionModelWithProjection
+    z = np.load(VISION_GOLDEN)
+    params = {k: torch.from_numpy(z[k].astype(np.float32)) for k in z.files
+              if not k.startswith(("pixel_values", "last_hidden_state_", "image_embeds_"))}
+    m = CLIPVisionModelWithProjection(CLIPVisionConfig(**TINY, hidden_act=act)).load_vision_state_dict(params).to(cuda)
+    return z, m
+
+
+@pytest.mark.parametrize("act", ["quick_gelu", "gelu"])
+@pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, ENC_BF16_TOL), (torch.float32, ENC_F32_TOL)])
+def test_tiny_fixture_through_the_hip_model(cuda, monkeypatch, act, dtype, tol):
+    from diffusion_pruning_amd import ops
+    monkeypatch.setattr(ops, "ACT_DTYPE", dtype)
+    z, m = _tiny_model(cuda, act)
+    out = m(torch.from_numpy(z["pixel_values"]).to(cuda))
+    torch.cuda.synchronize()
+    assert out.image_embeds.dtype == torch.float32 and tuple(out.image_embeds.shape) == (2, 64)
+    assert out.last_hidden_state.dtype == torch.float32 and tuple(out.last_hidden_state.shape) == (2, 17, 128)
+    check(rel_l2(out.last_hidden_state, torch.from_numpy(z[f"last_hidden_state_{act}"])), tol, f"tiny ViT {act} {dtype} last_hidden_state")
+    check(rel_l2(out[0], torch.from_numpy(z[f"image_embeds_{act}"])), tol, f"tiny ViT {act} {dtype} image_embeds")
+    assert out[1] is out.last_hidden_state and m(torch.from_numpy(z["pixel_values"]).to(cuda), return_dict=False)[0].shape == (2, 64)
+
+
+def _full(cuda, which):
+    from diffusion_pruning_amd.image_encoder import CLIPVisionConfig, CLIPVisionModelWithProjection
+    cfg = CLIPVisionConfig() if which == "L14-336" else CLIPVisionConfig.vit_b_32()
+    m = CLIPVisionModelWithProjection(cfg).init_synthetic(0)
+    img = torch.rand(2, 96, 80, 3, generator=torch.Generator().manual_seed(7))
+    px = O.preprocess(img, cfg.image_size, dtype=torch.float32)
+    emb, h = O.clip_vision_forward(m.state_dict(), px, heads=cfg.num_attention_heads, layers=cfg.num_hidden_layers,
+                                   patch=cfg.patch_size, hidden_act=cfg.hidden_act)
+    return cfg, m.to(cuda), img, px, emb, h
+
+
+@pytest.mark.parametrize("which", ["L14-336", "B32"])
+def test_full_size_encoder_against_the_oracle(cuda, monkeypatch, which):
+    """ViT-L/14-336 (CMMD's model) and ViT-B/32 (the CLIP score's) under init_synthetic at B = 2: bf16 and the fp32 parity path,
+    from pixel_values and from raw images (the front end's resize), determinism, and replay of a captured encode"""
+    from diffusion_pruning_amd import ops
+    cfg, m, img, px, emb, h = _full(cuda, which)
+    pxd = px.to(cuda)
+    for dtype, tol in ((torch.float32, ENC_F32_TOL), (torch.bfloat16, ENC_BF16_TOL)):
+        monkeypatch.setattr(ops, "ACT_DTYPE", dtype)
+        out = m(pxd)
+        torch.cuda.synchronize()
+        check(rel_l2(out.last_hidden_state, h), tol, f"{which} {dtype} last_hidden_state")
+        check(rel_l2(out.image_embeds, emb), tol, f"{which} {dtype} image_embeds")
+        e2 = m.embed_images(img.to(cuda))
+        check(rel_l2(e2, emb), tol, f"{which} {dtype} image_embeds from raw images")
+        out2 = m(pxd)
+        assert torch.equal(out2.image_embeds, out.image_embeds) and torch.equal(out2.last_hidden_state, out.last_hidden_state)
+    # bf16: capture after the eager calls above, replay bit-equal, also on new pixels
+    graph = torch.cuda.CUDAGraph()
+    static = pxd.clone()
+    with torch.cuda.graph(graph):
+        cap = m(static)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(cap.image_embeds, out.image_embeds) and torch.equal(cap.last_hidden_state, out.last_hidden_state)
+    static.copy_(pxd.flip(0))
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(cap.image_embeds, out.image_embeds.flip(0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# aptp_mmd_rbf, the CLIP score, CMMD
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,m,D", O.MMD_CASES)
+@pytest.mark.parametrize("shift", O.MMD_SHIFTS)
+def test_mmd_rbf_against_the_fp64_oracle(cuda, n, m, D, shift):
+    from diffusion_pruning_amd import metrics, ops
+    x, y = O.cmmd_embeddings(n, m, D, shift)
+    ref = O.mmd(x, y)
+    xd, yd = torch.from_numpy(x).to(cuda), torch.from_numpy(y).to(cuda)
+    got = ops.mmd_rbf(xd, yd)
+    torch.cuda.synchronize()
+    assert got.dtype == torch.float64 and got.dim() == 0
+    print(f"mmd_rbf n={n} m={m} D={D} shift={shift}: {float(got):.9f} oracle {ref:.9f} abs err {abs(float(got) - ref):.3e}")
+    check(abs(float(got) - ref), MMD_BOUND, f"mmd_rbf n={n} m={m} D={D} shift={shift}")
+    check(abs(float(ops.mmd_rbf(xd, xd))), MMD_BOUND, f"mmd_rbf(x, x) n={n} D={D}")
+    assert torch.equal(ops.mmd_rbf(xd, yd, parts=True), ops.mmd_rbf(xd, yd, parts=True))           # bit-equal across runs
+    assert float(metrics.mmd(x, y)) == float(got) and float(metrics.mmd(xd, y)) == float(got)      # numpy and mixed inputs
+    # sigma and scale are parameters
+    check(abs(float(ops.mmd_rbf(xd, yd, sigma=5.0, scale=10.0)) - O.mmd(x, y, sigma=5.0, scale=10.0)), 10 * 4 * 2.0 ** -23,
+          f"mmd_rbf sigma=5 scale=10 n={n} m={m}")
+
+
+def test_mmd_rbf_never_stores_a_kernel_matrix(cuda):
+    """n = m = 16384, D = 768: one materialised Gram matrix alone would be 1 GiB; the call may allocate less than 64 MiB"""
+    from diffusion_pruning_amd import ops
+    g = torch.Generator(device=cuda).manual_seed(0)
+    x = F.normalize(torch.randn(16384, 768, device=cuda, generator=g) + 1.0)
+    y = F.normalize(torch.randn(16384, 768, device=cuda, generator=g) + 1.1)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    got = ops.mmd_rbf(x, y)
+    torch.cuda.synchronize()
+    rise = torch.cuda.max_memory_allocated() - before
+    print(f"mmd_rbf 16384 x 16384 x 768: {float(got):.6f}, peak allocation over the inputs {rise / 2 ** 20:.3f} MiB")
+    assert rise < 64 * 2 ** 20, rise
+    assert math.isfinite(float(got)) and float(got) > 0
+
+
+def test_clip_score_against_the_oracle(cuda):
+    from diffusion_pruning_amd import metrics
+    g = torch.Generator().manual_seed(3)
+    a, b = torch.randn(33, 512, generator=g), torch.randn(33, 512, generator=g)
+    b = b + 0.5 * a
+    ref = O.clip_score(a, b)
+    got = float(metrics.clip_score(a.to(cuda), b.to(cuda)))
+    check(abs(got - ref) / abs(ref), 1e-5, "clip_score")
+    check(abs(float(metrics.clip_score(a.numpy(), b.numpy(), logit_scale=2.5)) - O.clip_score(a, b, 2.5)) / abs(O.clip_score(a, b, 2.5)), 1e-5,
+          "clip_score numpy, logit_scale")
+
+
+# relative deviation of the bf16 path's CMMD from the fp64 oracle's on the two seeded image sets below, as measured on MI355X:
+# oracle 1.262166, bf16 path 1.262359, deviation 1.5221e-04 (the fp32 parity path: 1.262166, absolute error 1.0e-07).  It cannot
+# be derived, so the test asserts twice the measured value
+CMMD_BF16_MEASURED_REL = 1.5221e-4
+
+
+def _image_sets():
+    rs = np.random.RandomState(11)
+    base = rs.uniform(0.0, 1.0, (1, 40, 48, 3))
+    ref = np.clip(base * 0.5 + 0.5 * rs.uniform(0.0, 1.0, (24, 40, 48, 3)), 0.0, 1.0).astype(np.float32)
+    ev = np.clip(base * 0.5 + 0.5 * rs.uniform(0.0, 1.0, (20, 40, 48, 3)) ** 1.5, 0.0, 1.0).astype(np.float32)
+    return ref, ev
+
+
+def test_compute_cmmd_end_to_end(cuda):
+    """two seeded image sets through ClipEmbeddingModel (ViT-B/32, synthetic weights) and aptp_mmd_rbf against the oracle's
+    preprocess -> encoder -> normalise -> mmd in fp64"""
+    from diffusion_pruning_amd import metrics
+    from diffusion_pruning_amd.image_encoder import CLIPVisionConfig, CLIPVisionModelWithProjection
+    cfg = CLIPVisionConfig.vit_b_32()
+    m = CLIPVisionModelWithProjection(cfg).init_synthetic(1)
+    ref_img, ev_img = _image_sets()
+
+    def oracle_embed(imgs):
+        e = O.clip_vision_forward(m.state_dict(), O.preprocess(torch.from_numpy(imgs), cfg.image_size), heads=12, layers=12, patch=32)[0]
+        return e / e.norm(dim=1, keepdim=True)
+    er, ee = oracle_embed(ref_img), oracle_embed(ev_img)
+    want = O.mmd(er, ee)
+    m.to(cuda)
+    em32 = metrics.ClipEmbeddingModel(m, precision="fp32")
+    e32 = em32.embed(ref_img, batch_size=7)                       # 24 images in chunks of 7, 7, 7, 3
+    assert e32.dtype == torch.float32 and tuple(e32.shape) == (24, 512) and e32.is_cuda
+    check(rel_l2(e32, er), ENC_F32_TOL, "ClipEmbeddingModel.embed fp32 vs oracle")
+    check(float((e32.norm(dim=1) - 1).abs().max()), 1e-5, "embeddings are unit-norm")
+    assert torch.equal(em32.embed(torch.from_numpy(ref_img).to(cuda), batch_size=7), e32)          # tensor input, same chunks
+    # (other chunks give other GEMM row counts, so other tiles and summation orders: equal to fp32 rounding, not bit for bit)
+    check(rel_l2(em32.embed(ref_img, batch_size=32), er), ENC_F32_TOL, "ClipEmbeddingModel.embed fp32, one chunk, vs oracle")
+    got32 = float(metrics.compute_cmmd(ref_img, ev_img, em32, batch_size=8))
+    print(f"CMMD oracle {want:.6f}, fp32 parity path {got32:.6f} (abs err {abs(got32 - want):.3e})")
+    check(abs(got32 - want), MMD_BOUND, "compute_cmmd fp32 parity path vs oracle")
+    assert float(metrics.compute_cmmd(e32, ev_img, em32)) == got32                                  # precomputed reference embeddings
+    got16 = float(metrics.compute_cmmd(ref_img, ev_img, metrics.ClipEmbeddingModel(m, precision="bf16")))
+    rel = abs(got16 - want) / abs(want)
+    print(f"CMMD bf16 path {got16:.6f}: relative deviation from the oracle {rel:.4e}")
+    assert math.isfinite(got16)
+    check(rel, 2 * CMMD_BF16_MEASURED_REL, "compute_cmmd bf16 path, relative deviation vs oracle")
+    assert float(metrics.compute_cmmd(ref_img, ev_img, m)) == float(metrics.compute_cmmd(ref_img, ev_img, metrics.ClipEmbeddingModel(m)))
