@@ -377,6 +377,49 @@ class MmdRbfParams(Structure):
     ]
 
 
+class ImagePatchesPilParams(Structure):
+    _fields_ = [
+        ("x", c_void_p),
+        ("B", c_int32), ("H", c_int32), ("W", c_int32),
+        ("S", c_int32), ("P", c_int32),
+        ("xbounds", c_void_p), ("xweights", c_void_p), ("xk", c_int32),
+        ("ybounds", c_void_p), ("yweights", c_void_p), ("yk", c_int32),
+        ("scratch", c_void_p),
+        ("mean", c_float * 3), ("std", c_float * 3),
+        ("out", c_void_p), ("ldo", c_int64),
+        ("out_f32", c_int32),
+    ]
+
+
+EOS_ARGMAX, EOS_FIRST = 0, 1
+
+
+class EosPoolLnParams(Structure):
+    _fields_ = [
+        ("ids", c_void_p),
+        ("x", c_void_p), ("x_stride_b", c_int64), ("x_stride_l", c_int64),
+        ("gamma", c_void_p), ("beta", c_void_p),
+        ("out", c_void_p),
+        ("out_act", c_void_p), ("ldo_act", c_int64),
+        ("index_out", c_void_p),
+        ("B", c_int32), ("L", c_int32), ("C", c_int32),
+        ("eos_mode", c_int32), ("eos_token_id", c_int32),
+        ("x_f32", c_int32), ("act_f32", c_int32),
+        ("eps", c_float),
+    ]
+
+
+class PairedCosineParams(Structure):
+    _fields_ = [
+        ("a", c_void_p), ("lda", c_int64),
+        ("b", c_void_p), ("ldb", c_int64),
+        ("cos_out", c_void_p),
+        ("sum_out", c_void_p),
+        ("n", c_int32), ("D", c_int32),
+        ("accumulate", c_int32),
+    ]
+
+
 # every symbol include/aptp_hip.h declares: (name, restype, argtypes)
 EXPORTS = [
     ("aptp_conv_gemm", c_int, [POINTER(ConvGemmParams), c_void_p]),
@@ -436,6 +479,11 @@ EXPORTS = [
     ("aptp_l2_normalize", c_int, [POINTER(L2NormalizeParams), c_void_p]),
     ("aptp_mmd_rbf_workspace_bytes", c_int64, [c_int32, c_int32]),
     ("aptp_mmd_rbf", c_int, [POINTER(MmdRbfParams), c_void_p]),
+    ("aptp_image_patches_pil_size", c_int, [c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                            POINTER(c_int32)]),
+    ("aptp_image_patches_pil", c_int, [POINTER(ImagePatchesPilParams), c_void_p]),
+    ("aptp_eos_pool_ln", c_int, [POINTER(EosPoolLnParams), c_void_p]),
+    ("aptp_paired_cosine", c_int, [POINTER(PairedCosineParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

@@ -7,13 +7,16 @@
   * ``compute_cmmd(ref, eval_images, model)`` is cmmd-pytorch/compute_cmmd.py's ``compute_cmmd`` on arrays instead of folders
     (tools/compute_cmmd.py reads the folders);
   * ``clip_score(image_embeds, text_features)`` is ``logit_scale * mean_i cos(img_i, txt_i)`` as clip_utils.py:159-170 forms it
-    per batch, with the text features precomputed (the reference reads them from the ``.npy`` files clip_features.py wrote).
+    per batch, with the text features precomputed (the reference reads them from the ``.npy`` files clip_features.py wrote);
+  * ``ClipScoreModel(clip_model)`` is the whole CLIP score end to end (clip_utils.py:141-263): ``text_features`` is
+    ``get_clip_features`` on token ids, ``image_features`` applies OpenAI CLIP's ``preprocess`` to uint8 images bit-exactly
+    (``ops.image_patches_pil``) and runs the image tower, ``score`` pairs them through ``ops.paired_cosine``.
 
 There is no CPU path: a model on the CPU is refused, numpy inputs are moved to the model's device.
 """
 from __future__ import annotations
 
-from typing import Union
+from typing import Optional, Union
 
 import numpy as np
 import torch
@@ -119,3 +122,115 @@ def clip_score(image_embeds: Array, text_features: Array, logit_scale: float = 1
                          f"and {tuple(b.shape)}")
     a, b = ops.l2_normalize(a), ops.l2_normalize(b)
     return logit_scale * (a * b).sum() / a.shape[0]
+
+
+class ClipScoreModel:
+    """The reference's CLIP score (pdm/utils/clip_utils.py: ``clip_features`` :224-263, ``clip_score`` :197-221,
+    ``calculate_clip_score`` :141-170) around a HIP ``clip_model.CLIPModel``.
+
+    precision: "bf16" runs both towers in their product format, "fp32" on the fp32 parity kernels (slower, the reference's
+    arithmetic).  The image front end is the same in both: integer arithmetic, bit-exact with PIL."""
+
+    def __init__(self, clip_model, precision: str = "bf16"):
+        if precision not in _PRECISIONS:
+            raise ValueError(f"ClipScoreModel: precision must be one of {sorted(_PRECISIONS)}, got {precision!r}")
+        if not all(hasattr(clip_model, a) for a in ("text_model", "vision_model", "logit_scale_exp")):
+            raise TypeError("ClipScoreModel: clip_model must be a diffusion_pruning_amd CLIPModel")
+        self._model = clip_model
+        self.precision = precision
+        self.logit_scale = float(clip_model.logit_scale_exp)
+        self.input_image_size = clip_model.vision_model.config.image_size
+
+    def _device(self):
+        return self._model.vision_model._device()
+
+    @torch.no_grad()
+    def text_features(self, input_ids: Array, batch_size: int = 64) -> torch.Tensor:
+        """token ids [n, L] (integers; numpy or tensor) -> unit-norm fp32 [n, proj] on the model's device: ``get_clip_features``"""
+        if batch_size < 1:
+            raise ValueError(f"ClipScoreModel.text_features: batch_size must be >= 1, got {batch_size}")
+        if isinstance(input_ids, np.ndarray):
+            input_ids = torch.from_numpy(np.ascontiguousarray(input_ids))
+        if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2 or input_ids.shape[0] < 1 \
+                or input_ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError("ClipScoreModel.text_features: input_ids must be an integer [n, L] array")
+        tm = self._model.text_model
+        dev = self._device()
+        out = torch.empty(input_ids.shape[0], tm.config.projection_dim, dtype=torch.float32, device=dev)
+        saved = ops.ACT_DTYPE
+        ops.ACT_DTYPE = _PRECISIONS[self.precision]
+        try:
+            for i in range(0, input_ids.shape[0], batch_size):
+                ops.l2_normalize(tm.embed_ids(input_ids[i:i + batch_size]), out=out[i:i + batch_size])
+        finally:
+            ops.ACT_DTYPE = saved
+        return out
+
+    def _image_chunk(self, chunk: torch.Tensor) -> torch.Tensor:
+        """uint8 [b, H, W, 3] on the device -> image_embeds fp32 [b, proj], not normalised (under the caller's ACT_DTYPE)"""
+        vm = self._model.vision_model
+        cfg = vm.config
+        patches = ops.image_patches_pil(chunk, cfg.image_size, cfg.patch_size, out_f32=ops.ACT_DTYPE == torch.float32)
+        return vm.encode_patches(patches, chunk.shape[0])[0]
+
+    @staticmethod
+    def _check_images(images, what: str):
+        shape = tuple(images.shape)
+        if len(shape) != 4 or shape[3] != 3 or min(shape[:3]) < 1:
+            raise ValueError(f"{what}: images must be [n, H, W, 3], got {shape}")
+        if (images.dtype != np.uint8) if isinstance(images, np.ndarray) else (images.dtype != torch.uint8):
+            raise ValueError(f"{what}: images must be uint8 (the arrays the generator saved), got {images.dtype}")
+
+    def _u8(self, chunk, dev) -> torch.Tensor:
+        if isinstance(chunk, np.ndarray):
+            chunk = torch.from_numpy(np.ascontiguousarray(chunk))
+        return chunk.to(dev).contiguous()
+
+    @torch.no_grad()
+    def image_features(self, images_uint8: Array, batch_size: int = 64) -> torch.Tensor:
+        """uint8 images [n, H, W, 3] -> unit-norm fp32 [n, proj]: CLIP's preprocess, the image tower, the projection"""
+        if batch_size < 1:
+            raise ValueError(f"ClipScoreModel.image_features: batch_size must be >= 1, got {batch_size}")
+        self._check_images(images_uint8, "ClipScoreModel.image_features")
+        dev = self._device()
+        n = images_uint8.shape[0]
+        out = torch.empty(n, self._model.projection_dim, dtype=torch.float32, device=dev)
+        saved = ops.ACT_DTYPE
+        ops.ACT_DTYPE = _PRECISIONS[self.precision]
+        try:
+            for i in range(0, n, batch_size):
+                ops.l2_normalize(self._image_chunk(self._u8(images_uint8[i:i + batch_size], dev)), out=out[i:i + batch_size])
+        finally:
+            ops.ACT_DTYPE = saved
+        return out
+
+    @torch.no_grad()
+    def score(self, images_uint8: Array, input_ids: Optional[Array] = None, *, text_features: Optional[Array] = None,
+              batch_size: int = 64, return_cosines: bool = False):
+        """``logit_scale * mean_i cos(image_i, text_i)`` of uint8 images [n, H, W, 3] and either token ids [n, L] or precomputed
+        text features [n, proj] (the ``.npy`` rows clip_features wrote; any norm).  Accumulated over chunks of batch_size pairs
+        as calculate_clip_score does: the sum over all pairs (fp64, fixed order) divided by n.  Returns an fp64 scalar tensor on
+        the device, and with return_cosines also the fp32 [n] cosines."""
+        if (input_ids is None) == (text_features is None):
+            raise ValueError("ClipScoreModel.score: give input_ids or text_features, not both")
+        if batch_size < 1:
+            raise ValueError(f"ClipScoreModel.score: batch_size must be >= 1, got {batch_size}")
+        self._check_images(images_uint8, "ClipScoreModel.score")
+        dev = self._device()
+        n = images_uint8.shape[0]
+        txt = self.text_features(input_ids, batch_size) if text_features is None else _to_device(text_features, dev, "ClipScoreModel.score")
+        if txt.dim() != 2 or tuple(txt.shape) != (n, self._model.projection_dim):
+            raise ValueError(f"ClipScoreModel.score: {n} images need text features [{n}, {self._model.projection_dim}], got {tuple(txt.shape)}")
+        total = torch.zeros((), dtype=torch.float64, device=dev)
+        cosines = []
+        saved = ops.ACT_DTYPE
+        ops.ACT_DTYPE = _PRECISIONS[self.precision]
+        try:
+            for i in range(0, n, batch_size):
+                emb = self._image_chunk(self._u8(images_uint8[i:i + batch_size], dev))
+                cos, _ = ops.paired_cosine(emb, txt[i:i + batch_size], total=total)
+                cosines.append(cos)
+        finally:
+            ops.ACT_DTYPE = saved
+        value = self.logit_scale * total / n
+        return (value, torch.cat(cosines)) if return_cosines else value

@@ -20,6 +20,7 @@ from ._lib import ImageInParams, LatentDistParams, UnetEpilogueParams, UnetProlo
 from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F401
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
+from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1241,6 +1242,200 @@ def mmd_rbf(x: torch.Tensor, y: torch.Tensor, sigma: float = MMD_SIGMA, scale: f
     p.sigma, p.scale, p.workspace, p.out = sigma, scale, ws.data_ptr(), out.data_ptr()
     _lib.check(lib.aptp_mmd_rbf(ctypes.byref(p), _stream()), "aptp_mmd_rbf")
     return out if parts else out[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the CLIP score's device path (csrc/clip_score_ops.hip)
+# ------------------------------------------------------------------------------------------------------------------
+PIL_PRECISION_BITS = 22           # PIL's fixed point for 8-bit images: 32 - 8 - 2 (Resample.c)
+
+
+def _pil_bicubic(x: float) -> float:
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def pil_bicubic_table(in_size: int, out_size: int):
+    """PIL's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for a bicubic resize of one axis, statement for statement in
+    Python floats (IEEE doubles, as PIL's C doubles): (bounds int32 [out, 2] = (xmin, count), weights int32 [out, ksize]) as numpy
+    arrays; weights past ``count`` are 0.  ksize = 2 ceil(2 max(in / out, 1)) + 1."""
+    import math
+
+    import numpy as np
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"pil_bicubic_table: sizes must be positive, got {in_size} -> {out_size}")
+    scale = filterscale = in_size / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = 2.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    bounds = np.zeros((out_size, 2), np.int32)
+    weights = np.zeros((out_size, ksize), np.int32)
+    one = float(1 << PIL_PRECISION_BITS)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)                  # int() truncates like C's cast
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        k = [_pil_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for w in k:
+            ww += w
+        if ww != 0.0:
+            k = [w / ww for w in k]
+        bounds[xx] = (xmin, xmax)
+        for x, w in enumerate(k):
+            weights[xx, x] = int(-0.5 + w * one) if w < 0 else int(0.5 + w * one)
+    return bounds, weights
+
+
+def pil_resized_size(H: int, W: int, size: int):
+    """(H1, W1, top, left): torchvision's Resize(size) of an H x W image -- the shorter side to size, the longer one to
+    int(size * long / short) -- and CenterCrop(size)'s offsets round((H1 - size) / 2), round((W1 - size) / 2) (Python's round)"""
+    if H < 1 or W < 1 or size < 1:
+        raise ValueError(f"pil_resized_size: sizes must be positive, got {H} x {W} -> {size}")
+    H1, W1 = (size, int(size * W / H)) if H <= W else (int(size * H / W), size)
+    return H1, W1, int(round((H1 - size) / 2.0)), int(round((W1 - size) / 2.0))
+
+
+_PIL_TABLES = {}
+_PIL_TABLES_CAP = 16
+
+
+def _pil_tables(H: int, W: int, size: int, device):
+    """device copies of the two coefficient tables of an (H, W) -> size preprocess, cached per (H, W, size, device); the entry of
+    an axis whose size does not change is None"""
+    key = (H, W, size, str(device))
+    t = _PIL_TABLES.get(key)
+    if t is None:
+        H1, W1, _, _ = pil_resized_size(H, W, size)
+        t = []
+        for n_in, n_out in ((W, W1), (H, H1)):
+            if n_in == n_out:
+                t.append(None)
+            else:
+                b, w = pil_bicubic_table(n_in, n_out)
+                t.append((torch.from_numpy(b).to(device), torch.from_numpy(w).to(device)))
+        if len(_PIL_TABLES) >= _PIL_TABLES_CAP:
+            _PIL_TABLES.pop(next(iter(_PIL_TABLES)))
+        _PIL_TABLES[key] = t
+    return t
+
+
+def image_patches_pil(x: torch.Tensor, size: int, patch: int, *, mean=CLIP_IMAGE_MEAN, std=CLIP_IMAGE_STD, out_f32: bool = False,
+                      out: Optional[torch.Tensor] = None, tables=None) -> torch.Tensor:
+    """Image front end of the CLIP score: uint8 images [B, H, W, 3] -> OpenAI CLIP's ``preprocess`` (PIL bicubic resize of the
+    shorter side to size, bit-exact; centre crop; / 255; (v - mean) / std) -> the rows of ``image_patches``: bf16 (fp32 when
+    out_f32) [B * (size / patch)^2, Kpad].  The coefficient tables of a new (H, W, size) are built on the host and uploaded, so
+    call once eagerly before capturing a graph of that shape.  tables: ((xbounds, xweights) | None, (ybounds, yweights) | None)
+    instead of the cached ones (tests)."""
+    lib = _lib.load()
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError(f"image_patches_pil: x must be a contiguous CUDA uint8 [B, H, W, 3] tensor, got {x.dtype} {tuple(x.shape)}")
+    if size < 1 or patch < 1 or size % patch != 0:
+        raise ValueError(f"image_patches_pil: size {size} must be a positive multiple of patch {patch}")
+    B, H, W, _ = x.shape
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"image_patches_pil: empty input {tuple(x.shape)}")
+    H1, W1, _, _ = pil_resized_size(H, W, size)
+    if tables is None:
+        if torch.cuda.is_current_stream_capturing() and (H, W, size, str(x.device)) not in _PIL_TABLES:
+            raise RuntimeError("image_patches_pil: run one eager call of this shape before capturing it")
+        tables = _pil_tables(H, W, size, x.device)
+    G = size // patch
+    kpad = round_up(3 * patch * patch, 64)
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty(B * G * G, kpad, dtype=odt, device=x.device)
+    elif tuple(out.shape) != (B * G * G, kpad) or out.dtype != odt or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"image_patches_pil: out must be a contiguous {odt} [{B * G * G}, {kpad}] tensor on {x.device}")
+    p = ImagePatchesPilParams()
+    p.x, p.B, p.H, p.W, p.S, p.P = x.data_ptr(), B, H, W, size, patch
+    for axis, n_out, tb in (("x", W1, tables[0]), ("y", H1, tables[1])):
+        if tb is None:
+            continue
+        bnd, wts = tb
+        if bnd.dtype != torch.int32 or wts.dtype != torch.int32 or tuple(bnd.shape) != (n_out, 2) or wts.dim() != 2 \
+                or wts.shape[0] != n_out or not bnd.is_contiguous() or not wts.is_contiguous() or bnd.device != x.device \
+                or wts.device != x.device:
+            raise ValueError(f"image_patches_pil: the {axis} table must be int32 [{n_out}, 2] bounds and int32 [{n_out}, k] weights on "
+                             f"{x.device}")
+        setattr(p, axis + "bounds", bnd.data_ptr())
+        setattr(p, axis + "weights", wts.data_ptr())
+        setattr(p, axis + "k", wts.shape[1])
+    scratch = torch.empty(B, H, W1, 3, dtype=torch.uint8, device=x.device) if W1 != W else None
+    p.scratch = None if scratch is None else scratch.data_ptr()
+    for c in range(3):
+        p.mean[c], p.std[c] = float(mean[c]), float(std[c])
+    p.out, p.ldo, p.out_f32 = out.data_ptr(), kpad, int(out_f32)
+    _lib.check(lib.aptp_image_patches_pil(ctypes.byref(p), _stream()), "aptp_image_patches_pil")
+    return out
+
+
+def eos_pool_ln(ids: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, *,
+                eos_mode: str = "argmax", eos_token_id: int = 2, return_index: bool = False):
+    """Pooled output of a CLIP text tower: per prompt, LayerNorm of the ONE row of the residual stream x [B, L, C] (bf16 or
+    fp32, before final_layer_norm) at the pooling position -- eos_mode "argmax": the first index of the largest id (OpenAI
+    encode_text; transformers with eos_token_id == 2); "first_eos": the first index equal to eos_token_id, 0 without one.
+    ids int64 [B, L]; gamma / beta fp32 [C].  Returns (fp32 [B, C], the same rows in x's dtype [B, C] for the projection GEMM)
+    and, with return_index, the int32 [B] positions."""
+    lib = _lib.load()
+    if ids.dtype != torch.int64 or ids.dim() != 2 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError(f"eos_pool_ln: ids must be a contiguous CUDA int64 [B, L] tensor, got {ids.dtype} {tuple(ids.shape)}")
+    B, L = ids.shape
+    if x.dtype not in (torch.bfloat16, torch.float32) or x.dim() != 3 or tuple(x.shape[:2]) != (B, L) or x.stride(2) != 1 \
+            or x.device != ids.device or B < 1 or L < 1:
+        raise ValueError(f"eos_pool_ln: x must be a bf16 or fp32 [{B}, {L}, C] tensor with contiguous channels on {ids.device}, got "
+                         f"{x.dtype} {tuple(x.shape)} on {x.device}")
+    C = x.shape[2]
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        if t.dtype != torch.float32 or tuple(t.shape) != (C,) or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"eos_pool_ln: {nm} must be a contiguous fp32 [{C}] tensor on the stream's device")
+    modes = {"argmax": EOS_ARGMAX, "first_eos": EOS_FIRST}
+    if eos_mode not in modes:
+        raise ValueError(f"eos_pool_ln: eos_mode must be one of {sorted(modes)}, got {eos_mode!r}")
+    out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    act = torch.empty(B, C, dtype=x.dtype, device=x.device)
+    idx = torch.empty(B, dtype=torch.int32, device=x.device) if return_index else None
+    p = EosPoolLnParams()
+    p.ids, p.x = ids.data_ptr(), x.data_ptr()
+    p.x_stride_l = x.stride(1) if L > 1 else max(x.stride(1), C)
+    p.x_stride_b = x.stride(0) if B > 1 else L * p.x_stride_l
+    p.gamma, p.beta, p.out, p.out_act, p.ldo_act = gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), act.data_ptr(), C
+    p.index_out = None if idx is None else idx.data_ptr()
+    p.B, p.L, p.C, p.eos_mode, p.eos_token_id = B, L, C, modes[eos_mode], int(eos_token_id)
+    p.x_f32 = p.act_f32 = int(x.dtype == torch.float32)
+    p.eps = eps
+    _lib.check(lib.aptp_eos_pool_ln(ctypes.byref(p), _stream()), "aptp_eos_pool_ln")
+    return (out, act, idx) if return_index else (out, act)
+
+
+def paired_cosine(a: torch.Tensor, b: torch.Tensor, total: Optional[torch.Tensor] = None):
+    """fp32 a, b [n, D] -> (cos fp32 [n] with cos[i] = a_i . b_i / (|a_i| |b_i|), their sum as an fp64 scalar tensor).  The sum is
+    added in a fixed order: bit-identical from run to run.  total: an fp64 scalar tensor the sum is ADDED to (and which is
+    returned), for scores accumulated over chunks."""
+    lib = _lib.load()
+    for t, nm in ((a, "a"), (b, "b")):
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda or t.shape[0] < 1:
+            raise ValueError(f"paired_cosine: {nm} must be a contiguous CUDA fp32 [n, D] tensor, got {t.dtype} {tuple(t.shape)}")
+    if tuple(a.shape) != tuple(b.shape) or a.shape[1] % 4 != 0 or a.shape[1] < 4 or a.device != b.device:
+        raise ValueError(f"paired_cosine: a and b must be equal [n, D] with D a multiple of 4 on one device, got {tuple(a.shape)} and "
+                         f"{tuple(b.shape)}")
+    if total is not None and (total.dtype != torch.float64 or total.numel() != 1 or total.device != a.device):
+        raise ValueError(f"paired_cosine: total must be an fp64 scalar tensor on {a.device}")
+    n, D = a.shape
+    cos = torch.empty(n, dtype=torch.float32, device=a.device)
+    s = torch.empty((), dtype=torch.float64, device=a.device) if total is None else total
+    p = PairedCosineParams()
+    p.a, p.lda, p.b, p.ldb, p.cos_out, p.sum_out, p.n, p.D = a.data_ptr(), D, b.data_ptr(), D, cos.data_ptr(), s.data_ptr(), n, D
+    p.accumulate = int(total is not None)
+    _lib.check(lib.aptp_paired_cosine(ctypes.byref(p), _stream()), "aptp_paired_cosine")
+    return cos, s
 
 
 # ------------------------------------------------------------------------------------------------------------------

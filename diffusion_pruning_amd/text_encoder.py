@@ -147,19 +147,26 @@ class CLIPTextModelOutput:
         return self.to_tuple()[i]
 
 
-class CLIPTextModel(nn.Module):
-    """``CLIPTextModel`` of transformers 4.34 for ``hidden_act == "gelu"`` and 64-wide heads, forward only (the reference freezes
-    the text encoder, trainer.py:725)."""
+_ACTS = {"gelu": ops.ACT_GELU, "quick_gelu": ops.ACT_QUICK_GELU}
 
-    def __init__(self, config: Optional[CLIPTextConfig] = None, **kw):
+
+class _TextTower(nn.Module):
+    """What ``CLIPTextModel`` and ``clip_model.CLIPTextModelWithProjection`` share: the ``text_model`` parameters, the packed
+    plans and the layer stack up to (not including) ``final_layer_norm``.  A subclass names the activations it accepts and adds
+    its own loading and outputs."""
+
+    _ACTS_ACCEPTED = ("gelu",)
+    _ACTS_NOTE = "only the exact-erf 'gelu' of SD-2.x"
+
+    def __init__(self, cfg: CLIPTextConfig):
         super().__init__()
-        cfg = config or CLIPTextConfig(**kw)
-        if cfg.hidden_act != "gelu":
-            raise NotImplementedError(f"CLIPTextModel: hidden_act {cfg.hidden_act!r} (only the exact-erf 'gelu' of SD-2.x)")
+        who = type(self).__name__
+        if cfg.hidden_act not in self._ACTS_ACCEPTED:
+            raise NotImplementedError(f"{who}: hidden_act {cfg.hidden_act!r} ({self._ACTS_NOTE})")
         if cfg.hidden_size % cfg.num_attention_heads != 0 or cfg.head_dim != 64:
-            raise NotImplementedError(f"CLIPTextModel: head dim {cfg.hidden_size / cfg.num_attention_heads:g} (only 64)")
+            raise NotImplementedError(f"{who}: head dim {cfg.hidden_size / cfg.num_attention_heads:g} (only 64)")
         if cfg.max_position_embeddings > ops.CAUSAL_MAX_L:
-            raise NotImplementedError(f"CLIPTextModel: max_position_embeddings {cfg.max_position_embeddings} > {ops.CAUSAL_MAX_L}")
+            raise NotImplementedError(f"{who}: max_position_embeddings {cfg.max_position_embeddings} > {ops.CAUSAL_MAX_L}")
         self.config = cfg
         self.text_model = _TextTransformer(cfg)
         # 2 dtypes x 2 LayerNorm forms fit unpinned: an encode of one form never evicts the other form's packs
@@ -167,7 +174,7 @@ class CLIPTextModel(nn.Module):
 
     # ---- weights ----------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def init_synthetic(self, seed: int = 0) -> "CLIPTextModel":
+    def init_synthetic(self, seed: int = 0):
         """Deterministic weights under which every layer changes the residual stream measurably: linear weights with std
         fan_in^-1/2 (out_proj and fc2 scaled by 0.5, so the stream grows slowly over the 23 residual additions), LayerNorm
         affine near identity, small biases, embeddings with std 0.5."""
@@ -184,20 +191,6 @@ class CLIPTextModel(nn.Module):
                 p.copy_(scale * p.shape[1] ** -0.5 * torch.randn(p.shape, generator=g))
         self.invalidate()
         return self
-
-    def load_text_state_dict(self, sd: Dict[str, torch.Tensor]) -> "CLIPTextModel":
-        """Strict load of a transformers CLIPTextModel state dict, with or without the ``text_model.`` prefix (transformers
-        4.34 writes it); ``embeddings.position_ids`` (a buffer some checkpoints carry) is ignored.  A missing, unexpected
-        or mis-shaped key raises."""
-        return load_strict(self, sd, lambda n: n if n.startswith("text_model.") else "text_model." + n,
-                           lambda n: n == "text_model.embeddings.position_ids")
-
-    @classmethod
-    def from_pretrained(cls, root: str, subfolder: Optional[str] = "text_encoder") -> "CLIPTextModel":
-        """Read ``config.json`` and ``model.safetensors`` of a transformers CLIPTextModel folder."""
-        cfg, sd = read_pretrained(CLIPTextConfig, root, subfolder, "model.safetensors",
-                                  skip=lambda n: n.endswith("embeddings.position_ids"))
-        return cls(cfg).load_text_state_dict(sd)
 
     def invalidate(self):
         self._plans.clear()
@@ -238,7 +231,11 @@ class CLIPTextModel(nn.Module):
             layers.append(e)
         pl = {"tok": f32(tm.embeddings.token_embedding.weight), "pos": f32(tm.embeddings.position_embedding.weight),
               "final": (f32(tm.final_layer_norm.weight), f32(tm.final_layer_norm.bias)), "layers": layers}
+        self._plan_extra(pl, device)
         return self._plans.put(key, version, pl)
+
+    def _plan_extra(self, pl: dict, device):
+        """packed weights a subclass needs beyond the tower's (the text projection)"""
 
     # ---- forward ----------------------------------------------------------------------------------------------------
     def _ln_linear(self, x, st, e, idx, name, **kw):
@@ -250,14 +247,16 @@ class CLIPTextModel(nn.Module):
         pw = e.get(name)
         if pw is None:
             if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("CLIPTextModel: run one eager encode of this shape before capturing it")
+                raise RuntimeError(f"{type(self).__name__}: run one eager encode of this shape before capturing it")
             pw = e[name] = e[name + "_make"]()
         g, b = e[f"ln{idx}"]
         return ops.linear(ops.layernorm(x, g, b, eps), pw, **kw)
 
-    def encode_nhwc(self, input_ids: torch.Tensor) -> torch.Tensor:
-        """int64 [B, L] ids on the device -> the final LayerNorm's output in ops.ACT_DTYPE [B, L, hidden]"""
+    def encode_stream(self, input_ids: torch.Tensor) -> Tuple[torch.Tensor, dict]:
+        """int64 [B, L] ids on the device -> (the residual stream after the last layer, before final_layer_norm, in
+        ops.ACT_DTYPE [B, L, hidden]; the plan that encoded it)"""
         cfg = self.config
+        act = _ACTS[cfg.hidden_act]
         fold = input_ids.numel() <= FOLD_LN_MAX_ROWS
         pl = self.plan(input_ids.device, fold)
         C, nh = cfg.hidden_size, cfg.num_attention_heads
@@ -268,10 +267,54 @@ class CLIPTextModel(nn.Module):
             qkv = self._ln_linear(x, st, e, 1, "qkv")
             o = ops.attention_causal(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], nh)
             x, st = ops.linear(o, e["out"], residual=x, rowstats=fold)
-            f = self._ln_linear(x, st, e, 2, "fc1", act=ops.ACT_GELU)
+            f = self._ln_linear(x, st, e, 2, "fc1", act=act)
             x, st = ops.linear(f, e["fc2"], residual=x, rowstats=fold)
+        return x, pl
+
+    def encode_nhwc(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """int64 [B, L] ids on the device -> the final LayerNorm's output in ops.ACT_DTYPE [B, L, hidden]"""
+        x, pl = self.encode_stream(input_ids)
         g, b = pl["final"]
-        return ops.layernorm(x, g, b, cfg.layer_norm_eps)
+        return ops.layernorm(x, g, b, self.config.layer_norm_eps)
+
+    def _device_ids(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """the argument checks of a forward: int64 [B, L] ids on the model's device"""
+        who = type(self).__name__
+        cfg = self.config
+        dev = self.text_model.embeddings.token_embedding.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"{who} runs on the HIP kernels only: move it to a GPU first (model.to('cuda'))")
+        if input_ids.dim() != 2 or input_ids.dtype not in (torch.int64, torch.int32):
+            raise ValueError(f"{who}: input_ids must be an integer [B, L] tensor, got {input_ids.dtype} {tuple(input_ids.shape)}")
+        B, L = input_ids.shape
+        if B < 1 or not 1 <= L <= cfg.max_position_embeddings:
+            raise ValueError(f"{who}: sequence length {L} outside [1, {cfg.max_position_embeddings}] (batch {B})")
+        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
+        if not torch.cuda.is_current_stream_capturing() and bool(((ids < 0) | (ids >= cfg.vocab_size)).any()):
+            raise ValueError(f"{who}: token ids outside [0, {cfg.vocab_size})")
+        return ids
+
+
+class CLIPTextModel(_TextTower):
+    """``CLIPTextModel`` of transformers 4.34 for ``hidden_act == "gelu"`` and 64-wide heads, forward only (the reference freezes
+    the text encoder, trainer.py:725)."""
+
+    def __init__(self, config: Optional[CLIPTextConfig] = None, **kw):
+        super().__init__(config or CLIPTextConfig(**kw))
+
+    def load_text_state_dict(self, sd: Dict[str, torch.Tensor]) -> "CLIPTextModel":
+        """Strict load of a transformers CLIPTextModel state dict, with or without the ``text_model.`` prefix (transformers
+        4.34 writes it); ``embeddings.position_ids`` (a buffer some checkpoints carry) is ignored.  A missing, unexpected
+        or mis-shaped key raises."""
+        return load_strict(self, sd, lambda n: n if n.startswith("text_model.") else "text_model." + n,
+                           lambda n: n == "text_model.embeddings.position_ids")
+
+    @classmethod
+    def from_pretrained(cls, root: str, subfolder: Optional[str] = "text_encoder") -> "CLIPTextModel":
+        """Read ``config.json`` and ``model.safetensors`` of a transformers CLIPTextModel folder."""
+        cfg, sd = read_pretrained(CLIPTextConfig, root, subfolder, "model.safetensors",
+                                  skip=lambda n: n.endswith("embeddings.position_ids"))
+        return cls(cfg).load_text_state_dict(sd)
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, attention_mask=None, position_ids=None, output_hidden_states: bool = False,
@@ -283,17 +326,8 @@ class CLIPTextModel(nn.Module):
             raise NotImplementedError("CLIPTextModel: attention_mask, position_ids, output_hidden_states and other arguments "
                                       "are not supported (SD-2.1's encoder runs with the causal mask only)")
         cfg = self.config
-        dev = self.text_model.embeddings.token_embedding.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("CLIPTextModel runs on the HIP kernels only: move it to a GPU first (model.to('cuda'))")
-        if input_ids.dim() != 2 or input_ids.dtype not in (torch.int64, torch.int32):
-            raise ValueError(f"CLIPTextModel: input_ids must be an integer [B, L] tensor, got {input_ids.dtype} {tuple(input_ids.shape)}")
-        B, L = input_ids.shape
-        if B < 1 or not 1 <= L <= cfg.max_position_embeddings:
-            raise ValueError(f"CLIPTextModel: sequence length {L} outside [1, {cfg.max_position_embeddings}] (batch {B})")
-        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if not torch.cuda.is_current_stream_capturing() and bool(((ids < 0) | (ids >= cfg.vocab_size)).any()):
-            raise ValueError(f"CLIPTextModel: token ids outside [0, {cfg.vocab_size})")
+        ids = self._device_ids(input_ids)
+        B, dev = ids.shape[0], ids.device
         h = self.encode_nhwc(ids).float()
         if cfg.eos_token_id == 2:
             eos_at = ids.argmax(dim=-1)

@@ -846,6 +846,70 @@ typedef struct {
 int64_t aptp_mmd_rbf_workspace_bytes(int32_t n, int32_t m);
 int aptp_mmd_rbf(const AptpMmdRbfParams* p, aptp_stream_t stream);
 
+/* Image front end of the CLIP score: OpenAI CLIP's `preprocess` (pdm/utils/clip_utils.py:209, :197-221) -- Resize(S, BICUBIC)
+ * on a PIL image, CenterCrop(S), ToTensor, Normalize -- on uint8 images x [B, H, W, 3], followed by the unfold of
+ * aptp_image_patches (same rows, same zero tail; bf16, or fp32 when out_f32).
+ *   size:     the shorter side goes to S, the longer one to (int)(S * long / short)  (aptp_image_patches_pil_size);
+ *   resample: PIL's 8-bit bicubic, bit for bit: A = -0.5, support 2 * max(in / out, 1) (antialiased), per output index the window
+ *             [xmin, xmin + count) and its normalised weights rounded to 22 fractional bits, the horizontal pass first, each
+ *             pass ending in clamp((acc + 2^21) >> 22, 0, 255) stored as uint8; a pass whose size does not change is skipped;
+ *   crop:     S x S at top = round((H1 - S) / 2), left likewise, halves to the even neighbour (Python's round);
+ *   values:   (u8 / 255 - mean[c]) / std[c] in fp32.
+ * The coefficient tables are built by the caller in double precision (ops.pil_bicubic_table) and only read here: the kernels do
+ * integer arithmetic.  Per axis: bounds int32 [out, 2] = (xmin, count), weights int32 [out, k] with k the declared window
+ * (xk, yk).  A declared window narrower than the resize needs, or an image with a side of 0, is refused with APTP_EINVAL; the
+ * kernels additionally clamp every window to the table's k and to the image, so no table can move a read out of range.
+ * Two launches: the horizontal pass writes the uint8 scratch image [B, H, W1, 3] (needed when W1 != W), the second launch reads
+ * it for the vertical pass, the crop, the normalisation and the unfold.  Tables of a pass that is skipped may be null. */
+typedef struct {
+  const uint8_t* x;
+  int32_t B, H, W;
+  int32_t S, P;
+  const int32_t* xbounds; const int32_t* xweights; int32_t xk;
+  const int32_t* ybounds; const int32_t* yweights; int32_t yk;
+  void* scratch;
+  float mean[3], std[3];
+  void* out; int64_t ldo;
+  int32_t out_f32;
+} AptpImagePatchesPilParams;
+/* the resized extents (H1, W1) and the crop offsets of an H x W image; any of the four pointers may be null */
+int aptp_image_patches_pil_size(int32_t H, int32_t W, int32_t S, int32_t* H1, int32_t* W1, int32_t* top, int32_t* left);
+int aptp_image_patches_pil(const AptpImagePatchesPilParams* p, aptp_stream_t stream);
+
+/* Pooled output of a CLIP text tower (transformers CLIPTextTransformer.forward, OpenAI encode_text): per prompt the pooling
+ * position -- APTP_EOS_ARGMAX: the first index of the largest id; APTP_EOS_FIRST: the first index equal to eos_token_id, 0 when
+ * the row has none -- and final_layer_norm of that one row of the residual stream x [B, L, C] (bf16, or fp32 when x_f32; strides
+ * in elements), statistics in fp32.  One wave per prompt; the other B * L - B rows are not touched.
+ * out fp32 [B, C]; out_act (may be null) [B, ldo_act] in bf16, or fp32 when act_f32, columns [C, ldo_act) zero: the operand of the
+ * projection GEMM; index_out (may be null) int32 [B], the chosen positions.  C a multiple of 8, at most 2048. */
+enum { APTP_EOS_ARGMAX = 0, APTP_EOS_FIRST = 1 };
+typedef struct {
+  const int64_t* ids;
+  const void* x; int64_t x_stride_b, x_stride_l;
+  const float* gamma; const float* beta;
+  float* out;
+  void* out_act; int64_t ldo_act;
+  int32_t* index_out;
+  int32_t B, L, C;
+  int32_t eos_mode, eos_token_id;
+  int32_t x_f32, act_f32;
+  float eps;
+} AptpEosPoolLnParams;
+int aptp_eos_pool_ln(const AptpEosPoolLnParams* p, aptp_stream_t stream);
+
+/* cos_out[i] = a_i . b_i / (|a_i| |b_i|) for fp32 a, b [n, D] (clip_utils.py:159-166 without the normalised copies), one wave per
+ * pair, and *sum_out = sum_i cos_out[i] in fp64 (accumulate: added to the value already there), summed by one workgroup in a fixed
+ * order: bit-identical from run to run.  D a multiple of 4; lda, ldb multiples of 4. */
+typedef struct {
+  const float* a; int64_t lda;
+  const float* b; int64_t ldb;
+  float* cos_out;
+  double* sum_out;
+  int32_t n, D;
+  int32_t accumulate;
+} AptpPairedCosineParams;
+int aptp_paired_cosine(const AptpPairedCosineParams* p, aptp_stream_t stream);
+
 const char* aptp_last_error(void);
 int aptp_version(void);
 
