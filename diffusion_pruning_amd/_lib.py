@@ -420,6 +420,36 @@ class PairedCosineParams(Structure):
     ]
 
 
+TRAIN_NO_TABLE = -1
+
+
+class TrainImageDesc(Structure):
+    _fields_ = [
+        ("src_off", c_int64),
+        ("scratch_off", c_int64),
+        ("xtab_off", c_int64), ("ytab_off", c_int64),
+        ("H", c_int32), ("W", c_int32),
+        ("H1", c_int32), ("W1", c_int32),
+        ("top", c_int32), ("left", c_int32), ("flip", c_int32),
+        ("xk", c_int32), ("yk", c_int32),
+        ("row0", c_int32), ("nrows", c_int32),
+        ("reserved", c_int32),
+    ]
+
+
+class TrainImagesParams(Structure):
+    _fields_ = [
+        ("images", c_void_p), ("images_bytes", c_int64),
+        ("desc", c_void_p),
+        ("desc_dev", c_void_p),
+        ("tables", c_void_p), ("tables_count", c_int64),
+        ("scratch", c_void_p), ("scratch_bytes", c_int64),
+        ("out", c_void_p),
+        ("B", c_int32), ("R", c_int32),
+        ("out_f32", c_int32),
+    ]
+
+
 # every symbol include/aptp_hip.h declares: (name, restype, argtypes)
 EXPORTS = [
     ("aptp_conv_gemm", c_int, [POINTER(ConvGemmParams), c_void_p]),
@@ -484,6 +514,7 @@ EXPORTS = [
     ("aptp_image_patches_pil", c_int, [POINTER(ImagePatchesPilParams), c_void_p]),
     ("aptp_eos_pool_ln", c_int, [POINTER(EosPoolLnParams), c_void_p]),
     ("aptp_paired_cosine", c_int, [POINTER(PairedCosineParams), c_void_p]),
+    ("aptp_train_images", c_int, [POINTER(TrainImagesParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

@@ -1260,19 +1260,18 @@ def _pil_bicubic(x: float) -> float:
     return 0.0
 
 
-def pil_bicubic_table(in_size: int, out_size: int):
-    """PIL's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for a bicubic resize of one axis, statement for statement in
-    Python floats (IEEE doubles, as PIL's C doubles): (bounds int32 [out, 2] = (xmin, count), weights int32 [out, ksize]) as numpy
-    arrays; weights past ``count`` are 0.  ksize = 2 ceil(2 max(in / out, 1)) + 1."""
+def _pil_filter_table(in_size: int, out_size: int, filt, filt_support: float, what: str):
+    """PIL's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for one axis and one filter, statement for statement in Python
+    floats (IEEE doubles, as PIL's C doubles)"""
     import math
 
     import numpy as np
     if in_size < 1 or out_size < 1:
-        raise ValueError(f"pil_bicubic_table: sizes must be positive, got {in_size} -> {out_size}")
+        raise ValueError(f"{what}: sizes must be positive, got {in_size} -> {out_size}")
     scale = filterscale = in_size / out_size
     if filterscale < 1.0:
         filterscale = 1.0
-    support = 2.0 * filterscale
+    support = filt_support * filterscale
     ksize = int(math.ceil(support)) * 2 + 1
     ss = 1.0 / filterscale
     bounds = np.zeros((out_size, 2), np.int32)
@@ -1282,7 +1281,7 @@ def pil_bicubic_table(in_size: int, out_size: int):
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)                  # int() truncates like C's cast
         xmax = min(int(center + support + 0.5), in_size) - xmin
-        k = [_pil_bicubic((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        k = [filt((x + xmin - center + 0.5) * ss) for x in range(xmax)]
         ww = 0.0
         for w in k:
             ww += w
@@ -1292,6 +1291,24 @@ def pil_bicubic_table(in_size: int, out_size: int):
         for x, w in enumerate(k):
             weights[xx, x] = int(-0.5 + w * one) if w < 0 else int(0.5 + w * one)
     return bounds, weights
+
+
+def pil_bicubic_table(in_size: int, out_size: int):
+    """PIL's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` for a bicubic resize of one axis, statement for statement in
+    Python floats (IEEE doubles, as PIL's C doubles): (bounds int32 [out, 2] = (xmin, count), weights int32 [out, ksize]) as numpy
+    arrays; weights past ``count`` are 0.  ksize = 2 ceil(2 max(in / out, 1)) + 1."""
+    return _pil_filter_table(in_size, out_size, _pil_bicubic, 2.0, "pil_bicubic_table")
+
+
+def _pil_bilinear(x: float) -> float:
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def pil_bilinear_table(in_size: int, out_size: int):
+    """The same for PIL's BILINEAR (the triangle filter: support 1, 1 - |x| inside it), the training transform's resize:
+    ksize = 2 ceil(max(in / out, 1)) + 1."""
+    return _pil_filter_table(in_size, out_size, _pil_bilinear, 1.0, "pil_bilinear_table")
 
 
 def pil_resized_size(H: int, W: int, size: int):
@@ -1374,6 +1391,147 @@ def image_patches_pil(x: torch.Tensor, size: int, patch: int, *, mean=CLIP_IMAGE
         p.mean[c], p.std[c] = float(mean[c]), float(std[c])
     p.out, p.ldo, p.out_f32 = out.data_ptr(), kpad, int(out_f32)
     _lib.check(lib.aptp_image_patches_pil(ctypes.byref(p), _stream()), "aptp_image_patches_pil")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the training dataloader's transform (csrc/train_image_ops.hip)
+# ------------------------------------------------------------------------------------------------------------------
+_BILINEAR_TABLES = {}             # (in, out, device) -> (flat int32 device tensor [out * (2 + k)], host bounds [out, 2], k)
+_BILINEAR_TABLES_CAP = 256        # a few KB each: one per distinct (source extent, resized extent) of a dataset
+
+
+def _bilinear_table_on(n_in: int, n_out: int, device):
+    """the bilinear table of one axis on the device in aptp_train_images' layout (bounds, then weights), cached per
+    (in, out, device); the least recently used entry leaves a full cache"""
+    key = (n_in, n_out, str(device))
+    t = _BILINEAR_TABLES.pop(key, None)
+    if t is None:
+        import numpy as np
+        b, w = pil_bilinear_table(n_in, n_out)
+        flat = torch.from_numpy(np.concatenate([b.reshape(-1), w.reshape(-1)])).to(device)
+        t = (flat, b, w.shape[1])
+        if len(_BILINEAR_TABLES) >= _BILINEAR_TABLES_CAP:
+            _BILINEAR_TABLES.pop(next(iter(_BILINEAR_TABLES)))
+    _BILINEAR_TABLES[key] = t         # (re)inserted last: the dict's order is the order of use
+    return t
+
+
+def _check_train_images(images, R, tops, lefts, flips, resized_sizes):
+    """argument checks of train_images, none of which touches a device: the resized sizes [(H1, W1)]"""
+    if not isinstance(images, (list, tuple)) or len(images) == 0:
+        raise ValueError("train_images: images must be a non-empty list of uint8 [H, W, 3] tensors")
+    if not isinstance(R, int) or R < 1:
+        raise ValueError(f"train_images: R must be a positive int, got {R!r}")
+    B = len(images)
+    for nm, v in (("tops", tops), ("lefts", lefts), ("flips", flips)):
+        if len(v) != B:
+            raise ValueError(f"train_images: {nm} has {len(v)} entries for {B} images")
+    if resized_sizes is not None and len(resized_sizes) != B:
+        raise ValueError(f"train_images: resized_sizes has {len(resized_sizes)} entries for {B} images")
+    sizes = []
+    for i, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.shape[0] < 1 \
+                or im.shape[1] < 1:
+            got = f"{im.dtype} {tuple(im.shape)}" if isinstance(im, torch.Tensor) else type(im).__name__
+            raise ValueError(f"train_images: image {i} must be a uint8 [H, W, 3] tensor, got {got}")
+        H, W = int(im.shape[0]), int(im.shape[1])
+        H1, W1 = pil_resized_size(H, W, R)[:2] if resized_sizes is None else (int(resized_sizes[i][0]), int(resized_sizes[i][1]))
+        if H1 < R or W1 < R:
+            raise ValueError(f"train_images: image {i} ({H} x {W}) is resized to {H1} x {W1}, smaller than the crop {R}")
+        top, left, flip = int(tops[i]), int(lefts[i]), int(flips[i])
+        if top < 0 or left < 0 or top + R > H1 or left + R > W1:
+            raise ValueError(f"train_images: image {i}: the crop window (top {top}, left {left}, size {R}) leaves the resized image "
+                             f"{H1} x {W1}")
+        if flip not in (0, 1):
+            raise ValueError(f"train_images: image {i}: flip must be 0 or 1, got {flips[i]!r}")
+        sizes.append((H1, W1))
+    return sizes
+
+
+def _train_images_plan(shapes, sizes, R, tops, lefts, flips, device):
+    """(descriptor rows, the concatenated table buffer on ``device`` or None, scratch bytes) of one batch: images of equal
+    (in, out) share a table; an image's scratch region holds only the rows its vertical windows reach"""
+    B = len(shapes)
+    desc = (_lib.TrainImageDesc * B)()
+    pieces, offsets, tab_len = [], {}, 0
+
+    def table(n_in, n_out):
+        nonlocal tab_len
+        t = _bilinear_table_on(n_in, n_out, device)
+        if (n_in, n_out) not in offsets:
+            offsets[(n_in, n_out)] = tab_len
+            pieces.append(t[0])
+            tab_len += t[0].numel()
+        return offsets[(n_in, n_out)], t[1], t[2]
+
+    src_off = scratch_len = 0
+    for i, (H, W) in enumerate(shapes):
+        d = desc[i]
+        H1, W1 = sizes[i]
+        d.src_off, d.H, d.W, d.H1, d.W1 = src_off, H, W, H1, W1
+        d.top, d.left, d.flip = int(tops[i]), int(lefts[i]), int(flips[i])
+        src_off += H * W * 3
+        d.xtab_off = d.ytab_off = _lib.TRAIN_NO_TABLE
+        row0, nrows = d.top, R                          # without a vertical pass the window's own rows
+        if H1 != H:
+            d.ytab_off, yb, d.yk = table(H, H1)
+            win = yb[d.top:d.top + R]
+            row0 = int(win[:, 0].min())
+            nrows = int((win[:, 0] + win[:, 1]).max()) - row0
+        if W1 != W:
+            d.xtab_off, _, d.xk = table(W, W1)
+            d.row0, d.nrows, d.scratch_off = row0, nrows, scratch_len
+            scratch_len += nrows * R * 3
+    tables = torch.cat(pieces) if len(pieces) > 1 else (pieces[0] if pieces else None)
+    return desc, tables, scratch_len
+
+
+def train_images(images, R: int, tops, lefts, flips, out_f32: bool = True, out: Optional[torch.Tensor] = None, *,
+                 resized_sizes=None, device=None) -> torch.Tensor:
+    """The training dataloader's transform on a ragged batch: a list of uint8 [H, W, 3] images (CPU or GPU tensors, any mix
+    of sizes) -> pixel_values NCHW [B, 3, R, R], fp32 (bf16 when not out_f32): PIL's bilinear Resize(R) bit for bit, the crop
+    window at (tops[i], lefts[i]) of the resized image, a horizontal flip where flips[i], ToTensor and Normalize(0.5, 0.5).
+    The draws are the caller's (data.draw_crop_flip).  resized_sizes: [(H1, W1)] per image, default pil_resized_size (the
+    shorter side to R).  Two launches for the whole batch; one host-to-device copy for the images (when they are on the CPU),
+    one for the descriptor table, and one per coefficient table not yet on the device (cached per (in, out, device), so none
+    in steady state) -- host copies: not for graph capture.  device: where to run when every image is on the CPU (default: the
+    current CUDA device)."""
+    sizes = _check_train_images(images, R, tops, lefts, flips, resized_sizes)
+    B = len(images)
+    odt = torch.float32 if out_f32 else torch.bfloat16
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, 3, R, R) or out.dtype != odt
+                            or not out.is_contiguous() or not out.is_cuda):
+        raise ValueError(f"train_images: out must be a contiguous CUDA {odt} [{B}, 3, {R}, {R}] tensor")
+    lib = _lib.load()
+    if device is None:
+        device = out.device if out is not None else next((im.device for im in images if im.is_cuda), None)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"train_images: the transform runs on HIP kernels only, got device {device}")
+    for i, im in enumerate(images):
+        if im.is_cuda and im.device != device:
+            raise ValueError(f"train_images: image {i} is on {im.device}, the batch on {device}")
+    if out is not None and out.device != device:
+        raise ValueError(f"train_images: out is on {out.device}, the batch on {device}")
+    with torch.cuda.device(device):
+        if all(not im.is_cuda for im in images):
+            flat = torch.cat([im.reshape(-1) for im in images]).to(device)              # one copy
+        else:
+            flat = torch.cat([im.to(device).reshape(-1) for im in images])
+        desc, tables, scratch_len = _train_images_plan([(int(im.shape[0]), int(im.shape[1])) for im in images], sizes, R, tops, lefts,
+                                                       flips, device)
+        desc_dev = torch.frombuffer(desc, dtype=torch.uint8).to(device)                  # one copy
+        scratch = torch.empty(scratch_len, dtype=torch.uint8, device=device) if scratch_len else None
+        if out is None:
+            out = torch.empty(B, 3, R, R, dtype=odt, device=device)
+        p = _lib.TrainImagesParams()
+        p.images, p.images_bytes = flat.data_ptr(), flat.numel()
+        p.desc, p.desc_dev = ctypes.addressof(desc), desc_dev.data_ptr()
+        p.tables, p.tables_count = (None, 0) if tables is None else (tables.data_ptr(), tables.numel())
+        p.scratch, p.scratch_bytes = (None, 0) if scratch is None else (scratch.data_ptr(), scratch_len)
+        p.out, p.B, p.R, p.out_f32 = out.data_ptr(), B, R, int(out_f32)
+        _lib.check(lib.aptp_train_images(ctypes.byref(p), _stream()), "aptp_train_images")
     return out
 
 

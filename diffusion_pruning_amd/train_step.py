@@ -916,6 +916,32 @@ def batch_from_images(vae, pixel_values: torch.Tensor, encoder_hidden_states: to
             "mpnet_embeddings": mpnet_embeddings, "timesteps": timesteps}
 
 
+def batch_from_uint8(vae, images, *, resolution: int, center_crop: bool = False, random_flip: bool = True,
+                     transform_generator=None, prompt_ids: Optional[torch.Tensor] = None, text_encoder=None,
+                     encoder_hidden_states: Optional[torch.Tensor] = None, mpnet_embeddings: Optional[torch.Tensor] = None,
+                     schedule: Optional[NoiseSchedule] = None, prediction_type: str = "v_prediction", generator=None,
+                     router_ids: Optional[torch.Tensor] = None, router_attention_mask: Optional[torch.Tensor] = None,
+                     prompt_encoder=None):
+    """batch_from_images from raw inputs: ``images`` is a list of decoded uint8 [H, W, 3] tensors of any sizes, which the
+    dataloader's transform (data.TrainTransform: bilinear Resize(resolution), RandomCrop or CenterCrop, RandomHorizontalFlip,
+    ToTensor, Normalize(0.5, 0.5); its draws from ``transform_generator``, a CPU generator) turns into pixel_values on the GPU;
+    the cross-attention input is either ``encoder_hidden_states`` or ``prompt_ids``, the CLIP token ids [B, 77], which
+    ``text_encoder`` (text_encoder.CLIPTextModel) encodes as the reference's steps do (trainer.py:1097-1126:
+    ``text_encoder(ids)[0]``); exactly one of the two.  Everything else is batch_from_images' and goes to it unchanged."""
+    if (prompt_ids is None) == (encoder_hidden_states is None):
+        raise ValueError("give exactly one of prompt_ids and encoder_hidden_states")
+    if prompt_ids is not None and text_encoder is None:
+        raise ValueError("prompt_ids need a text_encoder (diffusion_pruning_amd.text_encoder.CLIPTextModel)")
+    from .data import TrainTransform
+    transform = TrainTransform(resolution, center_crop=center_crop, random_flip=random_flip)
+    transform.resized_sizes(images)                            # the images are checked before anything runs
+    if prompt_ids is not None:
+        encoder_hidden_states = text_encoder(prompt_ids)[0]
+    pixel_values = transform(images, generator=transform_generator)
+    return batch_from_images(vae, pixel_values, encoder_hidden_states, mpnet_embeddings, schedule, prediction_type, generator,
+                             router_ids=router_ids, router_attention_mask=router_attention_mask, prompt_encoder=prompt_encoder)
+
+
 @dataclass
 class FinetuneLossConfig:
     """configs/finetuning/sd-2-1_cc3m.yaml:86-95"""

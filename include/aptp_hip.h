@@ -910,6 +910,59 @@ typedef struct {
 } AptpPairedCosineParams;
 int aptp_paired_cosine(const AptpPairedCosineParams* p, aptp_stream_t stream);
 
+/* The training dataloader's transform (pdm/utils/data_utils.py:61-82) on a ragged batch of uint8 RGB images: Resize(R, BILINEAR)
+ * on a PIL image, RandomCrop(R) or CenterCrop(R), RandomHorizontalFlip, ToTensor, Normalize(0.5, 0.5) -> pixel_values, NCHW
+ * [B, 3, R, R] in fp32 (bf16 when out_f32 is 0):
+ *   out[b, c, y, x] = (u / 255 - 0.5) / 0.5 in fp32,  u = resized_b[top + y, left + (flip ? R - 1 - x : x), c].
+ * images: one flat uint8 buffer of images_bytes bytes, image b = [H, W, 3] at byte src_off.  The resize is PIL's 8-bit
+ * ImagingResample as in aptp_image_patches_pil: the horizontal pass into a uint8 scratch image, then the vertical pass, each an
+ * int32 accumulator that starts at 2^21, an arithmetic shift by 22 and a clamp to [0, 255].  The random draws are the caller's
+ * (data.draw_crop_flip): the entry takes top, left and flip per image.
+ *
+ * tables: one int32 buffer of tables_count elements holding every coefficient table, built on the host (ops.pil_bilinear_table;
+ * any filter in that format).  The table of an axis that goes from `in` to `out` samples with a window of k taps is, at its
+ * element offset, bounds int32 [out, 2] = (first, count) followed by weights int32 [out, k] in 22-bit fixed point: out * (2 + k)
+ * elements.  An axis whose size does not change takes no pass and has no table: its offset is APTP_TRAIN_NO_TABLE, the null
+ * offset (an offset must be null exactly when the size does not change).  Images of equal sizes may share tables.
+ *
+ * Only what the crop window reads is computed.  The horizontal pass writes columns [left, left + R) of rows
+ * [row0, row0 + nrows) of the source -- the rows the vertical windows of output rows [top, top + R) reach, from the caller's
+ * vertical table; [top, top + R) itself when the height does not change -- into the image's scratch region, uint8 [nrows, R, 3]
+ * at byte scratch_off (regions of different images must not overlap).  The second pass writes out.  Without a horizontal pass
+ * scratch_off, row0 and nrows are not read.
+ *
+ * One descriptor row per image, 80 bytes, plain integers: */
+#define APTP_TRAIN_NO_TABLE (-1)
+typedef struct {
+  int64_t src_off;             /* byte offset of the image in `images` */
+  int64_t scratch_off;         /* byte offset of its region in `scratch` */
+  int64_t xtab_off, ytab_off;  /* int32-element offsets of the horizontal / vertical table in `tables`, or APTP_TRAIN_NO_TABLE */
+  int32_t H, W;                /* source extents */
+  int32_t H1, W1;              /* resized extents */
+  int32_t top, left, flip;     /* crop offsets in the resized image; flip 0 or 1 */
+  int32_t xk, yk;              /* taps per row of the horizontal / vertical table */
+  int32_t row0, nrows;         /* source rows the horizontal pass computes */
+  int32_t reserved;            /* 0 */
+} AptpTrainImageDesc;
+/* desc is read on the HOST during the call and checked before anything is launched -- every offset and size against
+ * images_bytes, tables_count and scratch_bytes, 0 <= top, top + R <= H1, 0 <= left, left + R <= W1, flip, the row range, R > 0,
+ * B > 0 (at most 65535), null pointers: APTP_EINVAL and nothing launched.  desc_dev is the same B rows in device memory, which the
+ * kernels read.  The kernels additionally clamp every window a table names to the rows and columns their pass owns, so no table
+ * content can move a read outside its image or its scratch region.
+ * At most two launches whatever the mix of sizes (the first only if some image's width changes), a 2-D grid: blockIdx.y is the
+ * image, blockIdx.x a run of 256 pixels, workgroups past an image's own count exit at once. */
+typedef struct {
+  const uint8_t* images; int64_t images_bytes;
+  const AptpTrainImageDesc* desc;          /* host */
+  const AptpTrainImageDesc* desc_dev;      /* device */
+  const int32_t* tables; int64_t tables_count;
+  void* scratch; int64_t scratch_bytes;
+  void* out;
+  int32_t B, R;
+  int32_t out_f32;
+} AptpTrainImagesParams;
+int aptp_train_images(const AptpTrainImagesParams* p, aptp_stream_t stream);
+
 const char* aptp_last_error(void);
 int aptp_version(void);
 
