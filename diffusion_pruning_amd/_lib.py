@@ -450,6 +450,29 @@ class TrainImagesParams(Structure):
     ]
 
 
+STEP_NOISE_BF16, STEP_NOISE_F32 = 0, 1
+STEP_DDIM, STEP_PNDM = 0, 1
+STEP_EPSILON, STEP_V_PREDICTION = 0, 1
+
+
+class GuidedStepParams(Structure):
+    _fields_ = [
+        ("noise", c_void_p),
+        ("sample", c_void_p),
+        ("out", c_void_p),
+        ("coef", c_void_p),
+        ("slot", c_void_p),
+        ("w", c_void_p),
+        ("flags", c_void_p),
+        ("E", c_void_p),
+        ("saved", c_void_p),
+        ("n", c_int64),
+        ("b", c_int32), ("noise_rows", c_int32),
+        ("noise_dtype", c_int32), ("scheduler", c_int32), ("prediction", c_int32), ("do_cfg", c_int32),
+        ("guidance_scale", c_float), ("guidance_rescale", c_float),
+    ]
+
+
 # every symbol include/aptp_hip.h declares: (name, restype, argtypes)
 EXPORTS = [
     ("aptp_conv_gemm", c_int, [POINTER(ConvGemmParams), c_void_p]),
@@ -515,6 +538,7 @@ EXPORTS = [
     ("aptp_eos_pool_ln", c_int, [POINTER(EosPoolLnParams), c_void_p]),
     ("aptp_paired_cosine", c_int, [POINTER(PairedCosineParams), c_void_p]),
     ("aptp_train_images", c_int, [POINTER(TrainImagesParams), c_void_p]),
+    ("aptp_guided_step", c_int, [POINTER(GuidedStepParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

@@ -21,6 +21,7 @@ from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F40
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
+from ._lib import GuidedStepParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1594,6 +1595,57 @@ def paired_cosine(a: torch.Tensor, b: torch.Tensor, total: Optional[torch.Tensor
     p.accumulate = int(total is not None)
     _lib.check(lib.aptp_paired_cosine(ctypes.byref(p), _stream()), "aptp_paired_cosine")
     return cos, s
+
+
+def guided_step(noise: torch.Tensor, sample: torch.Tensor, state: dict, *, scheduler: str, prediction_type: str,
+                guidance_scale: float = 1.0, guidance_rescale: float = 0.0, do_cfg: bool = False,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Everything a denoise step does after the U-Net call, in one launch (csrc/sched_step.hip): classifier-free guidance
+    ``u + s (t - u)`` on noise [2b, ...] = [uncond; text] (do_cfg; otherwise noise is [b, ...]), the guidance rescale
+    (guidance_rescale > 0: the guided output takes the text branch's per-sample standard deviation, blended by that factor)
+    and the scheduler update.  noise: bf16 or fp32, contiguous; sample: fp32 [b, ...]; state: the scheduler's per-step
+    device tensors (``make_state`` / ``load_step`` of pipeline.DDIMSchedulerLite -- "coef" [4] -- or PNDMSchedulerLite --
+    "slot", "w", "coef", "flags", "E", "saved"; E and saved are updated in place).  scheduler: "ddim" or "pndm".  Returns the
+    fp32 next sample (``out`` if given).  No host synchronisation: safe to capture."""
+    lib = _lib.load()
+    kinds = {"ddim": _lib.STEP_DDIM, "pndm": _lib.STEP_PNDM}
+    preds = {"epsilon": _lib.STEP_EPSILON, "v_prediction": _lib.STEP_V_PREDICTION}
+    if scheduler not in kinds:
+        raise ValueError(f"guided_step: scheduler must be one of {sorted(kinds)}, got {scheduler!r}")
+    if prediction_type not in preds:
+        raise ValueError(f"guided_step: prediction_type must be one of {sorted(preds)}, got {prediction_type!r}")
+    if sample.dtype != torch.float32 or not sample.is_contiguous() or not sample.is_cuda or sample.dim() < 1 or sample.numel() == 0:
+        raise ValueError(f"guided_step: sample must be a contiguous CUDA fp32 [b, ...] tensor, got {sample.dtype} {tuple(sample.shape)}")
+    if not noise.is_contiguous() or noise.device != sample.device or noise.dim() != sample.dim() \
+            or tuple(noise.shape[1:]) != tuple(sample.shape[1:]):
+        raise ValueError(f"guided_step: noise must be contiguous [b or 2b, ...] like sample {tuple(sample.shape)} on {sample.device}, got "
+                         f"{tuple(noise.shape)} on {noise.device}")
+    b = sample.shape[0]
+    n = sample.numel() // b
+    if out is None:
+        out = torch.empty_like(sample)
+    elif out.dtype != torch.float32 or tuple(out.shape) != tuple(sample.shape) or not out.is_contiguous() or out.device != sample.device:
+        raise ValueError(f"guided_step: out must be a contiguous fp32 {tuple(sample.shape)} tensor on {sample.device}")
+    names = ("coef",) if scheduler == "ddim" else ("slot", "w", "coef", "flags", "E", "saved")
+    want = {"coef": (torch.float32, 4 if scheduler == "ddim" else 2), "slot": (torch.int64, 1), "w": (torch.float32, 5),
+            "flags": (torch.float32, 2), "E": (torch.float32, 5 * b * n), "saved": (torch.float32, b * n)}
+    for nm in names:
+        t = state.get(nm)
+        dt, cnt = want[nm]
+        if t is None or t.dtype != dt or t.numel() != cnt or not t.is_contiguous() or t.device != sample.device:
+            raise ValueError(f"guided_step: state[{nm!r}] must be a contiguous {dt} tensor of {cnt} elements on {sample.device}")
+    p = GuidedStepParams()
+    p.noise, p.sample, p.out, p.coef = noise.data_ptr(), sample.data_ptr(), out.data_ptr(), state["coef"].data_ptr()
+    if scheduler == "pndm":
+        p.slot, p.w, p.flags = state["slot"].data_ptr(), state["w"].data_ptr(), state["flags"].data_ptr()
+        p.E, p.saved = state["E"].data_ptr(), state["saved"].data_ptr()
+    p.n, p.b, p.noise_rows = n, b, noise.shape[0]
+    # (a dtype the kernel does not know goes through as such and is refused there)
+    p.noise_dtype = {torch.bfloat16: _lib.STEP_NOISE_BF16, torch.float32: _lib.STEP_NOISE_F32}.get(noise.dtype, -1)
+    p.scheduler, p.prediction, p.do_cfg = kinds[scheduler], preds[prediction_type], int(bool(do_cfg))
+    p.guidance_scale, p.guidance_rescale = float(guidance_scale), float(guidance_rescale)
+    _lib.check(lib.aptp_guided_step(ctypes.byref(p), _stream()), "aptp_guided_step")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------------

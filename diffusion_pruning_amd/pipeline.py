@@ -10,14 +10,42 @@ MI355X-first differences:
   * one step (U-Net + CFG combine + DDIM update, all on the device, timestep and scheduler coefficients read from
     device tensors) is captured into a HIP graph and replayed ``num_inference_steps`` times;
   * a hard, batch-shared architecture code (one expert per call, as in generate_fid_images.py) takes the
-    compacted-weight fast path of the U-Net; per-prompt codes fall back to fused per-sample gates.
+    compacted-weight fast path of the U-Net; per-prompt codes fall back to fused per-sample gates in PruningDenoiseLoop;
+  * ExpertDispatchLoop instead groups a routed batch by expert and runs every group through that expert's compacted
+    weights, one captured step per (expert, bucket size), results back in the caller's prompt order;
+  * ``fused_step=True`` replaces everything after the U-Net call of a step -- guidance, the optional guidance rescale, the
+    scheduler update -- by one launch (ops.guided_step, csrc/sched_step.hip).
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Optional
 
 import torch
+
+
+def rescale_noise_cfg(noise_cfg: torch.Tensor, noise_pred_text: torch.Tensor, guidance_rescale: float = 0.0) -> torch.Tensor:
+    """Guidance rescale of Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed" (2023), section 3.4, as
+    the reference applies it after classifier-free guidance (pruning_pipelines.py:809-811, diffusers' ``rescale_noise_cfg``):
+    the guided output is scaled to the text branch's per-sample standard deviation (over all non-batch elements, unbiased as
+    ``Tensor.std``) and blended with the unscaled one by ``guidance_rescale``.
+    PARITY PIN: diffusers is absent, so this is restated from the reference's call site and the paper (eq. 15-16) --
+    unpinned against a live run; tests pin it against an fp64 evaluation written out in the test."""
+    dims = list(range(1, noise_pred_text.ndim))
+    std_text = noise_pred_text.std(dim=dims, keepdim=True)
+    std_cfg = noise_cfg.std(dim=dims, keepdim=True)
+    rescaled = noise_cfg * (std_text / std_cfg)
+    return guidance_rescale * rescaled + (1 - guidance_rescale) * noise_cfg
+
+
+def _fused(kind: str, scheduler, noise, sample, state, guidance_scale, guidance_rescale, do_cfg):
+    from . import ops
+    if sample.dtype != torch.float32:
+        raise ValueError(f"fused_step: the sample must be fp32, got {sample.dtype}")
+    return ops.guided_step(noise if noise.is_contiguous() else noise.contiguous(), sample.contiguous(), state, scheduler=kind,
+                           prediction_type=scheduler.prediction_type, guidance_scale=guidance_scale,
+                           guidance_rescale=guidance_rescale, do_cfg=do_cfg)
 
 
 class DDIMSchedulerLite:
@@ -74,6 +102,11 @@ class DDIMSchedulerLite:
 
     def step(self, model_output: torch.Tensor, sample: torch.Tensor, state: dict) -> torch.Tensor:
         return self.step_coef(model_output, state["coef"], sample)
+
+    def fused_step(self, noise: torch.Tensor, sample: torch.Tensor, state: dict, *, guidance_scale: float = 1.0,
+                   guidance_rescale: float = 0.0, do_cfg: bool = False) -> torch.Tensor:
+        """guidance (noise [2b, ...] = [uncond; text] with do_cfg), the optional rescale and ``step`` in one HIP launch"""
+        return _fused("ddim", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
 
 
 class PNDMSchedulerLite:
@@ -172,6 +205,12 @@ class PNDMSchedulerLite:
         out = (a_p / a_t).sqrt() * base - (a_p - a_t) * comb / denom
         return out.to(sample.dtype)
 
+    def fused_step(self, noise: torch.Tensor, sample: torch.Tensor, state: dict, *, guidance_scale: float = 1.0,
+                   guidance_rescale: float = 0.0, do_cfg: bool = False) -> torch.Tensor:
+        """guidance (noise [2b, ...] = [uncond; text] with do_cfg), the optional rescale and ``step`` in one HIP launch;
+        the ring ``E`` and ``saved`` are left as ``step`` would leave them"""
+        return _fused("pndm", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
+
 
 @dataclass
 class PipelineOutput:
@@ -180,6 +219,13 @@ class PipelineOutput:
     arch_vectors_quantized: Optional[torch.Tensor]
     resource_ratios: Optional[torch.Tensor] = None
     images: Optional[object] = None      # decoded images for output_type "pt" / "np" / "pil" (None for "latent")
+
+
+@dataclass
+class DispatchOutput(PipelineOutput):
+    """PipelineOutput of ExpertDispatchLoop: the parent's fields (latents / images in the caller's prompt order) plus the groups
+    the batch ran as"""
+    groups: Optional[list] = None        # [(expert index, row indices, bucket size, graph_was_reused)]
 
 
 class PruningDenoiseLoop:
@@ -204,12 +250,17 @@ class PruningDenoiseLoop:
         self.unet.set_structure(sep)
         return arch_q, idx
 
-    def _one_step(self, latents, t, state, ctx, guidance_scale, do_cfg):
+    def _one_step(self, latents, t, state, ctx, guidance_scale, do_cfg, guidance_rescale=0.0, fused_step=False, unet=None):
         x = torch.cat([latents] * 2) if do_cfg else latents                       # pruning_pipelines.py:792
-        noise = self.unet(x, t, ctx, return_dict=False)[0]                       # :796-802
+        noise = (self.unet if unet is None else unet)(x, t, ctx, return_dict=False)[0]   # :796-802
+        if fused_step:                                                           # :805-814 in one launch
+            return self.scheduler.fused_step(noise, latents, state, guidance_scale=guidance_scale,
+                                             guidance_rescale=guidance_rescale if do_cfg else 0.0, do_cfg=do_cfg)
         if do_cfg:
             uncond, text = noise.chunk(2)
             noise = uncond + guidance_scale * (text - uncond)                    # :805-807
+            if guidance_rescale > 0.0:
+                noise = rescale_noise_cfg(noise, text, guidance_rescale)         # :809-811
         return self.scheduler.step(noise, latents, state)                        # :810-814
 
     @torch.no_grad()
@@ -218,7 +269,8 @@ class PruningDenoiseLoop:
                  negative_prompt_embeds: Optional[torch.Tensor] = None, use_graph: bool = True,
                  output_type: str = "latent", *, prompt_ids: Optional[torch.Tensor] = None,
                  negative_prompt_ids: Optional[torch.Tensor] = None, router_ids: Optional[torch.Tensor] = None,
-                 router_attention_mask: Optional[torch.Tensor] = None) -> PipelineOutput:
+                 router_attention_mask: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0,
+                 fused_step: bool = False) -> PipelineOutput:
         """prompt_embeds [B,77,X] (+ negative_prompt_embeds for CFG, concatenated as [uncond, cond] like the
         reference, :765); latents [B,4,h,w] ~ N(0,1) on the device.  output_type "latent" returns the latents only;
         "pt" (fp32 [B,3,H,W] in [0, 1]), "np" (fp32 [B,H,W,3] numpy) and "pil" (list of PIL images) also decode them
@@ -227,7 +279,71 @@ class PruningDenoiseLoop:
         ``text_encoder`` -- [negative_prompt_ids; prompt_ids] in ONE encoder call with CFG, prompt_ids alone without --
         then the same loop as with the embeddings.
         router_ids (+ router_attention_mask): the MPNet token ids of the prompts instead of hyper_net_input, which is then
-        ``prompt_encoder.encode(router_ids, router_attention_mask)`` (get_mpnet_embeddings, pdm/utils/data_utils.py:130-155)."""
+        ``prompt_encoder.encode(router_ids, router_attention_mask)`` (get_mpnet_embeddings, pdm/utils/data_utils.py:130-155).
+        guidance_rescale > 0 (with CFG): ``rescale_noise_cfg`` on the guided output (:809-811).  fused_step: guidance, rescale
+        and the scheduler update of every step as ONE HIP launch (ops.guided_step) instead of the tensor expressions; both are
+        part of the captured step's key, and the defaults leave the step exactly as it was."""
+        prompt_embeds, negative_prompt_embeds, hyper_net_input = self._inputs(
+            prompt_embeds, latents, hyper_net_input, negative_prompt_embeds, output_type, prompt_ids, negative_prompt_ids,
+            router_ids, router_attention_mask, guidance_scale)
+        dev = latents.device
+        arch_q = idx = None
+        if self.hyper_net is not None and hyper_net_input is not None:
+            arch_q, idx = self.route(hyper_net_input.to(dev))
+        do_cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None
+        ehs = torch.cat([negative_prompt_embeds, prompt_embeds]) if do_cfg else prompt_embeds
+        ctx = self.unet.precompute_context(ehs.to(dev))                           # cross-attn K/V once per prompt batch
+        ts = self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        latents = latents * self.scheduler.init_noise_sigma
+        B = latents.shape[0] * (2 if do_cfg else 1)
+        extra = (float(guidance_rescale), bool(fused_step))
+        if not use_graph:
+            latents = self._eager(latents, ts, ctx, B, guidance_scale, do_cfg, *extra)
+        else:
+            # one captured step per (scheduler, shapes, CFG, guidance, installed architecture): later calls with the same key
+            # (the FID-generation loop: many prompt batches through one expert) only refresh the static buffers
+            key = (type(self.scheduler).__name__, self.scheduler.prediction_type, tuple(latents.shape), latents.dtype, do_cfg,
+                   float(guidance_scale), str(dev), ctx.key, getattr(self.unet, "_structure_epoch", None)) + extra
+            if ctx.key is None or self._graph_key != key:
+                self._graph = self._capture(latents, ts, ctx, B, guidance_scale, do_cfg, *extra)
+                self._graph_key = key if ctx.key is not None else None
+            latents = self._replay(self._graph, latents, ts, ctx, B)
+        ratios = None
+        if getattr(self.unet, "resource_info_dict", None) is not None:
+            # pruning_pipelines.py:822-824
+            ratios = self.unet.calc_macs()["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"]
+        images = None
+        if output_type != "latent":
+            images = self.decode_latents(latents, output_type)
+        return PipelineOutput(latents=latents, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios,
+                              images=images)
+
+    def _eager(self, latents, ts, ctx, B, guidance_scale, do_cfg, guidance_rescale=0.0, fused_step=False, unet=None):
+        state = self.scheduler.make_state(latents)
+        for i in range(self.scheduler.n_model_calls()):
+            self.scheduler.load_step(state, i)
+            latents = self._one_step(latents, ts[i].expand(B), state, ctx, guidance_scale, do_cfg, guidance_rescale, fused_step, unet)
+        return latents
+
+    def _replay(self, g, latents, ts, ctx, B):
+        """refresh a captured step's static buffers and replay it once per model call"""
+        g["lat"].copy_(latents)
+        g["ctx"].ehs.copy_(ctx.ehs)
+        for k_, v_ in ctx.kv.items():
+            g["ctx"].kv[k_].copy_(v_)
+        for name, t_ in self.scheduler.make_state(latents).items():
+            g["state"][name].copy_(t_)
+        for i in range(self.scheduler.n_model_calls()):
+            g["t"].copy_(ts[i].expand(B))
+            self.scheduler.load_step(g["state"], i)
+            g["graph"].replay()
+            g["lat"].copy_(g["out"])
+        return g["lat"].clone()
+
+    def _inputs(self, prompt_embeds, latents, hyper_net_input, negative_prompt_embeds, output_type, prompt_ids, negative_prompt_ids,
+                router_ids, router_attention_mask, guidance_scale):
+        """argument checks of a call, and the encoders: token ids -> text states (one CLIP call for the whole batch), MPNet
+        token ids -> the router's input.  Returns (prompt_embeds, negative_prompt_embeds, hyper_net_input)."""
         if router_ids is not None or router_attention_mask is not None:
             if hyper_net_input is not None:
                 raise ValueError("give either hyper_net_input or router_ids / router_attention_mask, not both")
@@ -259,54 +375,9 @@ class PruningDenoiseLoop:
             raise ValueError(f"output_type {output_type!r}: expected 'latent', 'pt', 'np' or 'pil'")
         if output_type != "latent" and self.vae is None:
             raise ValueError(f"output_type {output_type!r} needs a vae (PruningDenoiseLoop(..., vae=AutoencoderKL))")
-        dev = latents.device
         if router_ids is not None:
             hyper_net_input = self.prompt_encoder.encode(router_ids, router_attention_mask)
-        arch_q = idx = None
-        if self.hyper_net is not None and hyper_net_input is not None:
-            arch_q, idx = self.route(hyper_net_input.to(dev))
-        do_cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None
-        ehs = torch.cat([negative_prompt_embeds, prompt_embeds]) if do_cfg else prompt_embeds
-        ctx = self.unet.precompute_context(ehs.to(dev))                           # cross-attn K/V once per prompt batch
-        ts = self.scheduler.set_timesteps(num_inference_steps, device=dev)
-        latents = latents * self.scheduler.init_noise_sigma
-        B = latents.shape[0] * (2 if do_cfg else 1)
-        n_calls = self.scheduler.n_model_calls()
-        if not use_graph:
-            state = self.scheduler.make_state(latents)
-            for i in range(n_calls):
-                self.scheduler.load_step(state, i)
-                latents = self._one_step(latents, ts[i].expand(B), state, ctx, guidance_scale, do_cfg)
-        else:
-            # one captured step per (scheduler, shapes, CFG, guidance, installed architecture): later calls with the same key
-            # (the FID-generation loop: many prompt batches through one expert) only refresh the static buffers
-            key = (type(self.scheduler).__name__, self.scheduler.prediction_type, tuple(latents.shape), latents.dtype, do_cfg,
-                   float(guidance_scale), str(dev), ctx.key, getattr(self.unet, "_structure_epoch", None))
-            if ctx.key is None or self._graph_key != key:
-                self._graph = self._capture(latents, ts, ctx, B, guidance_scale, do_cfg)
-                self._graph_key = key if ctx.key is not None else None
-            g = self._graph
-            g["lat"].copy_(latents)
-            g["ctx"].ehs.copy_(ctx.ehs)
-            for k_, v_ in ctx.kv.items():
-                g["ctx"].kv[k_].copy_(v_)
-            for name, t_ in self.scheduler.make_state(latents).items():
-                g["state"][name].copy_(t_)
-            for i in range(n_calls):
-                g["t"].copy_(ts[i].expand(B))
-                self.scheduler.load_step(g["state"], i)
-                g["graph"].replay()
-                g["lat"].copy_(g["out"])
-            latents = g["lat"].clone()
-        ratios = None
-        if getattr(self.unet, "resource_info_dict", None) is not None:
-            # pruning_pipelines.py:822-824
-            ratios = self.unet.calc_macs()["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"]
-        images = None
-        if output_type != "latent":
-            images = self.decode_latents(latents, output_type)
-        return PipelineOutput(latents=latents, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios,
-                              images=images)
+        return prompt_embeds, negative_prompt_embeds, hyper_net_input
 
     @torch.no_grad()
     def decode_latents(self, latents: torch.Tensor, output_type: str = "pt"):
@@ -322,7 +393,7 @@ class PruningDenoiseLoop:
             return img.permute(0, 2, 3, 1).float().cpu().numpy()
         return img
 
-    def _capture(self, latents, ts, ctx, B, guidance_scale, do_cfg):
+    def _capture(self, latents, ts, ctx, B, guidance_scale, do_cfg, guidance_rescale=0.0, fused_step=False, unet=None):
         lat_buf = latents.clone()
         t_buf = ts[0].expand(B).clone()
         state = self.scheduler.make_state(latents)
@@ -331,9 +402,172 @@ class PruningDenoiseLoop:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            self._one_step(lat_buf, t_buf, state, ctx, guidance_scale, do_cfg)
+            self._one_step(lat_buf, t_buf, state, ctx, guidance_scale, do_cfg, guidance_rescale, fused_step, unet)
         torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
+        from . import graph_utils
+        graph = graph_utils.new_graph()            # (torch.cuda.CUDAGraph(); kept inspectable under graph_utils.KEEP_GRAPHS)
         with torch.cuda.graph(graph):
-            out = self._one_step(lat_buf, t_buf, state, ctx, guidance_scale, do_cfg)
+            out = self._one_step(lat_buf, t_buf, state, ctx, guidance_scale, do_cfg, guidance_rescale, fused_step, unet)
         return {"graph": graph, "lat": lat_buf, "t": t_buf, "state": state, "out": out, "ctx": ctx}
+
+
+def plan_groups(idx_list, group_sizes=(1, 2, 4, 8)):
+    """Group the prompts of a routed batch by expert: ``idx_list[i]`` is prompt i's expert index; returns
+    ``[(expert, rows, bucket)]`` -- experts in ascending index, the rows of one expert in ascending prompt order, cut into
+    chunks of at most the largest bucket, each chunk in the smallest bucket of ``group_sizes`` that holds it.  Every row
+    appears exactly once.  Pure host logic, deterministic."""
+    sizes = sorted({int(s) for s in group_sizes})
+    if not sizes or sizes[0] < 1:
+        raise ValueError(f"plan_groups: group_sizes must be positive integers, got {group_sizes!r}")
+    by_expert = {}
+    for row, e in enumerate(idx_list):
+        by_expert.setdefault(int(e), []).append(row)
+    groups = []
+    for e in sorted(by_expert):
+        rows = by_expert[e]
+        for s in range(0, len(rows), sizes[-1]):
+            chunk = rows[s:s + sizes[-1]]
+            groups.append((e, chunk, next(b for b in sizes if b >= len(chunk))))
+    return groups
+
+
+class ExpertDispatchLoop(PruningDenoiseLoop):
+    """The routed call of StableDiffusionPruningPipeline (pruning_pipelines.py:746-759: route, ``set_structure``, loop) for a
+    batch whose prompts go to MORE than one expert, at each expert's own cost: the batch is routed once, grouped by expert
+    (``plan_groups``), and every group runs the whole denoise loop with that expert's hard code installed as a batch-shared
+    structure -- the compacted-weight path of the U-Net (gated semantics, exact through the border table) instead of dense
+    compute with per-sample gates.  A group is padded to a bucket size of ``group_sizes`` by repeating its last row (samples
+    are independent: the padded rows are computed and dropped), so a handful of captured steps serves any split.  Results
+    come back in the caller's prompt order.  Every step is the fused one (``fused_step`` of the scheduler).
+
+    Groups run one after another on the current stream.
+
+    experts: ``{index: UNet2DConditionModelPruned | UNet2DConditionModelGated}`` -- fine-tuned experts with weights of their
+    own (checkpoint.from_pretrained).  Group e then runs on ``experts[e]`` as it is installed, without ``set_structure``;
+    routing still comes from ``hyper_net`` / ``quantizer``; an index the router picks that is missing raises KeyError.
+
+    Captured steps: one per (expert identity, the bytes of its hard code, bucket, scheduler class, prediction type, latent
+    shape, dtype, CFG, guidance scale, guidance rescale, device), in an LRU of at most ``max_graphs`` entries.  A capture
+    pins the packed-weight plans it touched in the modules' plan caches until ``invalidate_plans()`` / ``clear()``: evicting
+    a graph here does NOT free its packs.  Re-installing a code finds its pinned plans again, so the bound is at most
+    ``max_graphs`` pinned plans per module for as long as no more than ``max_graphs`` distinct codes are captured between
+    two ``invalidate_plans()``; every further distinct code that is captured pins one more."""
+
+    def __init__(self, unet, hyper_net=None, quantizer=None, scheduler=None, vae=None, text_encoder=None, prompt_encoder=None,
+                 experts=None, group_sizes=(1, 2, 4, 8), max_graphs: int = 16):
+        super().__init__(unet, hyper_net, quantizer, scheduler, vae, text_encoder, prompt_encoder)
+        self.experts = None if experts is None else dict(experts)
+        self.group_sizes = tuple(sorted({int(s) for s in group_sizes}))
+        if not self.group_sizes or self.group_sizes[0] < 1:
+            raise ValueError(f"group_sizes must be positive integers, got {group_sizes!r}")
+        if max_graphs < 1:
+            raise ValueError(f"max_graphs must be at least 1, got {max_graphs}")
+        self.max_graphs = int(max_graphs)
+        self._graphs = OrderedDict()               # key -> captured step, least recently used first
+        self._installed = None                     # (structure epoch of self.unet, code bytes) this loop installed last
+
+    @torch.no_grad()
+    def route_indices(self, hyper_net_input: torch.Tensor):
+        """hyper_net -> quantizer (eval) WITHOUT installing anything: (arch_q [B, D] hard codes, idx [B])"""
+        self.hyper_net.eval()
+        self.quantizer.eval()
+        arch_q, (_, _, idx) = self.quantizer(self.hyper_net(hyper_net_input))
+        return arch_q, idx
+
+    def _install(self, code_row: torch.Tensor, code: bytes):
+        """the expert's code as a batch-shared structure of self.unet (skipped when it is what this loop installed last
+        and nobody has installed anything since)"""
+        if self._installed == (getattr(self.unet, "_structure_epoch", None), code):
+            return
+        self.unet.set_structure(self.hyper_net.transform_structure_vector(code_row))
+        self._installed = (self.unet._structure_epoch, code)
+
+    @torch.no_grad()
+    def __call__(self, prompt_embeds: Optional[torch.Tensor] = None, latents: Optional[torch.Tensor] = None,
+                 num_inference_steps: int = 50, guidance_scale: float = 7.5, hyper_net_input: Optional[torch.Tensor] = None,
+                 negative_prompt_embeds: Optional[torch.Tensor] = None, use_graph: bool = True,
+                 output_type: str = "latent", *, prompt_ids: Optional[torch.Tensor] = None,
+                 negative_prompt_ids: Optional[torch.Tensor] = None, router_ids: Optional[torch.Tensor] = None,
+                 router_attention_mask: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0,
+                 fused_step: bool = True) -> DispatchOutput:
+        """The arguments of PruningDenoiseLoop.__call__; hyper_net_input or router_ids is required (there is nothing to
+        dispatch on otherwise), and the step is always the fused one.  Returns latents / images in the caller's prompt order,
+        ``arch_indices`` [B], ``resource_ratios`` [B] and ``groups``."""
+        if not fused_step:
+            raise ValueError("ExpertDispatchLoop runs the fused step only")
+        if self.hyper_net is None or self.quantizer is None:
+            raise ValueError("ExpertDispatchLoop needs a hyper_net and a quantizer to route with")
+        prompt_embeds, negative_prompt_embeds, hyper_net_input = self._inputs(
+            prompt_embeds, latents, hyper_net_input, negative_prompt_embeds, output_type, prompt_ids, negative_prompt_ids,
+            router_ids, router_attention_mask, guidance_scale)
+        if hyper_net_input is None:
+            raise ValueError("ExpertDispatchLoop needs hyper_net_input or router_ids")
+        dev = latents.device
+        nB = latents.shape[0]
+        arch_q, idx = self.route_indices(hyper_net_input.to(dev))
+        # ONE device-to-host copy: the indices and the hard codes (a byte per entry) together
+        host = torch.cat([idx.to(torch.int16).view(torch.uint8).reshape(nB, 2), (arch_q >= 0.5).to(torch.uint8)], dim=1).cpu()
+        idx_list = host[:, :2].contiguous().view(torch.int16).reshape(nB).tolist()
+        codes = [bytes(host[i, 2:].tolist()) for i in range(nB)]
+        groups = plan_groups(idx_list, self.group_sizes)
+        if self.experts is not None:
+            for e, _, _ in groups:
+                if e not in self.experts:
+                    raise KeyError(f"the router picked expert {e}, which is not in experts ({sorted(self.experts)})")
+        do_cfg = guidance_scale > 1.0 and negative_prompt_embeds is not None
+        prompt_embeds = prompt_embeds.to(dev)
+        if do_cfg:
+            negative_prompt_embeds = negative_prompt_embeds.to(dev)
+        ts = self.scheduler.set_timesteps(num_inference_steps, device=dev)
+        latents = latents * self.scheduler.init_noise_sigma
+        out = torch.empty_like(latents)
+        ratios = None
+        report = []
+        rescale = float(guidance_rescale) if do_cfg else 0.0
+        for e, rows, bucket in groups:
+            code = codes[rows[0]]
+            assert all(codes[r] == code for r in rows), f"rows {rows} of expert {e} carry different codes"
+            if self.experts is not None:
+                model = self.experts[e]
+            else:
+                model = self.unet
+                self._install(arch_q[rows[0]:rows[0] + 1], code)
+            rows_t = torch.tensor(rows, dtype=torch.long, device=dev)
+            take = torch.tensor(rows + [rows[-1]] * (bucket - len(rows)), dtype=torch.long, device=dev)
+            lat_g = latents.index_select(0, take)
+            ehs = prompt_embeds.index_select(0, take)
+            if do_cfg:
+                ehs = torch.cat([negative_prompt_embeds.index_select(0, take), ehs])
+            ctx = model.precompute_context(ehs)                                   # after the install: K/V packs are per structure
+            Bm = bucket * (2 if do_cfg else 1)
+            reused = False
+            if not use_graph:
+                res = self._eager(lat_g, ts, ctx, Bm, guidance_scale, do_cfg, rescale, True, model)
+            else:
+                key = (e, id(model), code, bucket, type(self.scheduler).__name__, self.scheduler.prediction_type,
+                       tuple(lat_g.shape), lat_g.dtype, do_cfg, float(guidance_scale), rescale, str(dev))
+                g = self._graphs.get(key)
+                reused = g is not None and ctx.key is not None and g["ctx"].key == ctx.key
+                if not reused:
+                    self._graphs.pop(key, None)
+                    while len(self._graphs) >= self.max_graphs:
+                        self._graphs.popitem(last=False)
+                    g = self._capture(lat_g, ts, ctx, Bm, guidance_scale, do_cfg, rescale, True, model)
+                    if ctx.key is not None:
+                        self._graphs[key] = g
+                else:
+                    self._graphs.move_to_end(key)
+                res = self._replay(g, lat_g, ts, ctx, Bm)
+            out.index_copy_(0, rows_t, res[:len(rows)].to(out.dtype))
+            if getattr(model, "resource_info_dict", None) is not None:
+                # pruning_pipelines.py:822-824, per group
+                r = model.calc_macs()["cur_prunable_macs"] / model.resource_info_dict["cur_prunable_macs"]
+                if ratios is None:
+                    ratios = torch.zeros(nB, dtype=torch.float32, device=dev)
+                ratios.index_copy_(0, rows_t, torch.as_tensor(r, dtype=torch.float32, device=dev).reshape(-1)[:1].expand(len(rows)))
+            report.append((e, list(rows), bucket, reused))
+        images = None
+        if output_type != "latent":
+            images = self.decode_latents(out, output_type)
+        return DispatchOutput(latents=out, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios,
+                              images=images, groups=report)

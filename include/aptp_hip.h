@@ -963,6 +963,46 @@ typedef struct {
 } AptpTrainImagesParams;
 int aptp_train_images(const AptpTrainImagesParams* p, aptp_stream_t stream);
 
+/* Everything a denoise step does after the U-Net call, in one launch: classifier-free guidance, the optional guidance
+ * rescale, and the scheduler update (pipeline.py: PruningDenoiseLoop._one_step after the forward, DDIMSchedulerLite.step_coef,
+ * PNDMSchedulerLite.step), in fp32, statement for statement.
+ *   noise    the model output, contiguous [noise_rows, n], bf16 or fp32 (noise_dtype); with do_cfg noise_rows = 2 b laid out
+ *            [uncond; text], without it noise_rows = b
+ *   sample   fp32 [b, n];  out fp32 [b, n] (may be sample itself)
+ *   g = u + guidance_scale (t - u)                                                       (do_cfg; otherwise g = noise)
+ *   g <- phi g std(t) / std(g) + (1 - phi) g,  phi = guidance_rescale > 0                (needs do_cfg and n >= 2)
+ *            std per sample over its n elements, unbiased (n - 1); summed in fp64 in a fixed order, no atomics
+ * The scheduler state is DEVICE memory, read by the kernel, so a captured launch serves every step:
+ *   DDIM     coef fp32 [4] = sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev)
+ *   PNDM     slot int64 [1], w fp32 [5], coef fp32 [2] = a_t, a_prev, flags fp32 [2] = use_saved, save, the ring E fp32
+ *            [5, b, n] and saved fp32 [b, n]; E[slot] <- g and saved are updated in place (a slot outside 0..4 is clamped)
+ * Without the rescale a flat grid over b n elements in groups of four (when every base is 16-byte aligned) plus single
+ * elements; with it one workgroup per sample.  APTP_EINVAL and nothing launched for: null pointers, an unknown dtype /
+ * scheduler / prediction type, noise_rows that is not b (2 b with do_cfg), misaligned pointers, guidance_rescale outside
+ * [0, 1], a rescale without do_cfg or with n < 2. */
+#define APTP_STEP_NOISE_BF16 0
+#define APTP_STEP_NOISE_F32 1
+#define APTP_STEP_DDIM 0
+#define APTP_STEP_PNDM 1
+#define APTP_STEP_EPSILON 0
+#define APTP_STEP_V_PREDICTION 1
+typedef struct {
+  const void* noise;
+  const float* sample;
+  float* out;
+  const float* coef;
+  const int64_t* slot;
+  const float* w;
+  const float* flags;
+  float* E;
+  float* saved;
+  int64_t n;
+  int32_t b, noise_rows;
+  int32_t noise_dtype, scheduler, prediction, do_cfg;
+  float guidance_scale, guidance_rescale;
+} AptpGuidedStepParams;
+int aptp_guided_step(const AptpGuidedStepParams* p, aptp_stream_t stream);
+
 const char* aptp_last_error(void);
 int aptp_version(void);
 
