@@ -20,15 +20,15 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass, fields
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional
 
 import torch
 
 from . import ops
 from .image_encoder import CLIPVisionConfig, CLIPVisionModelWithProjection
 from .loading import load_strict, read_pretrained, read_safetensors
+from .modules import LinearP, ModelOutput
 from .text_encoder import CLIPTextConfig, _TextTower
-from .unet import LinearP
 
 
 @dataclass(frozen=True)
@@ -53,18 +53,10 @@ class CLIPTextProjectionConfig(CLIPTextConfig):
 
 
 @dataclass
-class CLIPTextModelOutput:
+class CLIPTextModelOutput(ModelOutput):
     """transformers' ``CLIPTextModelOutput``: ``.text_embeds`` / ``out[0]``, then ``last_hidden_state``."""
     text_embeds: torch.Tensor
     last_hidden_state: torch.Tensor
-
-    def to_tuple(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        return (self.text_embeds, self.last_hidden_state)
-
-    def __getitem__(self, i):
-        if isinstance(i, str):
-            return getattr(self, i)
-        return self.to_tuple()[i]
 
 
 def _is_foreign(name: str) -> bool:

@@ -16,9 +16,10 @@ patch_embedding.weight, position_embedding.weight}``, ``vision_model.pre_layrnor
     its epilogue -> fc2 with the residual in its epilogue;
   * ``post_layernorm`` on the class row only, then ``visual_projection`` (fp32 output): ``image_embeds``.
 
-The LayerNorms are stand-alone ``ops.layernorm`` launches.  The folded form of the text encoder (text_encoder.py,
-``FOLD_LN_MAX_ROWS``) paid off only under ~512 rows; one image is already 577 rows, and the A/B at this encoder's shapes has not
-been measured, so the form that was faster at every comparable size is the one that ships.
+The layer loop and its packing are the text tower's (``modules.run_clip_layers`` / ``pack_clip_layers``) with ``ops.attention``
+and stand-alone ``ops.layernorm`` launches.  The folded form of the text encoder (text_encoder.py, ``FOLD_LN_MAX_ROWS``) paid off
+only under ~512 rows; one image is already 577 rows, and the A/B at this encoder's shapes has not been measured, so the form that
+was faster at every comparable size is the one that ships.
 
 With ``ops.ACT_DTYPE = torch.float32`` the same code runs the fp32 parity instantiations of every kernel.  Every launch goes to
 torch's current stream and ``forward`` makes no host sync, so an encode can be captured with ``torch.cuda.graph`` after one eager
@@ -34,8 +35,9 @@ import torch.nn as nn
 
 from . import ops
 from .loading import load_strict, read_pretrained
-from .text_encoder import _Encoder, _LayerNorm
-from .unet import LinearP, _PlanCache, _versions
+from .modules import (ACTS, LinearP, ModelOutput, PlannedModule, _LayerNorm, _PlanCache, _versions, clip_init_rule, init_synthetic_,
+                      pack_clip_layers, run_clip_layers)
+from .text_encoder import _Encoder
 
 
 @dataclass(frozen=True)
@@ -91,9 +93,6 @@ def image_encoder_flops(cfg: CLIPVisionConfig) -> float:
     return patch + cfg.num_hidden_layers * (lin + attn) + 2.0 * H * cfg.projection_dim
 
 
-_ACTS = {"gelu": ops.ACT_GELU, "quick_gelu": ops.ACT_QUICK_GELU}
-
-
 class _PatchEmbedding(nn.Module):
     def __init__(self, cin: int, c: int, p: int):
         super().__init__()
@@ -124,18 +123,10 @@ class _VisionTransformer(nn.Module):
 
 
 @dataclass
-class CLIPVisionModelOutput:
+class CLIPVisionModelOutput(ModelOutput):
     """transformers' ``CLIPVisionModelOutput`` as CMMD uses it: ``.image_embeds`` / ``out[0]``, then ``last_hidden_state``."""
     image_embeds: torch.Tensor
     last_hidden_state: torch.Tensor
-
-    def to_tuple(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        return (self.image_embeds, self.last_hidden_state)
-
-    def __getitem__(self, i):
-        if isinstance(i, str):
-            return getattr(self, i)
-        return self.to_tuple()[i]
 
 
 def _is_foreign(name: str) -> bool:
@@ -144,14 +135,14 @@ def _is_foreign(name: str) -> bool:
             or name.endswith("embeddings.position_ids"))
 
 
-class CLIPVisionModelWithProjection(nn.Module):
+class CLIPVisionModelWithProjection(PlannedModule):
     """``CLIPVisionModelWithProjection`` of transformers for 64-wide heads, 3-channel images and ``hidden_act`` "quick_gelu" or
     "gelu", forward only."""
 
     def __init__(self, config: Optional[CLIPVisionConfig] = None, **kw):
         super().__init__()
         cfg = config or CLIPVisionConfig(**kw)
-        if cfg.hidden_act not in _ACTS:
+        if cfg.hidden_act not in ACTS:
             raise NotImplementedError(f"CLIPVisionModelWithProjection: hidden_act {cfg.hidden_act!r} (only 'quick_gelu' and 'gelu')")
         if cfg.hidden_size % cfg.num_attention_heads != 0 or cfg.head_dim != 64:
             raise NotImplementedError(f"CLIPVisionModelWithProjection: head dim {cfg.hidden_size / cfg.num_attention_heads:g} (only 64)")
@@ -167,26 +158,11 @@ class CLIPVisionModelWithProjection(nn.Module):
         self._plans = _PlanCache(cap=2)          # one plan per activation dtype
 
     # ---- weights ----------------------------------------------------------------------------------------------------
-    @torch.no_grad()
     def init_synthetic(self, seed: int = 0) -> "CLIPVisionModelWithProjection":
         """Deterministic weights under which every layer changes the residual stream measurably (the text encoder's recipe):
         linear weights with std fan_in^-1/2 (out_proj and fc2 scaled by 0.5), the patch convolution likewise over its 3 P^2
         inputs, LayerNorm affine near identity, small biases, class and position embeddings with std 0.5."""
-        g = torch.Generator().manual_seed(seed)
-        for name, p in self.named_parameters():
-            if "patch_embedding" in name:
-                p.copy_(p[0].numel() ** -0.5 * torch.randn(p.shape, generator=g))
-            elif "embedding" in name:
-                p.copy_(0.5 * torch.randn(p.shape, generator=g))
-            elif name.endswith("bias"):
-                p.copy_(0.02 * torch.randn(p.shape, generator=g))
-            elif p.dim() == 1:                                   # LayerNorm gamma
-                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
-            else:
-                scale = 0.5 if (".out_proj." in name or ".fc2." in name) else 1.0
-                p.copy_(scale * p.shape[1] ** -0.5 * torch.randn(p.shape, generator=g))
-        self.invalidate()
-        return self
+        return init_synthetic_(self, seed, clip_init_rule)
 
     def load_vision_state_dict(self, sd: Dict[str, torch.Tensor]) -> "CLIPVisionModelWithProjection":
         """Strict load of a transformers CLIPVisionModelWithProjection state dict.  ``position_ids`` buffers are ignored, and so
@@ -200,14 +176,6 @@ class CLIPVisionModelWithProjection(nn.Module):
         cfg, sd = read_pretrained(CLIPVisionConfig, root, subfolder, "model.safetensors", skip=_is_foreign)
         return cls(cfg).load_vision_state_dict(sd)
 
-    def invalidate(self):
-        self._plans.clear()
-        self.__dict__.pop("_vparams", None)
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate()
-        return super()._apply(fn, *a, **k)
-
     # ---- packed weights ---------------------------------------------------------------------------------------------
     def plan(self, device) -> dict:
         """packed weights per (device, ACT_DTYPE) in the _PlanCache: a plan seen during a capture outlives the graph; a weight
@@ -219,21 +187,12 @@ class CLIPVisionModelWithProjection(nn.Module):
         f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
         ln = lambda m: (f32(m.weight), f32(m.bias))                     # noqa: E731
         vm = self.vision_model
-        layers = []
-        for ly in vm.encoder.layers:
-            a = ly.self_attn
-            wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).detach()
-            bqkv = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0).detach()
-            layers.append({"ln1": ln(ly.layer_norm1), "ln2": ln(ly.layer_norm2),
-                           "qkv": ops.pack_weight(wqkv, bqkv, device=device),
-                           "out": ops.pack_weight(a.out_proj.weight.detach(), a.out_proj.bias.detach(), device=device),
-                           "fc1": ops.pack_weight(ly.mlp.fc1.weight.detach(), ly.mlp.fc1.bias.detach(), device=device),
-                           "fc2": ops.pack_weight(ly.mlp.fc2.weight.detach(), ly.mlp.fc2.bias.detach(), device=device)})
         emb = vm.embeddings
         pl = {"patch": ops.pack_weight(emb.patch_embedding.weight.detach().flatten(1), None, device=device),   # rows in (c, py, px) order
               "cls": f32(emb.class_embedding), "pos": f32(emb.position_embedding.weight),
               "pre": ln(vm.pre_layrnorm), "post": ln(vm.post_layernorm),
-              "proj": ops.pack_weight(self.visual_projection.weight.detach(), None, device=device), "layers": layers}
+              "proj": ops.pack_weight(self.visual_projection.weight.detach(), None, device=device),
+              "layers": pack_clip_layers(vm.encoder.layers, device, fold=False)}
         return self._plans.put(key, version, pl)
 
     # ---- forward ----------------------------------------------------------------------------------------------------
@@ -248,18 +207,12 @@ class CLIPVisionModelWithProjection(nn.Module):
         ops.ACT_DTYPE [B, tokens, hidden])"""
         cfg = self.config
         pl = self.plan(patches.device)
-        C, nh, eps = cfg.hidden_size, cfg.num_attention_heads, cfg.layer_norm_eps
-        f32 = ops.ACT_DTYPE == torch.float32
-        act = _ACTS[cfg.hidden_act]
+        C, eps = cfg.hidden_size, cfg.layer_norm_eps
         G2 = cfg.grid * cfg.grid
         pe = ops.linear(patches.view(B, G2, patches.shape[1])[..., :pl["patch"].Cin], pl["patch"], out_f32=True)
-        x = ops.vit_embed_ln(pe.view(B * G2, C), B, pl["cls"], pl["pos"], *pl["pre"], eps=eps, out_f32=f32)
-        for e in pl["layers"]:
-            qkv = ops.linear(ops.layernorm(x, *e["ln1"], eps), e["qkv"])
-            o = ops.attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], nh)
-            x = ops.linear(o, e["out"], residual=x)
-            f = ops.linear(ops.layernorm(x, *e["ln2"], eps), e["fc1"], act=act)
-            x = ops.linear(f, e["fc2"], residual=x)
+        x = ops.vit_embed_ln(pe.view(B * G2, C), B, pl["cls"], pl["pos"], *pl["pre"], eps=eps, out_f32=ops.ACT_DTYPE == torch.float32)
+        x = run_clip_layers(x, pl["layers"], attn=ops.attention, heads=cfg.num_attention_heads, act=ACTS[cfg.hidden_act], eps=eps,
+                            who="CLIPVisionModelWithProjection")
         pooled = ops.layernorm(x[:, 0, :].unsqueeze(0), *pl["post"], eps)          # the class rows as one [1, B, C] strided view
         emb = ops.linear(pooled, pl["proj"], out_f32=True)
         return emb[0], x

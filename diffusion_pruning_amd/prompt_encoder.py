@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, fields
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
@@ -34,7 +34,8 @@ import torch.nn as nn
 from . import ops
 from .launch_policy import _lean_tile
 from .loading import load_strict, read_pretrained
-from .unet import LinearP, _PlanCache, _versions
+from .modules import (LinearP, ModelOutput, PlannedModule, _Embedding, _LayerNorm, _PlanCache, _versions, cat_qkv, check_token_ids,
+                      init_synthetic_)
 
 # True: every linear of the bf16 path is launched on the lean tile of its row count with no K split, so every output element is one
 # K-ordered accumulation whatever else shares the batch, and a prompt's embedding does not depend on the other prompts or on the
@@ -103,20 +104,6 @@ def relative_bias_table(weight: torch.Tensor, L: int) -> torch.Tensor:
     return weight.detach().float().cpu()[bucket].t().contiguous()
 
 
-class _Embedding(nn.Module):
-    def __init__(self, n: int, c: int):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(n, c))
-
-
-class _LayerNorm(nn.Module):
-    def __init__(self, c: int, eps: float):
-        super().__init__()
-        self.eps = eps
-        self.weight = nn.Parameter(torch.empty(c))
-        self.bias = nn.Parameter(torch.empty(c))
-
-
 class _Embeddings(nn.Module):
     def __init__(self, cfg: MPNetConfig):
         super().__init__()
@@ -167,17 +154,21 @@ class _Encoder(nn.Module):
 
 
 @dataclass
-class MPNetModelOutput:
+class MPNetModelOutput(ModelOutput):
     """transformers' ``BaseModelOutput`` as the reference uses it: ``out[0]`` / ``.last_hidden_state``."""
     last_hidden_state: torch.Tensor
 
-    def to_tuple(self) -> Tuple[torch.Tensor]:
-        return (self.last_hidden_state,)
 
-    def __getitem__(self, i):
-        if isinstance(i, str):
-            return getattr(self, i)
-        return self.to_tuple()[i]
+def _init_rule(name: str, p: torch.Tensor) -> Optional[float]:
+    """init_synthetic_'s rule: a relative-position table with std 1 (O(1) score terms), embeddings with std 0.5, o and the output
+    dense scaled by 0.5"""
+    if name == "encoder.relative_attention_bias.weight":
+        return 1.0
+    if "embeddings.weight" in name:
+        return 0.5
+    if p.dim() == 2 and (".attn.o." in name or ".output.dense." in name):
+        return 0.5 * p.shape[1] ** -0.5
+    return None
 
 
 def _ignored_key(n: str) -> bool:
@@ -185,7 +176,7 @@ def _ignored_key(n: str) -> bool:
     return n.startswith("pooler.") or n == "embeddings.position_ids"
 
 
-class MPNetModel(nn.Module):
+class MPNetModel(PlannedModule):
     """``MPNetModel`` of transformers without the pooler, for ``hidden_act == "gelu"`` and 64-wide heads, forward only (the
     reference runs the router's encoder under no_grad)."""
 
@@ -207,26 +198,11 @@ class MPNetModel(nn.Module):
         self._plans = _PlanCache(cap=2)          # one per activation dtype
 
     # ---- weights ----------------------------------------------------------------------------------------------------
-    @torch.no_grad()
     def init_synthetic(self, seed: int = 0) -> "MPNetModel":
         """Deterministic weights under which every layer moves the residual stream measurably: linear weights with std
         fan_in^-1/2 (o and the output dense scaled by 0.5; the stream is re-normalised after every sum), LayerNorm affine
         near identity, small biases, embeddings with std 0.5, and a relative-position table with std 1 (O(1) score terms)."""
-        g = torch.Generator().manual_seed(seed)
-        for name, p in self.named_parameters():
-            if name == "encoder.relative_attention_bias.weight":
-                p.copy_(torch.randn(p.shape, generator=g))
-            elif "embeddings.weight" in name:
-                p.copy_(0.5 * torch.randn(p.shape, generator=g))
-            elif name.endswith("bias"):
-                p.copy_(0.02 * torch.randn(p.shape, generator=g))
-            elif p.dim() == 1:                                   # LayerNorm gamma
-                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
-            else:
-                scale = 0.5 if (".attn.o." in name or ".output.dense." in name) else 1.0
-                p.copy_(scale * p.shape[1] ** -0.5 * torch.randn(p.shape, generator=g))
-        self.invalidate()
-        return self
+        return init_synthetic_(self, seed, _init_rule)
 
     def load_mpnet_state_dict(self, sd: Dict[str, torch.Tensor]) -> "MPNetModel":
         """Strict load of a transformers MPNetModel state dict (with or without an ``mpnet.`` prefix); ``pooler.*`` and
@@ -240,14 +216,6 @@ class MPNetModel(nn.Module):
                                   skip=lambda n: n.endswith("embeddings.position_ids"))
         return cls(cfg).load_mpnet_state_dict(sd)
 
-    def invalidate(self):
-        self._plans.clear()
-        self.__dict__.pop("_vparams", None)
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate()
-        return super()._apply(fn, *a, **k)
-
     # ---- packed weights ---------------------------------------------------------------------------------------------
     def plan(self, device) -> dict:
         """packed weights per (device, ACT_DTYPE) in the _PlanCache, with the relative-bias tables per L"""
@@ -260,9 +228,7 @@ class MPNetModel(nn.Module):
         layers = []
         for ly in self.encoder.layer:
             a = ly.attention.attn
-            wqkv = torch.cat([a.q.weight, a.k.weight, a.v.weight], 0).detach()
-            bqkv = torch.cat([a.q.bias, a.k.bias, a.v.bias], 0).detach()
-            layers.append({"qkv": ops.pack_weight(wqkv, bqkv, device=device), "o": pack(a.o),
+            layers.append({"qkv": ops.pack_weight(*cat_qkv(a.q, a.k, a.v), device=device), "o": pack(a.o),
                            "ln1": (f32(ly.attention.LayerNorm.weight), f32(ly.attention.LayerNorm.bias)),
                            "in": pack(ly.intermediate.dense), "out": pack(ly.output.dense),
                            "ln2": (f32(ly.output.LayerNorm.weight), f32(ly.output.LayerNorm.bias))})
@@ -303,16 +269,8 @@ class MPNetModel(nn.Module):
     def _check_inputs(self, input_ids, attention_mask):
         cfg = self.config
         dev = self.embeddings.word_embeddings.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("MPNetModel runs on the HIP kernels only: move it to a GPU first (model.to('cuda'))")
-        if input_ids.dim() != 2 or input_ids.dtype not in (torch.int64, torch.int32):
-            raise ValueError(f"MPNetModel: input_ids must be an integer [B, L] tensor, got {input_ids.dtype} {tuple(input_ids.shape)}")
-        B, L = input_ids.shape
-        if B < 1 or not 1 <= L <= cfg.max_length:
-            raise ValueError(f"MPNetModel: sequence length {L} outside [1, {cfg.max_length}] (batch {B})")
-        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if not torch.cuda.is_current_stream_capturing() and bool(((ids < 0) | (ids >= cfg.vocab_size)).any()):
-            raise ValueError(f"MPNetModel: token ids outside [0, {cfg.vocab_size})")
+        ids = check_token_ids("MPNetModel", input_ids, dev, cfg.max_length, cfg.vocab_size)
+        B, L = ids.shape
         mask = None
         if attention_mask is not None:
             if tuple(attention_mask.shape) != (B, L):

@@ -19,6 +19,7 @@ their bias, and finish the normalisation in their epilogue (include/aptp_hip.h, 
 the stack.  Layer 0's LN1 (its input comes from the embedding) and any launch whose producer could not emit statistics
 take the stand-alone ``ops.layernorm``.  Larger encodes use stand-alone LayerNorms everywhere: measured on MI355X, the folded
 form is 3.4 % faster at 2 x 77 tokens and 4.9 % / 1.8 % slower at 16 x 77 / 64 x 77 (profiles/r8_text_encoder_bench_line.json).
+The layer loop and its packing are ``modules.run_clip_layers`` / ``pack_clip_layers``, which image_encoder.py runs too.
 
 With ``ops.ACT_DTYPE = torch.float32`` the same code runs the fp32 parity instantiations of every kernel.
 Every launch goes to torch's current stream; ``forward`` makes no host sync while a graph is being captured (the id range
@@ -34,7 +35,8 @@ import torch.nn as nn
 
 from . import ops
 from .loading import load_strict, read_pretrained
-from .unet import LinearP, _PlanCache, _versions
+from .modules import (ACTS, LinearP, ModelOutput, PlannedModule, _Embedding, _LayerNorm, _PlanCache, _versions, check_token_ids,
+                      clip_init_rule, init_synthetic_, pack_clip_layers, run_clip_layers)
 
 # encodes of at most this many tokens (B * L) fold LN1 / LN2 into the q|k|v and fc1 GEMMs, larger ones launch stand-alone
 # LayerNorms.  Measured (tools/bench_text_encoder.py, graph replays, both forms alternately): folded 1.455 vs 1.503 ms at
@@ -74,20 +76,6 @@ def text_encoder_flops(cfg: CLIPTextConfig, L: int) -> float:
     lin = 2.0 * L * (4 * H * H + 2 * H * I)
     attn = 2.0 * 2.0 * H * L * (L + 1) / 2
     return cfg.num_hidden_layers * (lin + attn)
-
-
-class _Embedding(nn.Module):
-    def __init__(self, n: int, c: int):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(n, c))
-
-
-class _LayerNorm(nn.Module):
-    def __init__(self, c: int, eps: float):
-        super().__init__()
-        self.eps = eps
-        self.weight = nn.Parameter(torch.empty(c))
-        self.bias = nn.Parameter(torch.empty(c))
 
 
 class _Attention(nn.Module):
@@ -133,24 +121,13 @@ class _TextTransformer(nn.Module):
 
 
 @dataclass
-class CLIPTextModelOutput:
+class CLIPTextModelOutput(ModelOutput):
     """transformers' ``BaseModelOutputWithPooling`` as the reference uses it: ``out[0]`` / ``.last_hidden_state``."""
     last_hidden_state: torch.Tensor
     pooler_output: torch.Tensor
 
-    def to_tuple(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        return (self.last_hidden_state, self.pooler_output)
 
-    def __getitem__(self, i):
-        if isinstance(i, str):
-            return getattr(self, i)
-        return self.to_tuple()[i]
-
-
-_ACTS = {"gelu": ops.ACT_GELU, "quick_gelu": ops.ACT_QUICK_GELU}
-
-
-class _TextTower(nn.Module):
+class _TextTower(PlannedModule):
     """What ``CLIPTextModel`` and ``clip_model.CLIPTextModelWithProjection`` share: the ``text_model`` parameters, the packed
     plans and the layer stack up to (not including) ``final_layer_norm``.  A subclass names the activations it accepts and adds
     its own loading and outputs."""
@@ -173,32 +150,11 @@ class _TextTower(nn.Module):
         self._plans = _PlanCache(cap=4)
 
     # ---- weights ----------------------------------------------------------------------------------------------------
-    @torch.no_grad()
     def init_synthetic(self, seed: int = 0):
         """Deterministic weights under which every layer changes the residual stream measurably: linear weights with std
         fan_in^-1/2 (out_proj and fc2 scaled by 0.5, so the stream grows slowly over the 23 residual additions), LayerNorm
         affine near identity, small biases, embeddings with std 0.5."""
-        g = torch.Generator().manual_seed(seed)
-        for name, p in self.named_parameters():
-            if "embedding" in name:
-                p.copy_(0.5 * torch.randn(p.shape, generator=g))
-            elif name.endswith("bias"):
-                p.copy_(0.02 * torch.randn(p.shape, generator=g))
-            elif p.dim() == 1:                                   # LayerNorm gamma
-                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
-            else:
-                scale = 0.5 if (".out_proj." in name or ".fc2." in name) else 1.0
-                p.copy_(scale * p.shape[1] ** -0.5 * torch.randn(p.shape, generator=g))
-        self.invalidate()
-        return self
-
-    def invalidate(self):
-        self._plans.clear()
-        self.__dict__.pop("_vparams", None)
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate()
-        return super()._apply(fn, *a, **k)
+        return init_synthetic_(self, seed, clip_init_rule)
 
     # ---- packed weights ---------------------------------------------------------------------------------------------
     def plan(self, device, fold: bool = True) -> dict:
@@ -210,27 +166,9 @@ class _TextTower(nn.Module):
             return pl
         f32 = lambda t: t.detach().float().to(device).contiguous()      # noqa: E731
         tm = self.text_model
-        layers = []
-        for i, ly in enumerate(tm.encoder.layers):
-            a = ly.self_attn
-            wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).detach()
-            bqkv = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], 0).detach()
-            e = {"ln1": (f32(ly.layer_norm1.weight), f32(ly.layer_norm1.bias)),
-                 "ln2": (f32(ly.layer_norm2.weight), f32(ly.layer_norm2.bias)),
-                 "out": ops.pack_weight(a.out_proj.weight.detach(), a.out_proj.bias.detach(), device=device),
-                 "fc2": ops.pack_weight(ly.mlp.fc2.weight.detach(), ly.mlp.fc2.bias.detach(), device=device)}
-            for nm, idx, w, b in (("qkv", 1, wqkv, bqkv), ("fc1", 2, ly.mlp.fc1.weight.detach(), ly.mlp.fc1.bias.detach())):
-                g_, b_ = e[f"ln{idx}"]
-                # folded form wherever the producer emits statistics (every launch but layer 0's q|k|v); the plain form for
-                # layer 0 and for the stand-alone LayerNorm path
-                if fold and not (i == 0 and nm == "qkv"):
-                    e[nm + "_ln"] = ops.pack_weight(w, b, device=device, ln_gamma=g_, ln_beta=b_)
-                    e[nm + "_make"] = (lambda w=w, b=b: ops.pack_weight(w, b, device=device))
-                else:
-                    e[nm] = ops.pack_weight(w, b, device=device)
-            layers.append(e)
         pl = {"tok": f32(tm.embeddings.token_embedding.weight), "pos": f32(tm.embeddings.position_embedding.weight),
-              "final": (f32(tm.final_layer_norm.weight), f32(tm.final_layer_norm.bias)), "layers": layers}
+              "final": (f32(tm.final_layer_norm.weight), f32(tm.final_layer_norm.bias)),
+              "layers": pack_clip_layers(tm.encoder.layers, device, fold)}
         self._plan_extra(pl, device)
         return self._plans.put(key, version, pl)
 
@@ -238,37 +176,15 @@ class _TextTower(nn.Module):
         """packed weights a subclass needs beyond the tower's (the text projection)"""
 
     # ---- forward ----------------------------------------------------------------------------------------------------
-    def _ln_linear(self, x, st, e, idx, name, **kw):
-        """linear(LayerNorm_idx(x)): one launch when the producer of x emitted row statistics, otherwise the stand-alone
-        LayerNorm kernel followed by the plain GEMM"""
-        eps = self.config.layer_norm_eps
-        if st is not None:
-            return ops.linear(x, e[name + "_ln"], ln=(st, eps), **kw)
-        pw = e.get(name)
-        if pw is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"{type(self).__name__}: run one eager encode of this shape before capturing it")
-            pw = e[name] = e[name + "_make"]()
-        g, b = e[f"ln{idx}"]
-        return ops.linear(ops.layernorm(x, g, b, eps), pw, **kw)
-
     def encode_stream(self, input_ids: torch.Tensor) -> Tuple[torch.Tensor, dict]:
         """int64 [B, L] ids on the device -> (the residual stream after the last layer, before final_layer_norm, in
         ops.ACT_DTYPE [B, L, hidden]; the plan that encoded it)"""
         cfg = self.config
-        act = _ACTS[cfg.hidden_act]
         fold = input_ids.numel() <= FOLD_LN_MAX_ROWS
         pl = self.plan(input_ids.device, fold)
-        C, nh = cfg.hidden_size, cfg.num_attention_heads
-        f32 = ops.ACT_DTYPE == torch.float32
-        x = ops.token_embed(input_ids, pl["tok"], pl["pos"], out_f32=f32)
-        st = None
-        for e in pl["layers"]:
-            qkv = self._ln_linear(x, st, e, 1, "qkv")
-            o = ops.attention_causal(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], nh)
-            x, st = ops.linear(o, e["out"], residual=x, rowstats=fold)
-            f = self._ln_linear(x, st, e, 2, "fc1", act=act)
-            x, st = ops.linear(f, e["fc2"], residual=x, rowstats=fold)
+        x = ops.token_embed(input_ids, pl["tok"], pl["pos"], out_f32=ops.ACT_DTYPE == torch.float32)
+        x = run_clip_layers(x, pl["layers"], attn=ops.attention_causal, heads=cfg.num_attention_heads, act=ACTS[cfg.hidden_act],
+                            eps=cfg.layer_norm_eps, who=type(self).__name__, fold=fold)
         return x, pl
 
     def encode_nhwc(self, input_ids: torch.Tensor) -> torch.Tensor:
@@ -279,20 +195,9 @@ class _TextTower(nn.Module):
 
     def _device_ids(self, input_ids: torch.Tensor) -> torch.Tensor:
         """the argument checks of a forward: int64 [B, L] ids on the model's device"""
-        who = type(self).__name__
         cfg = self.config
-        dev = self.text_model.embeddings.token_embedding.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError(f"{who} runs on the HIP kernels only: move it to a GPU first (model.to('cuda'))")
-        if input_ids.dim() != 2 or input_ids.dtype not in (torch.int64, torch.int32):
-            raise ValueError(f"{who}: input_ids must be an integer [B, L] tensor, got {input_ids.dtype} {tuple(input_ids.shape)}")
-        B, L = input_ids.shape
-        if B < 1 or not 1 <= L <= cfg.max_position_embeddings:
-            raise ValueError(f"{who}: sequence length {L} outside [1, {cfg.max_position_embeddings}] (batch {B})")
-        ids = input_ids.to(device=dev, dtype=torch.int64).contiguous()
-        if not torch.cuda.is_current_stream_capturing() and bool(((ids < 0) | (ids >= cfg.vocab_size)).any()):
-            raise ValueError(f"{who}: token ids outside [0, {cfg.vocab_size})")
-        return ids
+        return check_token_ids(type(self).__name__, input_ids, self.text_model.embeddings.token_embedding.weight.device,
+                               cfg.max_position_embeddings, cfg.vocab_size)
 
 
 class CLIPTextModel(_TextTower):

@@ -34,16 +34,12 @@ import torch.nn as nn
 
 from . import ops
 from .gates import DepthGate, LinearWidthGate, WidthGate
+from .modules import LinearP, PlannedModule, _capturing, _Params, _PlanCache, _versions  # noqa: F401  (their old home)
 from .ops import PackedWeight
 
 # ----------------------------------------------------------------------------------------------------------------
 # parameter containers (diffusers names / shapes at the state-dict boundary; never called)
 # ----------------------------------------------------------------------------------------------------------------
-
-
-class _Params(nn.Module):
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("parameter container; the owning block launches the HIP kernels")
 
 
 class Conv2dP(_Params):
@@ -52,14 +48,6 @@ class Conv2dP(_Params):
         self.in_channels, self.out_channels, self.kernel_size = cin, cout, (k, k)
         self.weight = nn.Parameter(torch.empty(cout, cin, k, k))
         self.bias = nn.Parameter(torch.empty(cout))
-
-
-class LinearP(_Params):
-    def __init__(self, cin, cout, bias=True):
-        super().__init__()
-        self.in_features, self.out_features = cin, cout
-        self.weight = nn.Parameter(torch.empty(cout, cin))
-        self.bias = nn.Parameter(torch.empty(cout)) if bias else None
 
 
 class NormP(_Params):
@@ -175,72 +163,10 @@ def _lnw(mod, x, gamma_p, beta_p, gamma, beta, eps, fork=False):
     return AG.LayerNormWFn.apply(x, gamma_p, beta_p, gamma, beta, eps, fork)
 
 
-def _capturing() -> bool:
-    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
-
-def _versions(mod: nn.Module) -> tuple:
-    """in-place update counters of a module's parameters: optimizer steps, ``param.data.copy_`` and ``load_state_dict``
-    all bump them, so packs made from older values can be recognised as stale without any hook on the training loop"""
-    if mod.__dict__.get("_pk") is not None:
-        return ()      # under a PackedTrainer the diffusers-layout masters are not what is trained: the packs ARE the state
-    ps = mod.__dict__.get("_vparams")
-    if ps is None:
-        ps = mod.__dict__["_vparams"] = list(mod.parameters())      # (dropped by invalidate(): .to() may replace parameters)
-    return tuple(p._version for p in ps)
-
-
-class _PlanCache:
-    """Packed-weight plans of one module, keyed by whatever the packs depend on besides the parameters (mask, semantics,
-    device, activation dtype, ...).  Every module of the package that packs weights keeps them here.
-
-    * At most ``cap`` UNPINNED entries; the oldest is evicted.  A plan that is created or looked up while a stream is
-      capturing is PINNED: a HIP graph bakes raw pointers to its packs, so it must outlive the graph and is only released
-      by ``clear()`` (``invalidate_plans``), however many other masks pass through the module in between.
-    * Every entry remembers the parameter versions it was packed from.  A lookup with newer versions is a miss and drops
-      the stale entry (a pinned one is parked, never returned again, so the memory a graph points to stays allocated):
-      fine-tuning forwards always compute with the current weights, whatever loop drives the optimizer."""
-
-    def __init__(self, cap: int = 4):
-        self.cap, self.entries, self.parked = cap, {}, []
-
-    def get(self, key, version):
-        e = self.entries.get(key)
-        if e is None:
-            return None
-        if e[0] != version:
-            del self.entries[key]
-            if e[2]:
-                self.parked.append(e[1])
-            return None
-        if not e[2] and _capturing():
-            e[2] = True
-        return e[1]
-
-    def put(self, key, version, plan):
-        unpinned = [k for k, e in self.entries.items() if not e[2]]
-        if len(unpinned) >= self.cap:
-            del self.entries[unpinned[0]]
-        self.entries[key] = [version, plan, _capturing()]
-        return plan
-
-    def lookup(self, key, version, make):
-        """the current plan under ``key``, made by ``make()`` on a miss"""
-        plan = self.get(key, version)
-        return plan if plan is not None else self.put(key, version, make())
-
-    def clear(self):
-        self.entries.clear()
-        self.parked.clear()
-
-    def __len__(self):
-        return len(self.entries)
-
-
 # ----------------------------------------------------------------------------------------------------------------
 # ResNet blocks
 # ----------------------------------------------------------------------------------------------------------------
-class ResnetBlock2DWidthGated(nn.Module):
+class ResnetBlock2DWidthGated(PlannedModule):
     """blocks.py:283-465.  GN32->SiLU->conv3x3->+time_emb_proj(SiLU(temb))->width gate->GN32->SiLU->conv3x3
     ->(+1x1 shortcut)->+x."""
     depth_gated = False
@@ -278,10 +204,6 @@ class ResnetBlock2DWidthGated(nn.Module):
         self.gate.set_structure_value(arch_vectors["width"][0])
         if self.depth_gated:
             self.depth_gate.set_structure_value(arch_vectors["depth"][0])
-
-    def invalidate(self):
-        self._plans.clear()
-        self.__dict__.pop("_vparams", None)
 
     # ---- execution plan -----------------------------------------------------------------------------------------
     def _mask_key(self):
@@ -596,7 +518,7 @@ class BasicTransformerBlockWidthGated(nn.Module):
             self.ff.net[0].gate.set_structure_value(arch_vectors["width"][2])
 
 
-class Transformer2DModelWidthGated(nn.Module):
+class Transformer2DModelWidthGated(PlannedModule):
     """blocks.py:941-1067 (forward inherited from diffusers Transformer2DModel, use_linear_projection=True):
     GN(32, eps 1e-6) -> proj_in -> [LN->self-attn->+res; LN->cross-attn->+res; LN->GEGLU FF->+res] -> proj_out -> +x."""
     depth_gated = False
@@ -632,10 +554,6 @@ class Transformer2DModelWidthGated(nn.Module):
         if self.depth_gated:
             self.depth_gate.set_structure_value(arch_vectors["depth"][0])
         self.transformer_blocks[0].set_gate_structure({"width": arch_vectors["width"], "depth": []})
-
-    def invalidate(self):
-        self._plans.clear()
-        self.__dict__.pop("_vparams", None)
 
     # ---- execution plan -------------------------------------------------------------------------------------------
     def _keys(self):
@@ -1022,7 +940,7 @@ class UNet2DConditionOutput:
     sample: torch.Tensor
 
 
-class _Resample2D(nn.Module):
+class _Resample2D(PlannedModule):
     """One 3x3 convolution that changes the resolution.  A subclass names the conv_gemm arguments (``conv_kw``) and the
     output size; packing (the dgrad pack is made on first use and lives in the same plan), staleness and the lifetime of
     packs a captured graph points to are the _PlanCache's."""
@@ -1032,10 +950,6 @@ class _Resample2D(nn.Module):
         super().__init__()
         self.conv = Conv2dP(channels, channels, 3)
         self._plans = _PlanCache(cap=1)
-
-    def invalidate(self):
-        self._plans.clear()
-        self.__dict__.pop("_vparams", None)
 
     def plan(self, device) -> dict:
         return self._plans.lookup(str(device), _versions(self), lambda: {

@@ -37,7 +37,8 @@ import torch.nn as nn
 
 from . import ops
 from .loading import load_strict, read_pretrained, read_safetensors  # noqa: F401  (vae.read_safetensors: the old home)
-from .unet import Conv2dP, LinearP, NormP, _PlanCache, _versions
+from .modules import LinearP, PlannedModule, _PlanCache, _versions
+from .unet import Conv2dP, NormP
 
 
 @dataclass(frozen=True)
@@ -410,7 +411,7 @@ def _nhwc_padded(x: torch.Tensor, cin: int) -> torch.Tensor:
 # ----------------------------------------------------------------------------------------------------------------
 # the module
 # ----------------------------------------------------------------------------------------------------------------
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(PlannedModule):
     """Decode half of diffusers' AutoencoderKL.  ``decode(z)`` equals diffusers' ``vae.decode(z)`` (z = latents /
     scaling_factor, NCHW); ``decode_images`` returns the postprocessed image in one more launch.
     ``with_encoder=True`` adds ``encoder`` and ``quant_conv``: ``encode(x).latent_dist`` equals diffusers' ``vae.encode(x)``
@@ -474,14 +475,6 @@ class AutoencoderKL(nn.Module):
         cfg, sd = read_pretrained(VAEConfig, root, subfolder, "diffusion_pytorch_model.safetensors")
         m = cls(cfg, with_encoder=with_encoder)
         return m.load_vae_state_dict(sd) if with_encoder else m.load_decoder_state_dict(sd)
-
-    def invalidate(self):
-        self._plans.clear()
-        self.__dict__.pop("_vparams", None)
-
-    def _apply(self, fn, *a, **k):
-        self.invalidate()
-        return super()._apply(fn, *a, **k)
 
     # ---- packed weights ---------------------------------------------------------------------------------------------
     def plan(self, device) -> dict:

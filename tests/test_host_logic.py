@@ -211,7 +211,7 @@ def test_vectorised_relaxation_equals_the_per_segment_loop():
 def test_plan_cache_pins_plans_seen_during_capture_and_drops_stale_ones(monkeypatch):
     """a captured HIP graph bakes pointers to a plan's packs, so a plan created or used during capture must
     survive any number of other masks; and packs made from older parameter values must never be served again."""
-    from diffusion_pruning_amd import unet as U
+    from diffusion_pruning_amd import modules as U
     c = U._PlanCache(cap=4)
     capturing = {"on": False}
     monkeypatch.setattr(U, "_capturing", lambda: capturing["on"])
@@ -236,7 +236,7 @@ def _captured_plan_outlives_updates(monkeypatch, mod, lookup, param):
     """a plan looked up "during capture" stays referenced by ``mod._plans`` (served or parked) through a lookup under the
     other ops.ACT_DTYPE and through an in-place weight update: a captured graph holds raw pointers to its packs.  Before
     these caches were _PlanCaches, AutoencoderKL's single slot per half and CLIPTextModel's dict released such a plan."""
-    from diffusion_pruning_amd import ops, unet as U
+    from diffusion_pruning_amd import modules as U, ops
     capturing = {"on": True}
     monkeypatch.setattr(U, "_capturing", lambda: capturing["on"])
     held = lambda: [id(e[1]) for e in mod._plans.entries.values()] + [id(q) for q in mod._plans.parked]      # noqa: E731
