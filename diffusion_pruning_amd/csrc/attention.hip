@@ -858,6 +858,8 @@ extern "C" int aptp_attention(const AptpAttentionParams* p, aptp_stream_t stream
   APTP_CHECK(((uintptr_t)p->q % 16) == 0 && ((uintptr_t)p->k % 16) == 0 && ((uintptr_t)p->v % 16) == 0 && ((uintptr_t)p->o % 8) == 0, "attention: pointer alignment");
   APTP_CHECK(p->q_stride_l >= (int64_t)p->heads * 64 && p->k_stride_l >= (int64_t)p->heads * 64 && p->v_stride_l >= (int64_t)p->heads * 64 && p->o_stride_l >= (int64_t)p->heads * 64, "attention: row stride < heads*64");
   APTP_CHECK(p->heads <= 65535 && p->B <= 65535, "attention: grid limits");
+  // the kernels take the running maximum over RAW scores and multiply it by c afterwards: right only for c > 0 (rejects NaN too)
+  APTP_CHECK(p->scale > 0.f, "attention: scale must be positive");
   AttnK k;
   k.q = (const __bf16*)p->q; k.qsb = p->q_stride_b; k.qsl = p->q_stride_l;
   k.k = (const __bf16*)p->k; k.ksb = p->k_stride_b; k.ksl = p->k_stride_l;

@@ -372,6 +372,11 @@ extern "C" int aptp_attention_bwd(const AptpAttentionBwdParams* p, aptp_stream_t
   for (int64_t s : strides) APTP_CHECK(s % 8 == 0, "attention_bwd: strides must be multiples of 8 elements");
   const void* ptrs[] = {p->q, p->k, p->v, p->o, p->dout, p->dq, p->dk, p->dv};
   for (const void* q : ptrs) APTP_CHECK(((uintptr_t)q % 16) == 0, "attention_bwd: pointers must be 16-byte aligned");
+  const int64_t row_strides[] = {p->q_stride_l, p->k_stride_l, p->v_stride_l, p->o_stride_l, p->dout_stride_l,
+                                 p->dq_stride_l, p->dk_stride_l, p->dv_stride_l};
+  for (int64_t s : row_strides) APTP_CHECK(s >= (int64_t)p->heads * 64, "attention_bwd: row stride < heads*64");
+  // P is recomputed as exp2(S*c - lse) from the forward's lse, and the forward takes scale > 0 only (rejects NaN too)
+  APTP_CHECK(p->scale > 0.f, "attention_bwd: scale must be positive");
   AttnBwdK k;
   k.q = (const __bf16*)p->q; k.qsb = p->q_stride_b; k.qsl = p->q_stride_l;
   k.k = (const __bf16*)p->k; k.ksb = p->k_stride_b; k.ksl = p->k_stride_l;

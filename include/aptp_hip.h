@@ -305,6 +305,8 @@ int aptp_layernorm(const AptpLayerNormParams* p, aptp_stream_t stream);
  * Replaces F.scaled_dot_product_attention in HeadGatedAttnProcessor2 (blocks.py:258-260).
  * q/k/v/o are bf16 with layout [B, L, heads, 64] expressed through strides (elements): element (b, l, h, d) at
  * ptr + b*stride_b + l*stride_l + h*64 + d, so fused QKV / KV GEMM outputs are consumed in place.
+ * APTP_EINVAL and nothing launched for: null pointers, extents < 1, strides that are not multiples of 8 elements (o: 4),
+ * misaligned pointers, a row stride below heads*64, and (bf16 path) scale <= 0 or NaN.
  */
 typedef struct {
   const void* q; int64_t q_stride_b, q_stride_l;
@@ -312,8 +314,8 @@ typedef struct {
   const void* v; int64_t v_stride_b, v_stride_l;
   void* o; int64_t o_stride_b, o_stride_l;
   int32_t B, heads, Lq, Lk;
-  float scale;
-  float* lse;   /* optional fp32 [B, heads, Lq]: log2-domain log-sum-exp of the scaled scores, consumed by aptp_attention_bwd */
+  float scale;  /* > 0: the kernels take the running maximum over the raw scores */
+  float* lse;  /* optional fp32 [B, heads, Lq]: log2-domain log-sum-exp of the scaled scores, consumed by aptp_attention_bwd */
   int32_t variant; /* 0 = auto; 1 = run the two key-range wave groups of the 8-wave kernel one phase apart (double-buffered
                     * K/V; measured slower than the lock-step form, kept for testing / A-B timing); 2 = force four key-range
                     * groups (16 waves); 3 = force two lock-step groups with single-buffered K/V (two barriers per key tile);
@@ -765,7 +767,9 @@ typedef struct {
 int aptp_layernorm_pgrad(const AptpLayerNormPgradParams* p, aptp_stream_t stream);
 
 /* Attention backward: dq, dk, dv from q, k, v, o, dout and the forward's lse; delta is fp32 scratch [B, heads, Lq].
- * Same strided [B, L, heads, 64] layout convention as aptp_attention. */
+ * Same strided [B, L, heads, 64] layout convention as aptp_attention.  APTP_EINVAL and nothing launched for: null pointers
+ * (lse and delta included), extents < 1, a stride that is not a multiple of 8 elements, a pointer that is not 16-byte aligned,
+ * a row stride below heads*64, scale <= 0 or NaN, q_split > 1 without an aligned workspace or above ceil(Lq / 64). */
 typedef struct {
   const void* q; int64_t q_stride_b, q_stride_l;
   const void* k; int64_t k_stride_b, k_stride_l;
@@ -777,8 +781,8 @@ typedef struct {
   void* dv; int64_t dv_stride_b, dv_stride_l;
   const float* lse; float* delta;
   int32_t B, heads, Lq, Lk;
-  float scale;
-  int32_t q_split;   /* dK/dV: split the query range over this many workgroups (0 / 1 = off; aptp_attention_bwd_q_split suggests
+  float scale;       /* > 0, the forward's */
+  int32_t q_split;  /* dK/dV: split the query range over this many workgroups (0 / 1 = off; aptp_attention_bwd_q_split suggests
                         it: few keys -- cross-attention's 77 -- leave one key tile per (b, head)), fp32 partials folded in slice order */
   void* workspace;   /* aptp_attention_bwd_workspace_bytes(p, q_split) bytes, 16-byte aligned, when q_split > 1 */
 } AptpAttentionBwdParams;
