@@ -12,20 +12,15 @@
 //   O[16 q][64 c]     += P V: P (bf16) goes through the wave's LDS strip, 32 keys per MFMA; when s + 1 is odd the tile
 //                      after the diagonal is written as zeros so the last 32-key step adds nothing from it.
 // Query rows past L (the end of the last strip) load row L - 1 and store nothing.
-#include "aptp_common.h"
+#include "attention_short.h"
 
 namespace {
 
-constexpr int D = 64;        // head width
-constexpr int LMAX = 128;    // longest sequence
-constexpr int KLD = 72;      // K image row stride (bf16): 144 B rows keep the 16-byte fragment reads aligned
-constexpr int TLD = 136;     // V^T and P image row stride (bf16): 272 B rows
+using namespace attn_short;
 
-struct CausalK {
-  const __bf16* q; int64_t qsb, qsl;
-  const __bf16* k; int64_t ksb, ksl;
-  const __bf16* v; int64_t vsb, vsl;
-  __bf16* o; int64_t osb, osl;
+constexpr int LMAX = KIMG;   // longest sequence: K and V of a (sample, head) pair are one LDS image
+
+struct CausalK : AttnView<__bf16> {
   int heads, L;
   float c;   // scale * log2(e)
 };
@@ -35,59 +30,32 @@ __global__ __launch_bounds__(256) void attn_causal_kernel(const CausalK p) {
   __shared__ __attribute__((aligned(16))) __bf16 Vt[D * TLD];
   __shared__ __attribute__((aligned(16))) __bf16 Ps[4 * 16 * TLD];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // the wave index as a scalar: the strip index s and every per-tile test (t <= s) are then uniform branches, not exec masks
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, g4 = lane >> 4;
   const int b = blockIdx.x / p.heads, h = blockIdx.x - b * p.heads;
   const int L = p.L;
-  const int Lp = (L + 31) & ~31;
 
   const __bf16* qp = p.q + (int64_t)b * p.qsb + h * D;
   const __bf16* kp = p.k + (int64_t)b * p.ksb + h * D;
   const __bf16* vp = p.v + (int64_t)b * p.vsb + h * D;
 
-  // ---- K -> Ks[key][c], V -> Vt[c][key]; rows past L are zeros (P = 0 must not meet a non-finite V) ---------------------
-  for (int e = tid; e < Lp * (D / 8); e += 256) {
-    const int r = e >> 3, c0 = (e & 7) * 8;
-    uint4 kq = make_uint4(0u, 0u, 0u, 0u), vq = make_uint4(0u, 0u, 0u, 0u);
-    if (r < L) {
-      kq = *reinterpret_cast<const uint4*>(kp + (int64_t)r * p.ksl + c0);
-      vq = *reinterpret_cast<const uint4*>(vp + (int64_t)r * p.vsl + c0);
-    }
-    *reinterpret_cast<uint4*>(Ks + r * KLD + c0) = kq;
-    union { uint4 q; __bf16 x[8]; } u;
-    u.q = vq;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) Vt[(c0 + j) * TLD + r] = u.x[j];
-  }
+  stage_kv(Ks, Vt, kp, p.ksl, vp, p.vsl, 0, L, tid, [&](int r) { return r < L; });
   __syncthreads();
 
   __bf16* const pw = Ps + wave * 16 * TLD;
   const int nstrips = (L + 15) >> 4;
   for (int s = wave; s < nstrips; s += 4) {
     const int q0 = 16 * s;
-    // Q fragments (A operand: lane holds Q[q0 + l16][32 ks + 8 g4 + j])
     bf16x8 qf[2];
-    {
-      const int qr = q0 + l16 < L ? q0 + l16 : L - 1;
-      const __bf16* src = qp + (int64_t)qr * p.qsl + 8 * g4;
-      qf[0] = *reinterpret_cast<const bf16x8*>(src);
-      qf[1] = *reinterpret_cast<const bf16x8*>(src + 32);
-    }
+    load_q(qf, qp, p.qsl, q0, L, l16, g4);
     // S tiles 0..s: sacc[t][r] = S[q0 + 4 g4 + r][16 t + l16]
-    f32x4 sacc[LMAX / 16];
-#pragma unroll
-    for (int t = 0; t < LMAX / 16; ++t) {
-      sacc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (t <= s) {
-        const __bf16* kr = Ks + (16 * t + l16) * KLD + 8 * g4;
-        sacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[0], *reinterpret_cast<const bf16x8*>(kr), sacc[t], 0, 0, 0);
-        sacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[1], *reinterpret_cast<const bf16x8*>(kr + 32), sacc[t], 0, 0, 0);
-      }
-    }
-    // masked, scaled scores and the row maxima (rows 4 g4 + r; a row's 16 lanes share g4)
+    f32x4 sacc[NT];
+    s_tiles(sacc, qf, Ks, s + 1, l16, g4);
+    // masked, scaled scores and the row maxima
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
-    for (int t = 0; t < LMAX / 16; ++t) {
+    for (int t = 0; t < NT; ++t) {
       if (t <= s) {
         const int key = 16 * t + l16;
 #pragma unroll
@@ -100,69 +68,19 @@ __global__ __launch_bounds__(256) void attn_causal_kernel(const CausalK p) {
       }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) mx[r] = fmaxf(mx[r], __shfl_xor(mx[r], off));
-    }
-    // P = exp2(S - max) (masked: exactly 0), row sums in fp32, P as bf16 into the wave's strip of LDS
-    float rs[4] = {0.f, 0.f, 0.f, 0.f};
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the previous strip's P reads are done
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int t = 0; t < LMAX / 16; ++t) {
-      if (t <= s) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pr = exp2f(sacc[t][r] - mx[r]);
-          rs[r] += pr;
-          pw[(4 * g4 + r) * TLD + 16 * t + l16] = (__bf16)pr;
-        }
-      } else if (t == s + 1 && (s & 1) == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pw[(4 * g4 + r) * TLD + 16 * t + l16] = (__bf16)0.f;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int off = 1; off < 16; off <<= 1) rs[r] += __shfl_xor(rs[r], off);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // P of this strip is visible to the whole wave
-    __builtin_amdgcn_wave_barrier();
-    // O = P V over 32-key steps: A = P[l16][32 kc + 8 g4 + j], B = V[32 kc + 8 g4 + j][16 db + l16] = Vt row
+    for (int r = 0; r < 4; ++r) mx[r] = row_max(mx[r]);
+    float rs[4];
+    write_p(pw, rs, sacc, mx, s + 1, l16, g4);
     f32x4 oacc[D / 16];
 #pragma unroll
     for (int db = 0; db < D / 16; ++db) oacc[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int nkc = (s + 2) >> 1;
-    for (int kc = 0; kc < nkc; ++kc) {
-      const bf16x8 pf = *reinterpret_cast<const bf16x8*>(pw + l16 * TLD + 32 * kc + 8 * g4);
-#pragma unroll
-      for (int db = 0; db < D / 16; ++db) {
-        const bf16x8 vf = *reinterpret_cast<const bf16x8*>(Vt + (16 * db + l16) * TLD + 32 * kc + 8 * g4);
-        oacc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vf, oacc[db], 0, 0, 0);
-      }
-    }
-    // oacc[db][r] = O[q0 + 4 g4 + r][16 db + l16]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int q = q0 + 4 * g4 + r;
-      if (q >= L) continue;
-      const float inv = 1.0f / rs[r];
-      __bf16* dst = p.o + (int64_t)b * p.osb + (int64_t)q * p.osl + h * D + l16;
-#pragma unroll
-      for (int db = 0; db < D / 16; ++db) dst[16 * db] = (__bf16)(oacc[db][r] * inv);
-    }
+    pv_acc(oacc, pw, Vt, s + 1, l16, g4);
+    store_rows(p.o + (int64_t)b * p.osb + h * D, p.osl, oacc, q0, L, l16, g4, [&](int r) { return 1.0f / rs[r]; });
   }
 }
 
-// ---- fp32 PARITY instantiation (never benchmarked): exact-fp32 arithmetic, one thread per query row, the keys 0..i of row i
-// in order through the same exp2-domain online softmax; K and V rows are read from global memory (the active lanes of a wave
-// read the same row at the same time).
-struct CausalF {
-  const float* q; int64_t qsb, qsl;
-  const float* k; int64_t ksb, ksl;
-  const float* v; int64_t vsb, vsl;
-  float* o; int64_t osb, osl;
+// ---- fp32 PARITY instantiation (never benchmarked): row_f32 over the keys 0..i of row i
+struct CausalF : AttnView<float> {
   int heads, L;
   float c;
 };
@@ -171,43 +89,8 @@ __global__ __launch_bounds__(LMAX) void attn_causal_f32_kernel(const CausalF p) 
   const int i = threadIdx.x;
   const int b = blockIdx.x / p.heads, h = blockIdx.x - b * p.heads;
   if (i >= p.L) return;
-  float q[D], acc[D];
-  const float* qr = p.q + (int64_t)b * p.qsb + (int64_t)i * p.qsl + h * D;
-#pragma unroll
-  for (int d = 0; d < D; d += 4) {
-    const float4 t = *reinterpret_cast<const float4*>(qr + d);
-    q[d] = t.x; q[d + 1] = t.y; q[d + 2] = t.z; q[d + 3] = t.w;
-    acc[d] = acc[d + 1] = acc[d + 2] = acc[d + 3] = 0.f;
-  }
-  float m_run = -INFINITY, l_run = 0.f;
-  const float* kb = p.k + (int64_t)b * p.ksb + h * D;
-  const float* vb = p.v + (int64_t)b * p.vsb + h * D;
-  for (int j = 0; j <= i; ++j) {
-    const float* kr = kb + (int64_t)j * p.ksl;
-    float sdot = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; d += 4) {
-      const float4 t = *reinterpret_cast<const float4*>(kr + d);
-      sdot += q[d] * t.x; sdot += q[d + 1] * t.y; sdot += q[d + 2] * t.z; sdot += q[d + 3] * t.w;
-    }
-    const float sv = sdot * p.c;
-    const float m_new = fmaxf(m_run, sv);
-    const float alpha = exp2f(m_run - m_new);            // -inf on the first key -> 0
-    const float pr = exp2f(sv - m_new);
-    l_run = l_run * alpha + pr;
-    m_run = m_new;
-    const float* vr = vb + (int64_t)j * p.vsl;
-#pragma unroll
-    for (int d = 0; d < D; d += 4) {
-      const float4 t = *reinterpret_cast<const float4*>(vr + d);
-      acc[d] = acc[d] * alpha + pr * t.x; acc[d + 1] = acc[d + 1] * alpha + pr * t.y;
-      acc[d + 2] = acc[d + 2] * alpha + pr * t.z; acc[d + 3] = acc[d + 3] * alpha + pr * t.w;
-    }
-  }
-  const float inv = 1.0f / l_run;
-  float* dst = p.o + (int64_t)b * p.osb + (int64_t)i * p.osl + h * D;
-#pragma unroll
-  for (int d = 0; d < D; d += 4) *reinterpret_cast<float4*>(dst + d) = make_float4(acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv);
+  row_f32(p, b, h, i, i + 1, [](int) { return false; }, [&](float sdot, int) { return sdot * p.c; },
+          [](float l_run) { return 1.0f / l_run; });
 }
 
 }  // namespace
@@ -217,38 +100,18 @@ extern "C" int aptp_attention_causal(const AptpAttentionCausalParams* p, aptp_st
   APTP_CHECK(p->B > 0 && p->heads > 0, "attention_causal: bad extents (B %d, heads %d)", p->B, p->heads);
   APTP_CHECK(p->L >= 1 && p->L <= LMAX, "attention_causal: L %d outside [1, %d]", p->L, LMAX);
   APTP_CHECK((int64_t)p->B * p->heads < (1ll << 31), "attention_causal: B * heads too large");
-  APTP_CHECK(p->scale > 0.f && p->scale < 1e30f, "attention_causal: scale must be positive and finite");
-  const int64_t sl[4] = {p->q_stride_l, p->k_stride_l, p->v_stride_l, p->o_stride_l};
-  const int64_t sb[4] = {p->q_stride_b, p->k_stride_b, p->v_stride_b, p->o_stride_b};
-  const void* ptr[4] = {p->q, p->k, p->v, p->o};
-  const int vec = p->io_f32 ? 4 : 8;        // elements per 16 bytes
-  for (int i = 0; i < 4; ++i) {
-    APTP_CHECK(sl[i] >= (int64_t)p->heads * D && sl[i] % vec == 0,
-               "attention_causal: row stride %lld must be >= heads * 64 and a multiple of %d", (long long)sl[i], vec);
-    APTP_CHECK(sb[i] >= 0 && sb[i] % vec == 0, "attention_causal: batch stride %lld must be a non-negative multiple of %d",
-               (long long)sb[i], vec);
-    APTP_CHECK(((uintptr_t)ptr[i] % 16) == 0, "attention_causal: pointers must be 16-byte aligned");
-  }
+  if (int rc = attn_check_view(p, "attention_causal", (int64_t)p->heads * D, "heads * 64")) return rc;
   const float c = p->scale * 1.44269504088896340736f;
   const dim3 grid((unsigned)(p->B * p->heads));
   if (p->io_f32) {
     CausalF k;
-    k.q = (const float*)p->q; k.qsb = p->q_stride_b; k.qsl = p->q_stride_l;
-    k.k = (const float*)p->k; k.ksb = p->k_stride_b; k.ksl = p->k_stride_l;
-    k.v = (const float*)p->v; k.vsb = p->v_stride_b; k.vsl = p->v_stride_l;
-    k.o = (float*)p->o; k.osb = p->o_stride_b; k.osl = p->o_stride_l;
-    k.heads = p->heads; k.L = p->L; k.c = c;
+    k.fill(p); k.heads = p->heads; k.L = p->L; k.c = c;
     hipLaunchKernelGGL(attn_causal_f32_kernel, grid, dim3(LMAX), 0, (hipStream_t)stream, k);
-    APTP_LAUNCH_CHECK();
-    return APTP_OK;
+  } else {
+    CausalK k;
+    k.fill(p); k.heads = p->heads; k.L = p->L; k.c = c;
+    hipLaunchKernelGGL(attn_causal_kernel, grid, dim3(256), 0, (hipStream_t)stream, k);
   }
-  CausalK k;
-  k.q = (const __bf16*)p->q; k.qsb = p->q_stride_b; k.qsl = p->q_stride_l;
-  k.k = (const __bf16*)p->k; k.ksb = p->k_stride_b; k.ksl = p->k_stride_l;
-  k.v = (const __bf16*)p->v; k.vsb = p->v_stride_b; k.vsl = p->v_stride_l;
-  k.o = (__bf16*)p->o; k.osb = p->o_stride_b; k.osl = p->o_stride_l;
-  k.heads = p->heads; k.L = p->L; k.c = c;
-  hipLaunchKernelGGL(attn_causal_kernel, grid, dim3(256), 0, (hipStream_t)stream, k);
   APTP_LAUNCH_CHECK();
   return APTP_OK;
 }

@@ -14,7 +14,7 @@
 // where 64-row tiles would leave half the chip idle; a 64-row tile would also need 128 fp32 accumulators per lane.
 // Ragged ends: query rows past Lq load a clamped row and store nothing; keys past Lk load a clamped (finite) row and get
 // score -inf, so their P is exactly 0.  Every tile holds >= 1 valid key, so the running maximum is finite after tile 0.
-#include "aptp_common.h"
+#include "attention_short.h"
 
 namespace {
 
@@ -27,11 +27,7 @@ constexpr int VLD = 40;      // V^T image row stride (bf16): 80 B rows keep the 
 constexpr int PLD = 40;      // P image row stride (bf16)
 constexpr int SLD = 33;      // S image row stride (fp32)
 
-struct WideK {
-  const __bf16* q; int64_t qsb, qsl;
-  const __bf16* k; int64_t ksb, ksl;
-  const __bf16* v; int64_t vsb, vsl;
-  __bf16* o; int64_t osb, osl;
+struct WideK : AttnView<__bf16> {
   int Lq, Lk;
   float c;   // scale * log2(e)
 };
@@ -192,11 +188,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ---- fp32 PARITY instantiation (never benchmarked): exact-fp32 arithmetic, same tiling of keys and the same exp2-domain
 // online softmax.  Workgroup = 16 query rows; the Q tile sits in LDS, K and V are read from global memory; scores are
 // plain channel-order dot products, one thread per (query, key) pair; each thread owns two output channels of all 16 rows.
-struct WideF {
-  const float* q; int64_t qsb, qsl;
-  const float* k; int64_t ksb, ksl;
-  const float* v; int64_t vsb, vsl;
-  float* o; int64_t osb, osl;
+struct WideF : AttnView<float> {
   int Lq, Lk;
   float c;
 };
@@ -281,37 +273,17 @@ extern "C" int aptp_attention_wide(const AptpAttentionWideParams* p, aptp_stream
   APTP_CHECK(p && p->q && p->k && p->v && p->o, "attention_wide: null pointer");
   APTP_CHECK(p->B > 0 && p->Lq > 0 && p->Lk > 0, "attention_wide: bad extents (B %d, Lq %d, Lk %d)", p->B, p->Lq, p->Lk);
   APTP_CHECK(p->B <= 65535, "attention_wide: B %d > 65535", p->B);
-  APTP_CHECK(p->scale > 0.f && p->scale < 1e30f, "attention_wide: scale must be positive and finite");
-  const int64_t sl[4] = {p->q_stride_l, p->k_stride_l, p->v_stride_l, p->o_stride_l};
-  const int64_t sb[4] = {p->q_stride_b, p->k_stride_b, p->v_stride_b, p->o_stride_b};
-  const void* ptr[4] = {p->q, p->k, p->v, p->o};
-  const int vec = p->io_f32 ? 4 : 8;        // elements per 16 bytes
-  for (int i = 0; i < 4; ++i) {
-    APTP_CHECK(sl[i] >= 512 && sl[i] % vec == 0, "attention_wide: row stride %lld must be >= 512 and a multiple of %d",
-               (long long)sl[i], vec);
-    APTP_CHECK(sb[i] >= 0 && sb[i] % vec == 0, "attention_wide: batch stride %lld must be a non-negative multiple of %d",
-               (long long)sb[i], vec);
-    APTP_CHECK(((uintptr_t)ptr[i] % 16) == 0, "attention_wide: pointers must be 16-byte aligned");
-  }
+  if (int rc = attn_check_view(p, "attention_wide", D, "512")) return rc;
   const float c = p->scale * 1.44269504088896340736f;
   if (p->io_f32) {
     WideF k;
-    k.q = (const float*)p->q; k.qsb = p->q_stride_b; k.qsl = p->q_stride_l;
-    k.k = (const float*)p->k; k.ksb = p->k_stride_b; k.ksl = p->k_stride_l;
-    k.v = (const float*)p->v; k.vsb = p->v_stride_b; k.vsl = p->v_stride_l;
-    k.o = (float*)p->o; k.osb = p->o_stride_b; k.osl = p->o_stride_l;
-    k.Lq = p->Lq; k.Lk = p->Lk; k.c = c;
+    k.fill(p); k.Lq = p->Lq; k.Lk = p->Lk; k.c = c;
     hipLaunchKernelGGL(attn_wide_f32_kernel, dim3((p->Lq + FQ - 1) / FQ, p->B), dim3(256), 0, (hipStream_t)stream, k);
-    APTP_LAUNCH_CHECK();
-    return APTP_OK;
+  } else {
+    WideK k;
+    k.fill(p); k.Lq = p->Lq; k.Lk = p->Lk; k.c = c;
+    hipLaunchKernelGGL(attn_wide_kernel, dim3((p->Lq + QT - 1) / QT, p->B), dim3(256), 0, (hipStream_t)stream, k);
   }
-  WideK k;
-  k.q = (const __bf16*)p->q; k.qsb = p->q_stride_b; k.qsl = p->q_stride_l;
-  k.k = (const __bf16*)p->k; k.ksb = p->k_stride_b; k.ksl = p->k_stride_l;
-  k.v = (const __bf16*)p->v; k.vsb = p->v_stride_b; k.vsl = p->v_stride_l;
-  k.o = (__bf16*)p->o; k.osb = p->o_stride_b; k.osl = p->o_stride_l;
-  k.Lq = p->Lq; k.Lk = p->Lk; k.c = c;
-  hipLaunchKernelGGL(attn_wide_kernel, dim3((p->Lq + QT - 1) / QT, p->B), dim3(256), 0, (hipStream_t)stream, k);
   APTP_LAUNCH_CHECK();
   return APTP_OK;
 }

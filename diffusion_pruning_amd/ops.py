@@ -1003,11 +1003,7 @@ def attention_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: i
     B, L = q.shape[0], q.shape[1]
     if out is None:
         out = torch.empty(B, L, heads * 64, dtype=q.dtype, device=q.device)
-    for t in (q, k, v, out):
-        if t.dtype != q.dtype or t.dtype not in (torch.bfloat16, torch.float32) or t.dim() != 3 or t.stride(2) != 1 \
-                or tuple(t.shape) != (B, L, heads * 64) or not t.is_cuda or t.device != q.device:
-            raise ValueError(f"attention_causal: q, k, v and out must be {q.dtype} [B, L, {heads * 64}] views with contiguous "
-                             f"channels on {q.device}, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    _check_heads64_views(q, k, v, out, B, L, heads, "attention_causal")
     p = AttentionCausalParams()
     p.io_f32 = int(q.dtype == torch.float32)
     _set_views(p, q=q, k=k, v=v, o=out)
@@ -1047,6 +1043,14 @@ def token_embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, out_f32
 BIAS_MAX_L = 512
 
 
+def _check_heads64_views(q, k, v, out, B: int, L: int, heads: int, name: str):
+    for t in (q, k, v, out):
+        if t.dtype != q.dtype or t.dtype not in (torch.bfloat16, torch.float32) or t.dim() != 3 or t.stride(2) != 1 \
+                or tuple(t.shape) != (B, L, heads * 64) or not t.is_cuda or t.device != q.device:
+            raise ValueError(f"{name}: q, k, v and out must be {q.dtype} [B, L, {heads * 64}] views with contiguous "
+                             f"channels on {q.device}, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+
+
 def _check_mask(mask: Optional[torch.Tensor], B: int, L: int, device, name: str):
     if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, L) or not mask.is_contiguous()
                              or mask.device != device):
@@ -1065,11 +1069,7 @@ def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     B, L = q.shape[0], q.shape[1]
     if out is None:
         out = torch.empty(B, L, heads * 64, dtype=q.dtype, device=q.device)
-    for t in (q, k, v, out):
-        if t.dtype != q.dtype or t.dtype not in (torch.bfloat16, torch.float32) or t.dim() != 3 or t.stride(2) != 1 \
-                or tuple(t.shape) != (B, L, heads * 64) or not t.is_cuda or t.device != q.device:
-            raise ValueError(f"attention_bias: q, k, v and out must be {q.dtype} [B, L, {heads * 64}] views with contiguous "
-                             f"channels on {q.device}, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    _check_heads64_views(q, k, v, out, B, L, heads, "attention_bias")
     if relbias.dtype != torch.float32 or tuple(relbias.shape) != (heads, 2 * L - 1) or not relbias.is_contiguous() \
             or relbias.device != q.device:
         raise ValueError(f"attention_bias: relbias must be a contiguous fp32 [{heads}, {2 * L - 1}] tensor on {q.device}, got "
