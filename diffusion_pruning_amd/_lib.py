@@ -451,7 +451,7 @@ class TrainImagesParams(Structure):
 
 
 STEP_NOISE_BF16, STEP_NOISE_F32 = 0, 1
-STEP_DDIM, STEP_PNDM = 0, 1
+STEP_DDIM, STEP_PNDM, STEP_DPMPP = 0, 1, 2
 STEP_EPSILON, STEP_V_PREDICTION = 0, 1
 
 

@@ -1,8 +1,9 @@
 // Everything a denoise step does after the U-Net call, in one launch:
 //   aptp_guided_step   classifier-free guidance g = u + s (t - u), optionally rescaled to the text branch's per-sample standard
-//                      deviation (Lin et al. 2023, section 3.4), then the DDIM or PNDM / PLMS update of pipeline.py's
-//                      DDIMSchedulerLite.step_coef / PNDMSchedulerLite.step, statement for statement in fp32.  The per-step
-//                      scheduler state is read from device memory, so one captured launch serves every step of a loop.
+//                      deviation (Lin et al. 2023, section 3.4), then the DDIM, PNDM / PLMS or DPM-Solver++ (2M) update of
+//                      pipeline.py's DDIMSchedulerLite.step_coef / PNDMSchedulerLite.step / DPMSolverMultistepSchedulerLite.step,
+//                      statement for statement in fp32.  The per-step scheduler state is read from device memory, so one
+//                      captured launch serves every step of a loop.
 // Memory-bound and tiny: a flat grid of 16-byte accesses with a scalar tail, or -- with the rescale, which needs two standard
 // deviations per sample first -- one workgroup per sample and fixed-order reductions (no floating-point atomics: bit-equal
 // from run to run and from capture to replay).
@@ -16,9 +17,9 @@ namespace {
 struct StepK {
   const void* noise; const float* sample; float* out;
   const float* coef; const int64_t* slot; const float* w; const float* flags;
-  float* E; float* saved;
+  float* E; float* saved;      // (DPM-Solver++: saved is the previous data prediction)
   int64_t n, total;            // elements per sample, b * n
-  int noise_f32, do_cfg, pndm, v_pred;
+  int noise_f32, do_cfg, pndm, dpm, v_pred;
   float scale, phi;
 };
 
@@ -26,12 +27,14 @@ struct StepK {
 struct StepCoef {
   float c0, c1, c2, c3;        // DDIM: sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev); PNDM: sqrt(a_t), sqrt(1 - a_t), sqrt(a_p / a_t), a_p - a_t
   float denom;                 // PNDM: a_t sqrt(1 - a_p) + sqrt(a_t (1 - a_t) a_p)
+  float c4;                    // DPM-Solver++: c0 .. c4 = alpha_s, sigma_s, c_x, c_0, c_1 of the table row
   float w[5], f0, f1;
   int slot;
 };
 
 __device__ __forceinline__ StepCoef load_coef(const StepK& p) {
   StepCoef c;
+  c.c4 = p.dpm ? p.coef[4] : 0.f;
   if (!p.pndm) {
     c.c0 = p.coef[0]; c.c1 = p.coef[1]; c.c2 = p.coef[2]; c.c3 = p.coef[3];
     c.denom = 1.f; c.f0 = c.f1 = 0.f; c.slot = 0;
@@ -93,7 +96,16 @@ template <int V>
 __device__ __forceinline__ void update(const StepK& p, const StepCoef& c, int64_t i, const float* g) {
   float x[V], o[V];
   ld<V>(p.sample + i, x);
-  if (!p.pndm) {
+  if (p.dpm) {
+    float pv[V], x0[V];
+    ld<V>(p.saved + i, pv);                                          // this lane's own elements, read before they are replaced
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      x0[j] = p.v_pred ? c.c0 * x[j] - c.c1 * g[j] : (x[j] - c.c1 * g[j]) / c.c0;
+      o[j] = (c.c2 * x[j] + c.c3 * x0[j]) + c.c4 * pv[j];
+    }
+    st<V>(p.saved + i, x0);
+  } else if (!p.pndm) {
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float x0, eps;
@@ -228,10 +240,14 @@ __global__ __launch_bounds__(RS_THREADS) void guided_step_rescale_kernel(const S
 }  // namespace
 
 extern "C" int aptp_guided_step(const AptpGuidedStepParams* p, aptp_stream_t stream) {
-  APTP_CHECK(p && p->noise && p->sample && p->out && p->coef, "guided_step: null pointer");
+  APTP_CHECK(p, "guided_step: null pointer");
+  APTP_CHECK(p->scheduler != APTP_STEP_DPMPP || (p->coef && p->saved && ((uintptr_t)p->coef % 4) == 0 && ((uintptr_t)p->saved % 4) == 0),
+             "guided_step: DPM-Solver needs coef (5 floats) and prev (passed as saved), both 4-byte aligned");
+  APTP_CHECK(p->noise && p->sample && p->out && p->coef, "guided_step: null pointer");
   APTP_CHECK(p->noise_dtype == APTP_STEP_NOISE_BF16 || p->noise_dtype == APTP_STEP_NOISE_F32,
              "guided_step: noise_dtype %d is neither bf16 (%d) nor fp32 (%d)", p->noise_dtype, APTP_STEP_NOISE_BF16, APTP_STEP_NOISE_F32);
-  APTP_CHECK(p->scheduler == APTP_STEP_DDIM || p->scheduler == APTP_STEP_PNDM, "guided_step: unknown scheduler %d", p->scheduler);
+  APTP_CHECK(p->scheduler == APTP_STEP_DDIM || p->scheduler == APTP_STEP_PNDM || p->scheduler == APTP_STEP_DPMPP,
+             "guided_step: unknown scheduler %d", p->scheduler);
   APTP_CHECK(p->prediction == APTP_STEP_EPSILON || p->prediction == APTP_STEP_V_PREDICTION, "guided_step: unknown prediction type %d",
              p->prediction);
   APTP_CHECK(p->do_cfg == 0 || p->do_cfg == 1, "guided_step: do_cfg is %d (0 or 1)", p->do_cfg);
@@ -245,7 +261,7 @@ extern "C" int aptp_guided_step(const AptpGuidedStepParams* p, aptp_stream_t str
   APTP_CHECK(!rescale || p->do_cfg, "guided_step: guidance_rescale needs classifier-free guidance (do_cfg)");
   APTP_CHECK(!rescale || p->n >= 2, "guided_step: guidance_rescale needs n >= 2 for an unbiased standard deviation, got %lld",
              (long long)p->n);
-  const bool f32 = p->noise_dtype == APTP_STEP_NOISE_F32, pndm = p->scheduler == APTP_STEP_PNDM;
+  const bool f32 = p->noise_dtype == APTP_STEP_NOISE_F32, pndm = p->scheduler == APTP_STEP_PNDM, dpm = p->scheduler == APTP_STEP_DPMPP;
   APTP_CHECK(((uintptr_t)p->noise % (f32 ? 4 : 2)) == 0 && ((uintptr_t)p->sample % 4) == 0 && ((uintptr_t)p->out % 4) == 0 &&
              ((uintptr_t)p->coef % 4) == 0, "guided_step: pointer alignment");
   if (pndm) {
@@ -257,7 +273,7 @@ extern "C" int aptp_guided_step(const AptpGuidedStepParams* p, aptp_stream_t str
   k.noise = p->noise; k.sample = p->sample; k.out = p->out;
   k.coef = p->coef; k.slot = p->slot; k.w = p->w; k.flags = p->flags; k.E = p->E; k.saved = p->saved;
   k.n = p->n; k.total = (int64_t)p->b * p->n;
-  k.noise_f32 = f32; k.do_cfg = p->do_cfg; k.pndm = pndm; k.v_pred = p->prediction == APTP_STEP_V_PREDICTION;
+  k.noise_f32 = f32; k.do_cfg = p->do_cfg; k.pndm = pndm; k.dpm = dpm; k.v_pred = p->prediction == APTP_STEP_V_PREDICTION;
   k.scale = p->guidance_scale; k.phi = p->guidance_rescale;
   // groups of four need every base the kernel forms to be aligned: 16 bytes for fp32, 8 for four bf16
   const int64_t unit = rescale ? p->n : k.total;          // rows start at multiples of this many elements
@@ -265,6 +281,7 @@ extern "C" int aptp_guided_step(const AptpGuidedStepParams* p, aptp_stream_t str
   bool aligned = ((uintptr_t)p->noise % nalign) == 0 && ((uintptr_t)p->sample % 16) == 0 && ((uintptr_t)p->out % 16) == 0;
   if (p->do_cfg) aligned = aligned && k.total % 4 == 0;   // the text half starts b * n elements in
   if (pndm) aligned = aligned && ((uintptr_t)p->E % 16) == 0 && ((uintptr_t)p->saved % 16) == 0 && k.total % 4 == 0;
+  if (dpm) aligned = aligned && ((uintptr_t)p->saved % 16) == 0;   // prev is indexed like sample
   if (rescale) aligned = aligned && unit % 4 == 0;
   if (rescale) {
     if (aligned)

@@ -1605,10 +1605,11 @@ def guided_step(noise: torch.Tensor, sample: torch.Tensor, state: dict, *, sched
     (guidance_rescale > 0: the guided output takes the text branch's per-sample standard deviation, blended by that factor)
     and the scheduler update.  noise: bf16 or fp32, contiguous; sample: fp32 [b, ...]; state: the scheduler's per-step
     device tensors (``make_state`` / ``load_step`` of pipeline.DDIMSchedulerLite -- "coef" [4] -- or PNDMSchedulerLite --
-    "slot", "w", "coef", "flags", "E", "saved"; E and saved are updated in place).  scheduler: "ddim" or "pndm".  Returns the
-    fp32 next sample (``out`` if given).  No host synchronisation: safe to capture."""
+    "slot", "w", "coef", "flags", "E", "saved"; E and saved are updated in place -- or DPMSolverMultistepSchedulerLite -- "coef"
+    [6], "prev"; prev is updated in place).  scheduler: "ddim", "pndm" or "dpmpp".  Returns the fp32 next sample (``out`` if
+    given).  No host synchronisation: safe to capture."""
     lib = _lib.load()
-    kinds = {"ddim": _lib.STEP_DDIM, "pndm": _lib.STEP_PNDM}
+    kinds = {"ddim": _lib.STEP_DDIM, "pndm": _lib.STEP_PNDM, "dpmpp": _lib.STEP_DPMPP}
     preds = {"epsilon": _lib.STEP_EPSILON, "v_prediction": _lib.STEP_V_PREDICTION}
     if scheduler not in kinds:
         raise ValueError(f"guided_step: scheduler must be one of {sorted(kinds)}, got {scheduler!r}")
@@ -1626,9 +1627,10 @@ def guided_step(noise: torch.Tensor, sample: torch.Tensor, state: dict, *, sched
         out = torch.empty_like(sample)
     elif out.dtype != torch.float32 or tuple(out.shape) != tuple(sample.shape) or not out.is_contiguous() or out.device != sample.device:
         raise ValueError(f"guided_step: out must be a contiguous fp32 {tuple(sample.shape)} tensor on {sample.device}")
-    names = ("coef",) if scheduler == "ddim" else ("slot", "w", "coef", "flags", "E", "saved")
-    want = {"coef": (torch.float32, 4 if scheduler == "ddim" else 2), "slot": (torch.int64, 1), "w": (torch.float32, 5),
-            "flags": (torch.float32, 2), "E": (torch.float32, 5 * b * n), "saved": (torch.float32, b * n)}
+    names = {"ddim": ("coef",), "pndm": ("slot", "w", "coef", "flags", "E", "saved"), "dpmpp": ("coef", "prev")}[scheduler]
+    want = {"coef": (torch.float32, {"ddim": 4, "pndm": 2, "dpmpp": 6}[scheduler]), "slot": (torch.int64, 1), "w": (torch.float32, 5),
+            "flags": (torch.float32, 2), "E": (torch.float32, 5 * b * n), "saved": (torch.float32, b * n),
+            "prev": (torch.float32, b * n)}
     for nm in names:
         t = state.get(nm)
         dt, cnt = want[nm]
@@ -1639,6 +1641,8 @@ def guided_step(noise: torch.Tensor, sample: torch.Tensor, state: dict, *, sched
     if scheduler == "pndm":
         p.slot, p.w, p.flags = state["slot"].data_ptr(), state["w"].data_ptr(), state["flags"].data_ptr()
         p.E, p.saved = state["E"].data_ptr(), state["saved"].data_ptr()
+    elif scheduler == "dpmpp":
+        p.saved = state["prev"].data_ptr()                   # the previous data prediction travels in ``saved``
     p.n, p.b, p.noise_rows = n, b, noise.shape[0]
     # (a dtype the kernel does not know goes through as such and is refused there)
     p.noise_dtype = {torch.bfloat16: _lib.STEP_NOISE_BF16, torch.float32: _lib.STEP_NOISE_F32}.get(noise.dtype, -1)

@@ -212,6 +212,112 @@ class PNDMSchedulerLite:
         return _fused("pndm", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
 
 
+class DPMSolverMultistepSchedulerLite:
+    """DPM-Solver++ (2M): the multistep second-order solver in the data-prediction form, midpoint variant, that the model
+    card of stabilityai/stable-diffusion-2-1 swaps in (``DPMSolverMultistepScheduler``), on exactly DDIMSchedulerLite's grid:
+    scaled-linear betas, "leading" spacing with steps_offset 1, ``prev = t - ratio``, ``alphas_cumprod[0]`` past the end;
+    epsilon or v-prediction; N inference steps are N U-Net calls.  With alpha = sqrt(a), sigma = sqrt(1 - a),
+    lambda = log(alpha / sigma), a step from s to t has h = lambda_t - lambda_s, A = alpha_t (1 - exp(-h)) and
+        first order    x_t = (sigma_t / sigma_s) x + A x0_s                                        (this is DDIM, eta = 0)
+        second order   x_t = (sigma_t / sigma_s) x + A (1 + 1 / (2 r)) x0_s - A / (2 r) x0_s',     r = (lambda_s - lambda_s') / h
+    where s' is the step before s and x0 the data prediction (``DDIMSchedulerLite.step_coef``'s statements).  Call 0 is first
+    order, every call with ``solver_order=1``, the last one with ``lower_order_final`` and N < 15, and the last one with
+    ``final_sigma="zero"``, which takes it to a_prev = 1 where the update returns the predicted x0 (``"alpha0"``, the default,
+    ends at ``alphas_cumprod[0]`` like DDIM).  Other spacings, Karras sigmas and the stochastic variants are not built.
+    PARITY PIN: diffusers is absent, so this is restated from the published algorithm (Lu et al., "DPM-Solver++: Fast Solver
+    for Guided Sampling of Diffusion Probabilistic Models", 2022, Algorithm 2; diffusers'
+    ``multistep_dpm_solver_second_order_update``) -- unpinned against a live run; tests pin order 1 against
+    DDIMSchedulerLite, order 2 against a plain-Python restatement with explicit history lists, and the table's order of
+    convergence against an exact probability-flow solution.
+    Graph-friendly form: ``set_timesteps`` evaluates everything above in fp64 on the host into a per-call table
+    ``[alpha_s, sigma_s, c_x, c_0, c_1, 0]`` (``table``, fp64, CPU; ``coef`` is its fp32 device copy), and a step is
+    ``out = (c_x x + c_0 x0) + c_1 prev; prev <- x0`` with the row copied into a static buffer, so one captured step serves
+    every call and every N.  ``prev`` starts zero-filled: c_1 = 0 on call 0, and 0 * NaN is NaN."""
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 prediction_type: str = "v_prediction", steps_offset: int = 1, solver_order: int = 2,
+                 lower_order_final: bool = True, final_sigma: str = "alpha0"):
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+        if final_sigma not in ("alpha0", "zero"):
+            raise ValueError(f"final_sigma must be 'alpha0' or 'zero', got {final_sigma!r}")
+        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self.final_alpha_cumprod = self.alphas_cumprod[0]
+        self.num_train_timesteps = num_train_timesteps
+        self.prediction_type = prediction_type
+        self.steps_offset = steps_offset
+        self.solver_order = solver_order
+        self.lower_order_final = lower_order_final
+        self.final_sigma = final_sigma
+        self.init_noise_sigma = 1.0
+        self.timesteps = None
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        import math
+        N = num_inference_steps
+        ratio = self.num_train_timesteps // N
+        ts = (torch.arange(0, N) * ratio).round().flip(0).long() + self.steps_offset
+        self.num_inference_steps = N
+        self.timesteps = ts.to(device) if device is not None else ts
+        acp = self.alphas_cumprod.double()
+
+        def lam(a):
+            return 0.5 * math.log(a / (1.0 - a))
+
+        rows, a_before = [], None                          # a_before: alphas_cumprod of the step before this one (s')
+        for i in range(N):
+            t = int(ts[i])
+            a_s = float(acp[t])
+            a_t = float(acp[t - ratio]) if t - ratio >= 0 else float(acp[0])
+            al_s, sg_s = math.sqrt(a_s), math.sqrt(1.0 - a_s)
+            last = i == N - 1
+            if last and self.final_sigma == "zero":
+                rows.append([al_s, sg_s, 0.0, 1.0, 0.0, 0.0])
+            else:
+                h = lam(a_t) - lam(a_s)
+                A = math.sqrt(a_t) * -math.expm1(-h)
+                first = i == 0 or self.solver_order == 1 or (last and self.lower_order_final and N < 15)
+                if first:
+                    c0, c1 = A, 0.0
+                else:
+                    r = (lam(a_s) - lam(a_before)) / h
+                    c0, c1 = A * (1.0 + 0.5 / r), -A * 0.5 / r
+                rows.append([al_s, sg_s, math.sqrt(1.0 - a_t) / sg_s, c0, c1, 0.0])
+            a_before = a_s
+        self.table = torch.tensor(rows, dtype=torch.float64)
+        self.coef = self.table.float()
+        if device is not None:
+            self.coef = self.coef.to(device)
+        return self.timesteps
+
+    def n_model_calls(self) -> int:
+        return self.num_inference_steps
+
+    def make_state(self, latents: torch.Tensor) -> dict:
+        return {"coef": self.coef[0].clone(), "prev": torch.zeros_like(latents, dtype=torch.float32)}
+
+    def load_step(self, state: dict, i: int):
+        state["coef"].copy_(self.coef[i])
+
+    def step(self, model_output: torch.Tensor, sample: torch.Tensor, state: dict) -> torch.Tensor:
+        c = state["coef"]
+        x, g = sample.float(), model_output.float()
+        if self.prediction_type == "v_prediction":
+            x0 = c[0] * x - c[1] * g
+        else:
+            x0 = (x - c[1] * g) / c[0]
+        out = (c[2] * x + c[3] * x0) + c[4] * state["prev"]
+        state["prev"].copy_(x0)
+        return out.to(sample.dtype)
+
+    def fused_step(self, noise: torch.Tensor, sample: torch.Tensor, state: dict, *, guidance_scale: float = 1.0,
+                   guidance_rescale: float = 0.0, do_cfg: bool = False) -> torch.Tensor:
+        """guidance (noise [2b, ...] = [uncond; text] with do_cfg), the optional rescale and ``step`` in one HIP launch;
+        ``prev`` is left as ``step`` would leave it"""
+        return _fused("dpmpp", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
+
+
 @dataclass
 class PipelineOutput:
     latents: torch.Tensor

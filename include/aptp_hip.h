@@ -969,7 +969,7 @@ int aptp_train_images(const AptpTrainImagesParams* p, aptp_stream_t stream);
 
 /* Everything a denoise step does after the U-Net call, in one launch: classifier-free guidance, the optional guidance
  * rescale, and the scheduler update (pipeline.py: PruningDenoiseLoop._one_step after the forward, DDIMSchedulerLite.step_coef,
- * PNDMSchedulerLite.step), in fp32, statement for statement.
+ * PNDMSchedulerLite.step, DPMSolverMultistepSchedulerLite.step), in fp32, statement for statement.
  *   noise    the model output, contiguous [noise_rows, n], bf16 or fp32 (noise_dtype); with do_cfg noise_rows = 2 b laid out
  *            [uncond; text], without it noise_rows = b
  *   sample   fp32 [b, n];  out fp32 [b, n] (may be sample itself)
@@ -980,14 +980,18 @@ int aptp_train_images(const AptpTrainImagesParams* p, aptp_stream_t stream);
  *   DDIM     coef fp32 [4] = sqrt(a_t), sqrt(1 - a_t), sqrt(a_prev), sqrt(1 - a_prev)
  *   PNDM     slot int64 [1], w fp32 [5], coef fp32 [2] = a_t, a_prev, flags fp32 [2] = use_saved, save, the ring E fp32
  *            [5, b, n] and saved fp32 [b, n]; E[slot] <- g and saved are updated in place (a slot outside 0..4 is clamped)
+ *   DPMPP    DPM-Solver++ (2M): coef fp32 [5] = alpha_s, sigma_s, c_x, c_0, c_1 and, in saved, prev fp32 [b, n], the previous
+ *            data prediction: x0 = alpha_s x - sigma_s g (v) or (x - sigma_s g) / alpha_s (epsilon),
+ *            out = (c_x x + c_0 x0) + c_1 prev, prev <- x0 in place (zero-filled before the first call)
  * Without the rescale a flat grid over b n elements in groups of four (when every base is 16-byte aligned) plus single
  * elements; with it one workgroup per sample.  APTP_EINVAL and nothing launched for: null pointers, an unknown dtype /
  * scheduler / prediction type, noise_rows that is not b (2 b with do_cfg), misaligned pointers, guidance_rescale outside
- * [0, 1], a rescale without do_cfg or with n < 2. */
+ * [0, 1], a rescale without do_cfg or with n < 2, DPMPP without coef or prev. */
 #define APTP_STEP_NOISE_BF16 0
 #define APTP_STEP_NOISE_F32 1
 #define APTP_STEP_DDIM 0
 #define APTP_STEP_PNDM 1
+#define APTP_STEP_DPMPP 2
 #define APTP_STEP_EPSILON 0
 #define APTP_STEP_V_PREDICTION 1
 typedef struct {

@@ -1,10 +1,12 @@
-"""Mixed prompt batches at SD-2.1 size: 8 prompts, CFG on, 25 PNDM steps (26 U-Net calls), routed to k in {1, 2, 4, 8} distinct
+"""Mixed prompt batches at SD-2.1 size: 8 prompts, CFG on, 25 PNDM steps (26 U-Net calls; --scheduler ddim / dpmpp: DDIM or
+DPM-Solver++ (2M), --steps calls), routed to k in {1, 2, 4, 8} distinct
 benchmark experts (bench.expert_mask), through
   (a) PruningDenoiseLoop: the per-prompt codes installed as one structure -- dense compute, per-sample gates in the epilogues;
   (b) ExpertDispatchLoop cold: a fresh loop, captures included;
   (c) ExpertDispatchLoop warm: new prompts through the captured steps;
 in ms per image, plus the graph-node count and the steady-state ms of one step with the fused step off and on (one expert, the
-whole batch).  Prints one JSON line.  usage: python tools/bench_dispatch.py [--steps 25] [--prompts 8] [--ks 1,2,4,8]"""
+whole batch).  Prints one JSON line.
+usage: python tools/bench_dispatch.py [--scheduler pndm|ddim|dpmpp] [--steps 25] [--prompts 8] [--ks 1,2,4,8]"""
 import argparse
 import json
 import os
@@ -18,11 +20,13 @@ import torch
 import bench
 from diffusion_pruning_amd import graph_utils
 from diffusion_pruning_amd.hypernet import HyperStructure
-from diffusion_pruning_amd.pipeline import ExpertDispatchLoop, PNDMSchedulerLite, PruningDenoiseLoop
+from diffusion_pruning_amd.pipeline import (DDIMSchedulerLite, DPMSolverMultistepSchedulerLite, ExpertDispatchLoop, PNDMSchedulerLite,
+                                            PruningDenoiseLoop)
 from diffusion_pruning_amd.quantizer import StructureVectorQuantizer
 from diffusion_pruning_amd.unet import UNet2DConditionModelGated
 
 ap = argparse.ArgumentParser()
+ap.add_argument("--scheduler", choices=["pndm", "ddim", "dpmpp"], default="pndm")
 ap.add_argument("--steps", type=int, default=25)
 ap.add_argument("--prompts", type=int, default=8)
 ap.add_argument("--ks", default="1,2,4,8")
@@ -52,7 +56,8 @@ qz = StructureVectorQuantizer(n_e=8, structure=st, temperature=0.4, base=BASE, r
 qz.embedding_gs.data = codes.clone()
 logits = 20.0 * (2.0 * (codes >= 0.5).float() - 1.0) - BASE                            # the relaxation saturates to the hard code
 g = torch.Generator().manual_seed(3)
-n_calls = a.steps + 1
+Scheduler = {"pndm": PNDMSchedulerLite, "ddim": DDIMSchedulerLite, "dpmpp": DPMSolverMultistepSchedulerLite}[a.scheduler]
+n_calls = a.steps + (1 if a.scheduler == "pndm" else 0)
 
 
 def batch(assign):
@@ -70,16 +75,17 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
-res = {"tool": "bench_dispatch", "prompts": a.prompts, "steps": a.steps, "unet_calls": n_calls, "scheduler": "PNDM", "cfg": True,
+res = {"tool": "bench_dispatch", "prompts": a.prompts, "steps": a.steps, "unet_calls": n_calls,
+       "scheduler": {"pndm": "PNDM", "ddim": "DDIM", "dpmpp": "DPM-Solver++ (2M)"}[a.scheduler], "cfg": True,
        "guidance_scale": a.guidance, "by_k": {}}
 for k in [int(v) for v in a.ks.split(",")]:
     assign = [i % k for i in range(a.prompts)]
-    parent = PruningDenoiseLoop(model, hn, qz, scheduler=PNDMSchedulerLite())
+    parent = PruningDenoiseLoop(model, hn, qz, scheduler=Scheduler())
     out = parent(**batch(assign))
     assert out.arch_indices.tolist() == assign, (out.arch_indices.tolist(), assign)
     ta = sorted(timed(lambda: parent(**batch(assign)))[0] for _ in range(3))[1]
     model.invalidate_plans()
-    loop = ExpertDispatchLoop(model, hn, qz, scheduler=PNDMSchedulerLite())
+    loop = ExpertDispatchLoop(model, hn, qz, scheduler=Scheduler())
     tb, out = timed(lambda: loop(**batch(assign)))
     assert out.arch_indices.tolist() == assign and torch.isfinite(out.latents).all()
     warm = [timed(lambda: loop(**batch(assign))) for _ in range(3)]
@@ -93,7 +99,7 @@ for k in [int(v) for v in a.ks.split(",")]:
 model.set_structure(bench.expert_mask(st, 2, dev))
 step = {}
 for fused in (False, True):
-    loop = PruningDenoiseLoop(model, scheduler=PNDMSchedulerLite())
+    loop = PruningDenoiseLoop(model, scheduler=Scheduler())
     kw = batch([2] * a.prompts)
     kw.pop("hyper_net_input")
     loop(**kw, fused_step=fused)
