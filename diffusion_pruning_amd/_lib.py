@@ -473,6 +473,22 @@ class GuidedStepParams(Structure):
     ]
 
 
+PHILOX_F32, PHILOX_BF16, PHILOX_RAW = 0, 1, 2
+
+
+class PhiloxNormalParams(Structure):
+    _fields_ = [
+        ("out", c_void_p),
+        ("base", c_void_p),
+        ("seeds_dev", c_void_p),
+        ("draw_dev", c_void_p),
+        ("scale_dev", c_void_p),
+        ("n", c_int64), ("offset", c_int64), ("draw", c_int64),
+        ("b", c_int32), ("out_kind", c_int32),
+        ("scale", c_float),
+    ]
+
+
 # every symbol include/aptp_hip.h declares: (name, restype, argtypes)
 EXPORTS = [
     ("aptp_conv_gemm", c_int, [POINTER(ConvGemmParams), c_void_p]),
@@ -539,6 +555,7 @@ EXPORTS = [
     ("aptp_paired_cosine", c_int, [POINTER(PairedCosineParams), c_void_p]),
     ("aptp_train_images", c_int, [POINTER(TrainImagesParams), c_void_p]),
     ("aptp_guided_step", c_int, [POINTER(GuidedStepParams), c_void_p]),
+    ("aptp_philox_normal", c_int, [POINTER(PhiloxNormalParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

@@ -21,7 +21,7 @@ from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F40
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
-from ._lib import GuidedStepParams
+from ._lib import GuidedStepParams, PhiloxNormalParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1650,6 +1650,115 @@ def guided_step(noise: torch.Tensor, sample: torch.Tensor, state: dict, *, sched
     p.guidance_scale, p.guidance_rescale = float(guidance_scale), float(guidance_rescale)
     _lib.check(lib.aptp_guided_step(ctypes.byref(p), _stream()), "aptp_guided_step")
     return out
+
+
+def _seed_tensor(seeds, b: int, device, what: str) -> torch.Tensor:
+    """seeds of b samples as a device int64 [b] tensor: an int (shared by all samples), b ints, or such a tensor already"""
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype != torch.int64 or seeds.dim() != 1 or not seeds.is_contiguous() or seeds.device != device:
+            raise ValueError(f"{what}: seeds must be a contiguous int64 [b] tensor on {device}, got {seeds.dtype} "
+                             f"{tuple(seeds.shape)} on {seeds.device}")
+        if seeds.shape[0] != b:
+            raise ValueError(f"{what}: {seeds.shape[0]} seeds for {b} samples")
+        return seeds
+    vals = [seeds] * b if isinstance(seeds, int) and not isinstance(seeds, bool) else list(seeds)
+    if len(vals) != b:
+        raise ValueError(f"{what}: {len(vals)} seeds for {b} samples")
+    for v in vals:
+        if not isinstance(v, int) or isinstance(v, bool) or not -(1 << 63) <= v < (1 << 64):
+            raise ValueError(f"{what}: a seed must be an int in [-2^63, 2^64), got {v!r}")
+    # the kernel reads the int64 as uint64: seeds from 2^63 up travel as their two's complement
+    return torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in vals], dtype=torch.int64, device=device)
+
+
+def _philox(what, kind, out, base, seeds, draw, draw_dev, offset, scale, scale_dev):
+    """the checks every form shares, then the launch; out [b, ...] is fully described by the caller"""
+    dev = out.device
+    b = out.shape[0]
+    n = out.numel() // b
+    for name, t, dt in (("draw_dev", draw_dev, torch.int64), ("scale_dev", scale_dev, torch.float32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or t.numel() != 1 or t.device != dev):
+            raise ValueError(f"{what}: {name} must be a {dt} tensor of one element on {dev}")
+    if not isinstance(draw, int) or draw < 0 or draw >= (1 << 63):
+        raise ValueError(f"{what}: draw must be an int in [0, 2^63), got {draw!r}")
+    if not isinstance(offset, int) or offset < 0 or offset > (1 << 62):
+        raise ValueError(f"{what}: offset must be an int in [0, 2^62], got {offset!r}")
+    if b > 65535 or b * n > (1 << 40):
+        raise ValueError(f"{what}: at most 65535 samples and 2^40 elements, got {b} x {n}")
+    lib = _lib.load()
+    p = PhiloxNormalParams()
+    p.out, p.base, p.seeds_dev = out.data_ptr(), None if base is None else base.data_ptr(), seeds.data_ptr()
+    p.draw_dev = None if draw_dev is None else draw_dev.data_ptr()
+    p.scale_dev = None if scale_dev is None else scale_dev.data_ptr()
+    p.n, p.offset, p.draw, p.b, p.out_kind, p.scale = n, offset, draw, b, kind, float(scale)
+    _lib.check(lib.aptp_philox_normal(ctypes.byref(p), _stream()), "aptp_philox_normal")
+    return out
+
+
+def _philox_out(what, shape, dtype, out, device, seeds):
+    shape = tuple(int(v) for v in shape)
+    if len(shape) < 1 or any(v < 1 for v in shape):
+        raise ValueError(f"{what}: shape must be [b, ...] with no empty dimension, got {shape}")
+    if out is None:
+        if device is None:
+            device = seeds.device if isinstance(seeds, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"{what}: the generator runs on the GPU, got device {device}")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return shape, None, device
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() \
+            or (device is not None and torch.device(device).type != "cuda"):
+        raise ValueError(f"{what}: out must be a contiguous CUDA {dtype} tensor of shape {shape}")
+    return shape, out, out.device
+
+
+def randn(shape, seeds, draw: int = 0, *, offset: int = 0, dtype=torch.float32, scale: float = 1.0,
+          out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """Seeded standard normals on the device (csrc/philox_normal.hip): ``scale * z`` of shape [b, ...], where row r's values are
+    a pure function of (seeds[r], draw, offset + element index) -- Philox4x32-10 and Box-Muller in fp32, the project's own
+    stream (not torch's generator): a row is the same whichever batch it is drawn in.  seeds: an int shared by all samples, b
+    ints, or a device int64 [b] tensor.  dtype fp32 or bf16 (the fp32 value rounded).  ``offset`` starts each row's stream that
+    many elements in: ``randn((b, n), s)[:, k:] == randn((b, n - k), s, offset=k)``."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"randn: dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+    shape, out, dev = _philox_out("randn", shape, dtype, out, device, seeds)
+    sd = _seed_tensor(seeds, shape[0], dev, "randn")
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    kind = _lib.PHILOX_F32 if dtype == torch.float32 else _lib.PHILOX_BF16
+    return _philox("randn", kind, out, None, sd, draw, None, offset, scale, None)
+
+
+def philox_bits(shape, seeds, draw: int = 0, *, offset: int = 0, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """The raw form of ``randn``: the uint32 word behind every element, as an int32 tensor holding its bits (view it as
+    uint32 on the host)."""
+    shape, out, dev = _philox_out("philox_bits", shape, torch.int32, out, device, seeds)
+    sd = _seed_tensor(seeds, shape[0], dev, "philox_bits")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32, device=dev)
+    return _philox("philox_bits", _lib.PHILOX_RAW, out, None, sd, draw, None, offset, 1.0, None)
+
+
+def add_noise(base: torch.Tensor, seeds_dev: torch.Tensor, draw_dev: torch.Tensor, scale_dev: torch.Tensor,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``base + scale_dev * z`` with z = ``randn(base.shape, seeds_dev, draw_dev)``: the capturable form, every scalar in device
+    memory (seeds_dev int64 [b], draw_dev int64 [1], scale_dev fp32 [1]), so one captured launch serves every step of a loop.
+    base fp32 [b, ...]; a multiply, then an add, as the tensor expression rounds.  Returns ``out`` (a new tensor by default;
+    ``out=base`` works in place).  No host synchronisation."""
+    if not isinstance(base, torch.Tensor) or base.dtype != torch.float32 or not base.is_cuda or not base.is_contiguous() \
+            or base.dim() < 1 or base.numel() == 0:
+        raise ValueError("add_noise: base must be a non-empty contiguous CUDA fp32 [b, ...] tensor")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != tuple(base.shape)
+                            or not out.is_contiguous() or out.device != base.device):
+        raise ValueError(f"add_noise: out must be a contiguous fp32 {tuple(base.shape)} tensor on {base.device}")
+    if not isinstance(seeds_dev, torch.Tensor) or draw_dev is None or scale_dev is None:
+        raise ValueError("add_noise: seeds_dev, draw_dev and scale_dev must be device tensors")
+    sd = _seed_tensor(seeds_dev, base.shape[0], base.device, "add_noise")
+    if out is None:
+        out = torch.empty_like(base)
+    return _philox("add_noise", _lib.PHILOX_F32, out, base, sd, 0, draw_dev, 0, 1.0, scale_dev)
 
 
 # ------------------------------------------------------------------------------------------------------------------

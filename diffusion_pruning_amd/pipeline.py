@@ -14,7 +14,11 @@ MI355X-first differences:
   * ExpertDispatchLoop instead groups a routed batch by expert and runs every group through that expert's compacted
     weights, one captured step per (expert, bucket size), results back in the caller's prompt order;
   * ``fused_step=True`` replaces everything after the U-Net call of a step -- guidance, the optional guidance rescale, the
-    scheduler update -- by one launch (ops.guided_step, csrc/sched_step.hip).
+    scheduler update -- by one launch (ops.guided_step, csrc/sched_step.hip);
+  * ``seeds=`` draws the latents on the device (ops.randn, csrc/philox_normal.hip: every normal a pure function of the
+    sample's seed, the draw index and the element, so a prompt's noise does not depend on its batch), and the stochastic
+    samplers -- DDIM with eta > 0, SDE-DPM-Solver++ -- add their step noise inside the captured step (ops.add_noise, one
+    more launch whose seeds, draw index and scale live in device memory).
 """
 from __future__ import annotations
 
@@ -48,13 +52,52 @@ def _fused(kind: str, scheduler, noise, sample, state, guidance_scale, guidance_
                            guidance_rescale=guidance_rescale, do_cfg=do_cfg)
 
 
+def _noise_state(sch, state: dict, latents: torch.Tensor, seeds) -> dict:
+    """the per-call entries a stochastic scheduler adds to its state: the noise scale and the draw index of this call (device
+    tensors that ``load_step`` refreshes) and the per-sample seeds (absent without seeds: ``step`` then needs ``noise=``)"""
+    dev = latents.device
+    state["noise_scale"] = sch.noise_coef[0:1].to(dev).clone()
+    state["draw"] = sch.draws[0:1].to(dev).clone()
+    if seeds is not None:
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.tensor([int(v) for v in ([seeds] * latents.shape[0] if isinstance(seeds, int) else seeds)], dtype=torch.int64)
+        if seeds.dtype != torch.int64 or tuple(seeds.shape) != (latents.shape[0],):
+            raise ValueError(f"make_state: seeds must be int64 [{latents.shape[0]}], got {seeds.dtype} {tuple(seeds.shape)}")
+        state["seeds"] = seeds.to(dev).clone()
+    return state
+
+
+def _load_noise_step(sch, state: dict, i: int):
+    state["noise_scale"].copy_(sch.noise_coef[i:i + 1])
+    state["draw"].copy_(sch.draws[i:i + 1])                      # call i uses draw i + 1; draw 0 is the initial latents
+
+
+def _add_noise(out: torch.Tensor, state: dict, noise) -> torch.Tensor:
+    """out + noise_scale z, a multiply then an add: z given (plain torch, any device) or drawn on the device from the state's
+    seeds and draw index, in place (ops.add_noise)"""
+    if noise is not None:
+        return out + state["noise_scale"] * noise.to(out.dtype)
+    if "seeds" not in state:
+        raise ValueError("a stochastic step needs seeds (make_state(latents, seeds)) or an explicit noise=")
+    from . import ops
+    return ops.add_noise(out, state["seeds"], state["draw"], state["noise_scale"], out=out)
+
+
 class DDIMSchedulerLite:
-    """Minimal DDIM (eta = 0) for SD-2.1's schedule: scaled-linear betas 0.00085..0.012 over 1000 steps, "leading"
+    """Minimal DDIM for SD-2.1's schedule: scaled-linear betas 0.00085..0.012 over 1000 steps, "leading"
     timestep spacing with steps_offset 1, v-prediction or epsilon.  Plain tensor math (device-agnostic), restated
-    from the published DDIM update; the reference uses diffusers' DDIM/PNDM schedulers (pruning_pipelines.py:805-814)."""
+    from the published DDIM update; the reference uses diffusers' DDIM/PNDM schedulers (pruning_pipelines.py:805-814).
+    eta = 0 (the default) is the deterministic sampler.  eta > 0 is the stochastic one of Song et al. 2021, eq. 12 / 16, as
+    diffusers' ``DDIMScheduler.step`` writes it: var = (1 - a_prev) / (1 - a_t) (1 - a_t / a_prev), std = eta sqrt(var), the
+    next sample sqrt(a_prev) x0 + sqrt(1 - a_prev - std^2) eps + std z.  The table's fourth column and ``noise_coef`` (std per
+    call) are then evaluated in fp64 on the host (``table``, ``noise_table``); z comes from the project's seeded device stream
+    (ops.add_noise: seed of the sample, draw i + 1 at call i), one more launch after the update."""
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
-                 prediction_type: str = "v_prediction", steps_offset: int = 1):
+                 prediction_type: str = "v_prediction", steps_offset: int = 1, eta: float = 0.0):
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta must be in [0, 1], got {eta!r}")
+        self.eta = float(eta)
         betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
         self.final_alpha_cumprod = self.alphas_cumprod[0]
@@ -74,9 +117,21 @@ class DDIMSchedulerLite:
         a_prev = torch.where(prev >= 0, self.alphas_cumprod[prev.clamp(min=0)], self.final_alpha_cumprod)
         # per-step coefficient table [steps, 4]: sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev)
         self.coef = torch.stack([a_t.sqrt(), (1 - a_t).sqrt(), a_prev.sqrt(), (1 - a_prev).sqrt()], dim=1)
+        self.noise_coef = torch.zeros(num_inference_steps, dtype=torch.float32)
+        if self.stochastic:
+            a_t, a_prev = a_t.double(), a_prev.double()
+            std = self.eta * ((1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)).sqrt()
+            self.table = torch.stack([a_t.sqrt(), (1 - a_t).sqrt(), a_prev.sqrt(), (1 - a_prev - std * std).sqrt()], dim=1)
+            self.noise_table = std
+            self.coef, self.noise_coef = self.table.float(), std.float()
+        self.draws = torch.arange(1, num_inference_steps + 1, dtype=torch.int64)
         if device is not None:
-            self.coef = self.coef.to(device)
+            self.coef, self.noise_coef, self.draws = self.coef.to(device), self.noise_coef.to(device), self.draws.to(device)
         return self.timesteps
+
+    @property
+    def stochastic(self) -> bool:
+        return self.eta > 0.0
 
     def step_coef(self, model_output: torch.Tensor, coef: torch.Tensor, sample: torch.Tensor) -> torch.Tensor:
         """x_{t-1} from the model output with coefficients coef = [sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev)]"""
@@ -94,19 +149,25 @@ class DDIMSchedulerLite:
     def n_model_calls(self) -> int:
         return self.num_inference_steps
 
-    def make_state(self, latents: torch.Tensor) -> dict:
-        return {"coef": self.coef[0].clone()}
+    def make_state(self, latents: torch.Tensor, seeds=None) -> dict:
+        state = {"coef": self.coef[0].clone()}
+        return _noise_state(self, state, latents, seeds) if self.stochastic else state
 
     def load_step(self, state: dict, i: int):
         state["coef"].copy_(self.coef[i])
+        if self.stochastic:
+            _load_noise_step(self, state, i)
 
-    def step(self, model_output: torch.Tensor, sample: torch.Tensor, state: dict) -> torch.Tensor:
-        return self.step_coef(model_output, state["coef"], sample)
+    def step(self, model_output: torch.Tensor, sample: torch.Tensor, state: dict, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``noise``: an explicit z for the stochastic form instead of the device stream (plain torch, any device)"""
+        out = self.step_coef(model_output, state["coef"], sample)
+        return _add_noise(out, state, noise) if self.stochastic else out
 
     def fused_step(self, noise: torch.Tensor, sample: torch.Tensor, state: dict, *, guidance_scale: float = 1.0,
                    guidance_rescale: float = 0.0, do_cfg: bool = False) -> torch.Tensor:
         """guidance (noise [2b, ...] = [uncond; text] with do_cfg), the optional rescale and ``step`` in one HIP launch"""
-        return _fused("ddim", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
+        out = _fused("ddim", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
+        return _add_noise(out, state, None) if self.stochastic else out
 
 
 class PNDMSchedulerLite:
@@ -223,7 +284,12 @@ class DPMSolverMultistepSchedulerLite:
     where s' is the step before s and x0 the data prediction (``DDIMSchedulerLite.step_coef``'s statements).  Call 0 is first
     order, every call with ``solver_order=1``, the last one with ``lower_order_final`` and N < 15, and the last one with
     ``final_sigma="zero"``, which takes it to a_prev = 1 where the update returns the predicted x0 (``"alpha0"``, the default,
-    ends at ``alphas_cumprod[0]`` like DDIM).  Other spacings, Karras sigmas and the stochastic variants are not built.
+    ends at ``alphas_cumprod[0]`` like DDIM).  Other spacings and Karras sigmas are not built.
+    ``algorithm_type="sde-dpmsolver++"`` is the stochastic variant (diffusers 0.23.1, midpoint) on the same grid and history
+    rule: with A2 = alpha_t (1 - exp(-2h)) the row is c_x = (sigma_t / sigma_s) exp(-h), c_0 = A2 (first order) or
+    A2 (1 + 1 / (2 r)), c_1 = 0 or -A2 / (2 r), and sigma_t sqrt(1 - exp(-2h)) z is added (``noise_coef`` per call, 0 on a
+    ``final_sigma="zero"`` last call; ``noise_table`` in fp64); z comes from the project's seeded device stream
+    (ops.add_noise: seed of the sample, draw i + 1 at call i), one more launch after the update.
     PARITY PIN: diffusers is absent, so this is restated from the published algorithm (Lu et al., "DPM-Solver++: Fast Solver
     for Guided Sampling of Diffusion Probabilistic Models", 2022, Algorithm 2; diffusers'
     ``multistep_dpm_solver_second_order_update``) -- unpinned against a live run; tests pin order 1 against
@@ -236,7 +302,10 @@ class DPMSolverMultistepSchedulerLite:
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  prediction_type: str = "v_prediction", steps_offset: int = 1, solver_order: int = 2,
-                 lower_order_final: bool = True, final_sigma: str = "alpha0"):
+                 lower_order_final: bool = True, final_sigma: str = "alpha0", algorithm_type: str = "dpmsolver++"):
+        if algorithm_type not in ("dpmsolver++", "sde-dpmsolver++"):
+            raise ValueError(f"algorithm_type must be 'dpmsolver++' or 'sde-dpmsolver++', got {algorithm_type!r}")
+        self.algorithm_type = algorithm_type
         if solver_order not in (1, 2):
             raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
         if final_sigma not in ("alpha0", "zero"):
@@ -266,6 +335,7 @@ class DPMSolverMultistepSchedulerLite:
             return 0.5 * math.log(a / (1.0 - a))
 
         rows, a_before = [], None                          # a_before: alphas_cumprod of the step before this one (s')
+        noise = []
         for i in range(N):
             t = int(ts[i])
             a_s = float(acp[t])
@@ -274,33 +344,52 @@ class DPMSolverMultistepSchedulerLite:
             last = i == N - 1
             if last and self.final_sigma == "zero":
                 rows.append([al_s, sg_s, 0.0, 1.0, 0.0, 0.0])
+                noise.append(0.0)
             else:
                 h = lam(a_t) - lam(a_s)
                 A = math.sqrt(a_t) * -math.expm1(-h)
+                c_x = math.sqrt(1.0 - a_t) / sg_s
+                if self.stochastic:
+                    A = math.sqrt(a_t) * -math.expm1(-2.0 * h)
+                    c_x = c_x * math.exp(-h)
+                    noise.append(math.sqrt(1.0 - a_t) * math.sqrt(-math.expm1(-2.0 * h)))
+                else:
+                    noise.append(0.0)
                 first = i == 0 or self.solver_order == 1 or (last and self.lower_order_final and N < 15)
                 if first:
                     c0, c1 = A, 0.0
                 else:
                     r = (lam(a_s) - lam(a_before)) / h
                     c0, c1 = A * (1.0 + 0.5 / r), -A * 0.5 / r
-                rows.append([al_s, sg_s, math.sqrt(1.0 - a_t) / sg_s, c0, c1, 0.0])
+                rows.append([al_s, sg_s, c_x, c0, c1, 0.0])
             a_before = a_s
         self.table = torch.tensor(rows, dtype=torch.float64)
         self.coef = self.table.float()
+        self.noise_table = torch.tensor(noise, dtype=torch.float64)
+        self.noise_coef = self.noise_table.float()
+        self.draws = torch.arange(1, N + 1, dtype=torch.int64)
         if device is not None:
-            self.coef = self.coef.to(device)
+            self.coef, self.noise_coef, self.draws = self.coef.to(device), self.noise_coef.to(device), self.draws.to(device)
         return self.timesteps
+
+    @property
+    def stochastic(self) -> bool:
+        return self.algorithm_type == "sde-dpmsolver++"
 
     def n_model_calls(self) -> int:
         return self.num_inference_steps
 
-    def make_state(self, latents: torch.Tensor) -> dict:
-        return {"coef": self.coef[0].clone(), "prev": torch.zeros_like(latents, dtype=torch.float32)}
+    def make_state(self, latents: torch.Tensor, seeds=None) -> dict:
+        state = {"coef": self.coef[0].clone(), "prev": torch.zeros_like(latents, dtype=torch.float32)}
+        return _noise_state(self, state, latents, seeds) if self.stochastic else state
 
     def load_step(self, state: dict, i: int):
         state["coef"].copy_(self.coef[i])
+        if self.stochastic:
+            _load_noise_step(self, state, i)
 
-    def step(self, model_output: torch.Tensor, sample: torch.Tensor, state: dict) -> torch.Tensor:
+    def step(self, model_output: torch.Tensor, sample: torch.Tensor, state: dict, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``noise``: an explicit z for the stochastic form instead of the device stream (plain torch, any device)"""
         c = state["coef"]
         x, g = sample.float(), model_output.float()
         if self.prediction_type == "v_prediction":
@@ -309,13 +398,16 @@ class DPMSolverMultistepSchedulerLite:
             x0 = (x - c[1] * g) / c[0]
         out = (c[2] * x + c[3] * x0) + c[4] * state["prev"]
         state["prev"].copy_(x0)
+        if self.stochastic:
+            out = _add_noise(out, state, noise)
         return out.to(sample.dtype)
 
     def fused_step(self, noise: torch.Tensor, sample: torch.Tensor, state: dict, *, guidance_scale: float = 1.0,
                    guidance_rescale: float = 0.0, do_cfg: bool = False) -> torch.Tensor:
         """guidance (noise [2b, ...] = [uncond; text] with do_cfg), the optional rescale and ``step`` in one HIP launch;
         ``prev`` is left as ``step`` would leave it"""
-        return _fused("dpmpp", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
+        out = _fused("dpmpp", self, noise, sample, state, guidance_scale, guidance_rescale, do_cfg)
+        return _add_noise(out, state, None) if self.stochastic else out
 
 
 @dataclass
@@ -376,7 +468,7 @@ class PruningDenoiseLoop:
                  output_type: str = "latent", *, prompt_ids: Optional[torch.Tensor] = None,
                  negative_prompt_ids: Optional[torch.Tensor] = None, router_ids: Optional[torch.Tensor] = None,
                  router_attention_mask: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0,
-                 fused_step: bool = False) -> PipelineOutput:
+                 fused_step: bool = False, seeds=None, latent_shape=None) -> PipelineOutput:
         """prompt_embeds [B,77,X] (+ negative_prompt_embeds for CFG, concatenated as [uncond, cond] like the
         reference, :765); latents [B,4,h,w] ~ N(0,1) on the device.  output_type "latent" returns the latents only;
         "pt" (fp32 [B,3,H,W] in [0, 1]), "np" (fp32 [B,H,W,3] numpy) and "pil" (list of PIL images) also decode them
@@ -388,10 +480,15 @@ class PruningDenoiseLoop:
         ``prompt_encoder.encode(router_ids, router_attention_mask)`` (get_mpnet_embeddings, pdm/utils/data_utils.py:130-155).
         guidance_rescale > 0 (with CFG): ``rescale_noise_cfg`` on the guided output (:809-811).  fused_step: guidance, rescale
         and the scheduler update of every step as ONE HIP launch (ops.guided_step) instead of the tensor expressions; both are
-        part of the captured step's key, and the defaults leave the step exactly as it was."""
+        part of the captured step's key, and the defaults leave the step exactly as it was.
+        seeds (an int, or one int per prompt) with latent_shape=(4, h, w) instead of latents: the latents are
+        ``ops.randn((B,) + latent_shape, seeds, draw=0)`` in fp32, the project's seeded device stream -- prompt i with seed s
+        starts from the same latents whichever batch it is in.  A stochastic scheduler (DDIM with eta > 0, SDE-DPM-Solver++)
+        needs seeds, with or without latents: call i adds draw i + 1 of every sample's seed, one more launch in the step."""
         prompt_embeds, negative_prompt_embeds, hyper_net_input = self._inputs(
             prompt_embeds, latents, hyper_net_input, negative_prompt_embeds, output_type, prompt_ids, negative_prompt_ids,
-            router_ids, router_attention_mask, guidance_scale)
+            router_ids, router_attention_mask, guidance_scale, seeds, latent_shape)
+        latents, seeds = self._noise_source(latents, seeds, latent_shape, prompt_embeds)
         dev = latents.device
         arch_q = idx = None
         if self.hyper_net is not None and hyper_net_input is not None:
@@ -404,16 +501,17 @@ class PruningDenoiseLoop:
         B = latents.shape[0] * (2 if do_cfg else 1)
         extra = (float(guidance_rescale), bool(fused_step))
         if not use_graph:
-            latents = self._eager(latents, ts, ctx, B, guidance_scale, do_cfg, *extra)
+            latents = self._eager(latents, ts, ctx, B, guidance_scale, do_cfg, *extra, seeds=seeds)
         else:
             # one captured step per (scheduler, shapes, CFG, guidance, installed architecture): later calls with the same key
             # (the FID-generation loop: many prompt batches through one expert) only refresh the static buffers
             key = (type(self.scheduler).__name__, self.scheduler.prediction_type, tuple(latents.shape), latents.dtype, do_cfg,
-                   float(guidance_scale), str(dev), ctx.key, getattr(self.unet, "_structure_epoch", None)) + extra
+                   float(guidance_scale), str(dev), ctx.key, getattr(self.unet, "_structure_epoch", None)) + extra \
+                + (self._stochastic(),)                                           # (a stochastic step has one more node)
             if ctx.key is None or self._graph_key != key:
-                self._graph = self._capture(latents, ts, ctx, B, guidance_scale, do_cfg, *extra)
+                self._graph = self._capture(latents, ts, ctx, B, guidance_scale, do_cfg, *extra, seeds=seeds)
                 self._graph_key = key if ctx.key is not None else None
-            latents = self._replay(self._graph, latents, ts, ctx, B)
+            latents = self._replay(self._graph, latents, ts, ctx, B, seeds=seeds)
         ratios = None
         if getattr(self.unet, "resource_info_dict", None) is not None:
             # pruning_pipelines.py:822-824
@@ -424,20 +522,45 @@ class PruningDenoiseLoop:
         return PipelineOutput(latents=latents, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios,
                               images=images)
 
-    def _eager(self, latents, ts, ctx, B, guidance_scale, do_cfg, guidance_rescale=0.0, fused_step=False, unet=None):
-        state = self.scheduler.make_state(latents)
+    def _stochastic(self) -> bool:
+        return bool(getattr(self.scheduler, "stochastic", False))
+
+    def _state(self, latents, seeds):
+        """the scheduler's per-step state; a stochastic one also carries the seeds"""
+        return self.scheduler.make_state(latents, seeds) if self._stochastic() else self.scheduler.make_state(latents)
+
+    def _noise_source(self, latents, seeds, latent_shape, prompt_embeds):
+        """(latents, seeds as a device int64 [B] tensor or None) of a call whose arguments ``_inputs`` has accepted: the
+        latents are drawn here when only seeds were given"""
+        if seeds is None:
+            return latents, None
+        from . import ops
+        nB = prompt_embeds.shape[0]
+        if latents is not None:
+            dev = latents.device
+        else:
+            dev = next((p.device for p in self.unet.parameters()), prompt_embeds.device) if hasattr(self.unet, "parameters") \
+                else prompt_embeds.device
+        seeds = ops._seed_tensor(seeds, nB, dev, "seeds")
+        if latents is None:
+            latents = ops.randn((nB,) + tuple(int(v) for v in latent_shape), seeds, draw=0)
+        return latents, seeds
+
+    def _eager(self, latents, ts, ctx, B, guidance_scale, do_cfg, guidance_rescale=0.0, fused_step=False, unet=None, seeds=None):
+        state = self._state(latents, seeds)
         for i in range(self.scheduler.n_model_calls()):
             self.scheduler.load_step(state, i)
             latents = self._one_step(latents, ts[i].expand(B), state, ctx, guidance_scale, do_cfg, guidance_rescale, fused_step, unet)
         return latents
 
-    def _replay(self, g, latents, ts, ctx, B):
-        """refresh a captured step's static buffers and replay it once per model call"""
+    def _replay(self, g, latents, ts, ctx, B, seeds=None):
+        """refresh a captured step's static buffers (the seeds of a stochastic scheduler among them) and replay it once per
+        model call"""
         g["lat"].copy_(latents)
         g["ctx"].ehs.copy_(ctx.ehs)
         for k_, v_ in ctx.kv.items():
             g["ctx"].kv[k_].copy_(v_)
-        for name, t_ in self.scheduler.make_state(latents).items():
+        for name, t_ in self._state(latents, seeds).items():
             g["state"][name].copy_(t_)
         for i in range(self.scheduler.n_model_calls()):
             g["t"].copy_(ts[i].expand(B))
@@ -447,7 +570,7 @@ class PruningDenoiseLoop:
         return g["lat"].clone()
 
     def _inputs(self, prompt_embeds, latents, hyper_net_input, negative_prompt_embeds, output_type, prompt_ids, negative_prompt_ids,
-                router_ids, router_attention_mask, guidance_scale):
+                router_ids, router_attention_mask, guidance_scale, seeds=None, latent_shape=None):
         """argument checks of a call, and the encoders: token ids -> text states (one CLIP call for the whole batch), MPNet
         token ids -> the router's input.  Returns (prompt_embeds, negative_prompt_embeds, hyper_net_input)."""
         if router_ids is not None or router_attention_mask is not None:
@@ -466,8 +589,22 @@ class PruningDenoiseLoop:
                 raise ValueError("prompt_ids need a text_encoder (PruningDenoiseLoop(..., text_encoder=CLIPTextModel))")
         elif prompt_embeds is None:
             raise ValueError("prompt_embeds or prompt_ids is required")
-        if latents is None:
+        if latents is None and seeds is None:
             raise ValueError("latents is required")
+        if seeds is not None:
+            # exactly one source of noise: latents or seeds; a stochastic scheduler draws its step noise from the seeds either way
+            if latents is not None and not self._stochastic():
+                raise ValueError("give either latents or seeds, not both (the scheduler is deterministic: seeds would only draw the latents)")
+            if latents is None and (latent_shape is None or len(tuple(latent_shape)) != 3 or any(int(v) < 1 for v in latent_shape)):
+                raise ValueError(f"seeds without latents need latent_shape=(4, h, w), got {latent_shape!r}")
+            n_prompts = (prompt_ids if prompt_ids is not None else prompt_embeds).shape[0]
+            if latents is not None and latents.shape[0] != n_prompts:
+                raise ValueError(f"{latents.shape[0]} latents for {n_prompts} prompts")
+            n_seeds = n_prompts if isinstance(seeds, int) and not isinstance(seeds, bool) else len(seeds)
+            if n_seeds != n_prompts:
+                raise ValueError(f"{n_seeds} seeds for {n_prompts} prompts")
+        elif self._stochastic():
+            raise ValueError(f"{type(self.scheduler).__name__} is stochastic here: it needs seeds=")
         if prompt_ids is not None:
             if guidance_scale > 1.0 and negative_prompt_ids is not None:
                 if tuple(negative_prompt_ids.shape) != tuple(prompt_ids.shape):
@@ -499,10 +636,10 @@ class PruningDenoiseLoop:
             return img.permute(0, 2, 3, 1).float().cpu().numpy()
         return img
 
-    def _capture(self, latents, ts, ctx, B, guidance_scale, do_cfg, guidance_rescale=0.0, fused_step=False, unet=None):
+    def _capture(self, latents, ts, ctx, B, guidance_scale, do_cfg, guidance_rescale=0.0, fused_step=False, unet=None, seeds=None):
         lat_buf = latents.clone()
         t_buf = ts[0].expand(B).clone()
-        state = self.scheduler.make_state(latents)
+        state = self._state(latents, seeds)
         self.scheduler.load_step(state, 0)
         # warm-up on a side stream (builds packed-weight plans), then capture one step
         side = torch.cuda.Stream()
@@ -553,7 +690,7 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
     routing still comes from ``hyper_net`` / ``quantizer``; an index the router picks that is missing raises KeyError.
 
     Captured steps: one per (expert identity, the bytes of its hard code, bucket, scheduler class, prediction type, latent
-    shape, dtype, CFG, guidance scale, guidance rescale, device), in an LRU of at most ``max_graphs`` entries.  A capture
+    shape, dtype, CFG, guidance scale, guidance rescale, device, stochastic or not), in an LRU of at most ``max_graphs`` entries.  A capture
     pins the packed-weight plans it touched in the modules' plan caches until ``invalidate_plans()`` / ``clear()``: evicting
     a graph here does NOT free its packs.  Re-installing a code finds its pinned plans again, so the bound is at most
     ``max_graphs`` pinned plans per module for as long as no more than ``max_graphs`` distinct codes are captured between
@@ -595,7 +732,7 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
                  output_type: str = "latent", *, prompt_ids: Optional[torch.Tensor] = None,
                  negative_prompt_ids: Optional[torch.Tensor] = None, router_ids: Optional[torch.Tensor] = None,
                  router_attention_mask: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0,
-                 fused_step: bool = True) -> DispatchOutput:
+                 fused_step: bool = True, seeds=None, latent_shape=None) -> DispatchOutput:
         """The arguments of PruningDenoiseLoop.__call__; hyper_net_input or router_ids is required (there is nothing to
         dispatch on otherwise), and the step is always the fused one.  Returns latents / images in the caller's prompt order,
         ``arch_indices`` [B], ``resource_ratios`` [B] and ``groups``."""
@@ -605,9 +742,10 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
             raise ValueError("ExpertDispatchLoop needs a hyper_net and a quantizer to route with")
         prompt_embeds, negative_prompt_embeds, hyper_net_input = self._inputs(
             prompt_embeds, latents, hyper_net_input, negative_prompt_embeds, output_type, prompt_ids, negative_prompt_ids,
-            router_ids, router_attention_mask, guidance_scale)
+            router_ids, router_attention_mask, guidance_scale, seeds, latent_shape)
         if hyper_net_input is None:
             raise ValueError("ExpertDispatchLoop needs hyper_net_input or router_ids")
+        latents, seeds = self._noise_source(latents, seeds, latent_shape, prompt_embeds)
         dev = latents.device
         nB = latents.shape[0]
         arch_q, idx = self.route_indices(hyper_net_input.to(dev))
@@ -641,6 +779,7 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
             rows_t = torch.tensor(rows, dtype=torch.long, device=dev)
             take = torch.tensor(rows + [rows[-1]] * (bucket - len(rows)), dtype=torch.long, device=dev)
             lat_g = latents.index_select(0, take)
+            seeds_g = None if seeds is None else seeds.index_select(0, take)      # (a padded row repeats its source row's seed)
             ehs = prompt_embeds.index_select(0, take)
             if do_cfg:
                 ehs = torch.cat([negative_prompt_embeds.index_select(0, take), ehs])
@@ -648,22 +787,22 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
             Bm = bucket * (2 if do_cfg else 1)
             reused = False
             if not use_graph:
-                res = self._eager(lat_g, ts, ctx, Bm, guidance_scale, do_cfg, rescale, True, model)
+                res = self._eager(lat_g, ts, ctx, Bm, guidance_scale, do_cfg, rescale, True, model, seeds_g)
             else:
                 key = (e, id(model), code, bucket, type(self.scheduler).__name__, self.scheduler.prediction_type,
-                       tuple(lat_g.shape), lat_g.dtype, do_cfg, float(guidance_scale), rescale, str(dev))
+                       tuple(lat_g.shape), lat_g.dtype, do_cfg, float(guidance_scale), rescale, str(dev), self._stochastic())
                 g = self._graphs.get(key)
                 reused = g is not None and ctx.key is not None and g["ctx"].key == ctx.key
                 if not reused:
                     self._graphs.pop(key, None)
                     while len(self._graphs) >= self.max_graphs:
                         self._graphs.popitem(last=False)
-                    g = self._capture(lat_g, ts, ctx, Bm, guidance_scale, do_cfg, rescale, True, model)
+                    g = self._capture(lat_g, ts, ctx, Bm, guidance_scale, do_cfg, rescale, True, model, seeds_g)
                     if ctx.key is not None:
                         self._graphs[key] = g
                 else:
                     self._graphs.move_to_end(key)
-                res = self._replay(g, lat_g, ts, ctx, Bm)
+                res = self._replay(g, lat_g, ts, ctx, Bm, seeds_g)
             out.index_copy_(0, rows_t, res[:len(rows)].to(out.dtype))
             if getattr(model, "resource_info_dict", None) is not None:
                 # pruning_pipelines.py:822-824, per group

@@ -1011,6 +1011,33 @@ typedef struct {
 } AptpGuidedStepParams;
 int aptp_guided_step(const AptpGuidedStepParams* p, aptp_stream_t stream);
 
+/* Seeded normal noise (csrc/philox_normal.hip, the stream itself in csrc/philox_normal.h): Philox4x32-10 and Box-Muller in fp32,
+ * every value a pure function of (seed of the sample, draw, element).  For sample r of b and element e of n:
+ *   key (seeds_dev[r] & 0xffffffff, seeds_dev[r] >> 32) (the int64 read as uint64);  g = offset + e, blk = g >> 2, lane = g & 3;
+ *   counter (blk & 0xffffffff, blk >> 32, d & 0xffffffff, d >> 32) with d = draw + draw_dev[0] (draw_dev may be null);
+ *   z = lane `lane` of the block's four normals;  s = scale * scale_dev[0] (scale_dev may be null: s = scale)
+ *   out[r, e] = s z,  or base[r, e] + s z with base (fp32 [b, n]; a multiply, then an add; out may be base)
+ *   out is fp32, bf16 (the fp32 value rounded) or -- APTP_PHILOX_RAW -- the uint32 word x[lane] itself (no base, no scale_dev).
+ * seeds_dev, draw_dev and scale_dev are DEVICE memory, read by the kernel, so a captured launch follows a loop.  A lane that owns
+ * a whole aligned block of four does one Philox evaluation and one vector store; a row's head and tail, and everything when an
+ * address is not aligned, go element by element with the same values.  APTP_EINVAL and nothing launched for: null out / seeds_dev,
+ * an unknown out_kind, b outside 1..65535, n < 1, b n > 2^40, a negative offset or draw, misaligned pointers, raw with base or
+ * scale_dev. */
+#define APTP_PHILOX_F32 0
+#define APTP_PHILOX_BF16 1
+#define APTP_PHILOX_RAW 2
+typedef struct {
+  void* out;
+  const float* base;
+  const int64_t* seeds_dev;
+  const int64_t* draw_dev;
+  const float* scale_dev;
+  int64_t n, offset, draw;
+  int32_t b, out_kind;
+  float scale;
+} AptpPhiloxNormalParams;
+int aptp_philox_normal(const AptpPhiloxNormalParams* p, aptp_stream_t stream);
+
 const char* aptp_last_error(void);
 int aptp_version(void);
 

@@ -5,8 +5,11 @@ benchmark experts (bench.expert_mask), through
   (b) ExpertDispatchLoop cold: a fresh loop, captures included;
   (c) ExpertDispatchLoop warm: new prompts through the captured steps;
 in ms per image, plus the graph-node count and the steady-state ms of one step with the fused step off and on (one expert, the
-whole batch).  Prints one JSON line.
-usage: python tools/bench_dispatch.py [--scheduler pndm|ddim|dpmpp] [--steps 25] [--prompts 8] [--ks 1,2,4,8]"""
+whole batch).  --seeds: the latents are drawn in the loop from one seed per prompt (ops.randn) instead of handed in.
+--eta X (DDIM) / --sde (SDE-DPM-Solver++): the stochastic samplers, seeded; the JSON line then also carries "noise_node": the
+fused step of the same scheduler class without and with the noise launch, measured in this same run.  Prints one JSON line.
+usage: python tools/bench_dispatch.py [--scheduler pndm|ddim|dpmpp] [--steps 25] [--prompts 8] [--ks 1,2,4,8] [--seeds]
+       [--eta X | --sde]"""
 import argparse
 import json
 import os
@@ -31,7 +34,18 @@ ap.add_argument("--steps", type=int, default=25)
 ap.add_argument("--prompts", type=int, default=8)
 ap.add_argument("--ks", default="1,2,4,8")
 ap.add_argument("--guidance", type=float, default=7.5)
+ap.add_argument("--seeds", action="store_true", help="draw the latents in the loop from one seed per prompt")
+ap.add_argument("--eta", type=float, default=0.0, help="stochastic DDIM (implies --scheduler ddim and --seeds)")
+ap.add_argument("--sde", action="store_true", help="SDE-DPM-Solver++ (implies --scheduler dpmpp and --seeds)")
 a = ap.parse_args()
+if a.eta > 0.0 and a.sde:
+    ap.error("--eta and --sde exclude each other")
+if a.eta > 0.0:
+    a.scheduler = "ddim"
+if a.sde:
+    a.scheduler = "dpmpp"
+stochastic = a.eta > 0.0 or a.sde
+a.seeds = a.seeds or stochastic
 dev = torch.device("cuda:0")
 graph_utils.KEEP_GRAPHS = True                     # so that a captured step can be asked for its node count
 model = UNet2DConditionModelGated().init_synthetic(seed=0).to(dev)
@@ -56,15 +70,28 @@ qz = StructureVectorQuantizer(n_e=8, structure=st, temperature=0.4, base=BASE, r
 qz.embedding_gs.data = codes.clone()
 logits = 20.0 * (2.0 * (codes >= 0.5).float() - 1.0) - BASE                            # the relaxation saturates to the hard code
 g = torch.Generator().manual_seed(3)
-Scheduler = {"pndm": PNDMSchedulerLite, "ddim": DDIMSchedulerLite, "dpmpp": DPMSolverMultistepSchedulerLite}[a.scheduler]
+
+
+def Scheduler(noise=True):
+    """the scheduler of this run; noise=False: the deterministic one of the same class"""
+    if a.scheduler == "ddim":
+        return DDIMSchedulerLite(eta=a.eta if noise else 0.0)
+    if a.scheduler == "dpmpp":
+        return DPMSolverMultistepSchedulerLite(algorithm_type="sde-dpmsolver++" if noise and a.sde else "dpmsolver++")
+    return PNDMSchedulerLite()
+
+
 n_calls = a.steps + (1 if a.scheduler == "pndm" else 0)
 
 
 def batch(assign):
     n = len(assign)
-    return dict(prompt_embeds=torch.randn(n, 77, 1024, generator=g).to(dev), latents=torch.randn(n, 4, 64, 64, generator=g).to(dev),
-                negative_prompt_embeds=torch.randn(n, 77, 1024, generator=g).to(dev), hyper_net_input=logits[assign],
-                num_inference_steps=a.steps, guidance_scale=a.guidance)
+    kw = dict(prompt_embeds=torch.randn(n, 77, 1024, generator=g).to(dev), latents=torch.randn(n, 4, 64, 64, generator=g).to(dev),
+              negative_prompt_embeds=torch.randn(n, 77, 1024, generator=g).to(dev), hyper_net_input=logits[assign],
+              num_inference_steps=a.steps, guidance_scale=a.guidance)
+    if a.seeds:
+        kw.update(latents=None, seeds=torch.randint(0, 2 ** 62, (n,), generator=g).tolist(), latent_shape=(4, 64, 64))
+    return kw
 
 
 def timed(fn):
@@ -76,8 +103,8 @@ def timed(fn):
 
 
 res = {"tool": "bench_dispatch", "prompts": a.prompts, "steps": a.steps, "unet_calls": n_calls,
-       "scheduler": {"pndm": "PNDM", "ddim": "DDIM", "dpmpp": "DPM-Solver++ (2M)"}[a.scheduler], "cfg": True,
-       "guidance_scale": a.guidance, "by_k": {}}
+       "scheduler": {"pndm": "PNDM", "ddim": "DDIM", "dpmpp": "DPM-Solver++ (2M)"}[a.scheduler] + (" SDE" if a.sde else ""), "cfg": True,
+       "eta": a.eta, "seeded_latents": a.seeds, "guidance_scale": a.guidance, "by_k": {}}
 for k in [int(v) for v in a.ks.split(",")]:
     assign = [i % k for i in range(a.prompts)]
     parent = PruningDenoiseLoop(model, hn, qz, scheduler=Scheduler())
@@ -106,4 +133,19 @@ for fused in (False, True):
     t = sorted(timed(lambda: loop(**kw, fused_step=fused))[0] for _ in range(3))[1]
     step["fused" if fused else "torch"] = {"graph_nodes": graph_utils.node_count(loop._graph["graph"]), "ms_per_step": round(t / n_calls, 3)}
 res["step"] = step
+if stochastic:
+    # the cost of the noise node: the fused step of the same class without and with it, interleaved in this run
+    loops = {nm: PruningDenoiseLoop(model, scheduler=Scheduler(noise=nm == "stochastic")) for nm in ("deterministic", "stochastic")}
+    kw = batch([2] * a.prompts)
+    kw.pop("hyper_net_input")
+    times = {nm: [] for nm in loops}
+    for rnd in range(6):
+        for nm, loop in loops.items():
+            t = timed(lambda: loop(**kw, fused_step=True))[0]
+            if rnd:                                     # (round 0 captures)
+                times[nm].append(t / n_calls)
+    res["noise_node"] = {nm: {"graph_nodes": graph_utils.node_count(loops[nm]._graph["graph"]),
+                              "ms_per_step": round(sorted(times[nm])[len(times[nm]) // 2], 4)} for nm in loops}
+    res["noise_node"]["delta_us_per_step"] = round(1e3 * (res["noise_node"]["stochastic"]["ms_per_step"]
+                                                          - res["noise_node"]["deterministic"]["ms_per_step"]), 1)
 print(json.dumps(res))
