@@ -489,6 +489,28 @@ class PhiloxNormalParams(Structure):
     ]
 
 
+TRAIN_NOISE_EPSILON, TRAIN_NOISE_V_PREDICTION = 0, 1
+
+
+class TrainNoiseParams(Structure):
+    _fields_ = [
+        ("moments", c_void_p),
+        ("latents_in", c_void_p),
+        ("sqrt_table", c_void_p),
+        ("seeds_dev", c_void_p),
+        ("draw_dev", c_void_p),
+        ("noisy", c_void_p),
+        ("target", c_void_p),
+        ("timesteps", c_void_p),
+        ("latents_out", c_void_p),
+        ("noise_out", c_void_p),
+        ("draw", c_int64),
+        ("B", c_int32), ("h", c_int32), ("w", c_int32), ("T", c_int32),
+        ("prediction", c_int32),
+        ("scale", c_float), ("noise_offset", c_float), ("input_perturbation", c_float),
+    ]
+
+
 # every symbol include/aptp_hip.h declares: (name, restype, argtypes)
 EXPORTS = [
     ("aptp_conv_gemm", c_int, [POINTER(ConvGemmParams), c_void_p]),
@@ -556,6 +578,7 @@ EXPORTS = [
     ("aptp_train_images", c_int, [POINTER(TrainImagesParams), c_void_p]),
     ("aptp_guided_step", c_int, [POINTER(GuidedStepParams), c_void_p]),
     ("aptp_philox_normal", c_int, [POINTER(PhiloxNormalParams), c_void_p]),
+    ("aptp_train_noise", c_int, [POINTER(TrainNoiseParams), c_void_p]),
     ("aptp_last_error", c_char_p, []),
     ("aptp_version", c_int, []),
 ]

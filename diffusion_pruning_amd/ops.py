@@ -21,7 +21,7 @@ from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F40
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
-from ._lib import GuidedStepParams, PhiloxNormalParams
+from ._lib import GuidedStepParams, PhiloxNormalParams, TrainNoiseParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1759,6 +1759,74 @@ def add_noise(base: torch.Tensor, seeds_dev: torch.Tensor, draw_dev: torch.Tenso
     if out is None:
         out = torch.empty_like(base)
     return _philox("add_noise", _lib.PHILOX_F32, out, base, sd, 0, draw_dev, 0, 1.0, scale_dev)
+
+
+def train_noise(moments: Optional[torch.Tensor] = None, *, latents: Optional[torch.Tensor] = None, sqrt_table: torch.Tensor, seeds,
+                draw: int = 0, draw_dev: Optional[torch.Tensor] = None, scale: float = 1.0, noise_offset: float = 0.0,
+                input_perturbation: float = 0.0, prediction_type: str = "v_prediction", want_latents: bool = False,
+                want_noise: bool = False, out: Optional[dict] = None) -> dict:
+    """A seeded training batch in one launch (csrc/train_noise.hip; the draw map and the arithmetic in csrc/train_noise.h, DESIGN
+    6m): ``moments`` fp32 [B, 8, h, w] (``vae.encode(x).latent_dist.parameters``; the posterior is sampled here, times ``scale``)
+    or ``latents`` fp32 [B, 4, h, w], exactly one of the two; ``sqrt_table`` fp32 [T, 2] (``NoiseSchedule.sqrt_table``; a
+    timestep is drawn from its T rows); ``seeds`` as ``randn`` takes them.  Sample r's timestep, noise, offset noise and input
+    perturbation are a pure function of (seeds[r], draw + draw_dev[0], element), whatever batch it sits in.  Returns
+    {"noisy_latents", "target", "timesteps"} and, when asked for, "latents" (x0) and "noise" (with its offset, without the
+    perturbation).  ``out`` is a dict of such tensors to write into; with it, and ``seeds`` / ``draw_dev`` device tensors, the
+    call is capturable.  No host synchronisation."""
+    what = "train_noise"
+    if (moments is None) == (latents is None):
+        raise ValueError(f"{what}: give exactly one of moments and latents")
+    src, ch = (moments, 8) if moments is not None else (latents, 4)
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.float32 or not src.is_cuda or not src.is_contiguous() or src.dim() != 4 \
+            or src.shape[1] != ch or src.numel() == 0:
+        got = f"{src.dtype} {tuple(src.shape)}" if isinstance(src, torch.Tensor) else type(src).__name__
+        raise ValueError(f"{what}: {'moments' if ch == 8 else 'latents'} must be a non-empty contiguous CUDA fp32 [B, {ch}, h, w] "
+                         f"tensor, got {got}")
+    dev = src.device
+    B, _, h, w = (int(v) for v in src.shape)
+    if B > 65535:
+        raise ValueError(f"{what}: at most 65535 samples, got {B}")
+    if not isinstance(sqrt_table, torch.Tensor) or sqrt_table.dtype != torch.float32 or sqrt_table.dim() != 2 or sqrt_table.shape[1] != 2 \
+            or sqrt_table.shape[0] < 1 or not sqrt_table.is_contiguous() or sqrt_table.device != dev:
+        raise ValueError(f"{what}: sqrt_table must be a contiguous fp32 [T, 2] tensor on {dev}")
+    if draw_dev is not None and (not isinstance(draw_dev, torch.Tensor) or draw_dev.dtype != torch.int64 or draw_dev.numel() != 1
+                                 or draw_dev.device != dev):
+        raise ValueError(f"{what}: draw_dev must be a {torch.int64} tensor of one element on {dev}")
+    if not isinstance(draw, int) or isinstance(draw, bool) or draw < 0 or draw >= (1 << 59):
+        raise ValueError(f"{what}: draw must be an int in [0, 2^59), got {draw!r}")
+    preds = {"epsilon": _lib.TRAIN_NOISE_EPSILON, "v_prediction": _lib.TRAIN_NOISE_V_PREDICTION}
+    if prediction_type not in preds:
+        raise ValueError(f"{what}: unknown prediction_type {prediction_type!r}")
+    for name, v in (("scale", scale), ("noise_offset", noise_offset), ("input_perturbation", input_perturbation)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+    sd = _seed_tensor(seeds, B, dev, what)
+    names = ["noisy_latents", "target", "timesteps"] + (["latents"] if want_latents else []) + (["noise"] if want_noise else [])
+    if out is not None and (not isinstance(out, dict) or any(nm not in out for nm in names)):
+        raise ValueError(f"{what}: out must be a dict with {names}")
+    res = {}
+    for nm in names:
+        shape, dt = ((B,), torch.int64) if nm == "timesteps" else ((B, 4, h, w), torch.float32)
+        if out is None:
+            res[nm] = torch.empty(shape, dtype=dt, device=dev)
+            continue
+        t = out[nm]
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: out[{nm!r}] must be a contiguous {dt} {shape} tensor on {dev}")
+        res[nm] = t
+    lib = _lib.load()
+    p = TrainNoiseParams()
+    p.moments = None if moments is None else moments.data_ptr()
+    p.latents_in = None if latents is None else latents.data_ptr()
+    p.sqrt_table, p.seeds_dev = sqrt_table.data_ptr(), sd.data_ptr()
+    p.draw_dev = None if draw_dev is None else draw_dev.data_ptr()
+    p.noisy, p.target, p.timesteps = res["noisy_latents"].data_ptr(), res["target"].data_ptr(), res["timesteps"].data_ptr()
+    p.latents_out = res["latents"].data_ptr() if want_latents else None
+    p.noise_out = res["noise"].data_ptr() if want_noise else None
+    p.draw, p.B, p.h, p.w, p.T, p.prediction = draw, B, h, w, int(sqrt_table.shape[0]), preds[prediction_type]
+    p.scale, p.noise_offset, p.input_perturbation = float(scale), float(noise_offset), float(input_perturbation)
+    _lib.check(lib.aptp_train_noise(ctypes.byref(p), _stream()), "aptp_train_noise")
+    return res
 
 
 # ------------------------------------------------------------------------------------------------------------------

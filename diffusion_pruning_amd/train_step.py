@@ -56,6 +56,20 @@ class NoiseSchedule:
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012):
         betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
         self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)
+        self._sqrt_tables: Dict[torch.device, torch.Tensor] = {}
+
+    def sqrt_table(self, device=None) -> torch.Tensor:
+        """fp32 [T, 2] = (sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)), the rows ops.train_noise reads: computed by torch on the
+        CPU from the fp32 alphas_cumprod, whatever device asks -- the expressions noisy_latents_and_target evaluates there, so
+        every rank and every device of a run reads the same rows -- and cached per device"""
+        device = torch.device("cpu" if device is None else device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        cache = self._sqrt_tables
+        if device not in cache:
+            ac = self.alphas_cumprod.detach().to(device="cpu", dtype=torch.float32)
+            cache[device] = torch.stack([ac ** 0.5, (1 - ac) ** 0.5], 1).contiguous().to(device)
+        return cache[device]
 
 
 def gather_with_local_grad(*tensors: torch.Tensor) -> List[torch.Tensor]:
@@ -886,32 +900,77 @@ def router_embeddings(prompt_encoder, router_ids: torch.Tensor, router_attention
     return prompt_encoder.encode(router_ids, router_attention_mask)
 
 
+def _check_noise_knobs(what: str, schedule: NoiseSchedule, noise_offset, input_perturbation, max_scheduler_steps) -> int:
+    """the three reference knobs (model.unet.noise_offset / input_perturbation / max_scheduler_steps) -> T of the timestep draw"""
+    for name, v in (("noise_offset", noise_offset), ("input_perturbation", input_perturbation)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+            raise ValueError(f"{what}: {name} must be a finite number, got {v!r}")
+    T = int(schedule.alphas_cumprod.shape[0])
+    if max_scheduler_steps is None:
+        return T
+    if isinstance(max_scheduler_steps, bool) or not isinstance(max_scheduler_steps, int) or not 1 <= max_scheduler_steps <= T:
+        raise ValueError(f"{what}: max_scheduler_steps must be an int in 1..{T}, got {max_scheduler_steps!r}")
+    return max_scheduler_steps
+
+
 def batch_from_images(vae, pixel_values: torch.Tensor, encoder_hidden_states: torch.Tensor,
                       mpnet_embeddings: Optional[torch.Tensor] = None,
                       schedule: Optional[NoiseSchedule] = None, prediction_type: str = "v_prediction", generator=None, *,
                       router_ids: Optional[torch.Tensor] = None, router_attention_mask: Optional[torch.Tensor] = None,
-                      prompt_encoder=None):
+                      prompt_encoder=None, seeds=None, draw: int = 0, noise_offset: float = 0.0, input_perturbation: float = 0.0,
+                      max_scheduler_steps: Optional[int] = None):
     """A training batch (synthetic_batch's keys) from images, as the reference's training steps build it
     (trainer.py:1097-1122): latents = vae.encode(pixel_values).latent_dist.sample() * scaling_factor (vae.encode_latents, one
     pass on the HIP encoder), then noise and timesteps, drawn in that order from ``generator``, add_noise and the target.
     pixel_values: NCHW [B, 3, H, W] in [-1, 1] on the GPU; H and W multiples of 8.
     The router's input is either ``mpnet_embeddings`` [B, 768] or ``router_ids`` (+ ``router_attention_mask``), the MPNet token
-    ids, which ``prompt_encoder`` encodes (router_embeddings); exactly one of the two."""
+    ids, which ``prompt_encoder`` encodes (router_embeddings); exactly one of the two.
+    ``noise_offset``, ``input_perturbation`` and ``max_scheduler_steps`` are the reference's ``model.unet.*`` keys
+    (trainer.py:1100-1123): drawn from ``generator`` in its order -- noise, offset randn(B, C, 1, 1), perturbation randn_like,
+    randint(0, max_scheduler_steps) -- and, at their defaults, not at all.  The target is built from the noise with its offset,
+    the noisy latents from the perturbed noise.
+    With ``seeds`` (an int, B ints or a device int64 [B] tensor) and ``draw`` (an epoch or a global step in [0, 2^59)) nothing
+    comes from a generator: the encoder returns its moments and ONE launch (ops.train_noise) samples the posterior,
+    the noise and the timesteps, each sample's a pure function of (its seed, draw), whatever batch or rank it sits in."""
     if (mpnet_embeddings is None) == (router_ids is None):
         raise ValueError("give exactly one of mpnet_embeddings and router_ids")
     if router_ids is None and router_attention_mask is not None:
         raise ValueError("router_attention_mask needs router_ids")
+    schedule = schedule or NoiseSchedule()
+    T = _check_noise_knobs("batch_from_images", schedule, noise_offset, input_perturbation, max_scheduler_steps)
+    if prediction_type not in ("epsilon", "v_prediction"):
+        raise ValueError(f"unknown prediction_type {prediction_type!r}")
+    if seeds is not None:
+        from .data import check_train_draw
+        if generator is not None:
+            raise ValueError("batch_from_images: give seeds or a generator, not both")
+        check_train_draw(draw, "batch_from_images")
+    elif draw != 0:
+        raise ValueError("batch_from_images: draw needs seeds")
     if router_ids is not None:
         mpnet_embeddings = router_embeddings(prompt_encoder, router_ids, router_attention_mask)
+    if seeds is not None:
+        moments = vae.encode(pixel_values).latent_dist.parameters
+        out = ops.train_noise(moments, sqrt_table=schedule.sqrt_table(moments.device)[:T], seeds=seeds, draw=draw,
+                              scale=vae.config.scaling_factor, noise_offset=noise_offset, input_perturbation=input_perturbation,
+                              prediction_type=prediction_type)
+        return {"noisy_latents": out["noisy_latents"], "target": out["target"], "encoder_hidden_states": encoder_hidden_states,
+                "mpnet_embeddings": mpnet_embeddings, "timesteps": out["timesteps"]}
     from .vae import randn_tensor
-    schedule = schedule or NoiseSchedule()
     latents = vae.encode_latents(pixel_values, generator=generator)
     dev = latents.device
     noise = randn_tensor(latents.shape, generator=generator, device=dev, dtype=latents.dtype)
-    T = schedule.alphas_cumprod.shape[0]
+    if noise_offset:
+        noise = noise + noise_offset * randn_tensor((latents.shape[0], latents.shape[1], 1, 1), generator=generator, device=dev,
+                                                    dtype=latents.dtype)
+    new_noise = noise
+    if input_perturbation:
+        new_noise = noise + input_perturbation * randn_tensor(latents.shape, generator=generator, device=dev, dtype=latents.dtype)
     tdev = generator.device if generator is not None else dev
     timesteps = torch.randint(0, T, (latents.shape[0],), generator=generator, device=tdev).to(dev)
     noisy, target = noisy_latents_and_target(latents, noise, timesteps, schedule.alphas_cumprod, prediction_type)
+    if input_perturbation:
+        noisy, _ = noisy_latents_and_target(latents, new_noise, timesteps, schedule.alphas_cumprod, "epsilon")
     return {"noisy_latents": noisy, "target": target, "encoder_hidden_states": encoder_hidden_states,
             "mpnet_embeddings": mpnet_embeddings, "timesteps": timesteps}
 
@@ -921,25 +980,85 @@ def batch_from_uint8(vae, images, *, resolution: int, center_crop: bool = False,
                      encoder_hidden_states: Optional[torch.Tensor] = None, mpnet_embeddings: Optional[torch.Tensor] = None,
                      schedule: Optional[NoiseSchedule] = None, prediction_type: str = "v_prediction", generator=None,
                      router_ids: Optional[torch.Tensor] = None, router_attention_mask: Optional[torch.Tensor] = None,
-                     prompt_encoder=None):
+                     prompt_encoder=None, seeds=None, draw: int = 0, noise_offset: float = 0.0, input_perturbation: float = 0.0,
+                     max_scheduler_steps: Optional[int] = None):
     """batch_from_images from raw inputs: ``images`` is a list of decoded uint8 [H, W, 3] tensors of any sizes, which the
     dataloader's transform (data.TrainTransform: bilinear Resize(resolution), RandomCrop or CenterCrop, RandomHorizontalFlip,
     ToTensor, Normalize(0.5, 0.5); its draws from ``transform_generator``, a CPU generator) turns into pixel_values on the GPU;
     the cross-attention input is either ``encoder_hidden_states`` or ``prompt_ids``, the CLIP token ids [B, 77], which
     ``text_encoder`` (text_encoder.CLIPTextModel) encodes as the reference's steps do (trainer.py:1097-1126:
-    ``text_encoder(ids)[0]``); exactly one of the two.  Everything else is batch_from_images' and goes to it unchanged."""
+    ``text_encoder(ids)[0]``); exactly one of the two.  Everything else is batch_from_images' and goes to it unchanged; with
+    ``seeds`` the crop and the flip of each image come from its seed too (data.draw_crop_flip_seeded), and neither generator is
+    taken."""
     if (prompt_ids is None) == (encoder_hidden_states is None):
         raise ValueError("give exactly one of prompt_ids and encoder_hidden_states")
     if prompt_ids is not None and text_encoder is None:
         raise ValueError("prompt_ids need a text_encoder (diffusion_pruning_amd.text_encoder.CLIPTextModel)")
+    if seeds is not None and (transform_generator is not None or generator is not None):
+        raise ValueError("batch_from_uint8: give seeds or generators, not both")
     from .data import TrainTransform
     transform = TrainTransform(resolution, center_crop=center_crop, random_flip=random_flip)
-    transform.resized_sizes(images)                            # the images are checked before anything runs
+    sizes = transform.resized_sizes(images)                    # the images are checked before anything runs
+    if seeds is not None:
+        from .data import seed_list, check_train_draw
+        check_train_draw(draw, "batch_from_uint8")
+        seed_list(seeds, len(sizes), "batch_from_uint8")      # and so are the seeds
+    elif draw != 0:
+        raise ValueError("batch_from_uint8: draw needs seeds")
     if prompt_ids is not None:
         encoder_hidden_states = text_encoder(prompt_ids)[0]
-    pixel_values = transform(images, generator=transform_generator)
+    pixel_values = transform(images, generator=transform_generator, seeds=seeds, draw=draw)
     return batch_from_images(vae, pixel_values, encoder_hidden_states, mpnet_embeddings, schedule, prediction_type, generator,
-                             router_ids=router_ids, router_attention_mask=router_attention_mask, prompt_encoder=prompt_encoder)
+                             router_ids=router_ids, router_attention_mask=router_attention_mask, prompt_encoder=prompt_encoder,
+                             seeds=seeds, draw=draw, noise_offset=noise_offset, input_perturbation=input_perturbation,
+                             max_scheduler_steps=max_scheduler_steps)
+
+
+class SeededBatchBuilder:
+    """The seeded batch assembly as a captured step would embed it: static ``seeds`` int64 [B], ``draw`` int64 [1] and output
+    buffers on the device, ``build(moments)`` ONE launch (ops.train_noise) into them with no host value but the constructor's, and
+    ``set(seeds, draw)`` two copies into the static tensors -- so a captured ``build`` follows them from replay to replay.
+    ``latent_shape`` is (4, h, w); ``scale`` the VAE's scaling_factor; the other knobs are batch_from_images'."""
+
+    def __init__(self, schedule: Optional[NoiseSchedule], batch: int, latent_shape, device, prediction_type: str = "v_prediction",
+                 noise_offset: float = 0.0, input_perturbation: float = 0.0, scale: float = 1.0,
+                 max_scheduler_steps: Optional[int] = None):
+        schedule = schedule or NoiseSchedule()
+        T = _check_noise_knobs("SeededBatchBuilder", schedule, noise_offset, input_perturbation, max_scheduler_steps)
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"unknown prediction_type {prediction_type!r}")
+        shape = tuple(int(v) for v in latent_shape)
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1 or len(shape) != 3 or shape[0] != 4 or min(shape) < 1:
+            raise ValueError(f"SeededBatchBuilder: batch >= 1 and latent_shape (4, h, w), got {batch!r} and {latent_shape!r}")
+        device = torch.device(device)
+        self.batch, self.latent_shape, self.prediction_type = batch, shape, prediction_type
+        self.noise_offset, self.input_perturbation, self.scale = float(noise_offset), float(input_perturbation), float(scale)
+        self.sqrt_table = schedule.sqrt_table(device)[:T]
+        self.seeds = torch.zeros(batch, dtype=torch.int64, device=device)
+        self.draw = torch.zeros(1, dtype=torch.int64, device=device)
+        self.out = {"noisy_latents": torch.empty((batch,) + shape, dtype=torch.float32, device=device),
+                    "target": torch.empty((batch,) + shape, dtype=torch.float32, device=device),
+                    "timesteps": torch.empty(batch, dtype=torch.int64, device=device)}
+
+    def set(self, seeds, draw: int):
+        """new seeds (an int, B ints or an int64 [B] tensor) and a new draw, copied into the static tensors on the current stream"""
+        from .data import seed_list, check_train_draw
+        check_train_draw(draw, "SeededBatchBuilder.set")
+        if isinstance(seeds, torch.Tensor):
+            if seeds.dtype != torch.int64 or tuple(seeds.shape) != (self.batch,):
+                raise ValueError(f"SeededBatchBuilder.set: a seeds tensor must be int64 [{self.batch}]")
+            self.seeds.copy_(seeds, non_blocking=True)
+        else:
+            vals = seed_list(seeds, self.batch, "SeededBatchBuilder.set")
+            self.seeds.copy_(torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in vals], dtype=torch.int64))
+        self.draw.copy_(torch.tensor([draw], dtype=torch.int64))
+        return self
+
+    def build(self, moments: torch.Tensor) -> dict:
+        """moments fp32 [B, 8, h, w] -> the static {"noisy_latents", "target", "timesteps"}"""
+        return ops.train_noise(moments, sqrt_table=self.sqrt_table, seeds=self.seeds, draw=0, draw_dev=self.draw, scale=self.scale,
+                               noise_offset=self.noise_offset, input_perturbation=self.input_perturbation,
+                               prediction_type=self.prediction_type, out=self.out)
 
 
 @dataclass

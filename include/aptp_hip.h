@@ -1038,6 +1038,44 @@ typedef struct {
 } AptpPhiloxNormalParams;
 int aptp_philox_normal(const AptpPhiloxNormalParams* p, aptp_stream_t stream);
 
+/* A seeded training batch in one launch (csrc/train_noise.hip, the draw map and the arithmetic in csrc/train_noise.h): VAE moments
+ * (or latents) and per-sample seeds -> noisy latents, target and timesteps, every value a pure function of (seed of the sample,
+ * draw, element) on the stream of aptp_philox_normal.  With d = draw + draw_dev[0] (draw_dev may be null), sub-draw k is Philox
+ * draw 8 d + k of seeds_dev[r]:  k = 1 posterior eps, 2 noise, 4 input perturbation (element e = c hw + y w + x of the sample's
+ * [4, h, w]), 3 offset noise (element c), 5 timestep (word x0 of block 0: t = (x0 T) >> 32 in uint64); k = 0 is the host's crop
+ * and flip.  In fp32, every product and sum rounded on its own, (sa, so) = sqrt_table[t]:
+ *   x0     = scale fmaf(expf(0.5f clamp(logvar, -30, 20)), z1, mean)   (moments fp32 [B, 8, h, w], mean then logvar; the one
+ *            fused multiply-add, as aptp_latent_dist's compiled statement has it: the same bits for the same eps)
+ *          | latents_in                                            (fp32 [B, 4, h, w]);  exactly one of the two
+ *   n      = z2 + noise_offset z3[c]         (z3 not drawn when noise_offset == 0)
+ *   m      = n + input_perturbation z4       (z4 not drawn when input_perturbation == 0)
+ *   noisy  = sa x0 + so m;   target = n (APTP_TRAIN_NOISE_EPSILON) | sa n - so x0 (APTP_TRAIN_NOISE_V_PREDICTION)
+ * sqrt_table is fp32 [T, 2] = sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod).  Outputs: noisy, target fp32 [B, 4, h, w],
+ * timesteps int64 [B], optionally latents_out (x0) and noise_out (n).  seeds_dev and draw_dev are DEVICE memory, read by the
+ * kernel, so a captured launch follows a device counter; the caller keeps d inside [0, 2^59).  A lane owns four elements of one
+ * channel when h w % 4 == 0 and every tensor is 16-byte aligned, a single element otherwise, with the same bits.  APTP_EINVAL
+ * and nothing launched (no host synchronisation) for: null required pointers, both or neither of moments and latents_in, B
+ * outside 1..65535, h w < 1, T < 1, draw outside [0, 2^59), misaligned 4- or 8-byte pointers, an unknown prediction. */
+#define APTP_TRAIN_NOISE_EPSILON 0
+#define APTP_TRAIN_NOISE_V_PREDICTION 1
+typedef struct {
+  const float* moments;
+  const float* latents_in;
+  const float* sqrt_table;
+  const int64_t* seeds_dev;
+  const int64_t* draw_dev;
+  float* noisy;
+  float* target;
+  int64_t* timesteps;
+  float* latents_out;
+  float* noise_out;
+  int64_t draw;
+  int32_t B, h, w, T;
+  int32_t prediction;
+  float scale, noise_offset, input_perturbation;
+} AptpTrainNoiseParams;
+int aptp_train_noise(const AptpTrainNoiseParams* p, aptp_stream_t stream);
+
 const char* aptp_last_error(void);
 int aptp_version(void);
 

@@ -5,7 +5,11 @@ transform with the images already on the device and with the images in host memo
 batch inside the timed call), encode_latents on the result, and, where PIL imports, the wall time a single-thread PIL + numpy
 loop takes for the same batch and the same draws on this host (Image.resize BILINEAR, crop, flip, / 255, Normalize).  Device
 times are medians of HIP-event timings after warm-up.  Prints ONE JSON line; --out also writes it to a file.
-usage: python tools/bench_train_input.py [--iters 20] [--out profiles/train_input_bench.json]"""
+--seeds adds the seeded path to the same line: the same batch through batch_from_uint8 with a generator and with
+seeds=, and the noise stage on its own -- everything after the encoder: the posterior eps, the noise, the timesteps, add_noise
+and the target, about a dozen torch launches from a generator against ONE ops.train_noise launch from seeds.  The variants run
+interleaved, round by round, in this one process; reported are the median and the minimum of the rounds.
+usage: python tools/bench_train_input.py [--iters 20] [--seeds] [--out profiles/train_input_bench.json]"""
 import argparse
 import json
 import os
@@ -43,6 +47,71 @@ def time_events(fn, iters, warmup=3):
     return ts[len(ts) // 2]
 
 
+def time_interleaved(variants, rounds, warmup=3):
+    """{name: fn} -> {name: (median ms, min ms)}: one HIP-event timing of every variant per round, round after round"""
+    for _ in range(warmup):
+        for fn in variants.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[k].append(a.elapsed_time(b))
+    return {k: (sorted(v)[len(v) // 2], min(v)) for k, v in ts.items()}
+
+
+def seeded_figures(res, vae, on_dev, px, dev, iters):
+    """the generator path and the seeded path side by side: the noise stage alone, then the whole batch_from_uint8"""
+    from diffusion_pruning_amd.train_step import NoiseSchedule, batch_from_uint8, noisy_latents_and_target
+    from diffusion_pruning_amd.vae import randn_tensor
+    sch = NoiseSchedule()
+    seeds = list(range(1000, 1000 + BATCH))
+    seeds_dev = torch.tensor(seeds, dtype=torch.int64, device=dev)
+    mom = vae.encode(px).latent_dist.parameters
+    lat = vae.encode_latents(px)
+    tab = sch.sqrt_table(dev)
+    scale = vae.config.scaling_factor
+    shape = tuple(lat.shape)
+
+    def from_generator(g):
+        def fn():
+            randn_tensor(shape, generator=g, device=dev, dtype=torch.float32)                 # the posterior's eps
+            noise = randn_tensor(shape, generator=g, device=dev, dtype=torch.float32)
+            t = torch.randint(0, 1000, (BATCH,), generator=g, device=g.device if g is not None else dev).to(dev)
+            return noisy_latents_and_target(lat, noise, t, sch.alphas_cumprod)
+        return fn
+
+    step = [0]
+
+    def seeded(sd):
+        def fn():
+            step[0] += 1
+            return ops.train_noise(mom, sqrt_table=tab, seeds=sd, draw=step[0], scale=scale)
+        return fn
+
+    stage = time_interleaved({"generator_device": from_generator(None), "generator_cpu": from_generator(torch.Generator().manual_seed(2)),
+                              "seeded_host_seeds": seeded(seeds), "seeded_device_seeds": seeded(seeds_dev)}, iters)
+    for k, (med, lo) in stage.items():
+        res[f"noise_stage_ms_{k}"] = round(med, 4)
+        res[f"noise_stage_min_ms_{k}"] = round(lo, 4)
+    res["noise_stage_generator_device_over_seeded"] = round(stage["generator_device"][0] / stage["seeded_device_seeds"][0], 2)
+    ehs = torch.zeros(BATCH, 77, 8, device=dev)
+    mp = torch.zeros(BATCH, 768, device=dev)
+    kw = dict(resolution=R, encoder_hidden_states=ehs, mpnet_embeddings=mp, schedule=sch)
+    gt = torch.Generator().manual_seed(3)
+    whole = time_interleaved({"generator": lambda: batch_from_uint8(vae, on_dev, transform_generator=gt, **kw),
+                              "seeded": lambda: batch_from_uint8(vae, on_dev, seeds=seeds, draw=step[0], **kw)},
+                             max(3, iters // 4), warmup=2)
+    for k, (med, lo) in whole.items():
+        res[f"batch_from_uint8_ms_{k}"] = round(med, 3)
+        res[f"batch_from_uint8_min_ms_{k}"] = round(lo, 3)
+
+
 def pil_loop(images, tops, lefts, flips):
     from PIL import Image
     out = np.empty((len(images), 3, R, R), np.float32)
@@ -59,6 +128,7 @@ def pil_loop(images, tops, lefts, flips):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--seeds", action="store_true", help="add the seeded path and the noise stage, beside the generator path")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -85,6 +155,8 @@ def main():
     res["transform_share_of_transform_plus_encode"] = round(
         res["transform_ms_images_on_device"] / (res["transform_ms_images_on_device"] + res["encode_latents_ms"]), 4)
     res["images_per_s_transform"] = round(BATCH / (res["transform_ms_images_on_device"] * 1e-3), 1)
+    if a.seeds:
+        seeded_figures(res, vae, on_dev, px, dev, a.iters)
     try:
         import PIL
     except ImportError:
