@@ -3,6 +3,11 @@
 Tolerances (bf16 operands, fp32 accumulate): relative L2 error <= 4e-3 per op against an fp32
 reference evaluated on the SAME bf16-rounded inputs (so only accumulation order and the bf16 output rounding
 differ), max-abs error bounded by a few bf16 ulps of the output scale.
+
+That whole-tensor figure is a coarse net: the bf16 store alone uses 1.65e-3 of it, and a truncating store or a tile that loses
+one K-step of a long contraction stay below it.  ELEMENTWISE and per-tile accuracy of the contraction kernels is asserted in
+tests/test_gemm_parity_gpu.py (fp64 reference, hard bound and bf16 format model of tests/gemm_model.py); the assertions here
+stay as they are.
 """
 import math
 
