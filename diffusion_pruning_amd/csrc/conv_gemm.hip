@@ -376,9 +376,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
   }
   set_tap(l_cc);
 
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr;
-
   auto issue_tile = [&](int buf) {
     const bool seg2 = l_ky >= p.KH;                                 // wave-uniform
     const bool last_cc = l_cc == (seg2 ? p.ncc2 : p.ncc) - 1;
@@ -408,13 +405,10 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
   };
 
   f32x4 acc[MF][NF];
-#pragma unroll
-  for (int i = 0; i < MF; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int frow = lane & 15, fq = lane >> 4;
-  auto compute = [&](int buf) {
+  auto compute = [&](int buf) {           // (local on purpose: see the note on the MFMA block in conv_gemm_kloop.h)
 #pragma unroll
     for (int s0 = 0; s0 < 2 / KS; ++s0) {
       const int s = KS == 2 ? ks : s0;          // 32-wide half of the K-tile
@@ -443,124 +437,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
   float ln_mean[MF], ln_rstd[MF];
 #pragma unroll
   for (int i = 0; i < MF; ++i) { ln_mean[i] = 0.f; ln_rstd[i] = 1.f; }
-  if constexpr (PP) {
-    // Ping-pong schedule (8 waves = two groups of four; waves w and w+4 share a SIMD).  Every K-step is two slots
-    // separated by workgroup barriers: in slot L a wave issues its share of the LDS-DMA for tile k+D, in slot C it
-    // reads the fragments of tile k from LDS and runs the MFMAs.  Group 1 runs one slot behind group 0, so on every
-    // SIMD one wave drives the matrix pipe (and the LDS read port) while the other drives the load path.  In the
-    // lockstep loops the three engines take turns (in-kernel stamps, 128x160 tile: DMA issue 490-550, LDS reads + MFMA
-    // 470-525, waits 400-550 cycles per K-step).
-    //   RAW: a wave waits for its own DMA rows of tile k+1 at the end of C(k); group 0 reads tile k+1 two barriers
-    //        later, group 1 three.
-    //   WAR: tile k+D lands in the stage of tile k+D-S = k-2 (S = D+2), last read by group 1 in its C(k-2), which ends
-    //        one barrier before group 0's L(k) starts.  (S = D+1 would let group 0's DMA overwrite the stage group 1 is
-    //        still reading in the same slot.)
-    static_assert(NWA == 8 && KS == 1 && STAGES >= 3, "ping-pong needs 8 waves and a ring of >= 3 stages");
-    static_assert(BM % RPP == 0, "ring: the activation tile must be whole row passes");
-    constexpr int D = STAGES - 2;
-    constexpr int A_FULL = BM / RPP, B_FULL = BN / RPP;
-    constexpr int NLD_LO = A_FULL + B_FULL, NLD_HI = A_PASS + B_PASS;
-    static_assert(NLD_HI * (D - 1) <= 63, "vmcnt immediate");
-    const bool hi = (NLD_HI != NLD_LO) && (wave * 8 + RPP * (B_PASS - 1) < BN);   // wave-uniform
-    const int grp = wave >> 2;
-    const int n = kt_end - kt_begin;
-    if (n > 0) {
-      const int pre = n < D ? n : D;
-      for (int t = 0; t < pre; ++t) issue_tile(t);
-      ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
-      if (pre == D) {
-        if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 1)) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (grp == 1) {                       // stagger: group 1 starts one slot late
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-      int cur = 0, nxt = D % STAGES;
-      for (int kt = 0; kt < n; ++kt) {
-        // ---- slot L(kt): the load path ----
-        const bool issue = kt + D < n;
-        if (issue) issue_tile(nxt);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");
-        // ---- slot C(kt): LDS reads + MFMAs ----
-        __builtin_amdgcn_s_setprio(1);
-        compute(cur);
-        __builtin_amdgcn_s_setprio(0);
-        asm volatile("" ::: "memory");
-        if (issue) {
-          if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
-          else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 1)) : "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");
-        cur = cur + 1 == STAGES ? 0 : cur + 1;
-        nxt = nxt + 1 == STAGES ? 0 : nxt + 1;
-      }
-      if (grp == 0) {                       // group 0 pairs group 1's last barrier
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-    }
-  } else
-  if constexpr (KU == 2) {
-    // Two K-tiles per synchronisation point (an effective K-step of 128): iteration i issues tiles 2i+D and 2i+D+1 into the
-    // two stages read in iteration i-1, runs the MFMAs of tiles 2i and 2i+1, waits until tiles 2i+2 and 2i+3 have landed
-    // (D-2 newer tiles stay in flight) and meets ONE barrier: half the s_waitcnt / s_barrier stops of the ring above.
-    static_assert(STAGES >= 4 && STAGES % 2 == 0, "pairs of stages");
-    constexpr int D = STAGES - 2;
-    constexpr int A_FULL = BM / RPP, B_FULL = BN / RPP;
-    constexpr int NLD_LO = A_FULL + B_FULL, NLD_HI = A_PASS + B_PASS;
-    static_assert(BM % RPP == 0, "ring: the activation tile must be whole row passes");
-    static_assert(NLD_HI * (D - 2) <= 63, "vmcnt immediate");
-    const bool hi = (NLD_HI != NLD_LO) && (wave * 8 + RPP * (B_PASS - 1) < BN);   // wave-uniform
-    const int n = kt_end - kt_begin;
-    if (n > 0) {
-      const int pre = n < D ? n : D;
-      for (int t = 0; t < pre; ++t) issue_tile(t);
-      ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
-      if (pre == D && D > 2) {   // tiles 0 and 1 landed, D-2 tiles still in flight
-        if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 2)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 2)) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      int cur = 0, nxt = D;
-      for (int kt = 0; kt < n; kt += 2) {
-        const int ni = n - (kt + D);          // tiles left to request: two per iteration while >= 2
-        if (ni >= 1) issue_tile(nxt);
-        if (ni >= 2) issue_tile(nxt + 1);
-        compute(cur);
-        if (kt + 1 < n) compute(cur + 1);
-        asm volatile("" ::: "memory");
-        if (ni >= 2 && D > 2) {
-          if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 2)) : "memory");
-          else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 2)) : "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (D == 2: plain double buffering of 128-wide steps) / tail
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        cur = cur + 2 == STAGES ? 0 : cur + 2;
-        nxt = nxt + 2 == STAGES ? 0 : nxt + 2;
-      }
-    }
-  } else
-  if constexpr (STAGES == 2) {
+  if constexpr (STAGES == 2 && !PP && KU == 1) {
     if (kt_begin < kt_end) {
       issue_tile(0);
       ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
@@ -574,49 +451,28 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
       }
     }
   } else {
-    // STAGES-deep ring, D = STAGES-1 tiles of LDS-DMA in flight across the barriers (counted vmcnt, raw s_barrier): the
-    // operand round trip (~1-2k cycles) is several K-steps long at these tile sizes, so one tile ahead is not enough.
-    //   iteration kt: issue tile kt+D into stage (kt+D)%S == (kt-1)%S (last read before the previous barrier),
-    //                 compute stage kt%S, wait until tile kt+1 has landed (D-1 newer tiles stay in flight), barrier.
+    // Ring schedules of conv_gemm_kloop.h: plain ring, two K-tiles per barrier (KU == 2) or 8-wave ping-pong (PP), D tiles of
+    // LDS-DMA in flight ahead of the one being multiplied, DW of them still in flight at a wait of the loop.
     // Waves may issue different numbers of DMAs per tile (partial last row pass): each waits on its own count.
-    constexpr int D = STAGES - 1;
+    constexpr int D = (PP || KU == 2) ? STAGES - 2 : STAGES - 1;
+    constexpr int DW = KU == 2 ? D - 2 : D - 1;
     constexpr int A_FULL = BM / RPP, B_FULL = BN / RPP;            // passes every wave takes part in
-    constexpr int NLD_LO = A_FULL + B_FULL;
-    constexpr int NLD_HI = A_PASS + B_PASS;
+    constexpr int NLD_LO = A_FULL + B_FULL, NLD_HI = A_PASS + B_PASS;
     static_assert(BM % RPP == 0, "ring: the activation tile must be whole row passes");
-    static_assert(NLD_HI * (D - 1) <= 63, "vmcnt immediate");
+    static_assert(!PP || (NWA == 8 && KS == 1 && KU == 1), "ping-pong needs 8 waves");
     const bool hi = (NLD_HI != NLD_LO) && (wave * 8 + RPP * (B_PASS - 1) < BN);   // wave-uniform
+    auto wait_ring = [&](bool full) { ring_wait<NLD_LO, NLD_HI, DW>(hi, full); };
     const int n = kt_end - kt_begin;
     if (n > 0) {
       const int pre = n < D ? n : D;
       for (int t = 0; t < pre; ++t) issue_tile(t);
       ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
-      if (pre == D) {   // tile 0 landed, D-1 tiles still in flight
-        if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 1)) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
+      wait_ring(pre == D);       // the first step's tile(s) landed, DW tiles still in flight
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      int cur = 0, nxt = D;          // stage of tile kt, stage of tile kt+D
-      for (int kt = 0; kt < n; ++kt) {
-        const bool issue = kt + D < n;
-        if (issue) issue_tile(nxt);
-        compute(cur);
-        asm volatile("" ::: "memory");
-        if (issue) {
-          if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
-          else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 1)) : "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // tail: everything still in flight is needed soon
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // this wave's LDS reads of `cur` are done
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        cur = cur + 1 == STAGES ? 0 : cur + 1;
-        nxt = nxt + 1 == STAGES ? 0 : nxt + 1;
-      }
+      if constexpr (PP) kloop_pp<STAGES, D>(n, wave >> 2, issue_tile, compute, wait_ring);
+      else if constexpr (KU == 2) kloop_ku2<STAGES, D>(n, issue_tile, compute, wait_ring);
+      else kloop_ring<STAGES, D>(n, issue_tile, compute, wait_ring);
     }
   }
 
@@ -642,19 +498,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64) void conv_gemm_dma_kernel(const 
     ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd, true);
   } else
   if (p.split_k > 1) {
-    float* ws = p.ws + (int64_t)kz * p.M * p.ws_ld;
-#pragma unroll
-    for (int i = 0; i < MF; ++i) {
-      const int m = m0 + wm * WTM + i * 16 + frow;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int j = 0; j < NF; ++j) {
-        const int n = n0 + wn * WTN + j * 16 + fq * 4;
-        if (n >= p.N) continue;
-        float4 o; o.x = acc[i][j][0]; o.y = acc[i][j][1]; o.z = acc[i][j][2]; o.w = acc[i][j][3];
-        *reinterpret_cast<float4*>(ws + (int64_t)m * p.ws_ld + n) = o;
-      }
-    }
+    store_splitk_slab(p, acc, kz, m0 + wm * WTM, n0 + wn * WTN, frow, fq);
     return;
   }
   static_assert(NW * 16 * (WTN + 4) * 4 <= (int)sizeof(smem), "epilogue transpose buffer");
@@ -719,8 +563,6 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const KParams p) {
     const unsigned off = ((unsigned)((b_img * p.Hin + iy) * p.Win + ix) * (unsigned)p.ldx) * 2u;   // < 2^31
     p_ptr[i] = ok ? reinterpret_cast<const char*>(p.x) + off + schunk * 16 : nullptr;
   }
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr;
   auto issue_patch = [&](int cc, int pbuf) {
     const bool bad = tail_bad && cc == p.ncc - 1;
 #pragma unroll
@@ -754,10 +596,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const KParams p) {
   };
 
   f32x4 acc[MF][NF];
-#pragma unroll
-  for (int i = 0; i < MF; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int frow = lane & 15, fq = lane >> 4;
   int prow0[MF];                                   // patch row of this lane's output pixel at tap (0, 0)
@@ -827,12 +666,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const KParams p) {
     const int pre = n < D ? n : D;
     for (int t = 0; t < pre; ++t) issue_w(kt_begin + t, t);
     ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd);
-    if (pre == D) {
-      if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * (D - 1)) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * (D - 1)) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    ring_wait<NLD_LO, NLD_HI, D - 1>(hi, pre == D);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     int cur = 0, nxt = D % STAGES;
@@ -863,19 +697,7 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const KParams p) {
     ln_rows_finish<MF>(p, lane, ln_raw, ln_mean, ln_rstd, true);
   } else
   if (p.split_k > 1) {
-    float* ws = p.ws + (int64_t)kz * p.M * p.ws_ld;
-#pragma unroll
-    for (int i = 0; i < MF; ++i) {
-      const int m = m0 + wm * WTM + i * 16 + frow;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int j = 0; j < NF; ++j) {
-        const int nn = n0 + wn * WTN + j * 16 + fq * 4;
-        if (nn >= p.N) continue;
-        float4 o; o.x = acc[i][j][0]; o.y = acc[i][j][1]; o.z = acc[i][j][2]; o.w = acc[i][j][3];
-        *reinterpret_cast<float4*>(ws + (int64_t)m * p.ws_ld + nn) = o;
-      }
-    }
+    store_splitk_slab(p, acc, kz, m0 + wm * WTM, n0 + wn * WTN, frow, fq);
     return;
   }
   static_assert(NW * 16 * (WTN + 4) * 4 <= (int)sizeof(smem), "epilogue transpose buffer");

@@ -1,6 +1,7 @@
 // Shared core of the implicit-GEMM kernels (conv_gemm.hip, conv_gemm_sk.hip): launch parameters, the XCD-aware
 // workgroup -> tile order, the fused epilogues (accumulator-layout and coalesced), folded-LayerNorm row statistics and
-// the in-kernel split-K combine.  Device code only; every function is inlined into the kernels of the including file.
+// the in-kernel split-K combine; conv_gemm_kloop.h (included at the end) adds the K loop shared by the LDS-DMA kernels.
+// Device code only; every function is inlined into the kernels of the including file.
 #pragma once
 #include "aptp_common.h"
 
@@ -892,3 +893,5 @@ bool aptp_conv_lean_eligible(const KParams& k, int tile);
 int aptp_launch_conv_lean(const KParams& k, int tile, hipStream_t s);
 
 }  // namespace aptp_cg
+
+#include "conv_gemm_kloop.h"      // the K loop the LDS-DMA kernels share: MFMA block, counted wait, ring schedules

@@ -24,9 +24,6 @@
 namespace {
 using namespace aptp_cg;
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* gbl_ptr;
-
 constexpr unsigned ZERO_OFF = 0x80000000u;   // past every operand's extent (< 2^31 bytes, checked on the host): reads zeros
 constexpr int NTAB = 10;                     // 9 filter taps + the x2 entry
 
@@ -63,16 +60,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_lean_kernel(const KParams p
   const int kt_begin = p.fd_sk.div(p.nK * kz);
   const int kt_end = p.fd_sk.div(p.nK * (kz + 1));
 
-  // ---- next launch's weights towards this XCD's L2: requested FIRST (see lin_gemm.hip: an LDS-DMA into pf_scratch issued after
-  // the operand stages makes the compiler's wait-count pass put a vmcnt(0) in front of the loop's fragment reads) ----
-  if (p.pf_ptr) {
-    const int xcd = blockIdx.x & 7;
-    const int x0 = (int)(((int64_t)p.pf_lines * xcd) >> 3), x1 = (int)(((int64_t)p.pf_lines * (xcd + 1)) >> 3);
-    const int l0 = x0 + (int)(blockIdx.x >> 3) * p.pf_per;
-    const int l1 = l0 + p.pf_per < x1 ? l0 + p.pf_per : x1;
-    for (int l = l0 + tid; l < l1; l += NT)
-      __builtin_amdgcn_global_load_lds((gbl_ptr)(p.pf_ptr + (int64_t)l * 64), (lds_ptr)pf_scratch, 4, 0, 0);
-  }
+  // ---- next launch's weights towards this XCD's L2: requested FIRST, ahead of the operand stages (see prefetch_hosted) ----
+  prefetch_hosted(p, tid, NT, pf_scratch);
 
   // ---- tap table: byte offset of every tap of this lane's staged rows (source chunk schunk already included) ----
   const int rowbase = tid >> 3;
@@ -161,12 +150,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_lean_kernel(const KParams p
   };
 
   f32x4 acc[MF][NF];
-#pragma unroll
-  for (int i = 0; i < MF; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int frow = lane & 15, fq = lane >> 4;
-  auto compute = [&](int stage) {
+  auto compute = [&](int stage) {         // (local on purpose: see the note on the MFMA block in conv_gemm_kloop.h)
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       bf16x8 af[MF], wf[NF];
@@ -190,18 +176,11 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_lean_kernel(const KParams p
   // ---- prologue: the first D stages, then the epilogue's inputs (un-split launches; a split's combining workgroup asks later) ----
   constexpr int D = PP ? STAGES - 2 : (KU == 2 ? STAGES - 2 : STAGES - 1);
   constexpr int DW = KU == 2 ? D - 2 : D - 1;                      // tiles still in flight at a wait of the loop
-  static_assert(STAGES >= 2 && D >= 1 && DW >= 0 && NLD_HI * DW <= 63, "ring");
-  static_assert(!PP || (NW == 8 && STAGES >= 3), "ping-pong: 8 waves, ring of >= 3 stages");
-  static_assert(KU == 1 || (!PP && STAGES >= 4 && STAGES % 2 == 0), "two K-tiles per barrier: pairs of stages");
+  static_assert(STAGES >= 2 && D >= 1, "ring");
+  static_assert(!PP || NW == 8, "ping-pong: 8 waves");
+  static_assert(KU == 1 || !PP, "two K-tiles per barrier: ring schedule only");
   const bool hi = (NLD_HI != NLD_LO) && (wave * 8 + RPP * (B_PASS - 1) < BN);   // wave-uniform: this wave takes the partial pass
-  auto wait_ring = [&](bool full) {       // tile(s) of the next step landed, DW newer tiles stay in flight
-    if (full && DW > 0) {
-      if (hi) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_HI * DW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD_LO * DW) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  };
+  auto wait_ring = [&](bool full) { ring_wait<NLD_LO, NLD_HI, DW>(hi, full); };
   const int n = kt_end - kt_begin;
   const int pre = n < D ? n : D;
   for (int t = 0; t < pre; ++t) issue_tile(t);
@@ -213,68 +192,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_lean_kernel(const KParams p
     wait_ring(pre == D);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    int cur_s = 0, nxt_s = D % STAGES;
-    if constexpr (PP) {
-      // ping-pong (conv_gemm_dma_kernel): group 1 runs one slot behind group 0; slot L issues the DMA, slot C reads + multiplies
-      const int grp = wave >> 2;
-      if (grp == 1) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-      for (int kt = 0; kt < n; ++kt) {
-        const bool issue = kt + D < n;
-        if (issue) issue_tile(nxt_s);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_setprio(1);
-        compute(cur_s);
-        __builtin_amdgcn_s_setprio(0);
-        asm volatile("" ::: "memory");
-        wait_ring(issue);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" ::: "memory");
-        cur_s = cur_s + 1 == STAGES ? 0 : cur_s + 1;
-        nxt_s = nxt_s + 1 == STAGES ? 0 : nxt_s + 1;
-      }
-      if (grp == 0) {
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-    } else if constexpr (KU == 2) {
-      for (int kt = 0; kt < n; kt += 2) {
-        const int ni = n - (kt + D);          // tiles left to request: two per iteration while >= 2
-        if (ni >= 1) issue_tile(nxt_s);
-        if (ni >= 2) issue_tile(nxt_s + 1);
-        compute(cur_s);
-        if (kt + 1 < n) compute(cur_s + 1);
-        asm volatile("" ::: "memory");
-        wait_ring(ni >= 2);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        cur_s = cur_s + 2 == STAGES ? 0 : cur_s + 2;
-        nxt_s = nxt_s + 2 == STAGES ? 0 : nxt_s + 2;
-      }
-    } else {
-      // STAGES-deep ring (STAGES == 2: double buffering), D = STAGES - 1 tiles in flight across the barriers
-      for (int kt = 0; kt < n; ++kt) {
-        const bool issue = kt + D < n;
-        if (issue) issue_tile(nxt_s);
-        compute(cur_s);
-        asm volatile("" ::: "memory");
-        wait_ring(issue);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        cur_s = cur_s + 1 == STAGES ? 0 : cur_s + 1;
-        nxt_s = nxt_s + 1 == STAGES ? 0 : nxt_s + 1;
-      }
-    }
+    if constexpr (PP) kloop_pp<STAGES, D>(n, wave >> 2, issue_tile, compute, wait_ring);
+    else if constexpr (KU == 2) kloop_ku2<STAGES, D>(n, issue_tile, compute, wait_ring);
+    else kloop_ring<STAGES, D>(n, issue_tile, compute, wait_ring);
   }
 
   // ---- split-K: slabs for the reduce launch, or the in-kernel combine ----
@@ -282,19 +202,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_lean_kernel(const KParams p
     if (!splitk_combine<NT, MF, NF>(p, acc, tm * tiles_n + tn, kz, tid, reinterpret_cast<int*>(smem))) return;
     lean_epi_load<WTM, WTN>(p, m0, n0, wm, wn, lane, ein);
   } else if (p.split_k > 1) {
-    float* ws = p.ws + (int64_t)kz * p.M * p.ws_ld;
-#pragma unroll
-    for (int i = 0; i < MF; ++i) {
-      const int m = m0 + wm * WTM + i * 16 + frow;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int j = 0; j < NF; ++j) {
-        const int nn = n0 + wn * WTN + j * 16 + fq * 4;
-        if (nn >= p.N) continue;
-        float4 o; o.x = acc[i][j][0]; o.y = acc[i][j][1]; o.z = acc[i][j][2]; o.w = acc[i][j][3];
-        *reinterpret_cast<float4*>(ws + (int64_t)m * p.ws_ld + nn) = o;
-      }
-    }
+    store_splitk_slab(p, acc, kz, m0 + wm * WTM, n0 + wn * WTN, frow, fq);
     return;
   }
   __syncthreads();                        // every wave is done reading the operand stages
@@ -304,15 +212,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_lean_kernel(const KParams p
 template <int BM, int BN, int WM, int WN, int STAGES, bool PP, int KU>
 void launch_lean(KParams k, hipStream_t s) {
   const int grid = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN) * k.split_k;
-  // next-launch prefetch: slice bounds on the host (lines of the xcd-th eighth per workgroup of that XCD, as in launch_lin)
-  k.pf_lines = 0; k.pf_per = 0;
-  if (k.pf_ptr) {
-    const int nper = (grid + 7) >> 3;
-    k.pf_lines = (int)(k.pf_bytes >> 6);
-    const int per_xcd = (k.pf_lines + 7) >> 3;
-    k.pf_per = (per_xcd + nper - 1) / nper;
-    if (k.pf_per < 1) k.pf_per = 1;
-  }
+  set_prefetch_slices(k, grid);
   hipLaunchKernelGGL((conv_lean_kernel<BM, BN, WM, WN, STAGES, PP, KU>), dim3(grid), dim3(WM * WN * 64), 0, s, k);
 }
 

@@ -27,9 +27,6 @@ using namespace aptp_cg;
 
 __device__ __attribute__((aligned(256))) unsigned char g_lin_zero_page[8192];
 
-typedef __attribute__((address_space(3))) void* lds_ptr;
-typedef const __attribute__((address_space(1))) void* gbl_ptr;
-
 // GELU: the fc1 + GELU launches of the CLIP text encoder get their own instantiation, so the code of every other launch is
 // the code it was before APTP_ACT_GELU existed; GELU == 2 is the QuickGELU instantiation of the CLIP image encoder's fc1
 template <int BM, int BN, int WM, int WN, int STAGES, int KU, bool GEGLU = false, int GELU = 0>
@@ -92,8 +89,10 @@ __global__ __launch_bounds__(WM * WN * 64) void lin_gemm_kernel(const KParams p)
     n = n < p.N ? n : p.N - 1;                                  // columns past N accumulate garbage that is never stored
     b_ptr[i] = reinterpret_cast<const char*>(p.w) + ((int64_t)n * p.Ktot + schunk * 8) * 2;
   }
-  auto issue_tile = [&](int t, int stage) {
-    const bool pad = (t == nk - 1) && tail_bad;
+  int l_kt = 0;                                                 // the NEXT K-tile to request
+  auto issue_tile = [&](int stage) {
+    const bool pad = (l_kt == nk - 1) && tail_bad;
+    ++l_kt;
 #pragma unroll
     for (int i = 0; i < A_PASS; ++i) {
       const char* src = pad ? zpage : a_ptr[i];
@@ -108,22 +107,13 @@ __global__ __launch_bounds__(WM * WN * 64) void lin_gemm_kernel(const KParams p)
       b_ptr[i] += BK * 2;
     }
   };
-  // next launch's weights towards this XCD's L2 (slice bounds from the host, launch_lin).  Requested BEFORE the operand tiles: an
-  // LDS-DMA into pf_scratch that is still pending when the K loop starts makes the compiler's wait-count pass put a vmcnt(0) in
-  // front of the loop's fragment reads (it cannot tell the scratch row from the operand stages), which serialises the ring.
-  if (p.pf_ptr) {
-    const int xcd = blockIdx.x & 7;
-    const int x0 = (int)(((int64_t)p.pf_lines * xcd) >> 3), x1 = (int)(((int64_t)p.pf_lines * (xcd + 1)) >> 3);
-    const int l0 = x0 + (int)(blockIdx.x >> 3) * p.pf_per;
-    const int l1 = l0 + p.pf_per < x1 ? l0 + p.pf_per : x1;
-    for (int l = l0 + tid; l < l1; l += NT)
-      __builtin_amdgcn_global_load_lds((gbl_ptr)(p.pf_ptr + (int64_t)l * 64), (lds_ptr)pf_scratch, 4, 0, 0);
-  }
+  // next launch's weights towards this XCD's L2: requested BEFORE the operand tiles (see prefetch_hosted)
+  prefetch_hosted(p, tid, NT, pf_scratch);
 
   const int pre = nk < D ? nk : D;
 #pragma unroll
   for (int t = 0; t < D; ++t)
-    if (t < pre) issue_tile(t, t);
+    if (t < pre) issue_tile(t);
 
   // ---- everything the epilogue will read, requested now (transposed domain: lane -> row lrow of a pass, columns c0 .. c0+7) ----
   const int lrow = lane / LPR, lc8 = lane - lrow * LPR;
@@ -210,12 +200,9 @@ __global__ __launch_bounds__(WM * WN * 64) void lin_gemm_kernel(const KParams p)
     }
   }
   f32x4 acc[MF][NF];
-#pragma unroll
-  for (int i = 0; i < MF; ++i)
-#pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int frow = lane & 15, fq = lane >> 4;
-  auto compute = [&](int stage) {
+  auto compute = [&](int stage) {         // (local on purpose: see the note on the MFMA block in conv_gemm_kloop.h)
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       bf16x8 af[MF], wf[NF];
@@ -237,38 +224,36 @@ __global__ __launch_bounds__(WM * WN * 64) void lin_gemm_kernel(const KParams p)
   };
 
   // ---- K loop: ring of STAGES stages, KU tiles per barrier, D tiles in flight ahead (counted vmcnt, raw s_barrier) ----
-  // Loads issued after the prologue tiles (residual, statistics, prefetch) only make a counted wait stricter for the older
-  // operand tiles, never weaker: vmcnt(X) completes all but the youngest X requests.
-  if (pre == D && D > KU) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD * (D - KU)) : "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // (every wave takes part in every row pass: one count, no `hi` waves)
+  auto wait_ring = [&](bool full) { ring_wait<NLD, NLD, D - KU>(false, full); };
+  wait_ring(pre == D);
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  {
+  if constexpr (KU == 1) {
+    kloop_ring<STAGES, D>(nk, issue_tile, compute, wait_ring);
+  } else {
+    // Not kloop_ku2: this loop multiplies two whole tiles per iteration and takes an odd last tile AFTER the loop, so its body
+    // has no conditional MFMA block (the accumulators stay put); kloop_ku2 keeps the convolutions' conditional second tile.
     int cur = 0, nxt = D;
-    const int nfull = nk / KU;                  // iterations that multiply KU whole tiles (KU == 2: an odd last tile follows the loop,
-    for (int it = 0; it < nfull; ++it) {        //  so the loop body has no conditional MFMA block -- the accumulators stay put)
-      const int kt = it * KU;
-#pragma unroll
-      for (int u = 0; u < KU; ++u)
-        if (kt + D + u < nk) issue_tile(kt + D + u, nxt + u);
+    for (int kt = 0; kt + 1 < nk; kt += 2) {
+      const int ni = nk - (kt + D);             // tiles left to request: two per iteration while >= 2
+      if (ni >= 1) issue_tile(nxt);
+      if (ni >= 2) issue_tile(nxt + 1);
       compute(cur);
-      if constexpr (KU == 2) compute(cur + 1);
+      compute(cur + 1);
       asm volatile("" ::: "memory");
-      if (kt + D + KU <= nk && D > KU) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD * (D - KU)) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // tail: everything still in flight is needed soon
+      wait_ring(ni >= 2);                       // tail: everything still in flight is needed soon
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // this wave's fragment reads are done
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      cur = cur + KU == STAGES ? 0 : cur + KU;
-      nxt = nxt + KU == STAGES ? 0 : nxt + KU;
+      cur = cur + 2 == STAGES ? 0 : cur + 2;
+      nxt = nxt + 2 == STAGES ? 0 : nxt + 2;
     }
-    if constexpr (KU == 2) {
-      if (nk & 1) {                             // (wave-uniform) the odd last tile: landed with the last wait above (vmcnt(0))
-        compute(cur);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
+    if (nk & 1) {                               // (wave-uniform) the odd last tile: landed with the last wait above (vmcnt(0))
+      compute(cur);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
     }
   }
 
@@ -411,15 +396,7 @@ template <int BM, int BN, int WM, int WN, int STAGES, int KU>
 void launch_lin(KParams k, hipStream_t s) {
   const bool geglu = k.act == APTP_ACT_GEGLU;
   const int tiles = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN);
-  // next-launch prefetch: slice bounds on the host (lines of the xcd-th eighth per workgroup of that XCD; aptp_prefetch_slice)
-  k.pf_lines = 0; k.pf_per = 0;
-  if (k.pf_ptr) {
-    const int nper = (tiles + 7) >> 3;                // workgroups per XCD under round-robin dispatch (upper bound)
-    k.pf_lines = (int)(k.pf_bytes >> 6);
-    const int per_xcd = (k.pf_lines + 7) >> 3;
-    k.pf_per = (per_xcd + nper - 1) / nper;
-    if (k.pf_per < 1) k.pf_per = 1;
-  }
+  set_prefetch_slices(k, tiles);
   if (geglu) hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, true>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
   else if (k.act == APTP_ACT_GELU) hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, false, 1>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
   else if (k.act == APTP_ACT_QUICK_GELU) hipLaunchKernelGGL((lin_gemm_kernel<BM, BN, WM, WN, STAGES, KU, false, 2>), dim3(tiles), dim3(WM * WN * 64), 0, s, k);
