@@ -179,7 +179,14 @@ class AdamWItem(Structure):
 class AdamWParams(Structure):
     _fields_ = [("items_dev", c_void_p), ("starts_dev", c_void_p), ("n_items", c_int32), ("total_blocks", c_int32),
                 ("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float),
-                ("step_dev", c_void_p), ("gate_dev", c_void_p), ("grad_scale", c_float)]
+                ("step_dev", c_void_p), ("gate_dev", c_void_p), ("grad_scale", c_float), ("warmup_steps", c_float)]
+
+
+GRAD_ACCUM_STORE, GRAD_ACCUM_ADD, GRAD_ACCUM_FINAL = 0, 1, 2
+
+
+class GradAccumParams(Structure):
+    _fields_ = [("acc", c_void_p), ("g", c_void_p), ("n", c_int64), ("mode", c_int32)]
 
 
 class MseParams(Structure):
@@ -545,6 +552,8 @@ EXPORTS = [
     ("aptp_pack_dgrad_many", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("aptp_adamw_blocks", c_int, [c_int64]),
     ("aptp_adamw_many", c_int, [POINTER(AdamWParams), c_void_p]),
+    ("aptp_grad_accumulate_blocks", c_int, [c_int64]),
+    ("aptp_grad_accumulate", c_int, [POINTER(GradAccumParams), c_void_p]),
     ("aptp_mse_nblocks", c_int, [c_int64, c_int32]),
     ("aptp_mse", c_int, [POINTER(MseParams), c_void_p]),
     ("aptp_groupnorm_bwd", c_int, [POINTER(GroupNormBwdParams), c_void_p]),

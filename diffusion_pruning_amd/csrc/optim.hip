@@ -8,6 +8,7 @@
 //   p <- p * (1 - lr * wd);  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2
 //   p <- p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // The table of tensors lives in device memory (built once; the gradient addresses are those of the captured backward).
+// Below it: aptp_grad_accumulate, the sum of a window of micro-batch gradients that such a step is applied to.
 #include "aptp_common.h"
 
 namespace {
@@ -20,6 +21,7 @@ struct AdamK {
   const float* step;                            // device scalar: number of steps taken BEFORE this one
   const float* gate;                            // optional device scalar: the step is applied only when it is finite
   float gscale;                                 // gradients are multiplied by this first (1 / world size of a summed exchange)
+  float warmup;                                 // 0 = off; else the rate ramps linearly over this many optimizer steps
 };
 
 __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
@@ -39,7 +41,11 @@ __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
   const AptpAdamWItem it = k.items[lo];
   const float t = k.step[0] + 1.0f;
   const float bc1 = 1.0f - powf(k.beta1, t), bc2 = 1.0f - powf(k.beta2, t);
-  const float step_size = k.lr / bc1, bc2_sqrt = sqrtf(bc2), decay = 1.0f - k.lr * k.wd;
+  // constant_with_warmup counted in optimizer steps: rate lr * min(1, k / W) at the step that follows k applied ones (the
+  // first runs at 0).  Uniform; W = 0 leaves lr as passed, so the arithmetic below is what it is without a warm-up.
+  float lr = k.lr;
+  if (k.warmup > 0.0f) lr = k.lr * fminf(1.0f, k.step[0] / k.warmup);
+  const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2), decay = 1.0f - lr * k.wd;
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   __bf16* sh = (__bf16*)it.shadow;
 #pragma unroll
@@ -88,9 +94,75 @@ extern "C" int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream) {
   APTP_CHECK(p && p->items_dev && p->starts_dev && p->step_dev && p->n_items >= 1 && p->total_blocks >= 1, "adamw_many: bad arguments");
   APTP_CHECK(p->lr >= 0.f && p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f && p->eps > 0.f, "adamw_many: hyper-parameters");
   APTP_CHECK(p->grad_scale >= 0.f, "adamw_many: grad_scale");
+  APTP_CHECK(p->warmup_steps >= 0.f, "adamw_many: warmup_steps");
   AdamK k{p->items_dev, p->starts_dev, p->n_items, p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->step_dev,
-          p->gate_dev, p->grad_scale == 0.f ? 1.0f : p->grad_scale};
+          p->gate_dev, p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->warmup_steps};
   hipLaunchKernelGGL(adamw_many_kernel, dim3((unsigned)p->total_blocks), dim3(256), 0, (hipStream_t)stream, k);
+  APTP_LAUNCH_CHECK();
+  return APTP_OK;
+}
+
+// ---- gradient accumulation over the micro-batches of an optimizer window ------------------------------------------------------
+// acc and g are the accumulator and the gradient arena of an expert (fp32, up to ~0.9 G elements: int64 indices).  Pure HBM
+// streaming: 8 B (STORE) or 12 B (ADD, FINAL) per element, nothing to reuse.  A block takes ELEMS_PER_BLOCK elements per trip --
+// its 4 float4 loads per operand are issued before the first add -- and the grid is capped, the rest is a grid stride: the
+// whole-arena launch of an SD-2.1 expert would otherwise be ~10^5 blocks of one trip each.
+namespace {
+
+constexpr int ACCUM_MAX_BLOCKS = 2048;          // 256 CUs x 8 resident blocks of 256 threads
+
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, float* __restrict__ g, const int64_t n) {
+  const int64_t n4 = n & ~(int64_t)3;           // the float4 part; acc and g are 16-byte aligned
+  const int64_t stride = (int64_t)gridDim.x * ELEMS_PER_BLOCK;
+  for (int64_t base = (int64_t)blockIdx.x * ELEMS_PER_BLOCK; base < n4; base += stride) {
+    float4 a[4], b[4];
+    int64_t e[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      e[i] = base + ((int64_t)i * 256 + threadIdx.x) * 4;
+      if (e[i] < n4) {
+        b[i] = *reinterpret_cast<const float4*>(g + e[i]);
+        if (MODE != APTP_GRAD_ACCUM_STORE) a[i] = *reinterpret_cast<const float4*>(acc + e[i]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (e[i] < n4) {
+        float4 r = b[i];
+        if (MODE != APTP_GRAD_ACCUM_STORE) { r.x = a[i].x + b[i].x; r.y = a[i].y + b[i].y; r.z = a[i].z + b[i].z; r.w = a[i].w + b[i].w; }
+        *reinterpret_cast<float4*>((MODE == APTP_GRAD_ACCUM_FINAL ? g : acc) + e[i]) = r;
+      }
+    }
+  }
+  if (blockIdx.x == 0 && n4 + threadIdx.x < n) {        // scalar tail: at most 3 elements
+    const int64_t x = n4 + threadIdx.x;
+    const float gv = g[x];
+    if (MODE == APTP_GRAD_ACCUM_STORE) acc[x] = gv;
+    else if (MODE == APTP_GRAD_ACCUM_ADD) acc[x] = acc[x] + gv;
+    else g[x] = acc[x] + gv;
+  }
+}
+
+}  // namespace
+
+extern "C" int aptp_grad_accumulate_blocks(int64_t n) {
+  if (n <= 0) return 0;
+  const int64_t b = (n + ELEMS_PER_BLOCK - 1) / ELEMS_PER_BLOCK;
+  return (int)(b < ACCUM_MAX_BLOCKS ? b : ACCUM_MAX_BLOCKS);
+}
+
+extern "C" int aptp_grad_accumulate(const AptpGradAccumParams* p, aptp_stream_t stream) {
+  APTP_CHECK(p && p->acc && p->g, "grad_accumulate: null pointer");
+  APTP_CHECK(p->n >= 1, "grad_accumulate: n must be >= 1");
+  APTP_CHECK(p->mode >= APTP_GRAD_ACCUM_STORE && p->mode <= APTP_GRAD_ACCUM_FINAL, "grad_accumulate: mode %d", (int)p->mode);
+  APTP_CHECK(((uintptr_t)p->acc & 15) == 0 && ((uintptr_t)p->g & 15) == 0, "grad_accumulate: acc and g must be 16-byte aligned");
+  APTP_CHECK(p->acc != p->g, "grad_accumulate: acc and g are the same buffer");
+  const dim3 grid((unsigned)aptp_grad_accumulate_blocks(p->n)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (p->mode == APTP_GRAD_ACCUM_STORE) hipLaunchKernelGGL(grad_accumulate_kernel<APTP_GRAD_ACCUM_STORE>, grid, block, 0, s, p->acc, p->g, p->n);
+  else if (p->mode == APTP_GRAD_ACCUM_ADD) hipLaunchKernelGGL(grad_accumulate_kernel<APTP_GRAD_ACCUM_ADD>, grid, block, 0, s, p->acc, p->g, p->n);
+  else hipLaunchKernelGGL(grad_accumulate_kernel<APTP_GRAD_ACCUM_FINAL>, grid, block, 0, s, p->acc, p->g, p->n);
   APTP_LAUNCH_CHECK();
   return APTP_OK;
 }

@@ -1991,6 +1991,22 @@ FOLD_DEFER = None
 # columns cost a zero fill per step (80 launches).  Every parameter is used once per step, so "write" equals "accumulate".
 GRAD_DIRECT = False
 
+GRAD_ACCUM_MODES = {"store": _lib.GRAD_ACCUM_STORE, "add": _lib.GRAD_ACCUM_ADD, "final": _lib.GRAD_ACCUM_FINAL}
+
+
+def grad_accumulate(acc: torch.Tensor, g: torch.Tensor, mode) -> None:
+    """One launch of the gradient window of train_step.GraphedFineTunerStep(accumulation_steps=N) over two contiguous fp32
+    ranges of equal length (csrc/optim.hip): "store" acc <- g (first micro-step: acc is not read), "add" acc <- acc + g,
+    "final" g <- acc + g (last micro-step: the sum lands where the exchange and the optimizer read).  Plain fp32 addition:
+    torch's ``acc + g`` bit for bit, non-finite values included.  `mode` may also be the integer of the C interface."""
+    assert acc.is_cuda and g.is_cuda and acc.device == g.device, "grad_accumulate: device tensors"
+    assert acc.dtype == torch.float32 and g.dtype == torch.float32 and acc.is_contiguous() and g.is_contiguous()
+    assert acc.numel() == g.numel(), "grad_accumulate: acc and g differ in length"
+    q = _lib.GradAccumParams()
+    q.acc, q.g, q.n = acc.data_ptr(), g.data_ptr(), acc.numel()
+    q.mode = GRAD_ACCUM_MODES[mode] if isinstance(mode, str) else int(mode)
+    _lib.check(_lib.load().aptp_grad_accumulate(ctypes.byref(q), _stream()), "aptp_grad_accumulate")
+
 
 class FoldBatch:
     def __init__(self, records):

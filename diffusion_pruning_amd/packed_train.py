@@ -294,14 +294,19 @@ class PackedAdamW:
     captured backward of GraphedFineTunerStep: the graph re-writes the same addresses at every replay)."""
 
     def __init__(self, trainer: PackedTrainer, lr: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 group_of=None):
+                 group_of=None, warmup_steps: int = 0):
         """group_of: optional map parameter -> group index (e.g. the gradient bucket that completes it, ArenaGradReducer.bucket_of):
         the table is built per group and ``step_group(i)`` applies one group per launch, so the optimizer can follow a
-        bucketed gradient exchange bucket by bucket; ``step()`` applies all groups."""
+        bucketed gradient exchange bucket by bucket; ``step()`` applies all groups.
+        warmup_steps W > 0: the rate of the step that follows k applied steps is lr * min(1, k / W) -- `constant_with_warmup` of
+        the fine-tune recipe (configs/finetuning/sd-2-1_cc3m.yaml:108-109) counted in optimizer steps; the kernel reads k from
+        the device-side step count, so a gated (skipped) step does not advance the ramp.  0: constant lr."""
         import ctypes
         from . import _lib
         self.trainer, self.lr, self.betas, self.eps, self.weight_decay = trainer, lr, betas, eps, weight_decay
         self.group_of = group_of
+        assert warmup_steps >= 0, "PackedAdamW: warmup_steps"
+        self.warmup_steps = warmup_steps
         entries = []                                   # (parameter, bf16 shadow or None)
         for e in trainer.gemms.values():
             entries.append((e.P, e.pw.w))
@@ -373,6 +378,7 @@ class PackedAdamW:
         q.step_dev = self.step_t.data_ptr()
         q.gate_dev = None if gate is None else gate.data_ptr()
         q.grad_scale = float(grad_scale)
+        q.warmup_steps = float(self.warmup_steps)
         _lib.check(lib.aptp_adamw_many(ctypes.byref(q), ops._stream()), "aptp_adamw_many")
 
     def _check_grads(self):

@@ -1164,12 +1164,28 @@ class GraphedFineTunerStep(FineTunerStep):
     gradients, the deferred folds, AdamW (trainer.py:1529-1540) and the refresh of the bf16 operands as a handful of launches
     (ops.WgradBatch, ops.FoldBatch, packed_train.PackedAdamW).  The ~10^4 launches of the eager step (which is host-bound)
     cost their device time only.  Same numbers as FineTunerStep on packed masters with the same optimizer, bit for bit
-    (tests/test_finetune_gpu.py)."""
+    (tests/test_finetune_gpu.py).
+
+    accumulation_steps=N > 1 (gradient_accumulation_steps of configs/finetuning/sd-2-1_cc3m.yaml): every train_step call is one
+    micro-batch through the same graphs; calls i = 0 .. N-1 form a window whose gradients are summed on the device
+    (ops.grad_accumulate: STORE, ADD .., FINAL), and the gradient exchange, AdamW and the operand refresh run once, on the call
+    that closes the window, on the mean over the window (and the ranks).  Arena slot 0 carries the sum of the window's losses,
+    so one non-finite micro-batch skips the whole window on every rank.  The window position lives in this object only:
+    PackedAdamW.state_dict() and PackedTrainer.export_() hold parameters, moments and the count of applied steps, so a
+    checkpoint taken in the middle of a window drops the micro-batches accumulated so far (``accum_index`` tells where a
+    window stands: save at 0).
+    lr_warmup_steps=W > 0: `constant_with_warmup` over W optimizer steps (PackedAdamW(warmup_steps=W))."""
 
     def __init__(self, student, teacher, cfg: Optional[FinetuneLossConfig] = None, schedule: Optional[NoiseSchedule] = None,
                  lr: float = 1e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
-                 data_parallel: bool = False, bucket_bytes: int = 256 << 20, reduce_mode: str = "rs_ag", nan_guard: bool = True):
+                 data_parallel: bool = False, bucket_bytes: int = 256 << 20, reduce_mode: str = "rs_ag", nan_guard: bool = True,
+                 accumulation_steps: int = 1, lr_warmup_steps: int = 0):
         super().__init__(student, teacher, cfg, schedule)
+        assert int(accumulation_steps) >= 1 and lr_warmup_steps >= 0
+        # accumulation_steps > 1: the gradients live in the arena (also without data_parallel) and one more fp32 tensor of its
+        # size holds the running sum of the window; allocated by capture()
+        self.accumulation_steps, self.lr_warmup_steps = int(accumulation_steps), lr_warmup_steps
+        self._accum, self.accum_index = None, 0
         # data_parallel (one expert on several GPUs, SURVEY C2): the replayed graph and the batched weight-gradient launches
         # leave this rank's gradients in ONE contiguous arena; ArenaGradReducer sums it over the ranks in place, bucket by bucket
         # on a communication stream, and the optimizer follows bucket by bucket (the mean is its grad_scale)
@@ -1237,7 +1253,7 @@ class GraphedFineTunerStep(FineTunerStep):
         # to reset between steps -- every parameter's live region is overwritten by each backward
         direct = self.direct_grads
         if direct:
-            self.trainer.ensure_grad_buffers(arena=self._dp_graphed, world=_world())
+            self.trainer.ensure_grad_buffers(arena=self._dp_graphed or self.accumulation_steps > 1, world=_world())
 
         def teacher_fwd():
             # own split-K counters / scratch: this graph replays NEXT TO the previous step's optimizer tail (ops.scratch_domain)
@@ -1333,7 +1349,11 @@ class GraphedFineTunerStep(FineTunerStep):
             off = {id(p_): o for p_, o in zip(self.trainer.parameters(), self.trainer.grad_offsets)}
             group_of = lambda p_: self.reducer.bucket_of(off[id(p_)], p_.numel())          # noqa: E731
         self.optimizer = PackedAdamW(self.trainer, lr=self.opt_kw["lr"], betas=self.opt_kw["betas"], eps=self.opt_kw["eps"],
-                                     weight_decay=self.opt_kw["weight_decay"], group_of=group_of)
+                                     weight_decay=self.opt_kw["weight_decay"], group_of=group_of,
+                                     warmup_steps=self.lr_warmup_steps)
+        if self.accumulation_steps > 1:
+            assert direct, "gradient accumulation sums the gradient arena of the direct-gradient mode"
+            self._accum, self.accum_index = torch.empty_like(self.trainer.grad_arena), 0      # (STORE writes it before any read)
         self._cap = dict(st=st, graph=graph, g_bwd=g_bwd, g_teacher=g_teacher, full_pred=full_pred, teacher_acts=teacher_acts,
                          pred=pred, student_acts=student_acts, side=concurrent_stream(log=self.stream_probe),
                          tail_stream=torch.cuda.Stream(), ev_bwd=torch.cuda.Event(), ev_tail=None, launch_log=launch_log, **out)
@@ -1385,20 +1405,37 @@ class GraphedFineTunerStep(FineTunerStep):
                 self._wgrads.run()               # every stride-1 weight gradient of the backward: one launch per filter size
             if self._folds is not None:
                 self._folds.run()                # every deferred slab / chunk fold of the backward: one launch
-            if self._dp_graphed and self.reducer is not None:
+            N, idx = self.accumulation_steps, self.accum_index
+            applied = idx == N - 1
+            if N > 1:
+                # one micro-batch of a window: its loss goes into arena slot 0 and the whole arena into the running sum; the
+                # call that closes the window gets the sum back in the arena (FINAL), where the exchange and AdamW read
+                arena = self.trainer.grad_arena
+                arena[0:1].copy_(cap["total"].reshape(1))
+                ops.grad_accumulate(self._accum, arena, "store" if idx == 0 else ("final" if applied else "add"))
+                self.accum_index = 0 if applied else idx + 1
+            if not applied:
+                pass                             # no exchange, no AdamW, no operand refresh, no step count: the window is open
+            elif self._dp_graphed and self.reducer is not None:
                 # sum over the ranks in place, bucket by bucket on the communication stream; AdamW follows bucket by bucket with
                 # grad_scale = 1 / world; arena slot 0 = sum of the ranks' losses = their common finite / non-finite verdict
                 arena = self.trainer.grad_arena
-                arena[0:1].copy_(cap["total"].reshape(1))
+                if N == 1:
+                    arena[0:1].copy_(cap["total"].reshape(1))
                 gate = arena[0:1] if self.nan_guard else None
-                scale = 1.0 / self.reducer.world
+                scale = 1.0 / (N * self.reducer.world)       # mean over the window's micro-batches and the ranks
                 self.reducer.exchange(lambda i: self.optimizer.step_group(i, gate, scale))
                 self.optimizer.finish_step(gate)
+            elif N > 1:
+                # slot 0 = sum of the window's losses: one non-finite micro-batch skips the window
+                self.optimizer.step(self.trainer.grad_arena[0:1] if self.nan_guard else None, grad_scale=1.0 / N)
             else:
                 self.optimizer.step(cap["total"] if self.nan_guard else None)
             ev = cap["ev_tail"] or torch.cuda.Event()
             ev.record(tail)
             cap["ev_tail"] = ev
         # (clones: the graph's static outputs are overwritten by the next replay, and callers accumulate losses over steps)
+        # the four losses are this micro-batch's; applied: this call ran the exchange and the optimizer (always, without
+        # accumulation; whether the step took effect is the device-side NaN verdict); accum_index: its place in the window
         return {"loss": cap["total"].clone(), "diff_loss": cap["diff"].clone(), "distillation_loss": cap["dist"].clone(),
-                "block_loss": cap["blk"].clone()}
+                "block_loss": cap["blk"].clone(), "applied": applied, "accum_index": idx}

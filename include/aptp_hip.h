@@ -689,9 +689,24 @@ typedef struct {
                            * by the same predicate */
   float grad_scale;       /* gradients are multiplied by this before use (0 = 1): 1 / world size folds the mean of a summed
                            * data-parallel exchange (DDP inside accelerator.backward, trainer.py:1616) into the optimizer pass */
+  float warmup_steps;     /* 0 = off; W > 0: the effective rate is lr * min(1, step_dev[0] / W) -- `constant_with_warmup` of
+                           * configs/finetuning/sd-2-1_cc3m.yaml:108-109 counted in optimizer steps: the first step runs at rate 0,
+                           * step W and later at lr; read from device memory, so a gated (skipped) step does not advance the ramp */
 } AptpAdamWParams;
 int aptp_adamw_blocks(int64_t n);
 int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream);
+
+/* Gradient accumulation over the micro-batches of one optimizer window (gradient_accumulation_steps of the fine-tune recipe,
+ * configs/finetuning/sd-2-1_cc3m.yaml): ONE launch over a contiguous fp32 range (the gradient arena of
+ * PackedTrainer.ensure_grad_buffers(arena=True)).  acc, g: fp32 [n], 16-byte aligned; plain fp32 addition, no gate: a
+ * non-finite value propagates into the sum.
+ *   STORE  acc[i] = g[i]            first micro-step: acc is not read, so it needs no zero fill    (8 B / element)
+ *   ADD    acc[i] = acc[i] + g[i]   micro-steps in between                                         (12 B / element)
+ *   FINAL  g[i]   = acc[i] + g[i]   last micro-step: the sum lands where the exchange and AdamW read (12 B / element) */
+enum { APTP_GRAD_ACCUM_STORE = 0, APTP_GRAD_ACCUM_ADD = 1, APTP_GRAD_ACCUM_FINAL = 2 };
+typedef struct { float* acc; float* g; int64_t n; int32_t mode; } AptpGradAccumParams;
+int aptp_grad_accumulate_blocks(int64_t n);   /* grid of the launch: 0 for n <= 0 */
+int aptp_grad_accumulate(const AptpGradAccumParams* p, aptp_stream_t stream);
 
 /* Mean squared error of two equally shaped activations, read where they lie (the loss terms of Pruner.step / FineTuner.step:
  * pdm/training/trainer.py:1197-1225 diffusion MSE, output distillation, block distillation; :1729-1752 for the fine-tune step).

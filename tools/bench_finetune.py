@@ -28,7 +28,15 @@ def main():
     ap.add_argument("--mode", choices=("graphed", "packed-eager", "eager"), default="graphed",
                     help="graphed: packed masters + HIP graphs (GraphedFineTunerStep); packed-eager: packed masters, eager; "
                          "eager: diffusers-layout masters, eager (the round-1 path)")
+    ap.add_argument("--accum", type=int, default=1,
+                    help="gradient accumulation (graphed mode): --batch is the micro-batch, every step a micro-step, and the "
+                         "exchange + AdamW run once per window of this many; --steps / --warmup are rounded up to whole windows")
+    ap.add_argument("--lr-warmup", type=int, default=0, help="constant_with_warmup over this many optimizer steps (graphed mode)")
     args = ap.parse_args()
+    assert args.accum >= 1 and (args.mode == "graphed" or (args.accum == 1 and args.lr_warmup == 0)), \
+        "--accum / --lr-warmup belong to the graphed step"
+    args.steps = -(-args.steps // args.accum) * args.accum
+    args.warmup = -(-args.warmup // args.accum) * args.accum
     # under torchrun: one expert per GPU (rank r -> expert r on cuda:LOCAL_RANK); the processes never communicate
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if "RANK" in os.environ:
@@ -48,7 +56,7 @@ def main():
     n_train = None
     if args.mode == "graphed":
         from diffusion_pruning_amd.train_step import GraphedFineTunerStep
-        step = GraphedFineTunerStep(student, teacher, lr=1e-5)
+        step = GraphedFineTunerStep(student, teacher, lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup)
         step.capture(batch, offload_masters=True)
         opt, n_train = None, step.trainer.n_trainable()
     elif args.mode == "packed-eager":
@@ -71,7 +79,9 @@ def main():
                       "value": round(1.0 / dt, 3), "unit": "steps/s", "ms_per_step": round(dt * 1e3, 1), "expert": args.expert,
                       "batch": args.batch, "loss": float(out["loss"].detach()),
                       "max_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1), "mode": args.mode,
-                      "trainable_parameters": n_train}))
+                      "trainable_parameters": n_train, "accumulation_steps": args.accum, "lr_warmup_steps": args.lr_warmup,
+                      "micro_steps_per_s": round(1.0 / dt, 3), "optimizer_steps_per_s": round(1.0 / (dt * args.accum), 3),
+                      "peak_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}))
 
 
 if __name__ == "__main__":
