@@ -199,6 +199,28 @@ class MseParams(Structure):
     ]
 
 
+LOSS_TERMS_MAX = 16
+
+
+class LossTerm(Structure):
+    _fields_ = [
+        ("a", c_void_p), ("lda", c_int64), ("b", c_void_p), ("ldb", c_int64),
+        ("rows", c_int64), ("rows_per_sample", c_int64),
+        ("C", c_int32), ("a_f32", c_int32), ("b_f32", c_int32), ("group", c_int32),
+        ("scale", c_float), ("reserved", c_int32),
+    ]
+
+
+class LossTermsParams(Structure):
+    _fields_ = [
+        ("terms", LossTerm * LOSS_TERMS_MAX),
+        ("n_terms", c_int32), ("n_groups", c_int32),
+        ("group_coef", c_float * LOSS_TERMS_MAX), ("group_div", c_float * LOSS_TERMS_MAX),
+        ("w", c_void_p),
+        ("partial", c_void_p), ("out", c_void_p), ("sample_out", c_void_p), ("running", c_void_p),
+    ]
+
+
 class GroupNormBwdParams(Structure):
     _fields_ = [
         ("x", c_void_p), ("ldx", c_int64), ("dy", c_void_p), ("lddy", c_int64), ("dx", c_void_p), ("lddx", c_int64),
@@ -556,6 +578,9 @@ EXPORTS = [
     ("aptp_grad_accumulate", c_int, [POINTER(GradAccumParams), c_void_p]),
     ("aptp_mse_nblocks", c_int, [c_int64, c_int32]),
     ("aptp_mse", c_int, [POINTER(MseParams), c_void_p]),
+    ("aptp_loss_terms_nblocks", c_int, [POINTER(LossTermsParams)]),
+    ("aptp_loss_terms_scratch_floats", c_int, [POINTER(LossTermsParams)]),
+    ("aptp_loss_terms", c_int, [POINTER(LossTermsParams), c_void_p]),
     ("aptp_groupnorm_bwd", c_int, [POINTER(GroupNormBwdParams), c_void_p]),
     ("aptp_layernorm_bwd", c_int, [POINTER(LayerNormBwdParams), c_void_p]),
     ("aptp_attention_bwd", c_int, [POINTER(AttentionBwdParams), c_void_p]),

@@ -21,7 +21,7 @@ from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F40
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
-from ._lib import GuidedStepParams, PhiloxNormalParams, TrainNoiseParams
+from ._lib import GuidedStepParams, LossTermsParams, PhiloxNormalParams, TrainNoiseParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1860,6 +1860,12 @@ def _mse_view(t: torch.Tensor, order=None):
     channel slices of NHWC buffers); anything else is copied once."""
     if order is not None and order != tuple(range(t.dim())):
         t = t.permute(order)
+    v = _mse_view_in_place(t)
+    return v if v is not None else _mse_view_in_place(t.contiguous())
+
+
+def _mse_view_in_place(t: torch.Tensor):
+    """_mse_view of a tensor already in its memory order, without the copy: None where t has no such view"""
     if t.is_contiguous():
         n = t.numel()
         C = t.shape[-1] if (t.dim() > 1 and t.shape[-1] % 8 == 0) else n
@@ -1871,7 +1877,7 @@ def _mse_view(t: torch.Tensor, order=None):
             ok = ok and t.stride(d - 1) == t.stride(d) * t.shape[d]
         if ok:
             return t, t.numel() // t.shape[-1], t.shape[-1], ld
-    return _mse_view(t.contiguous())
+    return None
 
 
 def _mse_operands(a: torch.Tensor, b: torch.Tensor):
@@ -1916,6 +1922,141 @@ def mse_bwd(a: torch.Tensor, b: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     for i, d in enumerate(order):
         inv[d] = i
     return da.permute(inv)
+
+
+@dataclass
+class LossTerm:
+    """one term of ops.LossTerms: mean((a - b)^2), times `scale`, added to group `group`; per_sample=True makes it the weighted
+    term: (1/B) sum_b weights[b] * mean((a[b] - b[b])^2)"""
+    a: torch.Tensor
+    b: torch.Tensor
+    group: int = 0
+    scale: float = 1.0
+    per_sample: bool = False
+
+
+class LossTerms:
+    """All loss terms of a validation step in three launches (csrc/loss_terms.hip).
+
+    terms: LossTerm objects or (a, b, group[, scale[, per_sample]]) tuples, at most 16.  The operands' views are the ones
+    ops.mse(a, b) -- for the per-sample term ops.mse(a[i], b[i]) -- chooses, so every unweighted term and every per-sample mean
+    has ops.mse's bits.  An operand ops.mse reads in place is read in place here; one it can only reach through a copy (the
+    4-channel NCHW face of a prediction sliced out of 8-wide rows, and the target walked in that order) gets a staging tensor,
+    allocated once and refreshed by one `copy_` per run() -- shared by the terms that read the same tensor in the same order.
+    No dtype casts are made: a bf16 operand against an fp32 one is read as it is.
+    out[g] = sum of value * scale over the terms of group g (divided by group_div[g] where given: the training step's block
+    loss is a sum divided by 9), out[G] = sum_g group_coef[g] * out[g].  `weights`: fp32 [B] device vector of the per-sample
+    term.  `running`: fp32 [G + 2] totals, running[g] += out[g] and running[G + 1] += 1 on every run(); the caller zeroes it.
+    The parameter block is built once: run() is the staging copies and three launches, safe to capture and replay as long as
+    the operands, `weights` and `running` stay where they are."""
+
+    def __init__(self, terms, group_coef, weights: Optional[torch.Tensor] = None, running: Optional[torch.Tensor] = None,
+                 group_div=None):
+        lib = _lib.load()
+        terms = [t if isinstance(t, LossTerm) else LossTerm(*t) for t in terms]
+        assert 1 <= len(terms) <= _lib.LOSS_TERMS_MAX, f"LossTerms takes 1..{_lib.LOSS_TERMS_MAX} terms"
+        G = len(group_coef)
+        assert 1 <= G <= _lib.LOSS_TERMS_MAX
+        p = LossTermsParams()
+        p.n_terms, p.n_groups = len(terms), G
+        for g in range(G):
+            p.group_coef[g] = float(group_coef[g])
+            p.group_div[g] = float(group_div[g]) if group_div is not None else 0.0
+        self._keep, self.n_samples = [weights, running], 0
+        self._staged, self.copies = {}, []                 # staging tensor by source view; (staging, source) in run() order
+        dev = terms[0].a.device
+        for i, t in enumerate(terms):
+            a, b = t.a, t.b
+            assert a.shape == b.shape and a.is_cuda and b.device == a.device
+            assert a.dtype in (torch.bfloat16, torch.float32) and b.dtype in (torch.bfloat16, torch.float32)
+            q = p.terms[i]
+            if t.per_sample:
+                B = a.shape[0]
+                order = (0,) + tuple(d + 1 for d in _mse_order(a[0]))       # the samples, each in the order ops.mse(a[i], b[i]) walks
+                ap, bp = a.permute(order), b.permute(order)
+                v = self._pair(ap[0], bp[0], stage=False)
+                ok = v is not None
+                for s in range(1, B if ok else 0):         # sample s lies rows * ld elements behind sample s - 1, in the same view?
+                    vs = self._pair(ap[s], bp[s], stage=False)
+                    ok = ok and vs is not None and vs[2:] == v[2:] \
+                        and vs[0].data_ptr() == v[0].data_ptr() + s * v[2] * v[4] * a.element_size() \
+                        and vs[1].data_ptr() == v[1].data_ptr() + s * v[2] * v[5] * b.element_size()
+                if not ok:                                  # stage both whole batches: sample s = rows s * rows .. of the staging
+                    ap, bp = self._stage(ap), self._stage(bp)
+                    v = self._pair(ap[0], bp[0], stage=False)
+                a2, b2, rows, C, lda, ldb = v
+                assert weights is not None and weights.dtype == torch.float32 and weights.is_contiguous() \
+                    and weights.numel() >= B and weights.device == a.device, "LossTerms: weights = fp32 [B] on the operands' device"
+                q.rows, q.rows_per_sample, self.n_samples = rows * B, rows, B
+                self._keep += [ap, bp]
+            else:
+                order = _mse_order(a)
+                a2, b2, rows, C, lda, ldb = self._pair(a.permute(order), b.permute(order), stage=True)
+                q.rows, q.rows_per_sample = rows, 0
+            q.a, q.lda, q.b, q.ldb, q.C = a2.data_ptr(), lda, b2.data_ptr(), ldb, C
+            q.a_f32, q.b_f32 = int(a.dtype == torch.float32), int(b.dtype == torch.float32)
+            q.group, q.scale = int(t.group), float(t.scale)
+            self._keep += [a, b, a2, b2]
+        if running is not None:
+            assert running.dtype == torch.float32 and running.is_contiguous() and running.numel() >= G + 2 and running.device == dev
+        p.w = _ptr(weights)
+        p.running = _ptr(running)
+        n_scratch = lib.aptp_loss_terms_scratch_floats(ctypes.byref(p))
+        if n_scratch <= 0:
+            _lib.check(lib.aptp_loss_terms(ctypes.byref(p), None), "aptp_loss_terms")      # (refuses the table with its reason)
+        self.n_groups, self.nblocks = G, lib.aptp_loss_terms_nblocks(ctypes.byref(p))
+        self.partial = self._alloc(n_scratch, dev)
+        self.out = self._alloc(G + 1, dev)
+        self.sample_out = self._alloc(self.n_samples, dev) if self.n_samples else None
+        p.partial, p.out, p.sample_out = self.partial.data_ptr(), self.out.data_ptr(), _ptr(self.sample_out)
+        self.running, self._p, self._lib = running, p, lib
+
+    @staticmethod
+    def _alloc(n: int, device) -> torch.Tensor:
+        return torch.empty(n, dtype=torch.float32, device=device)
+
+    def _stage(self, src: torch.Tensor) -> torch.Tensor:
+        """contiguous staging tensor of the view `src`, refreshed by every run(); one per distinct view"""
+        key = (src.data_ptr(), tuple(src.shape), tuple(src.stride()), src.dtype)
+        if key not in self._staged:
+            self._staged[key] = torch.empty(src.shape, dtype=src.dtype, device=src.device)
+            self.copies.append((self._staged[key], src))
+        return self._staged[key]
+
+    def _pair(self, a: torch.Tensor, b: torch.Tensor, stage: bool):
+        """_mse_operands for a pair already permuted into the first operand's memory order: (a2, b2, rows, C, lda, ldb) with the
+        same row shapes.  Where _mse_operands would copy an operand, `stage` puts a staging tensor in its place; without
+        `stage` the answer is None."""
+        views = []
+        for t in (a, b):
+            v = _mse_view_in_place(t)
+            if v is None:
+                if not stage:
+                    return None
+                v = _mse_view_in_place(self._stage(t))
+            views.append(v)
+        (a2, rows, C, lda), (b2, rows_b, C_b, ldb) = views
+        if (rows_b, C_b) != (rows, C):                     # different row shapes for the same elements: flatten both
+            if not stage and not (a2.is_contiguous() and b2.is_contiguous()):
+                return None
+            a2, rows, C, lda = _mse_view_in_place((a2 if a2.is_contiguous() else self._stage(a2)).reshape(-1))
+            b2, _, _, ldb = _mse_view_in_place((b2 if b2.is_contiguous() else self._stage(b2)).reshape(-1))
+        assert C % 8 == 0, "aptp_loss_terms needs a multiple of 8 elements per row"
+        return a2, b2, rows, C, lda, ldb
+
+    def run(self) -> torch.Tensor:
+        """the staging copies (none for operands ops.mse reads in place) and three launches on the current stream; returns `out`
+        ([G + 1]: the groups, then their weighted sum), which the next run() overwrites"""
+        for dst, src in self.copies:
+            dst.copy_(src)
+        _lib.check(self._lib.aptp_loss_terms(ctypes.byref(self._p), _stream()), "aptp_loss_terms")
+        return self.out
+
+
+def loss_terms(terms, group_coef, weights: Optional[torch.Tensor] = None, running: Optional[torch.Tensor] = None, group_div=None):
+    """one-off LossTerms(...).run(): (out [G + 1], per-sample means of the weighted term or None)"""
+    lt = LossTerms(terms, group_coef, weights, running, group_div)
+    return lt.run(), lt.sample_out
 
 
 def fold_rows(partials: torch.Tensor, n_rows: int, C: int, out: Optional[torch.Tensor] = None,

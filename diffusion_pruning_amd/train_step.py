@@ -344,6 +344,62 @@ def _mse_per_sample(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return d.mean(dim=list(range(1, d.dim())))
 
 
+# ---- validation (Pruner.validate / FineTuner.validate, trainer.py:1026-1095, 1767-1818) -------------------------------------
+VAL_KEYS = ("loss", "diff_loss", "distillation_loss", "block_loss")
+
+
+def _min_snr_weights(cfg, schedule, timesteps) -> torch.Tensor:
+    """min-SNR-gamma weights as fp32 [B] (trainer.py:1203-1213, 1736-1749): the expression of the training steps"""
+    if cfg.snr_gamma is None:
+        return torch.ones(timesteps.shape[0], device=timesteps.device)
+    snr = compute_snr(schedule, timesteps)
+    if cfg.prediction_type == "v_prediction":
+        snr = snr + 1
+    return (torch.stack([snr, cfg.snr_gamma * torch.ones_like(timesteps)], dim=1).min(dim=1)[0] / snr).float()
+
+
+def _unet_loss_terms(cfg, model_pred, target, full_pred, acts_s, acts_t, w, group_coef, blocks: bool = True,
+                     running: Optional[torch.Tensor] = None) -> "ops.LossTerms":
+    """The U-Net loss terms of a validation step as ONE ops.LossTerms (three launches instead of two per term and sample):
+    group 0 the diffusion term (min-SNR weighted per sample unless snr_gamma is None), group 1 the mean of the block terms (a sum
+    divided by their count, as the training steps form it), group 2 the output distillation; out[3] = sum_g group_coef[g] * out[g]"""
+    terms = [ops.LossTerm(model_pred, target, 0, 1.0, cfg.snr_gamma is not None)]
+    n_blocks = len(acts_s) if blocks else 0
+    if n_blocks:
+        terms += [ops.LossTerm(acts_s[k], acts_t[k].detach(), 1) for k in acts_s]
+    terms.append(ops.LossTerm(model_pred, full_pred, 2))
+    return ops.LossTerms(terms, group_coef, weights=w if cfg.snr_gamma is not None else None, running=running,
+                         group_div=(0.0, float(n_blocks), 0.0))
+
+
+def reduce_validation_totals(totals: torch.Tensor, reduce: bool = True) -> torch.Tensor:
+    """`accelerator.reduce(.., "mean")` of trainer.py:1069-1080 / 1802-1810 for the whole vector of validation totals: ONE
+    all-reduce and a division by the world size, in place; a no-op without an initialised process group of more than one rank.
+    Takes a device tensor (RCCL) or a host tensor (gloo)."""
+    if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(totals)
+        totals /= dist.get_world_size()
+    return totals
+
+
+def _validate_eager(eval_fn, batches, keys, reduce: bool) -> Dict[str, float]:
+    """Mean of eval_fn(batch)[key] over `batches`: the totals stay tensors on the batches' device, so the host waits once, at
+    the end.  Reference quirk (trainer.py:1048-1067, 1787-1800): a batch without samples is skipped but the divisor is
+    len(batches), so every empty batch pulls the reported means towards zero."""
+    batches = list(batches)
+    totals = None
+    for batch in batches:
+        if batch["noisy_latents"].numel() == 0:
+            continue
+        out = eval_fn(batch)
+        vals = torch.stack([out[k].detach().float().reshape(()) for k in keys])
+        totals = vals if totals is None else totals + vals
+    if totals is None:
+        return {k: 0.0 for k in keys}
+    totals = reduce_validation_totals(totals, reduce).tolist()
+    return {k: v / len(batches) for k, v in zip(keys, totals)}
+
+
 class PrunerStep:
     def __init__(self, unet, hyper_net, quantizer, cfg: Optional[PruningLossConfig] = None,
                  schedule: Optional[NoiseSchedule] = None):
@@ -435,6 +491,60 @@ class PrunerStep:
                 "block_loss": block_loss.detach(), "contrastive_loss": contrastive_loss.detach(),
                 "resource_loss": resource_loss.detach(), "resource_ratio": ratios.mean().detach(),
                 "arch_vector_quantized": arch_vector_quantized.detach()}
+
+    @torch.no_grad()
+    def eval_step(self, batch: dict, pretrain: bool = False):
+        """One validation batch (trainer.py:1043-1052): `step` without autograd, with hyper_net and quantizer in eval() for the
+        call (restored afterwards; quantizer.py branches on `training`), and on the GPU with the three U-Net terms from ONE
+        ops.LossTerms call instead of two launches per term and sample.  Returns the six losses the reference's validate()
+        reports, as device scalars; nothing here waits for the device."""
+        nl, ts, ehs = batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"]
+        text_embeddings, target = batch["mpnet_embeddings"], batch["target"]
+        cfg = self.cfg
+        was = (self.hyper_net.training, self.quantizer.training)
+        self.hyper_net.eval()
+        self.quantizer.eval()
+        try:
+            if not nl.is_cuda:                 # host tensors (the CPU suite's emulated runs): the training step's own loss code
+                out = self.step(nl, ts, ehs, text_embeddings, target, pretrain=pretrain)
+                return {k: out[k].detach() for k in VAL_KEYS + ("contrastive_loss", "resource_loss")}
+            arch_vector = self.hyper_net(text_embeddings)
+            arch_vector_quantized, _ = self.quantizer(arch_vector)
+            arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)
+            arch_vector = self._single_arch_repeat(arch_vector, text_embeddings.shape[0])
+            arch_wdn = self.quantizer.width_depth_normalize(arch_vector)
+            text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)
+            sep = self.hyper_net.transform_structure_vector(arch_vector if pretrain else arch_vector_quantized)
+            contrastive_loss = self.contrastive(text_all, arch_all)
+            self.unet.set_structure(self.hyper_net.transform_structure_vector(torch.ones_like(arch_vector)))
+            full_pred = self.unet(nl, ts, ehs).sample
+            teacher_acts = dict(self.block_activations)
+            self.unet.set_structure(sep)
+            model_pred = self.unet(nl, ts, ehs).sample
+            student_acts = dict(self.block_activations)
+            w = _min_snr_weights(cfg, self.schedule, ts)
+            u = _unet_loss_terms(cfg, model_pred, target, full_pred, student_acts, teacher_acts, w, (1.0, 0.0, 0.0)).run()
+            diff_loss, block_loss, distillation_loss = u[0], u[1], u[2]
+            macs = self.unet.calc_macs()
+            ratios = macs["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"].squeeze()
+            resource_loss = self.resource(ratios.mean())
+            max_loss = 1.0 - torch.max(ratios)
+            std_loss = -torch.std(ratios)
+            loss = diff_loss + cfg.resource_weight * resource_loss + cfg.contrastive_weight * contrastive_loss \
+                + cfg.distillation_weight * distillation_loss + cfg.block_weight * block_loss \
+                + cfg.std_weight * std_loss + cfg.max_weight * max_loss                   # (the expression of `step`)
+            return {"loss": loss, "diff_loss": diff_loss, "distillation_loss": distillation_loss, "block_loss": block_loss,
+                    "contrastive_loss": contrastive_loss, "resource_loss": resource_loss}
+        finally:
+            self.hyper_net.train(was[0])
+            self.quantizer.train(was[1])
+
+    def validate(self, batches, pretrain: bool = False, reduce: bool = True) -> Dict[str, float]:
+        """Pruner.validate (trainer.py:1026-1090): the six validation means over `batches` as Python floats, with one host sync
+        at the end and, under an initialised process group, one all-reduce ("mean" over the ranks).  Reference quirk, kept: an
+        empty batch is skipped but still counts in the divisor (see _validate_eager)."""
+        return _validate_eager(lambda b: self.eval_step(b, pretrain=pretrain), batches,
+                               VAL_KEYS + ("contrastive_loss", "resource_loss"), reduce)
 
     def _single_arch_repeat(self, arch_vector, batch: int):
         """trainer.py:1134-1136 (the single-architecture baseline): the ONE learned architecture vector serves the whole batch
@@ -1128,6 +1238,34 @@ class FineTunerStep:
         return {"loss": loss, "diff_loss": diff_loss, "distillation_loss": distillation_loss.detach(),
                 "block_loss": block_loss.detach()}
 
+    def _group_coef(self):
+        cfg = self.cfg
+        return (cfg.diffusion_weight, cfg.block_weight if cfg.block_weight > 0 else 0.0, cfg.distillation_weight)
+
+    @torch.no_grad()
+    def eval_step(self, noisy_latents, timesteps, encoder_hidden_states, target):
+        """One validation batch (FineTuner.validate's call of step, trainer.py:1787-1794): teacher and student forward without
+        autograd -- under an attached PackedTrainer the student reads the packed, trained state (unet._ft_mode) -- and every loss
+        term from ONE ops.LossTerms call: three launches where `step` under no_grad issues two per term and per sample plus the
+        torch glue.  Returns the four device scalars under the keys of `step`; distillation and block loss have step's bits, the
+        diffusion loss differs by the order of its B-term weighted sum.  Host tensors take `step` itself."""
+        if not noisy_latents.is_cuda:
+            out = self.step(noisy_latents, timesteps, encoder_hidden_states, target)
+            return {k: out[k].detach() for k in VAL_KEYS}
+        full_pred = self.teacher(noisy_latents, timesteps, encoder_hidden_states).sample
+        model_pred = self.student(noisy_latents, timesteps, encoder_hidden_states).sample
+        w = _min_snr_weights(self.cfg, self.schedule, timesteps)
+        o = _unet_loss_terms(self.cfg, model_pred, target, full_pred, self.acts_s, self.acts_t, w, self._group_coef(),
+                             blocks=self.cfg.block_weight > 0).run()
+        return {"loss": o[3], "diff_loss": o[0], "distillation_loss": o[2], "block_loss": o[1]}
+
+    def validate(self, batches, reduce: bool = True) -> Dict[str, float]:
+        """FineTuner.validate (trainer.py:1767-1818): the four validation means over `batches` as Python floats; one host sync
+        at the end and, under an initialised process group, one all-reduce ("mean" over the ranks).  Reference quirk, kept: an
+        empty batch is skipped but still counts in the divisor (see _validate_eager)."""
+        return _validate_eager(lambda b: self.eval_step(b["noisy_latents"], b["timesteps"], b["encoder_hidden_states"], b["target"]),
+                               batches, VAL_KEYS, reduce)
+
     def _packed_reducer(self):
         """Under a PackedTrainer the gradients the optimizer consumes are those of the PACKED tensors (the diffusers-layout
         parameters receive none): the data-parallel exchange must run over them, or the ranks silently diverge."""
@@ -1203,6 +1341,7 @@ class GraphedFineTunerStep(FineTunerStep):
         self.optimizer = None
         self._cap = None
         self.stream_probe = []          # what graph_utils.concurrent_stream measured when it chose the teacher's / router's side streams
+        self._val, self._val_running = {}, None      # forward-only validation graphs by batch size (capture_validation), their totals
 
     def _losses(self, model_pred, full_pred, w, target):
         cfg = self.cfg
@@ -1366,6 +1505,123 @@ class GraphedFineTunerStep(FineTunerStep):
         cap = self._cap
         if cap is not None and cap.get("ev_tail") is not None:
             torch.cuda.current_stream().wait_event(cap["ev_tail"])
+
+    MAX_VALIDATION_GEOMETRIES = 2      # the full validation batch and the ragged last one
+
+    def capture_validation(self, batch: dict, warmup_iters: int = 1):
+        """Forward-only HIP graphs of one validation batch of this geometry: teacher forward (side stream, own pool, own scratch
+        domain) next to the student forward, then ONE loss-terms call that also adds the batch to the running totals.  The student
+        graph reads the packed bf16 operands, which PackedAdamW rewrites IN PLACE after every optimizer step: the addresses the
+        capture baked in stay the model, so one capture serves the whole run.  Graphs are kept per batch size, at most
+        MAX_VALIDATION_GEOMETRIES of them; the least recently used one goes.  Call after capture()."""
+        assert self._cap is not None, "call capture(batch) first: validation reads the packed state it builds"
+        self.finish()
+        B = int(batch["noisy_latents"].shape[0])
+        dev = batch["noisy_latents"].device
+        st = {k: batch[k].clone() for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target")}
+        st["snr_w"] = self._snr_weights(st["timesteps"])
+        if self._val_running is None:
+            self._val_running = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float32, device=dev)      # [diff, block, distill, loss, batches]
+        box = {}
+
+        def teacher_fwd():
+            with torch.no_grad(), ops.scratch_domain("val_teacher"):
+                st["snr_w"].copy_(self._snr_weights(st["timesteps"]))
+                fp = self.teacher(st["noisy_latents"], st["timesteps"], st["encoder_hidden_states"]).sample
+            return fp, dict(self.acts_t)
+
+        def student_fwd():
+            with torch.no_grad():
+                pred = self.student(st["noisy_latents"], st["timesteps"], st["encoder_hidden_states"]).sample
+            return pred, dict(self.acts_s)
+
+        def losses(pred, student_acts, full_pred, teacher_acts, running):
+            with torch.no_grad():
+                lt = _unet_loss_terms(self.cfg, pred, st["target"], full_pred, student_acts, teacher_acts, st["snr_w"],
+                                      self._group_coef(), blocks=self.cfg.block_weight > 0, running=running)
+                lt.run()
+            return lt
+
+        user_log, ops.LAUNCH_LOG = ops.LAUNCH_LOG, None
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(max(1, warmup_iters)):          # allocator and plan caches of this geometry; totals untouched
+                    fp, ta = teacher_fwd()
+                    losses(*student_fwd(), fp, ta, None)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            g_teacher, g_student, g_loss = new_graph(), new_graph(), new_graph()
+            with torch.cuda.graph(g_teacher):
+                full_pred, teacher_acts = teacher_fwd()
+            with torch.cuda.graph(g_student):
+                pred, student_acts = student_fwd()
+            with torch.cuda.graph(g_loss, pool=g_student.pool()):
+                box["lt"] = losses(pred, student_acts, full_pred, teacher_acts, self._val_running)
+        finally:
+            ops.LAUNCH_LOG = user_log
+            self.acts_s.clear()
+            self.acts_t.clear()
+        self._val.pop(B, None)
+        while len(self._val) >= self.MAX_VALIDATION_GEOMETRIES:
+            self._val.pop(next(iter(self._val)))               # (dicts keep insertion order: the first key is the least recently used)
+        self._val[B] = dict(st=st, g_teacher=g_teacher, g_student=g_student, g_loss=g_loss, lt=box["lt"], full_pred=full_pred,
+                            teacher_acts=teacher_acts, pred=pred, student_acts=student_acts, side=self._cap["side"])
+        return self
+
+    def _replay_validation(self, batch: dict):
+        """one validation batch through the graphs of its batch size (captured on first use); adds it to the running totals"""
+        B = int(batch["noisy_latents"].shape[0])
+        if B not in self._val:
+            self.capture_validation(batch)
+        cap = self._val[B] = self._val.pop(B)                 # most recently used: to the end
+        with torch.no_grad():
+            for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target"):
+                cap["st"][k].copy_(batch[k])
+        main, side = torch.cuda.current_stream(), cap["side"]
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            cap["g_teacher"].replay()
+        cap["g_student"].replay()
+        main.wait_stream(side)
+        cap["g_loss"].replay()
+        return cap["lt"].out
+
+    def eval_step_graphed(self, batch: dict):
+        """the four losses of one batch from the validation graphs, as clones of the graphs' static outputs (what eval_step
+        returns, replayed); the running totals of validate() take this batch too"""
+        self.finish()
+        o = self._replay_validation(batch).clone()
+        return {"loss": o[3], "diff_loss": o[0], "distillation_loss": o[2], "block_loss": o[1]}
+
+    def validate(self, batches, reduce: bool = True) -> Dict[str, float]:
+        """FineTuner.validate (trainer.py:1767-1818) from the validation graphs: finish() the pending optimizer tail, zero the
+        device totals, replay every batch (staged copies + three graph replays, no host wait), then ONE host sync; under an
+        initialised process group one all-reduce of the totals ("mean" over the ranks).  Returns the four means as Python floats.
+        Reference quirk, kept (trainer.py:1788-1800): a batch without samples is skipped but the divisor is len(batches), so every
+        empty batch pulls the means towards zero.  Forward-only: parameters, moments, step count, the gradient arena, the
+        accumulator and accum_index are left as they are, also in the middle of an accumulation window."""
+        batches = list(batches)
+        self.finish()
+        if not batches:
+            return {k: 0.0 for k in VAL_KEYS}
+        if self._val_running is not None:
+            self._val_running.zero_()
+        for batch in batches:
+            if batch["noisy_latents"].numel() == 0:
+                continue
+            self._replay_validation(batch)
+        if self._val_running is None:                        # nothing but empty batches
+            return {k: 0.0 for k in VAL_KEYS}
+        diff, blk, dist_l, loss = reduce_validation_totals(self._val_running[:4].clone(), reduce).tolist()
+        n = len(batches)
+        return {"loss": loss / n, "diff_loss": diff / n, "distillation_loss": dist_l / n, "block_loss": blk / n}
+
+    def validation_graph_nodes(self):
+        """nodes of the validation graphs by batch size, for those captured while graph_utils.KEEP_GRAPHS was set"""
+        return {B: {"teacher": node_count(c["g_teacher"]), "student_fwd": node_count(c["g_student"]), "losses": node_count(c["g_loss"])}
+                for B, c in self._val.items()}
 
     def graph_nodes(self):
         """nodes of the captured teacher + student forward / backward graph, when it was kept (graph_utils.KEEP_GRAPHS)"""

@@ -724,6 +724,43 @@ typedef struct {
 int aptp_mse_nblocks(int64_t rows, int32_t C);
 int aptp_mse(const AptpMseParams* p, aptp_stream_t stream);
 
+/* Every loss term of one validation step at once (Pruner.validate / FineTuner.validate: pdm/training/trainer.py:1026-1095,
+ * 1767-1818), with running totals kept on the device: three launches, no atomics, nothing to zero per call.
+ * A term is mean((a - b)^2) of two equally shaped operands read where they lie, with the operand rules of AptpMseParams and a
+ * dtype flag PER OPERAND (a bf16 activation against an fp32 target needs no cast).
+ *   rows_per_sample = 0: one mean over the whole term.
+ *   rows_per_sample > 0: B = rows / rows_per_sample per-sample means m_b; the term's value is (1/B) sum_b w[b] * m_b, summed in
+ *                        fp32 in sample order (the min-SNR diffusion term, trainer.py:1736-1749).  At most one such term.
+ * Every unweighted term gets the workgroups, the grid stride, the in-block fold and the finish order aptp_mse gives the same
+ * view, and so does every sample of the weighted term: these values are bit-identical to aptp_mse's.
+ *   out[g]  = (sum over the terms of group g, in index order, of value * scale), divided by group_div[g] where that is not 0
+ *             (the training step's block loss is (m_1 + .. + m_9) / 9: scale 1 and group_div 9 give its bits, scale 1/9 does not)
+ *   out[G]  = sum_g group_coef[g] * out[g], in index order     (G = n_groups; out: fp32 [G + 1], written on every call)
+ *   sample_out (optional): fp32 [B], the per-sample means of the weighted term
+ *   running (optional): fp32 [G + 2]; running[g] += out[g] for g = 0..G and running[G + 1] += 1, by one thread.  The caller
+ *             zeroes it once per validation run.  Non-finite values pass through.
+ * partial: fp32 [aptp_loss_terms_scratch_floats(p)] scratch, every slot that is read is written first. */
+#define APTP_LOSS_TERMS_MAX 16
+typedef struct {
+  const void* a; int64_t lda;
+  const void* b; int64_t ldb;
+  int64_t rows; int64_t rows_per_sample;
+  int32_t C; int32_t a_f32; int32_t b_f32; int32_t group;
+  float scale; int32_t reserved;
+} AptpLossTerm;
+typedef struct {
+  AptpLossTerm terms[APTP_LOSS_TERMS_MAX];
+  int32_t n_terms; int32_t n_groups;
+  float group_coef[APTP_LOSS_TERMS_MAX];
+  float group_div[APTP_LOSS_TERMS_MAX];
+  const float* w;
+  float* partial; float* out; float* sample_out; float* running;
+} AptpLossTermsParams;
+int aptp_loss_terms_nblocks(const AptpLossTermsParams* p);          /* workgroups of the first launch: the sum of aptp_mse_nblocks
+                                                                      over the terms and samples; 0 for a table it would refuse */
+int aptp_loss_terms_scratch_floats(const AptpLossTermsParams* p);   /* those partials plus one value per term / sample */
+int aptp_loss_terms(const AptpLossTermsParams* p, aptp_stream_t stream);
+
 /* Data-gradient operand from the forward operand of the same contraction (both in packed bf16 layout):
  * dst[c][taps-1-t][n] = src[n][t][c] for n < N, c < C, zero in the rest of dst's [dst_rows][taps][dst_ld] image.
  * (ops.pack_weight_dgrad of the same weights, without going through the diffusers layout.) */

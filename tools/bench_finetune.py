@@ -2,7 +2,11 @@
 SD-2.1 size, one expert per GPU (rank r fine-tunes expert r: keep ratio 0.4..0.75, 0-4 depth gates off).
 Experts never communicate (scripts/aptp/finetune.py:27-28), so N GPUs = N independent processes; this tool runs ONE expert
 (--expert k) on cuda:0 and prints one JSON line; under `python -m torch.distributed.run --nproc-per-node 8` every rank takes
-expert = RANK on cuda:LOCAL_RANK and prints its own line."""
+expert = RANK on cuda:LOCAL_RANK and prints its own line.
+
+--validate K (graphed mode) runs K validation batches of --val-batch samples through GraphedFineTunerStep.validate after the
+timed steps and adds their rate to the line; --validate-baseline times the same batches through torch.no_grad() +
+FineTunerStep.step under the attached trainer as well (what validation cost before the graphs existed), alternating the two."""
 import argparse
 import json
 import os
@@ -19,6 +23,55 @@ from diffusion_pruning_amd.unet import UNet2DConditionModelGated, UNet2DConditio
 from bench import expert_mask  # noqa: E402,F401  (the eight benchmark experts live with the benchmark)
 
 
+def time_validation(step, batches, baseline: bool, rounds: int = 2):
+    """validate() over `batches`, `rounds` times after one untimed pass (capture + warm-up); with `baseline` every round also runs
+    the batches through no_grad + FineTunerStep.step (one host sync at the end of the pass, like validate), right after the
+    graphed pass, so both see the same machine state"""
+    def graphed():
+        return step.validate(batches)
+
+    def eager():
+        tot = None
+        with torch.no_grad():
+            for b in batches:
+                out = FineTunerStep.step(step, b["noisy_latents"], b["timesteps"], b["encoder_hidden_states"], b["target"])
+                v = torch.stack([out[k].detach() for k in ("loss", "diff_loss", "distillation_loss", "block_loss")])
+                tot = v if tot is None else tot + v
+        return dict(zip(("loss", "diff_loss", "distillation_loss", "block_loss"), (tot / len(batches)).tolist()))
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / len(batches), res
+
+    graphed()
+    if baseline:
+        eager()
+    tg, te, res, res_e = [], [], None, None
+    for _ in range(rounds):
+        t, res = timed(graphed)
+        tg.append(t)
+        if baseline:
+            t, res_e = timed(eager)
+            te.append(t)
+    out = {"validate_batches": len(batches), "validate_batch": int(batches[0]["noisy_latents"].shape[0]),
+           "validate_ms_per_batch": round(min(tg) * 1e3, 2), "validate_batches_per_s": round(1.0 / min(tg), 3),
+           "validate_ms_per_batch_rounds": [round(t * 1e3, 2) for t in tg], "validate_losses": res,
+           "peak_gib_with_validation": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+    # launches of one validation batch: the graphs again, captured with their hipGraph_t kept so that the runtime can count nodes
+    from diffusion_pruning_amd import graph_utils
+    graph_utils.KEEP_GRAPHS = True
+    step.capture_validation(batches[0])
+    out["validate_graph_nodes"] = step.validation_graph_nodes()[out["validate_batch"]]
+    graph_utils.KEEP_GRAPHS = False
+    if baseline:
+        out.update({"validate_baseline_ms_per_batch": round(min(te) * 1e3, 2),
+                    "validate_baseline_ms_per_batch_rounds": [round(t * 1e3, 2) for t in te], "validate_baseline_losses": res_e})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--expert", type=int, default=0)
@@ -32,7 +85,12 @@ def main():
                     help="gradient accumulation (graphed mode): --batch is the micro-batch, every step a micro-step, and the "
                          "exchange + AdamW run once per window of this many; --steps / --warmup are rounded up to whole windows")
     ap.add_argument("--lr-warmup", type=int, default=0, help="constant_with_warmup over this many optimizer steps (graphed mode)")
+    ap.add_argument("--validate", type=int, default=0, help="validation batches to run through the forward-only graphs (graphed mode)")
+    ap.add_argument("--val-batch", type=int, default=32, help="validation batch size (validation_batch_size of the fine-tune config)")
+    ap.add_argument("--validate-baseline", action="store_true",
+                    help="also time the same batches through torch.no_grad() + FineTunerStep.step, alternating with the graphs")
     args = ap.parse_args()
+    assert args.validate == 0 or args.mode == "graphed", "--validate belongs to the graphed step"
     assert args.accum >= 1 and (args.mode == "graphed" or (args.accum == 1 and args.lr_warmup == 0)), \
         "--accum / --lr-warmup belong to the graphed step"
     args.steps = -(-args.steps // args.accum) * args.accum
@@ -75,13 +133,17 @@ def main():
         out = step.train_step(opt, batch)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    peak_train, val = torch.cuda.max_memory_allocated(), {}
+    if args.validate:
+        val = time_validation(step, [synthetic_batch(args.val_batch, 64, dev, seed=100 + i) for i in range(args.validate)],
+                              args.validate_baseline)
     print(json.dumps({"metric": "expert-finetune-steps/s (SD-2.1 pruned expert, 64x64 latents, teacher fwd + student fwd/bwd/wgrad + AdamW)",
                       "value": round(1.0 / dt, 3), "unit": "steps/s", "ms_per_step": round(dt * 1e3, 1), "expert": args.expert,
                       "batch": args.batch, "loss": float(out["loss"].detach()),
-                      "max_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1), "mode": args.mode,
+                      "max_mem_GiB": round(peak_train / 2 ** 30, 1), "mode": args.mode,
                       "trainable_parameters": n_train, "accumulation_steps": args.accum, "lr_warmup_steps": args.lr_warmup,
                       "micro_steps_per_s": round(1.0 / dt, 3), "optimizer_steps_per_s": round(1.0 / (dt * args.accum), 3),
-                      "peak_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}))
+                      "peak_gib": round(peak_train / 2 ** 30, 2), **val}))
 
 
 if __name__ == "__main__":
