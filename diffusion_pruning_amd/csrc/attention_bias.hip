@@ -9,7 +9,11 @@
 // sit in LDS (36 KB) whatever L is; up to L = 128 there is one chunk and the rescaling multiplies by exp2(-inf) = 0 once.
 //   kend               1 + the last valid key of the sample (L without a mask).  Chunks, key tiles and query strips at or
 //                      past kend are never computed: with a prefix mask the cost follows the caption, not the padding.
-//                      Query rows at or past kend are padding (their own mask is 0) and are written as zeros.
+//                      Every query row below L is written.  Query rows at or past kend are padding (their own mask is 0):
+//                      a 16-row strip that STARTS at or past kend -- so every strip of a 128-row query block with
+//                      qbase >= kend -- is written as exact zeros; the rows past kend inside the strip that straddles
+//                      kend are computed like any other row and hold ordinary attention values (what the fp32 parity
+//                      kernel below computes for every row below L).  Callers must not read meaning into padding rows.
 //   S[16 q][16 keys]   mfma_f32_16x16x32_bf16 over the 64 channels, Q fragments from global memory (kept in registers over
 //                      the chunks), K fragments from LDS; the chunk's tiles stay in registers (8 x 4 fp32 per lane);
 //   softmax            score * scale*log2(e) + bias*log2(e) (LDS table over j - i) + 0 / -inf per key (LDS); the running maximum
@@ -154,7 +158,7 @@ __global__ __launch_bounds__(256) void attn_bias_kernel(const BiasK p) {
     __syncthreads();       // the chunk's K, V and mask images are free
   }
 
-  // padding rows (strips at or past kend) are written as zeros
+  // every row below L is stored; strips that start at or past kend never accumulated anything and come out as exact zeros
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int q0 = qbase + 16 * (wave + 4 * u);

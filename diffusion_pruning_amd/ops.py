@@ -1064,7 +1064,12 @@ def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
     """softmax(q k^T * scale + relbias[h, j - i + L - 1] + key mask) v with head_dim 64 and 1 <= L <= 512 (MPNet's
     self-attention).  q, k, v and out [B, L, heads*64] are views with a contiguous last dim on one device (e.g. column slices
     of a fused q|k|v buffer); bf16, or fp32 for the parity path.  relbias fp32 [heads, 2L-1]; key_mask fp32 [B, L] (0 = masked,
-    any pattern) or None for all valid: a masked key gets weight exactly 0.  Default scale 64^-0.5."""
+    any pattern) or None for all valid: a masked key gets weight exactly 0.  Default scale 64^-0.5.
+
+    Every row of out below L is written.  With kend = 1 + the last valid key of a sample (0 when it has none), the bf16 kernel
+    writes exact zeros into every 16-row strip that starts at or past kend (so into every row of a sample without a valid key)
+    and ordinary attention values into the rows past kend inside the strip that straddles it; the fp32 path computes every row
+    (zeros only for a sample without a valid key).  Rows at or past kend are padding either way."""
     lib = _lib.load()
     B, L = q.shape[0], q.shape[1]
     if out is None:
