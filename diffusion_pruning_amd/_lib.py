@@ -182,6 +182,22 @@ class AdamWParams(Structure):
                 ("step_dev", c_void_p), ("gate_dev", c_void_p), ("grad_scale", c_float), ("warmup_steps", c_float)]
 
 
+class GroupAdamWItem(Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("step", c_void_p), ("n", c_int64),
+                ("group", c_int32)]
+
+
+class AdamWGroup(Structure):
+    _fields_ = [("lr", c_float), ("weight_decay", c_float), ("warmup_steps", c_float)]
+
+
+class GroupAdamWParams(Structure):
+    _fields_ = [("items_dev", c_void_p), ("starts_dev", c_void_p), ("n_items", c_int32), ("total_blocks", c_int32),
+                ("groups_dev", c_void_p), ("n_groups", c_int32), ("counters_dev", c_void_p),
+                ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("grad_scale", c_float), ("zero_grad", c_int32),
+                ("gate_dev", c_void_p), ("items_host", c_void_p)]
+
+
 GRAD_ACCUM_STORE, GRAD_ACCUM_ADD, GRAD_ACCUM_FINAL = 0, 1, 2
 
 
@@ -574,6 +590,8 @@ EXPORTS = [
     ("aptp_pack_dgrad_many", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("aptp_adamw_blocks", c_int, [c_int64]),
     ("aptp_adamw_many", c_int, [POINTER(AdamWParams), c_void_p]),
+    ("aptp_group_adamw_blocks", c_int, [c_int64]),
+    ("aptp_group_adamw", c_int, [POINTER(GroupAdamWParams), c_void_p]),
     ("aptp_grad_accumulate_blocks", c_int, [c_int64]),
     ("aptp_grad_accumulate", c_int, [POINTER(GradAccumParams), c_void_p]),
     ("aptp_mse_nblocks", c_int, [c_int64, c_int32]),

@@ -31,6 +31,7 @@ from .graph_utils import concurrent_stream, new_graph, node_count
 from . import ops
 from .dist_utils import _rank, _span, _world
 from .losses import ContrastiveLoss, ResourceLoss, compute_snr
+from .router_optim import RouterAdamW
 
 
 @dataclass
@@ -558,8 +559,59 @@ class PrunerStep:
     def trainable_parameters(self):
         return [p for p in list(self.hyper_net.parameters()) + list(self.quantizer.parameters()) if p.requires_grad]
 
+    def finish(self):
+        pass
+
+    @staticmethod
+    def backward(out: dict):
+        out["loss"].backward()
+
+    @staticmethod
+    def _phase_key(pretrain: bool):
+        return ("phase", bool(pretrain))
+
+    def _probe_phase_table(self, optimizer, pretrain: bool, run_backward):
+        """a phase's table holds exactly the parameters its backward reaches (in the pre-training phase the codebook gets no
+        gradient, trainer.py:1165-1168: like a torch parameter whose .grad is None it keeps value, moments and step count, weight
+        decay included): one backward with every .grad = None tells.  The probing gradients are moved into the static tensors."""
+        key = self._phase_key(pretrain)
+        if key in optimizer.tables:
+            return key, False
+        for p in optimizer.params:
+            p.grad = None
+        run_backward()
+        reached = [p for p in optimizer.params if p.grad is not None]
+        optimizer.adopt_grads()
+        optimizer.add_table(key, reached)
+        return key, True
+
+    def _train_step_eager_router_hip(self, optimizer, batch: dict, pretrain: bool):
+        """the router run eagerly under a RouterAdamW (no router graphs for this phase, a process group, or eval()): the same
+        per-phase table, gate and skip rule as the captured step"""
+        self.finish()
+        out = {}
+
+        def run():
+            out.update(self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
+                                 batch["mpnet_embeddings"], batch["target"], pretrain=pretrain))
+            self.backward(out)
+        key, probed = self._probe_phase_table(optimizer, pretrain, run)
+        if not probed:
+            optimizer.zero_grad()
+            run()
+        allreduce_mean_grads(self.trainable_parameters())
+        optimizer.adopt_grads()
+        gate = out["loss"].detach().to(torch.float32).reshape(1).clone()
+        with torch.no_grad():
+            before = optimizer.counters[0:1].clone()
+            optimizer.step(table=key, gate=gate)
+            out["applied"] = optimizer.counters[0:1] - before
+        return out
+
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
         """forward + backward + fused gradient all-reduce + optimizer step (trainer.py:913-933)"""
+        if isinstance(optimizer, RouterAdamW):
+            return self._train_step_eager_router_hip(optimizer, batch, bool(pretrain))
         optimizer.zero_grad(set_to_none=True)
         out = self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
                         batch["mpnet_embeddings"], batch["target"], pretrain=pretrain)
@@ -635,7 +687,9 @@ class GraphedPrunerStep(PrunerStep):
         (and no process group is initialised: the router's collectives stay eager), the ROUTER is captured too -- hyper-net,
         quantiser incl. Sinkhorn, Gumbel relaxation, MAC losses as one graph ahead of the student's forward, and the chain rule
         into the router + the optimizer step as one graph behind the U-Net backward (trainer.py:1129-1138, :922-931) -- for this
-        value of `pretrain`; its Gumbel noise keeps coming from the host generator (estimation_utils.NoiseTape)."""
+        value of `pretrain`; its Gumbel noise keeps coming from the host generator (estimation_utils.NoiseTape).
+        A torch optimizer here is for a FRESH optimizer at a CONSTANT rate (the capture zeroes its state and bakes the rate in); a
+        router_optim.RouterAdamW serves both phases, a warm-up, the NaN batch skip and a resume from one capture."""
         cfg = self.cfg
         dev = batch["noisy_latents"].device
         st = {k: batch[k].clone() for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target")}
@@ -741,7 +795,10 @@ class GraphedPrunerStep(PrunerStep):
                          loss=loss, dist=dist, blk=blk, grad=grad, full_pred=full_pred, side=concurrent_stream(log=self.stream_probe), vmacs=vmacs,
                          launch_log=launch_log, router=None)
         if optimizer is not None and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            self._capture_router(batch, optimizer, pretrain)       # (`dist` is the distillation loss in this scope)
+            if isinstance(optimizer, RouterAdamW):
+                self._capture_router_hip(batch, optimizer, pretrain)
+            else:
+                self._capture_router(batch, optimizer, pretrain)       # (`dist` is the distillation loss in this scope)
         return self
 
     # ---- the router as two more graphs ----------------------------------------------------------------------------------
@@ -829,15 +886,113 @@ class GraphedPrunerStep(PrunerStep):
                 self._finish_hooks.append(m.register_forward_pre_hook(lambda *_a, **_k: self.finish()))
                 self._finish_hooks.append(m.register_state_dict_pre_hook(lambda *_a, **_k: self.finish()))
 
+    # ---- the router under router_optim.RouterAdamW: both phases from one capture -----------------------------------
+    def capture_router(self, batch: dict, pretrain: bool, optimizer=None):
+        """Capture the router graphs of the OTHER training phase next to the ones capture(batch, optimizer=RouterAdamW, pretrain=)
+        made: train_step(optimizer, batch, pretrain=) then picks a set by its argument, so the switch at
+        hypernet_pretraining_steps (trainer.py:892) costs nothing.  Legal in any state of the run: parameters, moments, step
+        counts, counters and the host generator are as before afterwards."""
+        assert self._cap is not None, "capture_router: call capture(batch, ...) first"
+        rt = self._cap.get("router")
+        optimizer = optimizer if optimizer is not None else (rt or {}).get("optimizer")
+        assert isinstance(optimizer, RouterAdamW), "capture_router: the router is captured per phase under a router_optim.RouterAdamW"
+        assert rt is None or (rt.get("hip") and rt["optimizer"] is optimizer), "capture_router: another optimizer was captured"
+        assert not (torch.distributed.is_available() and torch.distributed.is_initialized()), \
+            "capture_router: with a process group the router stays eager (its collectives are not captured)"
+        self._capture_router_hip(batch, optimizer, pretrain)
+        return self
+
+    def _capture_router_hip(self, batch, optimizer, pretrain):
+        from . import estimation_utils as EU
+        cfg, cap = self.cfg, self._cap
+        pretrain = bool(pretrain)
+        rt = cap.get("router")
+        assert rt is None or rt.get("hip"), "capture: the router was already captured under a torch optimizer"
+        assert set(map(id, self.trainable_parameters())) == set(map(id, optimizer.params)), \
+            "capture: the RouterAdamW must hold exactly trainable_parameters()"
+        optimizer.before_access = self.finish
+        self.finish()
+        text = batch["mpnet_embeddings"].clone()
+        tape = EU.NoiseTape()
+        dev = text.device
+        gate = torch.zeros(1, dtype=torch.float32, device=dev)          # the step's total loss: AptpGroupAdamWParams.gate_dev
+        applied = torch.zeros(1, dtype=torch.float32, device=dev)       # 1 when the step was applied, 0 when it was skipped
+        # capturing costs the run nothing, in any state: everything the warm-up iterations change is put back IN PLACE (the
+        # addresses are in the kernel's tables and go into the graphs) -- nothing is blanket-zeroed
+        snap = optimizer._snapshot()
+        host_rng = torch.get_rng_state()
+
+        def fwd():
+            tape.begin()
+            EU.NOISE_TAPE = tape
+            try:
+                r = self._router_forward(text, pretrain)
+            finally:
+                EU.NOISE_TAPE = None
+            with torch.no_grad():
+                cap["install_code"](r["arch_used"])
+            return r
+
+        def backward_only(r):
+            ts = [r["arch_used"]] if r["arch_used"].requires_grad else []
+            torch.autograd.backward([r["router_loss"]] + ts, [None] + ([cap["grad"]] if ts else []))
+
+        def bwd(r, key):
+            backward_only(r)                                         # accumulates into the static, zero-filled .grad tensors in place
+            with torch.no_grad():
+                total = r["router_loss"].detach() + cap["loss"] + cfg.distillation_weight * cap["dist"] + cfg.block_weight * cap["blk"]
+                gate.copy_(total.reshape(1))
+                applied.copy_(optimizer.counters[0:1])
+                optimizer.step(table=key, gate=gate)
+                torch.sub(optimizer.counters[0:1], applied, out=applied)
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            key, _ = self._probe_phase_table(optimizer, pretrain, lambda: backward_only(fwd()))
+            optimizer.zero_grad()
+            for _ in range(2):
+                bwd(fwd(), key)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        optimizer._restore(snap)
+        torch.cuda.synchronize()
+        g_fwd = new_graph()
+        with torch.cuda.graph(g_fwd):
+            r = fwd()
+        g_bwd = new_graph()
+        with torch.cuda.graph(g_bwd, pool=g_fwd.pool()):
+            bwd(r, key)
+        torch.set_rng_state(host_rng)
+        if rt is None:
+            rt = cap["router"] = dict(hip=True, optimizer=optimizer, stream=concurrent_stream(log=self.stream_probe),
+                                      ev_entry=torch.cuda.Event(), ev_code=torch.cuda.Event(), ev_bwd=torch.cuda.Event(),
+                                      ev_tail=torch.cuda.Event(), pending=False)
+        rt[pretrain] = dict(g_fwd=g_fwd, g_bwd=g_bwd, out=r, text=text, tape=tape, gate=gate, applied=applied, table=key)
+        if not self._finish_hooks:
+            for m in (self.hyper_net, self.quantizer):
+                self._finish_hooks.append(m.register_forward_pre_hook(lambda *_a, **_k: self.finish()))
+                self._finish_hooks.append(m.register_state_dict_pre_hook(lambda *_a, **_k: self.finish()))
+
     def graph_nodes(self):
         """nodes (kernel launches + torch's few memcpy / memset nodes) of the three captured graphs, when they were kept
-        (graph_utils.KEEP_GRAPHS): {"teacher", "student_fwd", "student_bwd"}"""
+        (graph_utils.KEEP_GRAPHS): {"teacher", "student_fwd", "student_bwd"}; with a captured router also "router_fwd" and
+        "router_bwd_and_optimizer" (under a RouterAdamW: of the main phase when it was captured, else of the pre-training phase,
+        whose own pair is then also reported with the suffix "_pretrain")"""
         cap = self._cap
         if cap is None:
             return None
         n = {"teacher": node_count(cap["g_teacher"]), "student_fwd": node_count(cap["g_student"]),
              "student_bwd": node_count(cap["g_student_bwd"])}
-        if cap.get("router"):
+        rt = cap.get("router")
+        if rt and rt.get("hip"):
+            if True in rt:
+                n["router_fwd_pretrain"] = node_count(rt[True]["g_fwd"])
+                n["router_bwd_and_optimizer_pretrain"] = node_count(rt[True]["g_bwd"])
+            ph = rt.get(False, rt.get(True))
+            n["router_fwd"] = node_count(ph["g_fwd"])
+            n["router_bwd_and_optimizer"] = node_count(ph["g_bwd"])
+        elif rt:
             n["router_fwd"] = node_count(cap["router"]["g_fwd"])
             n["router_bwd_and_optimizer"] = node_count(cap["router"]["g_bwd"])
         return n
@@ -909,6 +1064,10 @@ class GraphedPrunerStep(PrunerStep):
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
         cap = self._cap
         rt = cap.get("router") if cap is not None else None
+        if isinstance(optimizer, RouterAdamW):
+            if rt is not None and rt.get("hip") and rt["optimizer"] is optimizer and bool(pretrain) in rt and self.hyper_net.training:
+                return self._train_step_captured_router(batch, rt[bool(pretrain)])
+            return self._train_step_eager_router_hip(optimizer, batch, bool(pretrain))
         if rt is not None and rt["optimizer"] is optimizer and rt["pretrain"] == bool(pretrain) and self.hyper_net.training:
             return self._train_step_captured_router(batch)
         self.finish()
@@ -920,7 +1079,7 @@ class GraphedPrunerStep(PrunerStep):
         optimizer.step()
         return out
 
-    def _train_step_captured_router(self, batch: dict):
+    def _train_step_captured_router(self, batch: dict, ph=None):
         """the whole step from five graphs: [teacher || router] -> student forward -> losses + U-Net backward -> chain rule into the
         router + optimizer.  The host only stages the batch and refills the Gumbel uniforms from its generator.
 
@@ -928,9 +1087,12 @@ class GraphedPrunerStep(PrunerStep):
         overlap_router (default) they replay on a stream of their own: the NEXT step's batch staging and teacher forward do not
         queue behind this step's router backward + optimizer, they run next to it; the student's forward waits for the code
         (ev_code), the router backward for the U-Net backward (ev_bwd).  Reading router parameters on another stream afterwards
-        needs finish() -- the router modules' forward / state_dict hooks and the eager train_step call it."""
+        needs finish() -- the router modules' forward / state_dict hooks and the eager train_step call it.
+        ph: the graph set of one training phase (router captured under a RouterAdamW); the returned dict then has "applied", a device
+        flag written on the router's stream (1: the step was applied, 0: skipped) -- call finish() before reading it."""
         cfg, cap = self.cfg, self._cap
         rt = cap["router"]
+        ph = rt if ph is None else ph
         main = torch.cuda.current_stream()
         rs = rt["stream"] if self.overlap_router else main
         rt["ev_entry"].record(main)                           # the batch tensors were produced on the caller's stream
@@ -938,9 +1100,9 @@ class GraphedPrunerStep(PrunerStep):
         with torch.cuda.stream(rs):
             rs.wait_event(rt["ev_entry"])
             with torch.no_grad():
-                rt["text"].copy_(batch["mpnet_embeddings"])
-            rt["tape"].refill()                               # host-RNG stream, consumed exactly as the eager calls consume it
-            rt["g_fwd"].replay()                              # router -> architecture code installed for the student
+                ph["text"].copy_(batch["mpnet_embeddings"])
+            ph["tape"].refill()                               # host-RNG stream, consumed exactly as the eager calls consume it
+            ph["g_fwd"].replay()                              # router -> architecture code installed for the student
             rt["ev_code"].record(rs)
         main.wait_event(rt["ev_code"])
         cap["g_student"].replay()
@@ -949,17 +1111,22 @@ class GraphedPrunerStep(PrunerStep):
         rt["ev_bwd"].record(main)
         with torch.cuda.stream(rs):
             rs.wait_event(rt["ev_bwd"])
-            rt["g_bwd"].replay()                              # d(router losses + U-Net terms)/d(router), optimizer step
+            ph["g_bwd"].replay()                              # d(router losses + U-Net terms)/d(router), optimizer step
+            applied = ph["applied"].clone() if "applied" in ph else None
             rt["ev_tail"].record(rs)
         rt["pending"] = rs is not main
-        r = rt["out"]
+        r = ph["out"]
         # (the router graph's outputs were complete at ev_code; the next router forward, which overwrites them, waits for the next
         #  step's ev_entry, i.e. for these clones)
         unet_loss = cap["loss"] + cfg.distillation_weight * cap["dist"] + cfg.block_weight * cap["blk"]
-        return {"loss": (r["router_loss"].detach() + unet_loss).clone(), "diff_loss": cap["loss"].clone(),
-                "distillation_loss": cap["dist"].clone(), "block_loss": cap["blk"].clone(),
-                "contrastive_loss": r["contrastive_loss"].detach().clone(), "resource_loss": r["resource_loss"].detach().clone(),
-                "resource_ratio": r["ratios"].mean().detach(), "arch_vector_quantized": r["arch_vector_quantized"].detach().clone()}
+        out = {"loss": (r["router_loss"].detach() + unet_loss).clone(), "diff_loss": cap["loss"].clone(),
+               "distillation_loss": cap["dist"].clone(), "block_loss": cap["blk"].clone(),
+               "contrastive_loss": r["contrastive_loss"].detach().clone(), "resource_loss": r["resource_loss"].detach().clone(),
+               "resource_ratio": r["ratios"].mean().detach(), "arch_vector_quantized": r["arch_vector_quantized"].detach().clone()}
+        if applied is not None:
+            applied.record_stream(main)
+            out["applied"] = applied
+        return out
 
     def finish(self):
         """make the current stream wait for the router backward + optimizer of the last captured step (they run on the router's own

@@ -708,6 +708,38 @@ typedef struct { float* acc; float* g; int64_t n; int32_t mode; } AptpGradAccumP
 int aptp_grad_accumulate_blocks(int64_t n);   /* grid of the launch: 0 for n <= 0 */
 int aptp_grad_accumulate(const AptpGradAccumParams* p, aptp_stream_t stream);
 
+/* AdamW over many small fp32 tensors with everything a schedule changes in DEVICE memory (csrc/router_optim.hip): the router's
+ * optimizer of a captured pruning step (pdm/training/trainer.py:804-834, 913-933; configs/pruning/sd-2-1_cc3m.yaml).  The
+ * arithmetic per element is aptp_adamw_many's, with
+ *   t      = step[0] + 1                              the ITEM's own count of applied steps (torch keeps one per parameter and
+ *                                                     skips a parameter without a gradient)
+ *   lr_eff = lr_g * min(1, applied / warmup_steps_g)  when warmup_steps_g > 0: `constant_with_warmup` counted in applied steps
+ * items_dev: n_items descriptors in device memory; p, g, m, v fp32 [n], 16-byte aligned; step: fp32 device scalar; group: index
+ * into groups_dev.  starts_dev: int32 [n_items + 1] prefix sums of aptp_group_adamw_blocks(n); total_blocks = starts[n_items].
+ * groups_dev: n_groups entries the host may rewrite between replays of a captured launch.
+ * counters_dev: fp32 [4], 16-byte aligned = {applied steps, skipped steps, bad-gradient flag (0 outside the call), reserved}.
+ * The step is SKIPPED when gate_dev[0] is non-finite or any gradient element of any item is non-finite (NaN or +-Inf; the
+ * reference's anomaly mode raises on NaN only): p, m, v, every step[0] and applied keep their bits and skipped advances by 1;
+ * otherwise every step[0] and applied advance by 1.  zero_grad != 0: the gradients are written to zero in both cases.
+ * Three launches on `stream`: scan, update, advance.  items_host: optional host copy of the table; when given, every item is
+ * checked (non-null, n >= 1, group in range, alignment, block count) before anything is launched.  APTP_EINVAL and nothing
+ * launched for: null pointers, n_items / n_groups / total_blocks < 1, betas outside [0, 1), eps <= 0, grad_scale < 0, a
+ * misaligned table or item. */
+typedef struct { float* p; float* g; float* m; float* v; float* step; int64_t n; int32_t group; } AptpGroupAdamWItem;
+typedef struct { float lr, weight_decay, warmup_steps; } AptpAdamWGroup;
+typedef struct {
+  const AptpGroupAdamWItem* items_dev; const int32_t* starts_dev; int32_t n_items, total_blocks;
+  const AptpAdamWGroup* groups_dev; int32_t n_groups;
+  float* counters_dev;
+  float beta1, beta2, eps;
+  float grad_scale;       /* gradients are multiplied by this before use (0 = 1); the scan looks at the unscaled values */
+  int32_t zero_grad;
+  const float* gate_dev;  /* optional fp32 device scalar, e.g. the step's total loss */
+  const AptpGroupAdamWItem* items_host;
+} AptpGroupAdamWParams;
+int aptp_group_adamw_blocks(int64_t n);
+int aptp_group_adamw(const AptpGroupAdamWParams* p, aptp_stream_t stream);
+
 /* Mean squared error of two equally shaped activations, read where they lie (the loss terms of Pruner.step / FineTuner.step:
  * pdm/training/trainer.py:1197-1225 diffusion MSE, output distillation, block distillation; :1729-1752 for the fine-tune step).
  * backward = 0: out[0] = mean((a - b)^2); partial: fp32 [aptp_mse_nblocks(rows, C)] scratch (every slot is written).

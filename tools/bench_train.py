@@ -22,6 +22,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--eager", action="store_true", help="no HIP graphs (the host-bound reference point)")
+    ap.add_argument("--router-optimizer", choices=("torch", "hip"), default="torch",
+                    help="torch: torch.optim.AdamW, router eager between the U-Net graphs; hip: router_optim.RouterAdamW, the router "
+                         "captured for both phases with its schedule in device memory (DESIGN 6p)")
+    ap.add_argument("--lr-warmup", type=int, default=0, help="hip: constant_with_warmup over this many applied steps")
+    ap.add_argument("--pretrain-steps", type=int, default=0, help="hip: the first P steps run the hyper-net pre-training phase")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     unet = UNet2DConditionModelGated().init_synthetic(seed=0).to(dev)
@@ -35,23 +40,54 @@ def main():
     hn.train(); qz.train()
     step = (PrunerStep if args.eager else GraphedPrunerStep)(unet, hn, qz)
     step.count_macs(args.latent)
-    opt = torch.optim.AdamW(step.trainable_parameters(), lr=2e-4)
+    hip = args.router_optimizer == "hip"
+    if not hip and (args.lr_warmup or args.pretrain_steps):
+        ap.error("--lr-warmup and --pretrain-steps need --router-optimizer hip")
     batch = synthetic_batch(args.batch, args.latent, dev)
-    if not args.eager:
-        step.capture(batch)
+    done = 0
+    if hip:
+        from diffusion_pruning_amd import graph_utils
+        from diffusion_pruning_amd.router_optim import RouterAdamW
+        graph_utils.KEEP_GRAPHS = True                      # (graph_nodes() below)
+        opt = RouterAdamW([{"params": [p for p in hn.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0},
+                           {"params": [p for p in qz.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0}],
+                          warmup_steps=args.lr_warmup)
+        if not args.eager:
+            step.capture(batch, optimizer=opt, pretrain=args.pretrain_steps > 0)
+            if args.pretrain_steps > 0:
+                step.capture_router(batch, pretrain=False)
+
+        def one():
+            nonlocal done
+            o = step.train_step(opt, batch, pretrain=done < args.pretrain_steps)
+            done += 1
+            return o
+    else:
+        opt = torch.optim.AdamW(step.trainable_parameters(), lr=2e-4)
+        if not args.eager:
+            step.capture(batch)
+
+        def one():
+            return step.train_step(opt, batch)
     for _ in range(args.warmup):
-        out = step.train_step(opt, batch)
+        out = one()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        out = step.train_step(opt, batch)
+        out = one()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    extra = {}
+    if hip:
+        if not args.eager:
+            step.finish()
+            extra["graph_nodes"] = step.graph_nodes()
+        extra.update(router_optimizer="hip", applied_steps=opt.applied_steps(), skipped_steps=opt.skipped_steps(), last_lr=opt.last_lr())
     print(json.dumps({"metric": "pruning-train-steps/s (SD-2.1, 64x64 latents, teacher fwd + student fwd/bwd + router)",
                       "value": round(1.0 / dt, 3), "unit": "steps/s", "ms_per_step": round(dt * 1e3, 2),
                       "batch": args.batch, "loss": float(out["loss"].detach()),
                       "resource_ratio": float(out["resource_ratio"]),
-                      "max_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), "mode": "eager (no HIP graph)" if args.eager else "U-Net passes replayed from HIP graphs, router eager"}))
+                      "max_mem_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2), "mode": "eager (no HIP graph)" if args.eager else ("U-Net passes and router replayed from HIP graphs" if hip else "U-Net passes replayed from HIP graphs, router eager"), **extra}))
 
 
 if __name__ == "__main__":
