@@ -2,9 +2,12 @@
 
 ``new_graph()`` is ``torch.cuda.CUDAGraph()``; with ``KEEP_GRAPHS`` set (bench.py does, before capturing) the captured
 hipGraph_t is kept next to its executable so that ``node_count`` can ask the runtime how many nodes -- kernel launches and
-the few memcpy / memset nodes torch adds -- one replay issues.  Nothing here touches the device unless a graph exists."""
+the few memcpy / memset nodes torch adds -- one replay issues.  ``warmup_stream()`` is the eager pass ahead of a capture and
+``concurrent_stream()`` picks the side stream a replayed graph overlaps on; nothing else here touches the device unless a graph
+exists."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Optional
 
@@ -35,6 +38,18 @@ def node_count(graph) -> Optional[int]:
         return int(n.value) if rc == 0 else None
     except Exception:  # noqa: BLE001
         return None
+
+
+@contextlib.contextmanager
+def warmup_stream():
+    """The eager warm-up ahead of a capture (allocator, plan caches, autograd's stream anchors) runs inside: on a fresh side
+    stream that waits for the current one; on the way out the current stream joins it and the host waits for the device"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        yield side
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
 
 
 def concurrent_stream(main: Optional["torch.cuda.Stream"] = None, tries: int = 12, spin_ms: float = 0.4, log=None) -> "torch.cuda.Stream":

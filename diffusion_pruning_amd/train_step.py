@@ -16,10 +16,10 @@ small all-gathers of the step are fused into one.
 """
 from __future__ import annotations
 
+import contextlib
+import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
-
-import os
 
 import torch
 import torch.distributed as dist
@@ -27,7 +27,7 @@ import torch.nn.functional as F
 
 from . import dist_utils
 from . import autograd as AG
-from .graph_utils import concurrent_stream, new_graph, node_count
+from .graph_utils import concurrent_stream, new_graph, node_count, warmup_stream
 from . import ops
 from .dist_utils import _rank, _span, _world
 from .losses import ContrastiveLoss, ResourceLoss, compute_snr
@@ -299,7 +299,7 @@ class ArenaGradReducer:
         if cuda:
             main = torch.cuda.current_stream()
             self.stream.wait_stream(main)              # the gradients are complete on the launching stream
-        ctx = torch.cuda.stream(self.stream) if cuda else _NullCtx()
+        ctx = torch.cuda.stream(self.stream) if cuda else contextlib.nullcontext()
         with ctx:
             for i, (bk, sh) in enumerate(zip(self.buckets, self.shards)):
                 with _span("grad bucket %d" % i):
@@ -317,14 +317,6 @@ class ArenaGradReducer:
                 torch.cuda.current_stream().wait_event(self.events[i])
             if on_bucket is not None:
                 on_bucket(i)
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
 
 
 def _mse(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -345,18 +337,76 @@ def _mse_per_sample(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return d.mean(dim=list(range(1, d.dim())))
 
 
-# ---- validation (Pruner.validate / FineTuner.validate, trainer.py:1026-1095, 1767-1818) -------------------------------------
-VAL_KEYS = ("loss", "diff_loss", "distillation_loss", "block_loss")
-
-
+# ---- the loss pieces of every step: eager and captured, training and validation, both families -----------------
 def _min_snr_weights(cfg, schedule, timesteps) -> torch.Tensor:
-    """min-SNR-gamma weights as fp32 [B] (trainer.py:1203-1213, 1736-1749): the expression of the training steps"""
+    """min-SNR-gamma weights as fp32 [B] (trainer.py:1203-1213, 1736-1749), with ``snr + 1`` for v-prediction; ones without a
+    gamma.  The captured steps keep the alpha-bar table on the device, so their teacher graphs evaluate this from the staged
+    timesteps"""
     if cfg.snr_gamma is None:
         return torch.ones(timesteps.shape[0], device=timesteps.device)
     snr = compute_snr(schedule, timesteps)
     if cfg.prediction_type == "v_prediction":
         snr = snr + 1
     return (torch.stack([snr, cfg.snr_gamma * torch.ones_like(timesteps)], dim=1).min(dim=1)[0] / snr).float()
+
+
+def _diffusion_term(cfg, model_pred, target, w) -> torch.Tensor:
+    """the diffusion loss (trainer.py:1197-1216, 1736-1752): plain MSE, or the mean of the per-sample MSEs times `w`
+    (_min_snr_weights)"""
+    if cfg.snr_gamma is None:
+        return _mse(model_pred, target)
+    return (_mse_per_sample(model_pred, target) * w).mean()
+
+
+def _block_term(acts_s, acts_t) -> torch.Tensor:
+    """block distillation (trainer.py:1220-1225, 1754-1759): the mean over the hooked blocks of MSE(student, teacher)"""
+    total = torch.zeros((), device=next(iter(acts_s.values())).device)
+    for k in acts_s:
+        total = total + _mse(acts_s[k], acts_t[k])
+    return total / len(acts_s)
+
+
+def _block_output_hooks(model, acts: dict) -> list:
+    """trainer.py:496-511: forward hooks that leave every block's output in `acts` under d0.. / m / u0.. (down blocks return
+    (output, residuals)); returns the handles"""
+    def mk(name, residuals_present):
+        if residuals_present:
+            return lambda m, i, o: acts.__setitem__(name, o[0])
+        return lambda m, i, o: acts.__setitem__(name, o)
+    hooks = [b.register_forward_hook(mk("d" + str(i), True)) for i, b in enumerate(model.down_blocks)]
+    hooks.append(model.mid_block.register_forward_hook(mk("m", False)))
+    hooks += [b.register_forward_hook(mk("u" + str(i), False)) for i, b in enumerate(model.up_blocks)]
+    return hooks
+
+
+# ---- what the captured steps share ---------------------------------------------------------------------------------------
+_BATCH_KEYS = ("noisy_latents", "timesteps", "encoder_hidden_states", "target")      # the tensors a captured U-Net pass reads
+
+
+def _stage_batch(st: dict, batch) -> None:
+    """copy a batch (a dict, or the four tensors in _BATCH_KEYS order) into the static tensors the graphs read"""
+    if not isinstance(batch, dict):
+        batch = dict(zip(_BATCH_KEYS, batch))
+    with torch.no_grad():
+        for k in _BATCH_KEYS:
+            st[k].copy_(batch[k])
+
+
+@contextlib.contextmanager
+def _launch_log_off():
+    """ops.LAUNCH_LOG (bench.py: the contractions of ONE step, re-timed for the family roofline) is filled by an eager warm-up pass,
+    never by a capture: a log entry keeps its operands alive, and a capture that cannot recycle any activation spreads the step
+    over several times the memory -- its replays were measured ~7 % slower.  None inside, restored on the way out, also by an
+    exception"""
+    user_log, ops.LAUNCH_LOG = ops.LAUNCH_LOG, None
+    try:
+        yield
+    finally:
+        ops.LAUNCH_LOG = user_log
+
+
+# ---- validation (Pruner.validate / FineTuner.validate, trainer.py:1026-1095, 1767-1818) -------------------------------------
+VAL_KEYS = ("loss", "diff_loss", "distillation_loss", "block_loss")
 
 
 def _unet_loss_terms(cfg, model_pred, target, full_pred, acts_s, acts_t, w, group_coef, blocks: bool = True,
@@ -410,22 +460,7 @@ class PrunerStep:
         self.contrastive = ContrastiveLoss(self.cfg.arch_vector_temperature, self.cfg.prompt_embedding_temperature)
         self.resource = ResourceLoss(p=self.cfg.pruning_target, loss_type=self.cfg.resource_type)
         self.block_activations: Dict[str, torch.Tensor] = {}
-        self._hooks = []
-        self._cast_block_act_hooks()
-
-    # trainer.py:496-511
-    def _cast_block_act_hooks(self):
-        acts = self.block_activations
-
-        def mk(name, residuals_present):
-            if residuals_present:
-                return lambda m, i, o: acts.__setitem__(name, o[0])
-            return lambda m, i, o: acts.__setitem__(name, o)
-        for i, b in enumerate(self.unet.down_blocks):
-            self._hooks.append(b.register_forward_hook(mk("d" + str(i), True)))
-        self._hooks.append(self.unet.mid_block.register_forward_hook(mk("m", False)))
-        for i, b in enumerate(self.unet.up_blocks):
-            self._hooks.append(b.register_forward_hook(mk("u" + str(i), False)))
+        self._hooks = _block_output_hooks(self.unet, self.block_activations)
 
     def remove_hooks(self):
         for h in self._hooks:
@@ -444,50 +479,64 @@ class PrunerStep:
         p = self.cfg.pruning_target
         self.resource.p = float(1 - (1 - p) * info["total_macs"] / float(torch.as_tensor(info["cur_prunable_macs"]).flatten()[0]))
 
-    def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False):
-        cfg = self.cfg
+    # ---- the router head and the MAC losses: one definition for the eager, the validation and the captured paths ----------------
+    def _route(self, text_embeddings, pretrain: bool):
+        """hyper-net -> quantiser -> Gumbel-sigmoid relaxation -> cross-rank gather -> contrastive loss (trainer.py:1129-1171).
+        Returns (arch_vector, arch_vector_quantized, arch_used, contrastive_loss); arch_used is the code the student runs under."""
         arch_vector = self.hyper_net(text_embeddings)                                           # :1129
         arch_vector_quantized, _ = self.quantizer(arch_vector)                                  # :1130
         arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)                          # :1132
         arch_vector = self._single_arch_repeat(arch_vector, text_embeddings.shape[0])           # :1134-1136
         arch_wdn = self.quantizer.width_depth_normalize(arch_vector)                            # :1138
         text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)                  # :1147-1162 (one collective)
-        sep = self.hyper_net.transform_structure_vector(arch_vector if pretrain else arch_vector_quantized)   # :1165-1168
+        arch_used = arch_vector if pretrain else arch_vector_quantized                          # :1165-1168
         contrastive_loss = self.contrastive(text_all, arch_all)                                 # :1170-1171
+        return arch_vector, arch_vector_quantized, arch_used, contrastive_loss
 
-        with torch.no_grad():                                                                   # :1185-1190 teacher
-            full = self.hyper_net.transform_structure_vector(torch.ones_like(arch_vector))
-            self.unet.set_structure(full)
-            full_pred = self.unet(noisy_latents, timesteps, encoder_hidden_states).sample.detach()
-            teacher_acts = dict(self.block_activations)
-        self.unet.set_structure(sep)                                                            # :1192-1195 student
-        model_pred = self.unet(noisy_latents, timesteps, encoder_hidden_states).sample
-        student_acts = dict(self.block_activations)
-
-        if cfg.snr_gamma is None:                                                               # :1197-1216
-            loss = _mse(model_pred, target)
-        else:
-            snr = compute_snr(self.schedule, timesteps)
-            if cfg.prediction_type == "v_prediction":
-                snr = snr + 1
-            w = torch.stack([snr, cfg.snr_gamma * torch.ones_like(timesteps)], dim=1).min(dim=1)[0] / snr
-            loss = (_mse_per_sample(model_pred, target) * w).mean()
-        distillation_loss = _mse(model_pred, full_pred)  # :1218
-        block_loss = torch.zeros((), device=model_pred.device)
-        for k in student_acts:                                                                  # :1220-1225
-            block_loss = block_loss + _mse(student_acts[k], teacher_acts[k])
-        block_loss = block_loss / len(student_acts)
-
-        macs = self.unet.calc_macs()                                                            # :1227-1238
+    def _mac_losses(self, macs):
+        """trainer.py:1227-1238 from a calc_macs()-style dict: (ratios, resource_loss, max_loss, std_loss)"""
         ratios = macs["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"].squeeze()
         resource_loss = self.resource(ratios.mean())
         max_loss = 1.0 - torch.max(ratios)
         std_loss = -torch.std(ratios)
+        return ratios, resource_loss, max_loss, std_loss
 
-        diff_loss = loss.detach().clone()
-        loss = loss + cfg.resource_weight * resource_loss + cfg.contrastive_weight * contrastive_loss \
+    def _unet_losses(self, model_pred, student_acts, full_pred, teacher_acts, w, target):
+        """the three U-Net terms in the pruner's order -- diffusion, output distillation, block distillation (trainer.py:1197-1225);
+        autograd sums into model_pred in reverse creation order, so the order is part of the gradients' bits"""
+        loss = _diffusion_term(self.cfg, model_pred, target, w)
+        distillation_loss = _mse(model_pred, full_pred)
+        return loss, distillation_loss, _block_term(student_acts, teacher_acts)
+
+    def _total_loss(self, loss, resource_loss, contrastive_loss, distillation_loss, block_loss, std_loss, max_loss):
+        """trainer.py:1240-1249, in the eager step's operand order"""
+        cfg = self.cfg
+        return loss + cfg.resource_weight * resource_loss + cfg.contrastive_weight * contrastive_loss \
             + cfg.distillation_weight * distillation_loss + cfg.block_weight * block_loss \
-            + cfg.std_weight * std_loss + cfg.max_weight * max_loss                               # :1240-1249
+            + cfg.std_weight * std_loss + cfg.max_weight * max_loss
+
+    def _forward_pair(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, pretrain: bool):
+        """router, dense teacher pass under no_grad, student pass under the routed code:
+        (_route's tuple, full_pred, teacher_acts, model_pred, student_acts)"""
+        route = self._route(text_embeddings, pretrain)
+        arch_vector, _, arch_used, _ = route
+        sep = self.hyper_net.transform_structure_vector(arch_used)
+        with torch.no_grad():                                                                   # :1185-1190 teacher
+            self.unet.set_structure(self.hyper_net.transform_structure_vector(torch.ones_like(arch_vector)))
+            full_pred = self.unet(noisy_latents, timesteps, encoder_hidden_states).sample.detach()
+            teacher_acts = dict(self.block_activations)
+        self.unet.set_structure(sep)                                                            # :1192-1195 student
+        model_pred = self.unet(noisy_latents, timesteps, encoder_hidden_states).sample
+        return route, full_pred, teacher_acts, model_pred, dict(self.block_activations)
+
+    def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False):
+        (_, arch_vector_quantized, _, contrastive_loss), full_pred, teacher_acts, model_pred, student_acts = \
+            self._forward_pair(noisy_latents, timesteps, encoder_hidden_states, text_embeddings, pretrain)
+        w = _min_snr_weights(self.cfg, self.schedule, timesteps)
+        loss, distillation_loss, block_loss = self._unet_losses(model_pred, student_acts, full_pred, teacher_acts, w, target)
+        ratios, resource_loss, max_loss, std_loss = self._mac_losses(self.unet.calc_macs())
+        diff_loss = loss.detach().clone()
+        loss = self._total_loss(loss, resource_loss, contrastive_loss, distillation_loss, block_loss, std_loss, max_loss)
         return {"loss": loss, "diff_loss": diff_loss, "distillation_loss": distillation_loss.detach(),
                 "block_loss": block_loss.detach(), "contrastive_loss": contrastive_loss.detach(),
                 "resource_loss": resource_loss.detach(), "resource_ratio": ratios.mean().detach(),
@@ -501,7 +550,6 @@ class PrunerStep:
         reports, as device scalars; nothing here waits for the device."""
         nl, ts, ehs = batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"]
         text_embeddings, target = batch["mpnet_embeddings"], batch["target"]
-        cfg = self.cfg
         was = (self.hyper_net.training, self.quantizer.training)
         self.hyper_net.eval()
         self.quantizer.eval()
@@ -509,31 +557,13 @@ class PrunerStep:
             if not nl.is_cuda:                 # host tensors (the CPU suite's emulated runs): the training step's own loss code
                 out = self.step(nl, ts, ehs, text_embeddings, target, pretrain=pretrain)
                 return {k: out[k].detach() for k in VAL_KEYS + ("contrastive_loss", "resource_loss")}
-            arch_vector = self.hyper_net(text_embeddings)
-            arch_vector_quantized, _ = self.quantizer(arch_vector)
-            arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)
-            arch_vector = self._single_arch_repeat(arch_vector, text_embeddings.shape[0])
-            arch_wdn = self.quantizer.width_depth_normalize(arch_vector)
-            text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)
-            sep = self.hyper_net.transform_structure_vector(arch_vector if pretrain else arch_vector_quantized)
-            contrastive_loss = self.contrastive(text_all, arch_all)
-            self.unet.set_structure(self.hyper_net.transform_structure_vector(torch.ones_like(arch_vector)))
-            full_pred = self.unet(nl, ts, ehs).sample
-            teacher_acts = dict(self.block_activations)
-            self.unet.set_structure(sep)
-            model_pred = self.unet(nl, ts, ehs).sample
-            student_acts = dict(self.block_activations)
-            w = _min_snr_weights(cfg, self.schedule, ts)
-            u = _unet_loss_terms(cfg, model_pred, target, full_pred, student_acts, teacher_acts, w, (1.0, 0.0, 0.0)).run()
+            (_, _, _, contrastive_loss), full_pred, teacher_acts, model_pred, student_acts = \
+                self._forward_pair(nl, ts, ehs, text_embeddings, pretrain)
+            w = _min_snr_weights(self.cfg, self.schedule, ts)
+            u = _unet_loss_terms(self.cfg, model_pred, target, full_pred, student_acts, teacher_acts, w, (1.0, 0.0, 0.0)).run()
             diff_loss, block_loss, distillation_loss = u[0], u[1], u[2]
-            macs = self.unet.calc_macs()
-            ratios = macs["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"].squeeze()
-            resource_loss = self.resource(ratios.mean())
-            max_loss = 1.0 - torch.max(ratios)
-            std_loss = -torch.std(ratios)
-            loss = diff_loss + cfg.resource_weight * resource_loss + cfg.contrastive_weight * contrastive_loss \
-                + cfg.distillation_weight * distillation_loss + cfg.block_weight * block_loss \
-                + cfg.std_weight * std_loss + cfg.max_weight * max_loss                   # (the expression of `step`)
+            _, resource_loss, max_loss, std_loss = self._mac_losses(self.unet.calc_macs())
+            loss = self._total_loss(diff_loss, resource_loss, contrastive_loss, distillation_loss, block_loss, std_loss, max_loss)
             return {"loss": loss, "diff_loss": diff_loss, "distillation_loss": distillation_loss, "block_loss": block_loss,
                     "contrastive_loss": contrastive_loss, "resource_loss": resource_loss}
         finally:
@@ -651,35 +681,20 @@ class GraphedPrunerStep(PrunerStep):
         self._finish_hooks = []
 
     # ---- capture ------------------------------------------------------------------------------------------------
-    def _snr_weights(self, timesteps):
-        """min-SNR-gamma weights (trainer.py:1203-1213); the alpha-bar table lives on the device (_schedule_on), so the captured
-        teacher graph computes them from the staged timesteps"""
-        cfg = self.cfg
-        if cfg.snr_gamma is None:
-            return torch.ones(timesteps.shape[0], device=timesteps.device)
-        snr = compute_snr(self.schedule, timesteps)
-        if cfg.prediction_type == "v_prediction":
-            snr = snr + 1
-        return (torch.stack([snr, cfg.snr_gamma * torch.ones_like(timesteps)], dim=1).min(dim=1)[0] / snr).float()
-
     def _schedule_on(self, device):
         # keep the alpha-bar table on the device: a pageable host->device copy per step would make the host wait for the
         # previous step's graphs
         if self.schedule.alphas_cumprod.device != device:
             self.schedule.alphas_cumprod = self.schedule.alphas_cumprod.to(device)
 
-    def _unet_losses(self, model_pred, student_acts, full_pred, teacher_acts, w, target):
+    # the captured step's total is router_loss.detach() + unet_loss: the eager sum (_total_loss) split where the graphs split it
+    def _router_loss(self, resource_loss, contrastive_loss, std_loss, max_loss):
         cfg = self.cfg
-        if cfg.snr_gamma is None:
-            loss = _mse(model_pred, target)
-        else:
-            loss = (_mse_per_sample(model_pred, target) * w).mean()
-        distillation_loss = _mse(model_pred, full_pred)
-        block_loss = torch.zeros((), device=model_pred.device)
-        for k in student_acts:
-            block_loss = block_loss + _mse(student_acts[k], teacher_acts[k])
-        block_loss = block_loss / len(student_acts)
-        return loss, distillation_loss, block_loss
+        return cfg.resource_weight * resource_loss + cfg.contrastive_weight * contrastive_loss \
+            + cfg.std_weight * std_loss + cfg.max_weight * max_loss
+
+    def _unet_loss(self, loss, distillation_loss, block_loss):
+        return loss + self.cfg.distillation_weight * distillation_loss + self.cfg.block_weight * block_loss
 
     def capture(self, batch: dict, optimizer=None, pretrain: bool = False):
         """Capture the graphs for this batch geometry (call once; later batches must have the same shapes).
@@ -692,9 +707,9 @@ class GraphedPrunerStep(PrunerStep):
         router_optim.RouterAdamW serves both phases, a warm-up, the NaN batch skip and a resume from one capture."""
         cfg = self.cfg
         dev = batch["noisy_latents"].device
-        st = {k: batch[k].clone() for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target")}
+        st = {k: batch[k].clone() for k in _BATCH_KEYS}
         self._schedule_on(dev)
-        st["snr_w"] = self._snr_weights(st["timesteps"])
+        st["snr_w"] = _min_snr_weights(cfg, self.schedule, st["timesteps"])
         B = st["noisy_latents"].shape[0]
         ones = torch.ones((B, self.quantizer.vq_embed_dim), device=dev)
         full = self.hyper_net.transform_structure_vector(ones)
@@ -736,7 +751,7 @@ class GraphedPrunerStep(PrunerStep):
             with torch.no_grad(), ops.scratch_domain("teacher"):
                 # the min-SNR weights of this batch: a dozen tiny launches that only the loss terms read -- inside this graph they
                 # run on the side stream next to the router instead of ahead of everything on the caller's stream (0.8 ms of a step)
-                st["snr_w"].copy_(self._snr_weights(st["timesteps"]))
+                st["snr_w"].copy_(_min_snr_weights(cfg, self.schedule, st["timesteps"]))
                 pred = self.unet(st["noisy_latents"], st["timesteps"], st["encoder_hidden_states"]).sample.detach()
                 return pred, dict(self.block_activations)
 
@@ -746,37 +761,29 @@ class GraphedPrunerStep(PrunerStep):
 
         def student_bwd(pred, acts, full_pred, teacher_acts):
             loss, dist, blk = self._unet_losses(pred, acts, full_pred, teacher_acts, st["snr_w"], st["target"])
-            total = loss + cfg.distillation_weight * dist + cfg.block_weight * blk
-            grads = torch.autograd.grad(total, gw + gd, allow_unused=True)
+            grads = torch.autograd.grad(self._unet_loss(loss, dist, blk), gw + gd, allow_unused=True)
             flat = torch.cat([(torch.zeros_like(t) if g is None else g).reshape(-1) for g, t in zip(grads, gw + gd)])
             grad = flat[inv].view(B, E)                        # back to the architecture vector's [B, 1634] order
             return loss.detach(), dist.detach(), blk.detach(), grad
 
         # warm-up on a side stream (allocator / plan caches), then capture: the module state at capture time decides what
         # is baked in, so the structure is installed right before each capture
-        # ops.LAUNCH_LOG (bench.py: the contractions of ONE step, re-timed for the family roofline) is filled by this eager pass,
-        # never by the captures: a log entry keeps its operands alive, and a capture that cannot recycle any activation spreads
-        # the step over several times the memory -- its replays were measured ~7 % slower
+        # ops.LAUNCH_LOG is filled by this eager pass, never by the captures (_launch_log_off)
         user_log = ops.LAUNCH_LOG
         log0 = None if user_log is None else len(user_log)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        with warmup_stream():
             self.unet.set_structure({"width": list(full["width"]), "depth": list(full["depth"])})
             fp, ta = teacher()
             self.unet.set_structure({"width": list(gw), "depth": list(gd)})
             student_bwd(*student_fwd(), fp, ta)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
         launch_log = None if user_log is None else user_log[log0:]
-        ops.LAUNCH_LOG = None
 
         # THREE graphs.  The student's forward does not read the teacher (only the loss terms do), so it is its own graph:
         # at replay it starts as soon as the router has produced the code, NEXT TO the teacher graph that has been running
         # on the side stream since the batch arrived; the loss + backward graph joins the two.  Graphs that replay
         # concurrently must not share a memory pool (a pool hands one capture's freed scratch to the next capture, which is
         # only safe when replays are serialised in capture order): the teacher has its own, the two student graphs share one.
-        try:
+        with _launch_log_off():
             self.unet.set_structure({"width": list(full["width"]), "depth": list(full["depth"])})
             g_teacher = new_graph()
             with torch.cuda.graph(g_teacher):
@@ -788,105 +795,26 @@ class GraphedPrunerStep(PrunerStep):
             g_student_bwd = new_graph()
             with torch.cuda.graph(g_student_bwd, pool=g_student.pool()):
                 loss, dist, blk, grad = student_bwd(pred, acts, full_pred, teacher_acts)
-        finally:
-            ops.LAUNCH_LOG = user_log
         # (everything a captured kernel reads must outlive the graphs: `inv` is an operand of the gather that ends g_student_bwd)
         self._cap = dict(st=st, ga=ga, install_code=install_code, perm=perm, inv=inv, full=full, pred=pred, acts=acts, teacher_acts=teacher_acts, gw=gw, gd=gd, g_teacher=g_teacher, g_student=g_student, g_student_bwd=g_student_bwd,
                          loss=loss, dist=dist, blk=blk, grad=grad, full_pred=full_pred, side=concurrent_stream(log=self.stream_probe), vmacs=vmacs,
                          launch_log=launch_log, router=None)
         if optimizer is not None and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
-            if isinstance(optimizer, RouterAdamW):
-                self._capture_router_hip(batch, optimizer, pretrain)
-            else:
-                self._capture_router(batch, optimizer, pretrain)       # (`dist` is the distillation loss in this scope)
+            self._capture_router(batch, optimizer, pretrain)           # (`dist` is the distillation loss in this scope)
         return self
 
-    # ---- the router as two more graphs ----------------------------------------------------------------------------------
+    # ---- the router as two more graphs per training phase -------------------------------------------
     def _router_forward(self, text_embeddings, pretrain: bool):
-        """hyper-net -> quantiser -> Gumbel-sigmoid relaxation -> contrastive / MAC losses (step() up to the student's code)"""
-        cfg, cap = self.cfg, self._cap
-        arch_vector = self.hyper_net(text_embeddings)
-        arch_vector_quantized, _ = self.quantizer(arch_vector)
-        arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)
-        arch_vector = self._single_arch_repeat(arch_vector, text_embeddings.shape[0])
-        arch_wdn = self.quantizer.width_depth_normalize(arch_vector)
-        text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)
-        arch_used = arch_vector if pretrain else arch_vector_quantized                          # trainer.py:1165-1168
-        contrastive_loss = self.contrastive(text_all, arch_all)
-        macs = cap["vmacs"](arch_used)
-        ratios = macs["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"].squeeze()
-        resource_loss = self.resource(ratios.mean())
-        max_loss = 1.0 - torch.max(ratios)
-        std_loss = -torch.std(ratios)
-        router_loss = cfg.resource_weight * resource_loss + cfg.contrastive_weight * contrastive_loss \
-            + cfg.std_weight * std_loss + cfg.max_weight * max_loss
+        """the router head and its own losses, MACs from the router-connected code (step() up to the student's code)"""
+        _, arch_vector_quantized, arch_used, contrastive_loss = self._route(text_embeddings, pretrain)
+        # MAC accounting is differentiable in the gates (calc_macs family): VectorizedMacs evaluates it on the router-connected
+        # architecture vector directly (same numbers as unet.calc_macs() after set_structure, tests/test_macs_pinned.py) in
+        # ~10 kernels instead of ~2,000, before the student replay is queued, so the host never waits on the graphs.
+        ratios, resource_loss, max_loss, std_loss = self._mac_losses(self._cap["vmacs"](arch_used))
         return dict(arch_used=arch_used, arch_vector_quantized=arch_vector_quantized, contrastive_loss=contrastive_loss,
-                    resource_loss=resource_loss, ratios=ratios, router_loss=router_loss)
+                    resource_loss=resource_loss, ratios=ratios,
+                    router_loss=self._router_loss(resource_loss, contrastive_loss, std_loss, max_loss))
 
-    def _capture_router(self, batch, optimizer, pretrain):
-        from . import estimation_utils as EU
-        cap = self._cap
-        assert optimizer.defaults.get("capturable", False), "GraphedPrunerStep.capture(optimizer=): the optimizer must be capturable"
-        params = self.trainable_parameters()
-        text = batch["mpnet_embeddings"].clone()
-        tape = EU.NoiseTape()
-        saved_p = [p.detach().clone() for p in params]
-        host_rng = torch.get_rng_state()
-
-        def fwd():
-            tape.begin()
-            EU.NOISE_TAPE = tape
-            try:
-                r = self._router_forward(text, pretrain)
-            finally:
-                EU.NOISE_TAPE = None
-            with torch.no_grad():
-                cap["install_code"](r["arch_used"])
-            return r
-
-        def bwd(r):
-            ts = [r["arch_used"]] if r["arch_used"].requires_grad else []
-            torch.autograd.backward([r["router_loss"]] + ts, [None] + ([cap["grad"]] if ts else []))
-            optimizer.step()
-
-        # warm-up on a side stream: allocator, caches (gather indices, segment maps), the optimizer's state tensors; then undo it --
-        # parameters, moments and step counts return to their values (in place: their addresses go into the graphs) and the host
-        # generator to its state, so capturing costs the training run nothing
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                for p in params:
-                    p.grad = None
-                bwd(fwd())
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        with torch.no_grad():
-            for p, s0 in zip(params, saved_p):
-                p.copy_(s0)
-            for stt in optimizer.state.values():
-                for v in stt.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-        for p in params:
-            p.grad = None
-        g_fwd = new_graph()
-        with torch.cuda.graph(g_fwd):
-            r = fwd()
-        g_bwd = new_graph()
-        with torch.cuda.graph(g_bwd, pool=g_fwd.pool()):
-            bwd(r)
-        torch.set_rng_state(host_rng)
-        cap["router"] = dict(g_fwd=g_fwd, g_bwd=g_bwd, out=r, text=text, tape=tape, optimizer=optimizer, pretrain=bool(pretrain),
-                             stream=concurrent_stream(log=self.stream_probe), ev_entry=torch.cuda.Event(), ev_code=torch.cuda.Event(),
-                             ev_bwd=torch.cuda.Event(), ev_tail=torch.cuda.Event(), pending=False)
-        if not self._finish_hooks:
-            # anything that reads the router's parameters outside the captured step first waits for the pending optimizer step
-            for m in (self.hyper_net, self.quantizer):
-                self._finish_hooks.append(m.register_forward_pre_hook(lambda *_a, **_k: self.finish()))
-                self._finish_hooks.append(m.register_state_dict_pre_hook(lambda *_a, **_k: self.finish()))
-
-    # ---- the router under router_optim.RouterAdamW: both phases from one capture (DESIGN 6p) -----------------------------------
     def capture_router(self, batch: dict, pretrain: bool, optimizer=None):
         """Capture the router graphs of the OTHER training phase next to the ones capture(batch, optimizer=RouterAdamW, pretrain=)
         made: train_step(optimizer, batch, pretrain=) then picks a set by its argument, so the switch at
@@ -896,31 +824,34 @@ class GraphedPrunerStep(PrunerStep):
         rt = self._cap.get("router")
         optimizer = optimizer if optimizer is not None else (rt or {}).get("optimizer")
         assert isinstance(optimizer, RouterAdamW), "capture_router: the router is captured per phase under a router_optim.RouterAdamW"
-        assert rt is None or (rt.get("hip") and rt["optimizer"] is optimizer), "capture_router: another optimizer was captured"
+        assert not rt or (rt["hip"] and rt["optimizer"] is optimizer), "capture_router: another optimizer was captured"
         assert not (torch.distributed.is_available() and torch.distributed.is_initialized()), \
             "capture_router: with a process group the router stays eager (its collectives are not captured)"
-        self._capture_router_hip(batch, optimizer, pretrain)
+        self._capture_router(batch, optimizer, pretrain)
         return self
 
-    def _capture_router_hip(self, batch, optimizer, pretrain):
+    def _capture_router(self, batch, optimizer, pretrain):
+        """One phase of the router as g_fwd (router -> code installed for the student) and g_bwd (chain rule into the router +
+        optimizer step) in one pool, under either kind of optimizer.  cap["router"] holds optimizer, stream, events and `pending`;
+        each captured phase sits under its bool(pretrain).  A torch optimizer (capturable, fresh, constant rate) has one phase: a
+        capture under it replaces the record.  A RouterAdamW adds phases to its record and gates the step on the total loss."""
         from . import estimation_utils as EU
-        cfg, cap = self.cfg, self._cap
-        pretrain = bool(pretrain)
+        cap, pretrain = self._cap, bool(pretrain)
+        hip = isinstance(optimizer, RouterAdamW)
         rt = cap.get("router")
-        assert rt is None or rt.get("hip"), "capture: the router was already captured under a torch optimizer"
-        assert set(map(id, self.trainable_parameters())) == set(map(id, optimizer.params)), \
-            "capture: the RouterAdamW must hold exactly trainable_parameters()"
-        optimizer.before_access = self.finish
-        self.finish()
+        params = self.trainable_parameters()
+        if hip:
+            assert not rt or rt["hip"], "capture: the router was already captured under a torch optimizer"
+            assert set(map(id, params)) == set(map(id, optimizer.params)), "capture: the RouterAdamW must hold exactly trainable_parameters()"
+            optimizer.before_access = self.finish
+            self.finish()
+        else:
+            assert optimizer.defaults.get("capturable", False), "GraphedPrunerStep.capture(optimizer=): the optimizer must be capturable"
+            rt = None
         text = batch["mpnet_embeddings"].clone()
         tape = EU.NoiseTape()
-        dev = text.device
-        gate = torch.zeros(1, dtype=torch.float32, device=dev)          # the step's total loss: AptpGroupAdamWParams.gate_dev
-        applied = torch.zeros(1, dtype=torch.float32, device=dev)       # 1 when the step was applied, 0 when it was skipped
-        # capturing costs the run nothing, in any state: everything the warm-up iterations change is put back IN PLACE (the
-        # addresses are in the kernel's tables and go into the graphs) -- nothing is blanket-zeroed
-        snap = optimizer._snapshot()
         host_rng = torch.get_rng_state()
+        ph = dict(text=text, tape=tape)
 
         def fwd():
             tape.begin()
@@ -937,39 +868,70 @@ class GraphedPrunerStep(PrunerStep):
             ts = [r["arch_used"]] if r["arch_used"].requires_grad else []
             torch.autograd.backward([r["router_loss"]] + ts, [None] + ([cap["grad"]] if ts else []))
 
-        def bwd(r, key):
-            backward_only(r)                                         # accumulates into the static, zero-filled .grad tensors in place
-            with torch.no_grad():
-                total = r["router_loss"].detach() + cap["loss"] + cfg.distillation_weight * cap["dist"] + cfg.block_weight * cap["blk"]
-                gate.copy_(total.reshape(1))
-                applied.copy_(optimizer.counters[0:1])
-                optimizer.step(table=key, gate=gate)
-                torch.sub(optimizer.counters[0:1], applied, out=applied)
+        # The warm-up (allocator, caches -- gather indices, segment maps --, the optimizer's state tensors) takes optimizer steps;
+        # capturing must cost the training run nothing, so they are undone IN PLACE (the addresses go into the graphs).
+        if hip:
+            # in any state of the run: everything the warm-up changes is snapshotted and put back, nothing is blanket-zeroed
+            ph["gate"] = gate = torch.zeros(1, dtype=torch.float32, device=text.device)     # the step's total loss: AptpGroupAdamWParams.gate_dev
+            ph["applied"] = applied = torch.zeros(1, dtype=torch.float32, device=text.device)   # 1: the step was applied, 0: skipped
+            snap = optimizer._snapshot()
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            key, _ = self._probe_phase_table(optimizer, pretrain, lambda: backward_only(fwd()))
-            optimizer.zero_grad()
+            def optimizer_step(r):                    # (the backward accumulated into the static, zero-filled .grad tensors in place)
+                with torch.no_grad():
+                    gate.copy_((r["router_loss"].detach() + self._unet_loss(cap["loss"], cap["dist"], cap["blk"])).reshape(1))
+                    applied.copy_(optimizer.counters[0:1])
+                    optimizer.step(table=ph["table"], gate=gate)
+                    torch.sub(optimizer.counters[0:1], applied, out=applied)
+
+            def undo_warmup():
+                optimizer._restore(snap)
+                torch.cuda.synchronize()
+        else:
+            # a fresh optimizer: parameters back to their values, moments and step counts to zero
+            saved_p = [p.detach().clone() for p in params]
+
+            def optimizer_step(r):
+                optimizer.step()
+
+            def undo_warmup():
+                with torch.no_grad():
+                    for p, s0 in zip(params, saved_p):
+                        p.copy_(s0)
+                    for stt in optimizer.state.values():
+                        for v in stt.values():
+                            if torch.is_tensor(v):
+                                v.zero_()
+                for p in params:
+                    p.grad = None
+
+        def bwd(r):
+            backward_only(r)
+            optimizer_step(r)
+
+        with warmup_stream():
+            if hip:
+                ph["table"], _ = self._probe_phase_table(optimizer, pretrain, lambda: backward_only(fwd()))
+                optimizer.zero_grad()
             for _ in range(2):
-                bwd(fwd(), key)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        optimizer._restore(snap)
-        torch.cuda.synchronize()
-        g_fwd = new_graph()
-        with torch.cuda.graph(g_fwd):
-            r = fwd()
-        g_bwd = new_graph()
-        with torch.cuda.graph(g_bwd, pool=g_fwd.pool()):
-            bwd(r, key)
+                if not hip:
+                    for p in params:
+                        p.grad = None
+                bwd(fwd())
+        undo_warmup()
+        ph["g_fwd"] = new_graph()
+        with torch.cuda.graph(ph["g_fwd"]):
+            ph["out"] = fwd()
+        ph["g_bwd"] = new_graph()
+        with torch.cuda.graph(ph["g_bwd"], pool=ph["g_fwd"].pool()):
+            bwd(ph["out"])
         torch.set_rng_state(host_rng)
-        if rt is None:
-            rt = cap["router"] = dict(hip=True, optimizer=optimizer, stream=concurrent_stream(log=self.stream_probe),
+        if not rt:
+            rt = cap["router"] = dict(hip=hip, optimizer=optimizer, stream=concurrent_stream(log=self.stream_probe),
                                       ev_entry=torch.cuda.Event(), ev_code=torch.cuda.Event(), ev_bwd=torch.cuda.Event(),
                                       ev_tail=torch.cuda.Event(), pending=False)
-        rt[pretrain] = dict(g_fwd=g_fwd, g_bwd=g_bwd, out=r, text=text, tape=tape, gate=gate, applied=applied, table=key)
+        rt[pretrain] = ph
         if not self._finish_hooks:
+            # anything that reads the router's parameters outside the captured step first waits for the pending optimizer step
             for m in (self.hyper_net, self.quantizer):
                 self._finish_hooks.append(m.register_forward_pre_hook(lambda *_a, **_k: self.finish()))
                 self._finish_hooks.append(m.register_state_dict_pre_hook(lambda *_a, **_k: self.finish()))
@@ -985,67 +947,44 @@ class GraphedPrunerStep(PrunerStep):
         n = {"teacher": node_count(cap["g_teacher"]), "student_fwd": node_count(cap["g_student"]),
              "student_bwd": node_count(cap["g_student_bwd"])}
         rt = cap.get("router")
-        if rt and rt.get("hip"):
-            if True in rt:
+        if rt:
+            if rt["hip"] and True in rt:
                 n["router_fwd_pretrain"] = node_count(rt[True]["g_fwd"])
                 n["router_bwd_and_optimizer_pretrain"] = node_count(rt[True]["g_bwd"])
             ph = rt.get(False, rt.get(True))
             n["router_fwd"] = node_count(ph["g_fwd"])
             n["router_bwd_and_optimizer"] = node_count(ph["g_bwd"])
-        elif rt:
-            n["router_fwd"] = node_count(cap["router"]["g_fwd"])
-            n["router_bwd_and_optimizer"] = node_count(cap["router"]["g_bwd"])
         return n
 
     # ---- one step -------------------------------------------------------------------------------------------------------
     def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False):
         if self._cap is None:
             return super().step(noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain)
-        cfg, cap = self.cfg, self._cap
-        self._stage_batch_and_launch_teacher(noisy_latents, timesteps, encoder_hidden_states, target)
-        arch_vector = self.hyper_net(text_embeddings)
-        arch_vector_quantized, _ = self.quantizer(arch_vector)
-        arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)
-        arch_vector = self._single_arch_repeat(arch_vector, text_embeddings.shape[0])
-        arch_wdn = self.quantizer.width_depth_normalize(arch_vector)
-        text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)
-        arch_used = arch_vector if pretrain else arch_vector_quantized                          # trainer.py:1165-1168
-        contrastive_loss = self.contrastive(text_all, arch_all)
-
-        # The teacher depends on the batch only: its graph replays on a side stream WHILE the router above (launch-bound
-        # kernels of a few microseconds each, during which the GPU is mostly idle) is still being issued on this stream.
+        cap = self._cap
+        # The teacher depends on the batch only: its graph replays on a side stream WHILE the router (launch-bound kernels of a
+        # few microseconds each, during which the GPU is mostly idle) is being issued on this stream.
         # Order on the device: batch copies -> [teacher graph || router] -> student graph.
-        # (The copies were queued first thing in this step, see _stage_batch_and_launch_teacher.)
-        # MAC accounting is differentiable in the gates (calc_macs family): VectorizedMacs evaluates it on the router-connected
-        # architecture vector directly (same numbers as unet.calc_macs() after set_structure, tests/test_macs_pinned.py) in
-        # ~10 kernels instead of ~2,000, before the student replay is queued, so the host never waits on the graphs.
-        macs = cap["vmacs"](arch_used)
-        ratios = macs["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"].squeeze()
-        resource_loss = self.resource(ratios.mean())
-        max_loss = 1.0 - torch.max(ratios)
-        std_loss = -torch.std(ratios)
-
+        self._stage_batch_and_launch_teacher(noisy_latents, timesteps, encoder_hidden_states, target)
+        r = self._router_forward(text_embeddings, pretrain)
         with torch.no_grad():
-            cap["install_code"](arch_used)
+            cap["install_code"](r["arch_used"])
         cap["g_student"].replay()                                     # forward: needs the code only
         torch.cuda.current_stream().wait_stream(cap["side"])          # teacher outputs ready
         cap["g_student_bwd"].replay()                                 # losses against the teacher + backward to the code
+        return {**self._captured_losses(r["router_loss"]),
+                "contrastive_loss": r["contrastive_loss"].detach(), "resource_loss": r["resource_loss"].detach(),
+                "resource_ratio": r["ratios"].mean().detach(), "arch_vector_quantized": r["arch_vector_quantized"].detach(),
+                "_router_loss": r["router_loss"], "_gate_tensors": [r["arch_used"]], "_gate_grads": [cap["grad"]]}
 
-        router_loss = cfg.resource_weight * resource_loss + cfg.contrastive_weight * contrastive_loss \
-            + cfg.std_weight * std_loss + cfg.max_weight * max_loss
-        unet_loss = cap["loss"] + cfg.distillation_weight * cap["dist"] + cfg.block_weight * cap["blk"]
-        return {"loss": (router_loss.detach() + unet_loss).clone(), "diff_loss": cap["loss"].clone(),
-                "distillation_loss": cap["dist"].clone(), "block_loss": cap["blk"].clone(),
-                "contrastive_loss": contrastive_loss.detach(), "resource_loss": resource_loss.detach(),
-                "resource_ratio": ratios.mean().detach(), "arch_vector_quantized": arch_vector_quantized.detach(),
-                "_router_loss": router_loss, "_gate_tensors": [arch_used], "_gate_grads": [cap["grad"]]}
+    def _captured_losses(self, router_loss):
+        """the step's total and the three U-Net terms as clones of g_student_bwd's static outputs (the next replay overwrites them)"""
+        cap = self._cap
+        return {"loss": (router_loss.detach() + self._unet_loss(cap["loss"], cap["dist"], cap["blk"])).clone(),
+                "diff_loss": cap["loss"].clone(), "distillation_loss": cap["dist"].clone(), "block_loss": cap["blk"].clone()}
 
     def _stage_batch_and_launch_teacher(self, noisy_latents, timesteps, encoder_hidden_states, target):
         cap = self._cap
-        with torch.no_grad():
-            for k, src in (("noisy_latents", noisy_latents), ("timesteps", timesteps),
-                           ("encoder_hidden_states", encoder_hidden_states), ("target", target)):
-                cap["st"][k].copy_(src)
+        _stage_batch(cap["st"], (noisy_latents, timesteps, encoder_hidden_states, target))
         side = cap["side"]                       # (the min-SNR weights are computed from the staged timesteps inside g_teacher)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -1062,14 +1001,12 @@ class GraphedPrunerStep(PrunerStep):
         torch.autograd.backward([out["_router_loss"]] + ts, [None] + gs)
 
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
-        cap = self._cap
-        rt = cap.get("router") if cap is not None else None
+        rt = self._cap.get("router") if self._cap is not None else None
+        ph = rt.get(bool(pretrain)) if rt and rt["optimizer"] is optimizer else None
+        if ph is not None and self.hyper_net.training:
+            return self._train_step_captured_router(batch, ph)
         if isinstance(optimizer, RouterAdamW):
-            if rt is not None and rt.get("hip") and rt["optimizer"] is optimizer and bool(pretrain) in rt and self.hyper_net.training:
-                return self._train_step_captured_router(batch, rt[bool(pretrain)])
             return self._train_step_eager_router_hip(optimizer, batch, bool(pretrain))
-        if rt is not None and rt["optimizer"] is optimizer and rt["pretrain"] == bool(pretrain) and self.hyper_net.training:
-            return self._train_step_captured_router(batch)
         self.finish()
         optimizer.zero_grad(set_to_none=True)
         out = self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
@@ -1079,7 +1016,7 @@ class GraphedPrunerStep(PrunerStep):
         optimizer.step()
         return out
 
-    def _train_step_captured_router(self, batch: dict, ph=None):
+    def _train_step_captured_router(self, batch: dict, ph: dict):
         """the whole step from five graphs: [teacher || router] -> student forward -> losses + U-Net backward -> chain rule into the
         router + optimizer.  The host only stages the batch and refills the Gumbel uniforms from its generator.
 
@@ -1088,11 +1025,10 @@ class GraphedPrunerStep(PrunerStep):
         queue behind this step's router backward + optimizer, they run next to it; the student's forward waits for the code
         (ev_code), the router backward for the U-Net backward (ev_bwd).  Reading router parameters on another stream afterwards
         needs finish() -- the router modules' forward / state_dict hooks and the eager train_step call it.
-        ph: the graph set of one training phase (router captured under a RouterAdamW); the returned dict then has "applied", a device
-        flag written on the router's stream (1: the step was applied, 0: skipped) -- call finish() before reading it."""
-        cfg, cap = self.cfg, self._cap
+        ph: the graph set of this training phase; captured under a RouterAdamW, the returned dict also has "applied", a device flag
+        written on the router's stream (1: the step was applied, 0: skipped) -- call finish() before reading it."""
+        cap = self._cap
         rt = cap["router"]
-        ph = rt if ph is None else ph
         main = torch.cuda.current_stream()
         rs = rt["stream"] if self.overlap_router else main
         rt["ev_entry"].record(main)                           # the batch tensors were produced on the caller's stream
@@ -1118,9 +1054,7 @@ class GraphedPrunerStep(PrunerStep):
         r = ph["out"]
         # (the router graph's outputs were complete at ev_code; the next router forward, which overwrites them, waits for the next
         #  step's ev_entry, i.e. for these clones)
-        unet_loss = cap["loss"] + cfg.distillation_weight * cap["dist"] + cfg.block_weight * cap["blk"]
-        out = {"loss": (r["router_loss"].detach() + unet_loss).clone(), "diff_loss": cap["loss"].clone(),
-               "distillation_loss": cap["dist"].clone(), "block_loss": cap["blk"].clone(),
+        out = {**self._captured_losses(r["router_loss"]),
                "contrastive_loss": r["contrastive_loss"].detach().clone(), "resource_loss": r["resource_loss"].detach().clone(),
                "resource_ratio": r["ratios"].mean().detach(), "arch_vector_quantized": r["arch_vector_quantized"].detach().clone()}
         if applied is not None:
@@ -1367,43 +1301,31 @@ class FineTunerStep:
         self.schedule = schedule or NoiseSchedule()
         self.acts_s: Dict[str, torch.Tensor] = {}
         self.acts_t: Dict[str, torch.Tensor] = {}
-        self._hooks = []
-        for model, acts in ((student, self.acts_s), (teacher, self.acts_t)):
-            def mk(name, residuals_present, acts=acts):
-                if residuals_present:
-                    return lambda m, i, o: acts.__setitem__(name, o[0])
-                return lambda m, i, o: acts.__setitem__(name, o)
-            for i, b in enumerate(model.down_blocks):
-                self._hooks.append(b.register_forward_hook(mk("d" + str(i), True)))
-            self._hooks.append(model.mid_block.register_forward_hook(mk("m", False)))
-            for i, b in enumerate(model.up_blocks):
-                self._hooks.append(b.register_forward_hook(mk("u" + str(i), False)))
+        self._hooks = _block_output_hooks(student, self.acts_s) + _block_output_hooks(teacher, self.acts_t)
+
+    def _losses(self, model_pred, full_pred, w, target):
+        """(total, diffusion, distillation, block) in the fine-tuner's order -- diffusion, block (skipped without a block weight),
+        output distillation (trainer.py:1736-1763); autograd sums into model_pred in reverse creation order, so the order is part
+        of the gradients' bits.  The block term reads the hooked activations of the last teacher and student passes."""
+        cfg = self.cfg
+        loss = _diffusion_term(cfg, model_pred, target, w)
+        total = loss * cfg.diffusion_weight
+        if cfg.block_weight > 0:
+            blk = _block_term(self.acts_s, self.acts_t)
+            total = total + cfg.block_weight * blk
+        else:
+            blk = torch.zeros((), device=model_pred.device)
+        dist_l = _mse(model_pred, full_pred)
+        total = total + cfg.distillation_weight * dist_l
+        return total, loss.detach(), dist_l.detach(), blk.detach()
 
     def step(self, noisy_latents, timesteps, encoder_hidden_states, target):
-        cfg = self.cfg
         with torch.no_grad():
             full_pred = self.teacher(noisy_latents, timesteps, encoder_hidden_states).sample.detach()      # :1726-1727
         model_pred = self.student(noisy_latents, timesteps, encoder_hidden_states).sample                  # :1729
-        if cfg.snr_gamma is None:
-            loss = _mse(model_pred, target)
-        else:
-            snr = compute_snr(self.schedule, timesteps)
-            if cfg.prediction_type == "v_prediction":
-                snr = snr + 1
-            w = torch.stack([snr, cfg.snr_gamma * torch.ones_like(timesteps)], dim=1).min(dim=1)[0] / snr
-            loss = (_mse_per_sample(model_pred, target) * w).mean()
-        diff_loss = loss.detach().clone()
-        loss = loss * cfg.diffusion_weight
-        block_loss = torch.zeros((), device=model_pred.device)
-        if cfg.block_weight > 0:
-            for k in self.acts_s:
-                block_loss = block_loss + _mse(self.acts_s[k], self.acts_t[k])
-            block_loss = block_loss / len(self.acts_s)
-            loss = loss + cfg.block_weight * block_loss
-        distillation_loss = _mse(model_pred, full_pred)
-        loss = loss + cfg.distillation_weight * distillation_loss
-        return {"loss": loss, "diff_loss": diff_loss, "distillation_loss": distillation_loss.detach(),
-                "block_loss": block_loss.detach()}
+        w = _min_snr_weights(self.cfg, self.schedule, timesteps)
+        loss, diff_loss, distillation_loss, block_loss = self._losses(model_pred, full_pred, w, target)
+        return {"loss": loss, "diff_loss": diff_loss.clone(), "distillation_loss": distillation_loss, "block_loss": block_loss}
 
     def _group_coef(self):
         cfg = self.cfg
@@ -1510,41 +1432,14 @@ class GraphedFineTunerStep(FineTunerStep):
         self.stream_probe = []          # what graph_utils.concurrent_stream measured when it chose the teacher's / router's side streams
         self._val, self._val_running = {}, None      # forward-only validation graphs by batch size (capture_validation), their totals
 
-    def _losses(self, model_pred, full_pred, w, target):
-        cfg = self.cfg
-        if cfg.snr_gamma is None:
-            loss = _mse(model_pred, target)
-        else:
-            loss = (_mse_per_sample(model_pred, target) * w).mean()
-        diff = loss.detach()
-        total = loss * cfg.diffusion_weight
-        blk = torch.zeros((), device=model_pred.device)
-        if cfg.block_weight > 0:
-            for k in self.acts_s:
-                blk = blk + _mse(self.acts_s[k], self.acts_t[k])
-            blk = blk / len(self.acts_s)
-            total = total + cfg.block_weight * blk
-        dist_l = _mse(model_pred, full_pred)
-        total = total + cfg.distillation_weight * dist_l
-        return total, diff, dist_l.detach(), blk.detach()
-
-    def _snr_weights(self, timesteps):
-        cfg = self.cfg
-        if cfg.snr_gamma is None:
-            return torch.ones(timesteps.shape[0], device=timesteps.device)
-        snr = compute_snr(self.schedule, timesteps)
-        if cfg.prediction_type == "v_prediction":
-            snr = snr + 1
-        return (torch.stack([snr, cfg.snr_gamma * torch.ones_like(timesteps)], dim=1).min(dim=1)[0] / snr).float()
-
     def capture(self, batch: dict, warmup_iters: int = 2, offload_masters: bool = False):
         """Build the packed trainable state, the three HIP graphs (teacher forward | student forward | losses + backward) for this
         batch geometry, and the one-launch AdamW over the gradients the backward graph and the batched launches leave behind."""
         dev = batch["noisy_latents"].device
-        st = {k: batch[k].clone() for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target")}
+        st = {k: batch[k].clone() for k in _BATCH_KEYS}
         if self.schedule.alphas_cumprod.device != dev:
             self.schedule.alphas_cumprod = self.schedule.alphas_cumprod.to(dev)
-        st["snr_w"] = self._snr_weights(st["timesteps"])
+        st["snr_w"] = _min_snr_weights(self.cfg, self.schedule, st["timesteps"])
         self.trainer.materialize(st["noisy_latents"], st["timesteps"], st["encoder_hidden_states"])
         # the block-output hooks kept the materialising forward's autograd graph (and through it every AccumulateGrad node)
         # alive: drop it before the warm-up builds the graphs the capture will re-use
@@ -1564,7 +1459,7 @@ class GraphedFineTunerStep(FineTunerStep):
         def teacher_fwd():
             # own split-K counters / scratch: this graph replays NEXT TO the previous step's optimizer tail (ops.scratch_domain)
             with torch.no_grad(), ops.scratch_domain("teacher"):
-                st["snr_w"].copy_(self._snr_weights(st["timesteps"]))      # (min-SNR weights: read by the loss terms only)
+                st["snr_w"].copy_(_min_snr_weights(self.cfg, self.schedule, st["timesteps"]))      # (min-SNR weights: read by the loss terms only)
                 fp = self.teacher(st["noisy_latents"], st["timesteps"], st["encoder_hidden_states"]).sample.detach()
             return fp, dict(self.acts_t)
 
@@ -1589,58 +1484,47 @@ class GraphedFineTunerStep(FineTunerStep):
             student_bwd(*student_fwd(), fp, ta)
 
         # warm-up (allocator, plan caches, autograd's stream anchors) runs forward + backward only: nothing to undo afterwards
-        # (ops.LAUNCH_LOG -- bench.py: the contractions of ONE step -- is filled by the last eager iteration, never by the captures:
-        #  see GraphedPrunerStep.capture)
+        # (ops.LAUNCH_LOG is filled by the last eager iteration, never by the captures: _launch_log_off)
         user_log, log0 = ops.LAUNCH_LOG, None
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
         ops.GRAD_DIRECT = direct
         try:
-            with torch.cuda.stream(side):
+            with warmup_stream():
                 for i in range(max(1, warmup_iters)):
                     if user_log is not None:
                         log0 = len(user_log)
                     fwd_bwd()
         finally:
             ops.GRAD_DIRECT = False
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
         launch_log = None if user_log is None else user_log[log0:]
-        ops.LAUNCH_LOG = None
         # TWO graphs.  The teacher's forward reads no trainable state, so step i+1's teacher pass does not have to wait for step
         # i's optimizer: it is its own graph (own memory pool: it replays NEXT TO the tail of the previous step, whose kernels
         # still read tensors of the student graph's pool), and train_step() issues the tail -- batched weight gradients, folds,
         # AdamW, operand refresh: 6.7 of 33.8 ms, HBM-bound for the most part -- on a second stream.
-        g_teacher = new_graph()
-        try:
-            with torch.cuda.graph(g_teacher):
-                full_pred, teacher_acts = teacher_fwd()
-        except BaseException:
-            ops.LAUNCH_LOG = user_log
-            raise
-        graph = new_graph()
+        g_teacher, graph, g_bwd = new_graph(), new_graph(), new_graph()
         # The slab folds of the split weight gradients (and the chunk folds of the norm-affine gradients) are only RECORDED while
         # the backward is captured and run as ONE launch behind every replay (ops.FoldBatch: 357 launches of ~8 us otherwise):
         # nothing reads a parameter gradient before the optimizer.
         # Likewise the stride-1 weight gradients: recorded, then ONE launch per filter size behind the replay (ops.WgradBatch),
         # with pixel slices sized for the batch instead of for a chip-filling launch each (most weights: no slabs, no fold).
-        ops.FOLD_DEFER = [] if (self.defer_folds and direct) else None
-        ops.WGRAD_DEFER = [] if (self.defer_wgrads and self.defer_folds and direct) else None
-        ops.GRAD_DIRECT = direct
-        g_bwd = new_graph()
         try:
-            # the student's forward does not read the teacher (only the loss terms do): its own graph, replayed NEXT TO the teacher
-            # graph on the side stream; the loss + backward graph joins the two (same pool as the forward: replayed in capture order)
-            with torch.cuda.graph(graph):
-                pred, student_acts = student_fwd()
-            with torch.cuda.graph(g_bwd, pool=graph.pool()):
-                student_bwd(pred, student_acts, full_pred, teacher_acts)
+            with _launch_log_off():
+                with torch.cuda.graph(g_teacher):
+                    full_pred, teacher_acts = teacher_fwd()
+                ops.FOLD_DEFER = [] if (self.defer_folds and direct) else None
+                ops.WGRAD_DEFER = [] if (self.defer_wgrads and self.defer_folds and direct) else None
+                ops.GRAD_DIRECT = direct
+                # the student's forward does not read the teacher (only the loss terms do): its own graph, replayed NEXT TO the
+                # teacher graph on the side stream; the loss + backward graph joins the two (same pool as the forward: replayed in
+                # capture order)
+                with torch.cuda.graph(graph):
+                    pred, student_acts = student_fwd()
+                with torch.cuda.graph(g_bwd, pool=graph.pool()):
+                    student_bwd(pred, student_acts, full_pred, teacher_acts)
             folds, wgrads = ops.FOLD_DEFER, ops.WGRAD_DEFER
         finally:
             ops.FOLD_DEFER = None
             ops.WGRAD_DEFER = None
             ops.GRAD_DIRECT = False
-            ops.LAUNCH_LOG = user_log
         self._wgrads = ops.WgradBatch(wgrads) if wgrads else None
         self._folds = ops.FoldBatch(folds) if folds else None
         # The optimizer is ONE launch over every trainable tensor and writes the bf16 operands in the same pass
@@ -1685,15 +1569,14 @@ class GraphedFineTunerStep(FineTunerStep):
         self.finish()
         B = int(batch["noisy_latents"].shape[0])
         dev = batch["noisy_latents"].device
-        st = {k: batch[k].clone() for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target")}
-        st["snr_w"] = self._snr_weights(st["timesteps"])
+        st = {k: batch[k].clone() for k in _BATCH_KEYS}
+        st["snr_w"] = _min_snr_weights(self.cfg, self.schedule, st["timesteps"])
         if self._val_running is None:
             self._val_running = torch.zeros(len(VAL_KEYS) + 1, dtype=torch.float32, device=dev)      # [diff, block, distill, loss, batches]
-        box = {}
 
         def teacher_fwd():
             with torch.no_grad(), ops.scratch_domain("val_teacher"):
-                st["snr_w"].copy_(self._snr_weights(st["timesteps"]))
+                st["snr_w"].copy_(_min_snr_weights(self.cfg, self.schedule, st["timesteps"]))
                 fp = self.teacher(st["noisy_latents"], st["timesteps"], st["encoder_hidden_states"]).sample
             return fp, dict(self.acts_t)
 
@@ -1709,31 +1592,26 @@ class GraphedFineTunerStep(FineTunerStep):
                 lt.run()
             return lt
 
-        user_log, ops.LAUNCH_LOG = ops.LAUNCH_LOG, None
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(max(1, warmup_iters)):          # allocator and plan caches of this geometry; totals untouched
-                    fp, ta = teacher_fwd()
-                    losses(*student_fwd(), fp, ta, None)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g_teacher, g_student, g_loss = new_graph(), new_graph(), new_graph()
-            with torch.cuda.graph(g_teacher):
-                full_pred, teacher_acts = teacher_fwd()
-            with torch.cuda.graph(g_student):
-                pred, student_acts = student_fwd()
-            with torch.cuda.graph(g_loss, pool=g_student.pool()):
-                box["lt"] = losses(pred, student_acts, full_pred, teacher_acts, self._val_running)
+            with _launch_log_off():
+                with warmup_stream():
+                    for _ in range(max(1, warmup_iters)):          # allocator and plan caches of this geometry; totals untouched
+                        fp, ta = teacher_fwd()
+                        losses(*student_fwd(), fp, ta, None)
+                g_teacher, g_student, g_loss = new_graph(), new_graph(), new_graph()
+                with torch.cuda.graph(g_teacher):
+                    full_pred, teacher_acts = teacher_fwd()
+                with torch.cuda.graph(g_student):
+                    pred, student_acts = student_fwd()
+                with torch.cuda.graph(g_loss, pool=g_student.pool()):
+                    lt = losses(pred, student_acts, full_pred, teacher_acts, self._val_running)
         finally:
-            ops.LAUNCH_LOG = user_log
             self.acts_s.clear()
             self.acts_t.clear()
         self._val.pop(B, None)
         while len(self._val) >= self.MAX_VALIDATION_GEOMETRIES:
             self._val.pop(next(iter(self._val)))               # (dicts keep insertion order: the first key is the least recently used)
-        self._val[B] = dict(st=st, g_teacher=g_teacher, g_student=g_student, g_loss=g_loss, lt=box["lt"], full_pred=full_pred,
+        self._val[B] = dict(st=st, g_teacher=g_teacher, g_student=g_student, g_loss=g_loss, lt=lt, full_pred=full_pred,
                             teacher_acts=teacher_acts, pred=pred, student_acts=student_acts, side=self._cap["side"])
         return self
 
@@ -1743,9 +1621,7 @@ class GraphedFineTunerStep(FineTunerStep):
         if B not in self._val:
             self.capture_validation(batch)
         cap = self._val[B] = self._val.pop(B)                 # most recently used: to the end
-        with torch.no_grad():
-            for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target"):
-                cap["st"][k].copy_(batch[k])
+        _stage_batch(cap["st"], batch)
         main, side = torch.cuda.current_stream(), cap["side"]
         side.wait_stream(main)
         with torch.cuda.stream(side):
@@ -1807,9 +1683,7 @@ class GraphedFineTunerStep(FineTunerStep):
         capture time is part of the graph"""
         cap = self._cap
         assert cap is not None, "call capture(batch) first"
-        with torch.no_grad():
-            for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target"):
-                cap["st"][k].copy_(batch[k])
+        _stage_batch(cap["st"], batch)
         main = torch.cuda.current_stream()       # (the min-SNR weights are computed from the staged timesteps inside g_teacher)
         side = cap["side"] if self.overlap_teacher else main
         side.wait_stream(main)                   # (the batch copies above)

@@ -1,7 +1,8 @@
 """CPU checks of the validation pass (csrc/loss_terms.hip, ops.LossTerms, the eval_step / validate methods of train_step.py): the
 parameter block has the C compiler's layout, the exported grid size is the sum of aptp_mse_nblocks over terms and samples,
 argument validation fails without launching, eval_step on host tensors is `step` under no_grad, validate divides by the number
-of batches (empty ones included: the reference's quirk), and the reduce helper is a mean over the ranks."""
+of batches (empty ones included: the reference's quirk), the reduce helper is a mean over the ranks, and the loss pieces every
+step shares (_min_snr_weights, _diffusion_term, _block_term) are the reference's expressions bit for bit."""
 import ctypes
 import os
 import subprocess
@@ -230,3 +231,89 @@ def test_reduce_helper_is_the_mean_over_the_ranks():
     for rank in (0, 1):
         assert torch.equal(res[rank]["mean"], torch.tensor([1.5, 3.0, 4.5, 6.0]))
         assert torch.equal(res[rank]["kept"], torch.tensor([1.0, 2.0, 3.0, 4.0]) * (rank + 1))
+
+
+@pytest.mark.parametrize("prediction_type", ["v_prediction", "epsilon"])
+@pytest.mark.parametrize("snr_gamma", [None, 5.0])
+def test_loss_pieces_are_the_reference_expressions(snr_gamma, prediction_type):
+    """_min_snr_weights, _diffusion_term and _block_term against trainer.py:1197-1225 written out here; bit for bit"""
+    import torch.nn.functional as F
+    from diffusion_pruning_amd.losses import compute_snr
+    from diffusion_pruning_amd.train_step import (FinetuneLossConfig, NoiseSchedule, PruningLossConfig, _block_term,
+                                                  _diffusion_term, _min_snr_weights)
+    g = torch.Generator().manual_seed(21)
+    pred = torch.randn(3, 4, 8, 8, generator=g, requires_grad=True)
+    target = torch.randn(3, 4, 8, 8, generator=g)
+    ts = torch.tensor([0, 417, 999])
+    acts_s = {"d0": torch.randn(3, 8, 4, 4, generator=g, requires_grad=True), "m": torch.randn(3, 6, 2, 2, generator=g, requires_grad=True)}
+    acts_t = {"d0": torch.randn(3, 8, 4, 4, generator=g), "m": torch.randn(3, 6, 2, 2, generator=g)}
+    schedule = NoiseSchedule()
+    for cfg in (PruningLossConfig(snr_gamma=snr_gamma, prediction_type=prediction_type),
+                FinetuneLossConfig(snr_gamma=snr_gamma, prediction_type=prediction_type)):
+        w = _min_snr_weights(cfg, schedule, ts)
+        assert w.dtype == torch.float32 and w.shape == (3,)
+        if snr_gamma is None:
+            assert torch.equal(w, torch.ones(3))
+            want = F.mse_loss(pred.float(), target.float(), reduction="mean")
+        else:
+            snr = compute_snr(schedule, ts)
+            if prediction_type == "v_prediction":
+                snr = snr + 1
+            w_ref = torch.stack([snr, snr_gamma * torch.ones_like(ts)], dim=1).min(dim=1)[0] / snr
+            assert torch.equal(w, w_ref) and bool((w > 0).all()) and bool((w <= 1).all())
+            assert float(w[2]) == 1.0 and float(w[0]) < 1.0          # t = 999: snr below gamma; t = 0: gamma / snr
+            per = F.mse_loss(pred.float(), target.float(), reduction="none")
+            want = (per.mean(dim=list(range(1, len(per.shape)))) * w_ref).mean()
+        got = _diffusion_term(cfg, pred, target, w)
+        assert torch.equal(got, want)
+        assert torch.equal(torch.autograd.grad(got, pred)[0], torch.autograd.grad(want, pred)[0])
+    blk_ref = torch.zeros(())
+    for k in acts_s:
+        blk_ref = blk_ref + F.mse_loss(acts_s[k].float(), acts_t[k].float(), reduction="mean")
+    blk_ref = blk_ref / len(acts_s)
+    blk = _block_term(acts_s, acts_t)
+    assert torch.equal(blk, blk_ref) and float(blk.detach()) > 0
+    for k in acts_s:
+        assert torch.equal(torch.autograd.grad(blk, acts_s[k], retain_graph=True)[0],
+                           torch.autograd.grad(blk_ref, acts_s[k], retain_graph=True)[0])
+
+
+@pytest.mark.parametrize("pretrain", [False, True])
+def test_pruner_eval_step_on_host_tensors_is_step_under_no_grad(pretrain):
+    """PrunerStep.eval_step = `step` without autograd and with the router modules in eval() for the call only"""
+    from diffusion_pruning_amd.hypernet import HyperStructure
+    from diffusion_pruning_amd.train_step import PrunerStep, synthetic_batch
+    from diffusion_pruning_amd.unet import UNet2DConditionModelGated
+    from oracle import unet_oracle as O
+    from tests.test_distributed_cpu import StubUNet, _quantizer
+    cfg = O.TINY
+    real = UNet2DConditionModelGated(block_out_channels=cfg.block_out_channels, attention_head_dim=cfg.num_heads,
+                                     cross_attention_dim=cfg.cross_attention_dim)
+    torch.manual_seed(1)
+    hn = HyperStructure(structure=real.get_structure(), input_dim=16, wn_flag=False, linear_bias=True)
+    qz = _quantizer(False)
+    step = PrunerStep(StubUNet(real), hn, qz)
+    step.count_macs(8)
+    b = synthetic_batch(2, 8, "cpu", seed=50, cross_dim=cfg.cross_attention_dim, text_dim=16)
+    keys = {"loss", "diff_loss", "distillation_loss", "block_loss", "contrastive_loss", "resource_loss"}
+    args = (b["noisy_latents"], b["timesteps"], b["encoder_hidden_states"], b["mpnet_embeddings"], b["target"])
+    hn.train()
+    qz.train()
+    torch.manual_seed(3)
+    with torch.no_grad():
+        step.step(*args, pretrain=pretrain)       # a training-mode pass leaves the relaxed codebook the eval-mode quantizer reads
+    for modes in ((True, True), (False, True), (False, False)):
+        hn.eval()
+        qz.eval()
+        torch.manual_seed(7)
+        with torch.no_grad():
+            want = step.step(*args, pretrain=pretrain)
+        hn.train(modes[0])
+        qz.train(modes[1])
+        torch.manual_seed(7)
+        got = step.eval_step(b, pretrain=pretrain)
+        assert (hn.training, qz.training) == modes
+        assert set(got) == keys
+        for k in keys:
+            assert not got[k].requires_grad and torch.equal(got[k], want[k]), k
+        assert float(got["loss"]) != 0.0 and torch.isfinite(got["loss"])

@@ -9,7 +9,7 @@ import torch
 
 from diffusion_pruning_amd.hypernet import HyperStructure
 from diffusion_pruning_amd.quantizer import StructureVectorQuantizer
-from diffusion_pruning_amd.train_step import GraphedPrunerStep, synthetic_batch
+from diffusion_pruning_amd.train_step import GraphedPrunerStep, _min_snr_weights, synthetic_batch
 from diffusion_pruning_amd.unet import UNet2DConditionModelGated
 
 dev = torch.device("cuda:0")
@@ -26,7 +26,8 @@ step.count_macs(64)
 opt = torch.optim.AdamW(step.trainable_parameters(), lr=2e-4, capturable=True)
 batch = synthetic_batch(4, 64, dev)
 step.capture(batch, optimizer=opt)
-cap, rt = step._cap, step._cap["router"]
+cap = step._cap
+rt = cap["router"][False]          # the graph set of the captured (main) phase
 print("side-stream probe:", step.stream_probe, flush=True)
 
 
@@ -55,7 +56,7 @@ for it in range(N + 3):
     with torch.no_grad():
         for k in ("noisy_latents", "timesteps", "encoder_hidden_states", "target"):
             cap["st"][k].copy_(batch[k])
-        cap["st"]["snr_w"].copy_(step._snr_weights(batch["timesteps"]))
+        cap["st"]["snr_w"].copy_(_min_snr_weights(step.cfg, step.schedule, batch["timesteps"]))
         rt["text"].copy_(batch["mpnet_embeddings"])
     side = cap["side"]
     side.wait_stream(main)
