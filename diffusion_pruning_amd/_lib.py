@@ -198,6 +198,20 @@ class GroupAdamWParams(Structure):
                 ("gate_dev", c_void_p), ("items_host", c_void_p)]
 
 
+EMA_UPDATE, EMA_SWAP = 0, 1
+
+
+class EmaItem(Structure):
+    _fields_ = [("p", c_void_p), ("ema", c_void_p), ("shadow", c_void_p), ("n", c_int64)]
+
+
+class EmaParams(Structure):
+    _fields_ = [("items_dev", c_void_p), ("starts_dev", c_void_p), ("n_items", c_int32), ("total_blocks", c_int32),
+                ("mode", c_int32), ("count_dev", c_void_p), ("gate_dev", c_void_p),
+                ("decay", c_float), ("min_decay", c_float), ("update_after_step", c_int32), ("use_warmup", c_int32),
+                ("inv_gamma", c_float), ("power", c_float), ("cur_decay_dev", c_void_p)]
+
+
 GRAD_ACCUM_STORE, GRAD_ACCUM_ADD, GRAD_ACCUM_FINAL = 0, 1, 2
 
 
@@ -590,6 +604,7 @@ EXPORTS = [
     ("aptp_pack_dgrad_many", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("aptp_adamw_blocks", c_int, [c_int64]),
     ("aptp_adamw_many", c_int, [POINTER(AdamWParams), c_void_p]),
+    ("aptp_ema_many", c_int, [POINTER(EmaParams), c_void_p]),
     ("aptp_group_adamw_blocks", c_int, [c_int64]),
     ("aptp_group_adamw", c_int, [POINTER(GroupAdamWParams), c_void_p]),
     ("aptp_grad_accumulate_blocks", c_int, [c_int64]),

@@ -437,3 +437,148 @@ class PackedAdamW:
         for i, j in enumerate(order):
             self.m[i].copy_(sd["exp_avg"][j])    # in place: the moments' addresses are part of the kernel's table
             self.v[i].copy_(sd["exp_avg_sq"][j])
+
+
+class PackedEMA:
+    """Exponential moving average of a PackedTrainer's state (`use_ema` of the reference's interface, pdm/utils/arg_utils.py:50-54;
+    the decay rule of diffusers' EMAModel) kept in the packed layout next to the masters: one fp32 tensor per ``_Gemm.P``,
+    ``_Gemm.Pb``, ``_Affine.Pg`` and ``_Affine.Pb``, initialised as a clone -- +4 B per trainable element -- and keyed by the names of
+    ``PackedTrainer.named_parameters()``.  ``step`` is ONE launch over a device table built once (csrc/ema.hip), gated and counted
+    on the device like PackedAdamW; ``swap_`` exchanges masters and averages in one launch and rewrites the bf16 forward operands,
+    so everything that reads the packed state at fixed addresses (validation graphs, ``export_``) reads the average."""
+
+    def __init__(self, trainer: PackedTrainer, optimizer: Optional[PackedAdamW] = None, decay: float = 0.9999, min_decay: float = 0.0,
+                 update_after_step: int = 0, use_ema_warmup: bool = False, inv_gamma: float = 1.0, power: float = 2.0 / 3.0):
+        from . import _lib
+        lib = _lib.load()
+        assert 0.0 <= decay <= 1.0 and 0.0 <= min_decay <= decay and int(update_after_step) >= 0 and inv_gamma > 0 and power > 0, \
+            "PackedEMA: hyper-parameters"
+        self.trainer, self.optimizer = trainer, optimizer
+        self.decay, self.min_decay, self.update_after_step = float(decay), float(min_decay), int(update_after_step)
+        self.use_ema_warmup, self.inv_gamma, self.power = bool(use_ema_warmup), float(inv_gamma), float(power)
+        entries = []                                   # (master, bf16 shadow or None)
+        for e in trainer.gemms.values():
+            entries.append((e.P, e.pw.w))
+            if e.Pb is not None:
+                entries.append((e.Pb, None))
+        for a in trainer.affines.values():
+            entries += [(a.Pg, None), (a.Pb, None)]
+        assert entries, "PackedEMA: the trainer has no packed tensors yet (PackedTrainer.materialize)"
+        by_id = {id(p): n for n, p in trainer.named_parameters()}
+        self.entries = entries
+        self.params = [p for p, _ in entries]
+        self.names = [by_id[id(p)] for p in self.params]
+        self.ema = [p.detach().clone() for p in self.params]
+        dev = self.params[0].device
+        self.count = torch.zeros((), dtype=torch.float32, device=dev)
+        self._cur_decay = torch.zeros((), dtype=torch.float32, device=dev)
+        self.swapped = False
+        items = (_lib.EmaItem * len(entries))()
+        starts = [0]
+        for i, ((p, sh), a) in enumerate(zip(entries, self.ema)):
+            assert p.dtype == torch.float32 and p.data.is_contiguous() and a.is_contiguous() and p.numel() >= 1
+            assert p.data_ptr() % 16 == 0 and a.data_ptr() % 16 == 0
+            it = items[i]
+            it.p, it.ema, it.n = p.data_ptr(), a.data_ptr(), p.numel()
+            if sh is not None:
+                assert sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() == p.numel() and sh.data_ptr() % 8 == 0
+                it.shadow = sh.data_ptr()
+            starts.append(starts[-1] + lib.aptp_adamw_blocks(p.numel()))
+        self.items = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(dev)
+        self.starts = torch.tensor(starts, dtype=torch.int32).to(dev)
+        self.n, self.total = len(entries), starts[-1]
+
+    def n_elements(self) -> int:
+        return sum(p.numel() for p in self.params)
+
+    def _launch(self, mode: int, gate: Optional[torch.Tensor] = None):
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        q = _lib.EmaParams()
+        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = self.items.data_ptr(), self.starts.data_ptr(), self.n, self.total
+        q.mode = mode
+        q.count_dev = self.count.data_ptr()
+        q.gate_dev = None if gate is None else gate.data_ptr()
+        q.decay, q.min_decay, q.update_after_step = self.decay, self.min_decay, self.update_after_step
+        q.use_warmup, q.inv_gamma, q.power = int(self.use_ema_warmup), self.inv_gamma, self.power
+        q.cur_decay_dev = self._cur_decay.data_ptr()
+        _lib.check(lib.aptp_ema_many(ctypes.byref(q), ops._stream()), "aptp_ema_many")
+
+    @torch.no_grad()
+    def step(self, gate: torch.Tensor = None):
+        """one EMA update over every tensor (one launch), then the count on the device.  gate: optional fp32 device scalar (the
+        step's loss): averages, decay and count stay as they are unless it is finite -- PackedAdamW's predicate.  No host sync."""
+        assert not self.swapped, "PackedEMA.step: the masters hold the average (swap_() back first)"
+        from . import _lib
+        self._launch(_lib.EMA_UPDATE, gate)
+        if gate is None:
+            self.count += 1.0
+        else:
+            self.count += torch.isfinite(gate.reshape(())).to(torch.float32)
+
+    @torch.no_grad()
+    def swap_(self):
+        """masters <-> averages in one launch; the bf16 forward operands follow the masters.  The data-gradient operands (pwb)
+        are NOT rewritten: only a backward reads them, no step runs while swapped, and the swap back returns the masters bit for
+        bit, so they are valid again."""
+        from . import _lib
+        sync = getattr(self.trainer, "sync", None)
+        if sync is not None:
+            sync()                                # (a graphed step's optimizer tail runs on its own stream)
+        self._launch(_lib.EMA_SWAP)
+        self.swapped = not self.swapped
+        return self
+
+    def applied(self):
+        """context manager: the packed state holds the average inside, the trained values again afterwards"""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            self.swap_()
+            try:
+                yield self
+            finally:
+                self.swap_()
+        return cm()
+
+    def cur_decay(self) -> float:
+        """the decay of the last applied update (host read: logging only)"""
+        return float(self._cur_decay)
+
+    def steps(self) -> int:
+        """applied updates (host read: logging only)"""
+        return int(self.count)
+
+    def state_dict(self):
+        """count and averages, keyed by the stable names of PackedTrainer.named_parameters()"""
+        assert not self.swapped, "PackedEMA.state_dict: swapped (the averages sit in the masters)"
+        sync = getattr(self.trainer, "sync", None)
+        if sync is not None:
+            sync()
+        return {"count": self.count.clone(), "cur_decay": self._cur_decay.clone(), "names": list(self.names),
+                "ema": [a.clone() for a in self.ema]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        assert not self.swapped, "PackedEMA.load_state_dict: swapped (the averages sit in the masters)"
+        names = sd["names"]
+        assert len(sd["ema"]) == len(names), "PackedEMA: malformed state"
+        pos = {n: i for i, n in enumerate(names)}
+        missing = [n for n in self.names if n not in pos]
+        assert not missing and len(pos) == len(names) == len(self.names), \
+            f"PackedEMA: the saved state belongs to another expert / tensor list (missing {missing[:3]}, " \
+            f"{len(names)} saved vs {len(self.names)} here)"
+        order = [pos[n] for n in self.names]
+        for i, j in enumerate(order):
+            assert self.ema[i].shape == sd["ema"][j].shape, \
+                f"PackedEMA: {self.names[i]}: saved average {tuple(sd['ema'][j].shape)} vs {tuple(self.ema[i].shape)}"
+        sync = getattr(self.trainer, "sync", None)
+        if sync is not None:
+            sync()
+        self.count.copy_(sd["count"])
+        if "cur_decay" in sd:
+            self._cur_decay.copy_(sd["cur_decay"])
+        for i, j in enumerate(order):
+            self.ema[i].copy_(sd["ema"][j])      # in place: the averages' addresses are part of the kernel's table

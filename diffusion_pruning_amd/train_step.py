@@ -1401,14 +1401,21 @@ class GraphedFineTunerStep(FineTunerStep):
     PackedAdamW.state_dict() and PackedTrainer.export_() hold parameters, moments and the count of applied steps, so a
     checkpoint taken in the middle of a window drops the micro-batches accumulated so far (``accum_index`` tells where a
     window stands: save at 0).
-    lr_warmup_steps=W > 0: `constant_with_warmup` over W optimizer steps (PackedAdamW(warmup_steps=W))."""
+    lr_warmup_steps=W > 0: `constant_with_warmup` over W optimizer steps (PackedAdamW(warmup_steps=W)).
+    ema=True or a dict of PackedEMA's arguments: an exponential moving average of the packed state (`use_ema` of the reference's
+    interface), one launch behind AdamW on the call that closes a window, under the same gate; validate(use_ema=True),
+    export_ema_() and save_ema_pretrained() read it through a swap of masters and averages."""
 
     def __init__(self, student, teacher, cfg: Optional[FinetuneLossConfig] = None, schedule: Optional[NoiseSchedule] = None,
                  lr: float = 1e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  data_parallel: bool = False, bucket_bytes: int = 256 << 20, reduce_mode: str = "rs_ag", nan_guard: bool = True,
-                 accumulation_steps: int = 1, lr_warmup_steps: int = 0):
+                 accumulation_steps: int = 1, lr_warmup_steps: int = 0, ema=None):
         super().__init__(student, teacher, cfg, schedule)
         assert int(accumulation_steps) >= 1 and lr_warmup_steps >= 0
+        # ema: None = no average (no allocation, no launch); True = packed_train.PackedEMA with its defaults; a dict = its keyword
+        # arguments (decay, min_decay, update_after_step, use_ema_warmup, inv_gamma, power).  Built by capture() as self.ema.
+        assert ema is None or ema is True or isinstance(ema, dict), "GraphedFineTunerStep: ema is None, True or a dict of PackedEMA's arguments"
+        self._ema_kw, self.ema = (None if ema is None else ({} if ema is True else dict(ema))), None
         # accumulation_steps > 1: the gradients live in the arena (also without data_parallel) and one more fp32 tensor of its
         # size holds the running sum of the window; allocated by capture()
         self.accumulation_steps, self.lr_warmup_steps = int(accumulation_steps), lr_warmup_steps
@@ -1541,6 +1548,9 @@ class GraphedFineTunerStep(FineTunerStep):
         self.optimizer = PackedAdamW(self.trainer, lr=self.opt_kw["lr"], betas=self.opt_kw["betas"], eps=self.opt_kw["eps"],
                                      weight_decay=self.opt_kw["weight_decay"], group_of=group_of,
                                      warmup_steps=self.lr_warmup_steps)
+        if self._ema_kw is not None:
+            from .packed_train import PackedEMA
+            self.ema = PackedEMA(self.trainer, self.optimizer, **self._ema_kw)
         if self.accumulation_steps > 1:
             assert direct, "gradient accumulation sums the gradient arena of the direct-gradient mode"
             self._accum, self.accum_index = torch.empty_like(self.trainer.grad_arena), 0      # (STORE writes it before any read)
@@ -1631,20 +1641,38 @@ class GraphedFineTunerStep(FineTunerStep):
         cap["g_loss"].replay()
         return cap["lt"].out
 
-    def eval_step_graphed(self, batch: dict):
-        """the four losses of one batch from the validation graphs, as clones of the graphs' static outputs (what eval_step
-        returns, replayed); the running totals of validate() take this batch too"""
+    def _ema_applied(self, use_ema: bool):
+        """context of a validation pass: with use_ema the packed state holds the average inside (PackedEMA.applied: one swap
+        launch in, one out in a `finally`).  The validation graphs read pw.w, the fp32 biases and the affines at fixed addresses,
+        so the SAME graphs score the average: nothing is re-captured."""
+        import contextlib
+        if not use_ema:
+            return contextlib.nullcontext()
+        assert self.ema is not None, "use_ema=True needs GraphedFineTunerStep(ema=...) and capture()"
         self.finish()
-        o = self._replay_validation(batch).clone()
+        return self.ema.applied()
+
+    def eval_step_graphed(self, batch: dict, use_ema: bool = False):
+        """the four losses of one batch from the validation graphs, as clones of the graphs' static outputs (what eval_step
+        returns, replayed); the running totals of validate() take this batch too.  use_ema: of the averaged weights."""
+        self.finish()
+        with self._ema_applied(use_ema):
+            o = self._replay_validation(batch).clone()
         return {"loss": o[3], "diff_loss": o[0], "distillation_loss": o[2], "block_loss": o[1]}
 
-    def validate(self, batches, reduce: bool = True) -> Dict[str, float]:
+    def validate(self, batches, reduce: bool = True, use_ema: bool = False) -> Dict[str, float]:
         """FineTuner.validate (trainer.py:1767-1818) from the validation graphs: finish() the pending optimizer tail, zero the
         device totals, replay every batch (staged copies + three graph replays, no host wait), then ONE host sync; under an
         initialised process group one all-reduce of the totals ("mean" over the ranks).  Returns the four means as Python floats.
         Reference quirk, kept (trainer.py:1788-1800): a batch without samples is skipped but the divisor is len(batches), so every
         empty batch pulls the means towards zero.  Forward-only: parameters, moments, step count, the gradient arena, the
-        accumulator and accum_index are left as they are, also in the middle of an accumulation window."""
+        accumulator and accum_index are left as they are, also in the middle of an accumulation window.
+        use_ema=True: the means of the averaged weights (self.ema): one swap launch, the same pass over the same graphs, one swap
+        back; the trained state returns bit for bit."""
+        with self._ema_applied(use_ema):
+            return self._validate(batches, reduce)
+
+    def _validate(self, batches, reduce: bool) -> Dict[str, float]:
         batches = list(batches)
         self.finish()
         if not batches:
@@ -1660,6 +1688,30 @@ class GraphedFineTunerStep(FineTunerStep):
         diff, blk, dist_l, loss = reduce_validation_totals(self._val_running[:4].clone(), reduce).tolist()
         n = len(batches)
         return {"loss": loss / n, "diff_loss": diff / n, "distillation_loss": dist_l / n, "block_loss": blk / n}
+
+    def export_ema_(self):
+        """write the AVERAGED weights into the diffusers-named parameters of the student and return it: PackedTrainer.export_()
+        under PackedEMA.applied().  The packed state is back at the trained values on return (the second swap); the model's
+        diffusers-named tensors hold the average until the next ``trainer.export_()`` -- which ``model.state_dict()`` runs itself
+        under an attached trainer, so read the tensors through ``named_parameters()``, or save with save_ema_pretrained."""
+        assert self.ema is not None, "export_ema_ needs GraphedFineTunerStep(ema=...) and capture()"
+        self.finish()
+        with self.ema.applied():
+            model = self.trainer.export_()
+        return model
+
+    def save_ema_pretrained(self, root: str, subfolder: str = "unet_ema", arch_vector=None) -> str:
+        """``<root>/unet_ema`` in the layout of checkpoint.save_pretrained (arch_vector.pt beside it, as for `unet`) from the
+        averaged weights.  Written while the packed state is swapped: save_pretrained reads ``model.state_dict()``, which exports
+        the packed state -- the average, then.  Afterwards the packed state and the diffusers-named tensors are the trained ones."""
+        from . import checkpoint
+        assert self.ema is not None, "save_ema_pretrained needs GraphedFineTunerStep(ema=...) and capture()"
+        self.finish()
+        try:
+            with self.ema.applied():
+                return checkpoint.save_pretrained(self.student, root, subfolder=subfolder, arch_vector=arch_vector)
+        finally:
+            self.trainer.export_()
 
     def validation_graph_nodes(self):
         """nodes of the validation graphs by batch size, for those captured while graph_utils.KEEP_GRAPHS was set"""
@@ -1683,6 +1735,8 @@ class GraphedFineTunerStep(FineTunerStep):
         capture time is part of the graph"""
         cap = self._cap
         assert cap is not None, "call capture(batch) first"
+        if self.ema is not None and self.ema.swapped:
+            raise RuntimeError("GraphedFineTunerStep.train_step: the masters hold the EMA (swap_() back first): a step would train it")
         _stage_batch(cap["st"], batch)
         main = torch.cuda.current_stream()       # (the min-SNR weights are computed from the staged timesteps inside g_teacher)
         side = cap["side"] if self.overlap_teacher else main
@@ -1725,9 +1779,15 @@ class GraphedFineTunerStep(FineTunerStep):
                 self.optimizer.finish_step(gate)
             elif N > 1:
                 # slot 0 = sum of the window's losses: one non-finite micro-batch skips the window
-                self.optimizer.step(self.trainer.grad_arena[0:1] if self.nan_guard else None, grad_scale=1.0 / N)
+                gate = self.trainer.grad_arena[0:1] if self.nan_guard else None
+                self.optimizer.step(gate, grad_scale=1.0 / N)
             else:
-                self.optimizer.step(cap["total"] if self.nan_guard else None)
+                gate = cap["total"] if self.nan_guard else None
+                self.optimizer.step(gate)
+            if applied and self.ema is not None:
+                # the average follows the optimizer on its stream, under its gate: one launch + the device-side count.  Local to
+                # the rank in data-parallel mode (identical masters give identical averages: no collective)
+                self.ema.step(gate)
             ev = cap["ev_tail"] or torch.cuda.Event()
             ev.record(tail)
             cap["ev_tail"] = ev

@@ -708,6 +708,34 @@ typedef struct { float* acc; float* g; int64_t n; int32_t mode; } AptpGradAccumP
 int aptp_grad_accumulate_blocks(int64_t n);   /* grid of the launch: 0 for n <= 0 */
 int aptp_grad_accumulate(const AptpGradAccumParams* p, aptp_stream_t stream);
 
+/* Exponential moving average of the trained weights over many tensors in ONE launch (csrc/ema.hip; `use_ema` of the reference's
+ * interface, pdm/utils/arg_utils.py:50-54, with the decay rule of diffusers' EMAModel).  items_dev: n_items descriptors in DEVICE
+ * memory; p, ema 16-byte aligned fp32 [n]; shadow optional bf16 [n] (8-byte aligned).  starts_dev: int32 [n_items + 1] prefix
+ * sums of aptp_adamw_blocks(n) in device memory; total_blocks = starts[n_items].
+ *   UPDATE  no-op unless gate_dev is null or gate_dev[0] is finite (the predicate of aptp_adamw_many); else, in fp32,
+ *             n = count_dev[0] + 1;  s = max(0, n - update_after_step - 1)
+ *             d = 0 when s <= 0, else max(min_decay, min(base, decay)) with
+ *             base = use_warmup ? 1 - (1 + s / inv_gamma)^(-power) : (1 + s) / (10 + s)
+ *             ema <- ema - (1 - d) * (ema - p)   (d = 0 stores p itself); p is read only, shadow ignored; cur_decay_dev[0] <- d
+ *           count_dev: fp32 device scalar = EMA steps applied BEFORE this call (the caller advances it by the same predicate).
+ *   SWAP    p <-> ema element by element, shadow <- bf16(new p) with the rounding of the AdamW pass; ungated, no count: two
+ *           swaps restore every bit of p, ema and shadow.
+ * APTP_EINVAL and nothing launched for: null tables, n_items or total_blocks < 1, another mode, UPDATE without count_dev, decay
+ * outside [0, 1], min_decay outside [0, decay], update_after_step < 0, inv_gamma <= 0, power <= 0. */
+enum { APTP_EMA_UPDATE = 0, APTP_EMA_SWAP = 1 };
+typedef struct { float* p; float* ema; void* shadow; int64_t n; } AptpEmaItem;
+typedef struct {
+  const AptpEmaItem* items_dev; const int32_t* starts_dev; int32_t n_items, total_blocks;
+  int32_t mode;
+  const float* count_dev;
+  const float* gate_dev;     /* optional fp32 device scalar, e.g. the step's total loss */
+  float decay, min_decay;
+  int32_t update_after_step, use_warmup;
+  float inv_gamma, power;
+  float* cur_decay_dev;      /* optional fp32 device scalar: written by an applied UPDATE */
+} AptpEmaParams;
+int aptp_ema_many(const AptpEmaParams* p, aptp_stream_t stream);
+
 /* AdamW over many small fp32 tensors with everything a schedule changes in DEVICE memory (csrc/router_optim.hip): the router's
  * optimizer of a captured pruning step (pdm/training/trainer.py:804-834, 913-933; configs/pruning/sd-2-1_cc3m.yaml).  The
  * arithmetic per element is aptp_adamw_many's, with

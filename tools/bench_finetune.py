@@ -6,7 +6,11 @@ expert = RANK on cuda:LOCAL_RANK and prints its own line.
 
 --validate K (graphed mode) runs K validation batches of --val-batch samples through GraphedFineTunerStep.validate after the
 timed steps and adds their rate to the line; --validate-baseline times the same batches through torch.no_grad() +
-FineTunerStep.step under the attached trainer as well (what validation cost before the graphs existed), alternating the two."""
+FineTunerStep.step under the attached trainer as well (what validation cost before the graphs existed), alternating the two.
+
+--ema (graphed mode) keeps an EMA of the trained weights (packed_train.PackedEMA) and adds `adamw_ms` / `ema_update_ms` (HIP
+events around the two launches, median over the timed steps), `ema_bytes` = 12 x trainable elements and the two rates; with
+--validate also `validate_losses_ema`, the means of the averaged weights from the same graphs."""
 import argparse
 import json
 import os
@@ -72,6 +76,29 @@ def time_validation(step, batches, baseline: bool, rounds: int = 2):
     return out
 
 
+class LaunchTimer:
+    """HIP events around every call of obj._launch while `on` (the one-launch AdamW / EMA passes of the optimizer tail): the
+    events go onto the stream the launch goes to, so a pair brackets that kernel alone"""
+
+    def __init__(self, obj):
+        self.pairs, self.on, inner = [], False, obj._launch
+
+        def timed(*a, **k):
+            if not self.on:
+                return inner(*a, **k)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            inner(*a, **k)
+            e1.record()
+            self.pairs.append((e0, e1))
+        obj._launch = timed
+
+    def ms(self):
+        """median over the recorded launches (call after a synchronize)"""
+        t = sorted(e0.elapsed_time(e1) for e0, e1 in self.pairs)
+        return t[len(t) // 2] if t else None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--expert", type=int, default=0)
@@ -89,8 +116,12 @@ def main():
     ap.add_argument("--val-batch", type=int, default=32, help="validation batch size (validation_batch_size of the fine-tune config)")
     ap.add_argument("--validate-baseline", action="store_true",
                     help="also time the same batches through torch.no_grad() + FineTunerStep.step, alternating with the graphs")
+    ap.add_argument("--ema", action="store_true",
+                    help="keep an EMA of the trained weights (graphed mode, PackedEMA defaults); adds the EMA and AdamW launch times "
+                         "(HIP events over the timed steps) and, with --validate, the validation means of the averaged weights")
     args = ap.parse_args()
     assert args.validate == 0 or args.mode == "graphed", "--validate belongs to the graphed step"
+    assert not args.ema or args.mode == "graphed", "--ema belongs to the graphed step"
     assert args.accum >= 1 and (args.mode == "graphed" or (args.accum == 1 and args.lr_warmup == 0)), \
         "--accum / --lr-warmup belong to the graphed step"
     args.steps = -(-args.steps // args.accum) * args.accum
@@ -111,12 +142,15 @@ def main():
     student.to(dev)
     student.prune(expert_mask(st, args.expert, dev))
     batch = synthetic_batch(args.batch, 64, dev)
-    n_train = None
+    n_train, timers = None, {}
     if args.mode == "graphed":
         from diffusion_pruning_amd.train_step import GraphedFineTunerStep
-        step = GraphedFineTunerStep(student, teacher, lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup)
+        step = GraphedFineTunerStep(student, teacher, lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup,
+                                    **({"ema": True} if args.ema else {}))
         step.capture(batch, offload_masters=True)
         opt, n_train = None, step.trainer.n_trainable()
+        if args.ema:
+            timers = {"adamw_ms": LaunchTimer(step.optimizer), "ema_update_ms": LaunchTimer(step.ema)}
     elif args.mode == "packed-eager":
         from diffusion_pruning_amd.packed_train import PackedTrainer
         step = FineTunerStep(student, teacher)
@@ -128,15 +162,29 @@ def main():
     for _ in range(args.warmup):
         out = step.train_step(opt, batch)
     torch.cuda.synchronize()
+    for t in timers.values():
+        t.on = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = step.train_step(opt, batch)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     peak_train, val = torch.cuda.max_memory_allocated(), {}
+    if args.ema:
+        # both passes stream the same tensors in the same geometry: 30 B per element (AdamW: p, g, m, v read; p, m, v and the
+        # bf16 operand of a weight written) against 12 B (EMA: p, ema read; ema written)
+        for t in timers.values():
+            t.on = False
+        val = {k: round(t.ms(), 4) for k, t in timers.items()}
+        n_el = step.ema.n_elements()
+        val.update({"ema_bytes": 12 * n_el, "ema_steps": step.ema.steps(), "ema_cur_decay": step.ema.cur_decay(),
+                    "ema_gb_per_s": round(12 * n_el / val["ema_update_ms"] * 1e-6, 1),
+                    "adamw_gb_per_s": round(30 * n_el / val["adamw_ms"] * 1e-6, 1)})
     if args.validate:
-        val = time_validation(step, [synthetic_batch(args.val_batch, 64, dev, seed=100 + i) for i in range(args.validate)],
-                              args.validate_baseline)
+        batches = [synthetic_batch(args.val_batch, 64, dev, seed=100 + i) for i in range(args.validate)]
+        val.update(time_validation(step, batches, args.validate_baseline))
+        if args.ema:
+            val["validate_losses_ema"] = step.validate(batches, use_ema=True)
     print(json.dumps({"metric": "expert-finetune-steps/s (SD-2.1 pruned expert, 64x64 latents, teacher fwd + student fwd/bwd/wgrad + AdamW)",
                       "value": round(1.0 / dt, 3), "unit": "steps/s", "ms_per_step": round(dt * 1e3, 1), "expert": args.expert,
                       "batch": args.batch, "loss": float(out["loss"].detach()),
