@@ -684,3 +684,33 @@ def check(rc: int, what: str):
     if rc != 0:
         msg = load().aptp_last_error()
         raise AptpError(f"{what} failed (rc={rc}): {msg.decode() if msg else ''}")
+
+
+class BlockTable:
+    """The device table of a launch whose workgroups find their item by bisection (csrc/packed_pass.h: item_of_block): a filled
+    ctypes array of item descriptors and the number of workgroups each item takes ->
+      items    the descriptors' bytes in device memory (uint8)
+      starts   int32 [n + 1]: first workgroup of item i; starts[n] == total, the grid size
+      host     the ctypes array itself (kept alive: aptp_group_adamw validates it on the host)
+    The caller checks the operands where it fills an item."""
+
+    def __init__(self, host, blocks, device):
+        import torch
+        self.host, self.blocks = host, [int(b) for b in blocks]
+        assert len(self.blocks) == len(host) >= 1, "BlockTable: one block count per item"
+        starts = [0]
+        for nb in self.blocks:
+            starts.append(starts[-1] + nb)
+        self.n, self.total = len(self.blocks), starts[-1]
+        self.items = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device)
+        self.starts = torch.tensor(starts, dtype=torch.int32).to(device)
+
+    def subset(self, indices):
+        """a table of its own over items[i] for i in indices, in that order: the same descriptors, block prefixes of their own"""
+        indices = list(indices)
+        host = (self.host._type_ * len(indices))(*[self.host[i] for i in indices])
+        return BlockTable(host, [self.blocks[i] for i in indices], self.items.device)
+
+    def args(self):
+        """(items_dev, starts_dev, n_items, total_blocks) as the C entry points take them"""
+        return self.items.data_ptr(), self.starts.data_ptr(), self.n, self.total

@@ -12,11 +12,11 @@
 //            d = max(min_decay, min(base, decay))
 //   ema <- ema - (1 - d) * (ema - p)
 // 1 - d == 1 stores p itself: ema - (ema - p) is p only up to a rounding of the difference.
-#include "aptp_common.h"
+#include "packed_pass.h"
+
+using namespace packed_pass;                    // the tables are laid out by aptp_adamw_blocks
 
 namespace {
-
-constexpr int ELEMS_PER_BLOCK = 4096;          // 256 threads x 4 float4: the geometry of aptp_adamw_blocks
 
 struct EmaK {
   const AptpEmaItem* items; const int32_t* starts; int n_items;
@@ -42,19 +42,12 @@ __global__ __launch_bounds__(256) void ema_many_kernel(const EmaK k) {
   if (MODE == APTP_EMA_UPDATE) {
     // same predicate as the AdamW pass: a non-finite loss leaves the average (and the reported decay) untouched; the caller
     // advances the count by the same predicate.  Uniform over the grid: one scalar load.
-    if (k.gate) {
-      const float gv = k.gate[0];
-      if (!(fabsf(gv) <= 3.0e38f)) return;
-    }
+    if (k.gate && non_finite(k.gate[0])) return;
     const float d = ema_decay(k);
     omd = 1.0f - d;
     if (b == 0 && threadIdx.x == 0 && k.cur_decay) k.cur_decay[0] = d;
   }
-  int lo = 0, hi = k.n_items;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (k.starts[mid] <= b) lo = mid; else hi = mid;
-  }
+  const int lo = item_of_block(k.starts, k.n_items, b);
   const AptpEmaItem it = k.items[lo];
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   const bool copy = omd == 1.0f;
@@ -64,15 +57,15 @@ __global__ __launch_bounds__(256) void ema_many_kernel(const EmaK k) {
   // the block's loads are requested before its first store
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    e[i] = base + ((int64_t)i * 256 + threadIdx.x) * 4;
-    if (e[i] + 3 < it.n) {
+    e[i] = base + ((int64_t)i * THREADS + threadIdx.x) * 4;
+    if (whole_quad(e[i], it.n)) {
       p[i] = *reinterpret_cast<const float4*>(it.p + e[i]);
       a[i] = *reinterpret_cast<const float4*>(it.ema + e[i]);
     }
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    if (e[i] + 3 < it.n) {
+    if (whole_quad(e[i], it.n)) {
       if (MODE == APTP_EMA_UPDATE) {
         float4 r = p[i];
         if (!copy) {

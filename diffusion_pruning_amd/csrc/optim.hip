@@ -7,13 +7,14 @@
 // the `capturable` fused form: step count read from device memory):
 //   p <- p * (1 - lr * wd);  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2
 //   p <- p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// (one body, packed_pass.h's adamw_element, shared with the router's optimizer in router_optim.hip).
 // The table of tensors lives in device memory (built once; the gradient addresses are those of the captured backward).
 // Below it: aptp_grad_accumulate, the sum of a window of micro-batch gradients that such a step is applied to.
-#include "aptp_common.h"
+#include "packed_pass.h"
+
+using namespace packed_pass;
 
 namespace {
-
-constexpr int ELEMS_PER_BLOCK = 4096;          // 256 threads x 4 float4
 
 struct AdamK {
   const AptpAdamWItem* items; const int32_t* starts; int n_items;
@@ -26,45 +27,25 @@ struct AdamK {
 
 __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
   const int b = blockIdx.x;
-  int lo = 0, hi = k.n_items;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (k.starts[mid] <= b) lo = mid; else hi = mid;
-  }
+  const int lo = item_of_block(k.starts, k.n_items, b);
   // NaN guard of a replayed graph (reference: pdm/training/trainer.py:921-929 skips the batch whose backward produced
   // NaNs): a non-finite loss leaves parameters, moments and operands untouched; the caller advances the step count by
   // the same predicate.  Uniform over the grid: one scalar load.
-  if (k.gate) {
-    const float gv = k.gate[0];
-    if (!(fabsf(gv) <= 3.0e38f)) return;
-  }
+  if (k.gate && non_finite(k.gate[0])) return;
   const AptpAdamWItem it = k.items[lo];
-  const float t = k.step[0] + 1.0f;
-  const float bc1 = 1.0f - powf(k.beta1, t), bc2 = 1.0f - powf(k.beta2, t);
-  // constant_with_warmup counted in optimizer steps: rate lr * min(1, k / W) at the step that follows k applied ones (the
-  // first runs at 0).  Uniform; W = 0 leaves lr as passed, so the arithmetic below is what it is without a warm-up.
-  float lr = k.lr;
-  if (k.warmup > 0.0f) lr = k.lr * fminf(1.0f, k.step[0] / k.warmup);
-  const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2), decay = 1.0f - lr * k.wd;
+  // the warm-up is counted in optimizer steps.  Uniform; W = 0 leaves lr as passed.
+  const AdamCoef c = adam_coef(warmup_lr(k.lr, k.step[0], k.warmup), k.wd, k.beta1, k.beta2, k.eps, k.gscale, k.step[0] + 1.0f);
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   __bf16* sh = (__bf16*)it.shadow;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int64_t e = base + ((int64_t)i * 256 + threadIdx.x) * 4;
-    if (e + 3 < it.n) {
+    const int64_t e = base + ((int64_t)i * THREADS + threadIdx.x) * 4;
+    if (whole_quad(e, it.n)) {
       float4 p = *reinterpret_cast<const float4*>(it.p + e);
       const float4 g = *reinterpret_cast<const float4*>(it.g + e);
       float4 m = *reinterpret_cast<const float4*>(it.m + e);
       float4 v = *reinterpret_cast<const float4*>(it.v + e);
-      float* pp = &p.x; const float* g0 = &g.x; float* mm = &m.x; float* vv = &v.x;
-      const float gg[4] = {g0[0] * k.gscale, g0[1] * k.gscale, g0[2] * k.gscale, g0[3] * k.gscale};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        pp[j] *= decay;
-        mm[j] = k.beta1 * mm[j] + (1.0f - k.beta1) * gg[j];
-        vv[j] = k.beta2 * vv[j] + (1.0f - k.beta2) * gg[j] * gg[j];
-        pp[j] -= step_size * mm[j] / (sqrtf(vv[j]) / bc2_sqrt + k.eps);
-      }
+      adamw_quad(c, p, g, m, v);
       *reinterpret_cast<float4*>(it.p + e) = p;
       *reinterpret_cast<float4*>(it.m + e) = m;
       *reinterpret_cast<float4*>(it.v + e) = v;
@@ -74,11 +55,8 @@ __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
       }
     } else {
       for (int64_t x = e; x < it.n && x < e + 4; ++x) {
-        float p = it.p[x] * decay;
-        const float g = it.g[x] * k.gscale;
-        const float m = k.beta1 * it.m[x] + (1.0f - k.beta1) * g;
-        const float v = k.beta2 * it.v[x] + (1.0f - k.beta2) * g * g;
-        p -= step_size * m / (sqrtf(v) / bc2_sqrt + k.eps);
+        float p = it.p[x], m = it.m[x], v = it.v[x];
+        adamw_element(c, p, it.g[x], m, v);
         it.p[x] = p; it.m[x] = m; it.v[x] = v;
         if (sh) sh[x] = (__bf16)p;
       }
@@ -88,7 +66,7 @@ __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
 
 }  // namespace
 
-extern "C" int aptp_adamw_blocks(int64_t n) { return n <= 0 ? 0 : (int)((n + ELEMS_PER_BLOCK - 1) / ELEMS_PER_BLOCK); }
+extern "C" int aptp_adamw_blocks(int64_t n) { return blocks_of(n); }
 
 extern "C" int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream) {
   APTP_CHECK(p && p->items_dev && p->starts_dev && p->step_dev && p->n_items >= 1 && p->total_blocks >= 1, "adamw_many: bad arguments");

@@ -6,7 +6,7 @@
 //   aptp_pack_dgrad  the data-gradient operand of a contraction from its forward operand: dst[c][taps-1-t][n] = src[n][t][c]
 //                    (180-degree rotated transpose, bf16 -> bf16) as one tiled transpose through LDS (was: flip + strided
 //                    copy, 6-9 ms per step over 350 weights).
-#include "aptp_common.h"
+#include "packed_pass.h"
 
 namespace {
 
@@ -95,11 +95,7 @@ __global__ __launch_bounds__(256) void fold_rows_many_kernel(const AptpFoldRowsP
                                                              const int32_t* __restrict__ starts, int n_items, int total_units) {
   int u = blockIdx.x * FOLD_UNITS;
   const int u_end = u + FOLD_UNITS < total_units ? u + FOLD_UNITS : total_units;
-  int lo = 0, hi = n_items;                     // invariant: starts[lo] <= u < starts[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (starts[mid] <= u) lo = mid; else hi = mid;
-  }
+  int lo = packed_pass::item_of_block(starts, n_items, u);
   int s0 = starts[lo], s1 = starts[lo + 1];
   FoldK k = fold_item(items[lo]);
   while (u < u_end) {
@@ -171,11 +167,7 @@ __global__ __launch_bounds__(256) void pack_dgrad_kernel(const PackK p) {
 __global__ __launch_bounds__(256) void pack_dgrad_many_kernel(const AptpPackDgradParams* __restrict__ items,
                                                               const int32_t* __restrict__ starts, int n_items) {
   const int b = blockIdx.x;
-  int lo = 0, hi = n_items;                     // invariant: starts[lo] <= b < starts[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (starts[mid] <= b) lo = mid; else hi = mid;
-  }
+  const int lo = packed_pass::item_of_block(starts, n_items, b);
   const AptpPackDgradParams it = items[lo];
   PackK p{(const __bf16*)it.src, (__bf16*)it.dst, it.N, it.C, it.taps, it.src_ld, it.dst_ld, it.dst_rows};
   int local = b - starts[lo];

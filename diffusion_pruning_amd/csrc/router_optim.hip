@@ -3,8 +3,8 @@
 // configs/pruning/sd-2-1_cc3m.yaml without a recapture: two parameter groups with their own rate and weight decay,
 // `constant_with_warmup`, the NaN batch skip of pdm/training/trainer.py:921-929, and a step count PER TENSOR.
 //
-// Per element the arithmetic is adamw_many_kernel's (optim.hip; torch.optim.AdamW: decoupled weight decay, bias correction,
-// fp32 throughout):
+// Per element the arithmetic is adamw_many_kernel's (optim.hip), one body for both: packed_pass.h's adamw_element
+// (torch.optim.AdamW: decoupled weight decay, bias correction, fp32 throughout):
 //   p <- p * (1 - lr * wd);  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2
 //   p <- p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // with t = step_i + 1 (the item's own count: torch keeps one `step` per parameter and skips a parameter without a gradient, so a
@@ -15,11 +15,11 @@
 //   1. scan    every gradient element (and the gate): anything non-finite raises counters[2]
 //   2. update  reads counters[2], counters[0], step_i; applies the step or leaves p, m, v alone; zeroes the gradients when asked
 //   3. advance one block: step_i += 1 for every item and applied += 1, or skipped += 1; clears counters[2]
-#include "aptp_common.h"
+#include "packed_pass.h"
+
+using namespace packed_pass;
 
 namespace {
-
-constexpr int ELEMS_PER_BLOCK = 4096;          // 256 threads x 4 float4
 
 struct GroupAdamK {
   const AptpGroupAdamWItem* items; const int32_t* starts; int n_items;
@@ -30,29 +30,18 @@ struct GroupAdamK {
   const float* gate;                            // optional device scalar: the step is applied only when it is finite
 };
 
-__device__ __forceinline__ bool non_finite(float x) { return !(fabsf(x) <= 3.402823466e38f); }
-
-__device__ __forceinline__ int item_of_block(const GroupAdamK& k, int b) {
-  int lo = 0, hi = k.n_items;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (k.starts[mid] <= b) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void group_adamw_scan_kernel(const GroupAdamK k) {
   const int b = blockIdx.x;
   if (b >= k.starts[k.n_items]) return;
-  const int lo = item_of_block(k, b);
+  const int lo = item_of_block(k.starts, k.n_items, b);
   const AptpGroupAdamWItem it = k.items[lo];
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   bool bad = false;
   if (b == 0 && threadIdx.x == 0 && k.gate) bad = non_finite(k.gate[0]);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int64_t e = base + ((int64_t)i * 256 + threadIdx.x) * 4;
-    if (e + 3 < it.n) {
+    const int64_t e = base + ((int64_t)i * THREADS + threadIdx.x) * 4;
+    if (whole_quad(e, it.n)) {
       const float4 g = *reinterpret_cast<const float4*>(it.g + e);
       bad = bad || non_finite(g.x) || non_finite(g.y) || non_finite(g.z) || non_finite(g.w);
     } else {
@@ -65,38 +54,26 @@ __global__ __launch_bounds__(256) void group_adamw_scan_kernel(const GroupAdamK 
 __global__ __launch_bounds__(256) void group_adamw_update_kernel(const GroupAdamK k) {
   const int b = blockIdx.x;
   if (b >= k.starts[k.n_items]) return;
-  const int lo = item_of_block(k, b);
+  const int lo = item_of_block(k.starts, k.n_items, b);
   const AptpGroupAdamWItem it = k.items[lo];
   if (it.group < 0 || it.group >= k.n_groups) return;
   const bool skip = k.counters[2] != 0.0f;      // uniform over the grid: written by the scan, cleared by the advance launch
   if (skip && !k.zero_grad) return;
   const AptpAdamWGroup gr = k.groups[it.group];
-  const float applied = k.counters[0];
-  const float t = it.step[0] + 1.0f;
-  const float bc1 = 1.0f - powf(k.beta1, t), bc2 = 1.0f - powf(k.beta2, t);
-  float lr = gr.lr;
-  if (gr.warmup_steps > 0.0f) lr = gr.lr * fminf(1.0f, applied / gr.warmup_steps);
-  const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2), decay = 1.0f - lr * gr.weight_decay;
+  const AdamCoef c = adam_coef(warmup_lr(gr.lr, k.counters[0], gr.warmup_steps), gr.weight_decay, k.beta1, k.beta2, k.eps, k.gscale,
+                               it.step[0] + 1.0f);
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int64_t e = base + ((int64_t)i * 256 + threadIdx.x) * 4;
-    if (e + 3 < it.n) {
+    const int64_t e = base + ((int64_t)i * THREADS + threadIdx.x) * 4;
+    if (whole_quad(e, it.n)) {
       if (!skip) {
         float4 p = *reinterpret_cast<const float4*>(it.p + e);
         const float4 g = *reinterpret_cast<const float4*>(it.g + e);
         float4 m = *reinterpret_cast<const float4*>(it.m + e);
         float4 v = *reinterpret_cast<const float4*>(it.v + e);
-        float* pp = &p.x; const float* g0 = &g.x; float* mm = &m.x; float* vv = &v.x;
-        const float gg[4] = {g0[0] * k.gscale, g0[1] * k.gscale, g0[2] * k.gscale, g0[3] * k.gscale};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          pp[j] *= decay;
-          mm[j] = k.beta1 * mm[j] + (1.0f - k.beta1) * gg[j];
-          vv[j] = k.beta2 * vv[j] + (1.0f - k.beta2) * gg[j] * gg[j];
-          pp[j] -= step_size * mm[j] / (sqrtf(vv[j]) / bc2_sqrt + k.eps);
-        }
+        adamw_quad(c, p, g, m, v);
         *reinterpret_cast<float4*>(it.p + e) = p;
         *reinterpret_cast<float4*>(it.m + e) = m;
         *reinterpret_cast<float4*>(it.v + e) = v;
@@ -105,11 +82,8 @@ __global__ __launch_bounds__(256) void group_adamw_update_kernel(const GroupAdam
     } else {
       for (int64_t x = e; x < it.n && x < e + 4; ++x) {
         if (!skip) {
-          float p = it.p[x] * decay;
-          const float g = it.g[x] * k.gscale;
-          const float m = k.beta1 * it.m[x] + (1.0f - k.beta1) * g;
-          const float v = k.beta2 * it.v[x] + (1.0f - k.beta2) * g * g;
-          p -= step_size * m / (sqrtf(v) / bc2_sqrt + k.eps);
+          float p = it.p[x], m = it.m[x], v = it.v[x];
+          adamw_element(c, p, it.g[x], m, v);
           it.p[x] = p; it.m[x] = m; it.v[x] = v;
         }
         if (k.zero_grad) it.g[x] = 0.0f;
@@ -135,7 +109,7 @@ __global__ __launch_bounds__(256) void group_adamw_advance_kernel(const GroupAda
 
 }  // namespace
 
-extern "C" int aptp_group_adamw_blocks(int64_t n) { return n <= 0 ? 0 : (int)((n + ELEMS_PER_BLOCK - 1) / ELEMS_PER_BLOCK); }
+extern "C" int aptp_group_adamw_blocks(int64_t n) { return blocks_of(n); }
 
 extern "C" int aptp_group_adamw(const AptpGroupAdamWParams* p, aptp_stream_t stream) {
   APTP_CHECK(p && p->items_dev && p->starts_dev && p->groups_dev && p->counters_dev, "group_adamw: null pointer");

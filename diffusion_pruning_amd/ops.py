@@ -2161,22 +2161,17 @@ class FoldBatch:
         assert records
         dev = records[0]["keep"][0].device
         items = (FoldRowsParams * len(records))()
-        starts = [0]
+        blocks = []
         for i, rec in enumerate(records):
             ctypes.memmove(ctypes.byref(items[i]), ctypes.byref(rec["params"]), ctypes.sizeof(FoldRowsParams))
-            nb = lib.aptp_fold_rows_blocks(ctypes.byref(items[i]))
-            assert nb > 0
-            starts.append(starts[-1] + nb)
-        assert starts[-1] < 2 ** 31
-        self.items = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(dev)
-        self.starts = torch.tensor(starts, dtype=torch.int32).to(dev)
-        self.n, self.total = len(records), starts[-1]
+            blocks.append(lib.aptp_fold_rows_blocks(ctypes.byref(items[i])))
+            assert blocks[-1] > 0
+        assert sum(blocks) < 2 ** 31
+        self.table = _lib.BlockTable(items, blocks, dev)
         self.keep = [r["keep"] for r in records]
 
     def run(self):
-        lib = _lib.load()
-        _lib.check(lib.aptp_fold_rows_many(self.items.data_ptr(), self.starts.data_ptr(), self.n, self.total, _stream()),
-                   "aptp_fold_rows_many")
+        _lib.check(_lib.load().aptp_fold_rows_many(*self.table.args(), _stream()), "aptp_fold_rows_many")
 
 
 # Batched weight gradients (round 3).  Issued layer by layer, each aptp_conv_wgrad launch has to fill the chip on its own: a
@@ -2252,25 +2247,18 @@ class PackDgradBatch:
         assert pairs
         dev = pairs[0][0].w.device
         items = (PackDgradParams * len(pairs))()
-        starts = [0]
         for i, (pw, pwb) in enumerate(pairs):
             assert pwb.KH == pw.KH and pwb.N >= pw.Cin and pwb.cin_pad >= pw.N and pw.Cin2 == 0
             assert pw.cin_pad % 8 == 0 and pwb.cin_pad % 8 == 0 and pw.w.data_ptr() % 16 == 0 and pwb.w.data_ptr() % 16 == 0
             p = items[i]
             p.src, p.dst, p.N, p.C, p.taps = pw.w.data_ptr(), pwb.w.data_ptr(), pw.N, pw.Cin, pw.KH * pw.KW
             p.src_ld, p.dst_ld, p.dst_rows = pw.cin_pad, pwb.cin_pad, pwb.N
-            starts.append(starts[-1] + lib.aptp_pack_dgrad_blocks(ctypes.byref(p)))
-        raw = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8)
-        self.items = raw.to(dev)
-        self.starts = torch.tensor(starts, dtype=torch.int32).to(dev)
-        self.n, self.total = len(pairs), starts[-1]
+        self.table = _lib.BlockTable(items, [lib.aptp_pack_dgrad_blocks(ctypes.byref(p)) for p in items], dev)
         self.keep = pairs
         self.key = tuple((pw.w.data_ptr(), pwb.w.data_ptr()) for pw, pwb in pairs)
 
     def run(self):
-        lib = _lib.load()
-        _lib.check(lib.aptp_pack_dgrad_many(self.items.data_ptr(), self.starts.data_ptr(), self.n, self.total, _stream()),
-                   "aptp_pack_dgrad_many")
+        _lib.check(_lib.load().aptp_pack_dgrad_many(*self.table.args(), _stream()), "aptp_pack_dgrad_many")
 
 
 def gate_bwd(dy: torch.Tensor, y0: torch.Tensor, gate: torch.Tensor, want_dgate: bool = True):

@@ -19,13 +19,25 @@ full-shape parameters stay the checkpoint interface: ``export_()`` writes the pa
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import autograd as AG
 from . import ops
+
+
+def _order_by_name(saved_names, own_names, who):
+    """for every own name the position of the same name in a saved state (resume: whatever order the modules first ran in)"""
+    pos = {n: i for i, n in enumerate(saved_names)}
+    missing = [n for n in own_names if n not in pos]
+    assert not missing and len(pos) == len(saved_names) == len(own_names), \
+        f"{who}: the saved state belongs to another expert / tensor list (missing {missing[:3]}, " \
+        f"{len(saved_names)} saved vs {len(own_names)} here)"
+    return [pos[n] for n in own_names]
 
 
 class _Gemm:
@@ -191,6 +203,26 @@ class PackedTrainer:
             ps += [a.Pg, a.Pb]
         return ps
 
+    def entries(self):
+        """(fp32 master, bf16 shadow or None) of every packed tensor, in the order of parameters(): what the table-driven passes
+        (PackedAdamW, PackedEMA) walk.  They call it, and _sync, as PackedTrainer.entries(trainer): anything with ``gemms`` and
+        ``affines`` serves as a trainer"""
+        out = []
+        for e in self.gemms.values():
+            out.append((e.P, e.pw.w))
+            if e.Pb is not None:
+                out.append((e.Pb, None))
+        for a in self.affines.values():
+            out += [(a.Pg, None), (a.Pb, None)]
+        return out
+
+    def _sync(self):
+        """wait for a pending optimizer tail (a graphed step runs it on its own stream and installs ``sync``) before the packed
+        state is read or rewritten from the current stream"""
+        sync = getattr(self, "sync", None)
+        if sync is not None:
+            sync()
+
     @torch.no_grad()
     def ensure_grad_buffers(self, arena: bool = False, world: int = 1):
         """persistent, zero-initialised .grad for every packed tensor (direct-gradient mode, ops.GRAD_DIRECT): the kernels write
@@ -278,9 +310,7 @@ class PackedTrainer:
     @torch.no_grad()
     def export_(self):
         """write the packed values back into the diffusers-named full-shape parameters (checkpoint interface)"""
-        sync = getattr(self, "sync", None)
-        if sync is not None:
-            sync()                                # (a graphed step's optimizer tail runs on its own stream)
+        self._sync()
         for e in self.gemms.values():
             e.export_()
         for a in self.affines.values():
@@ -301,20 +331,11 @@ class PackedAdamW:
         warmup_steps W > 0: the rate of the step that follows k applied steps is lr * min(1, k / W) -- `constant_with_warmup` of
         the fine-tune recipe (configs/finetuning/sd-2-1_cc3m.yaml:108-109) counted in optimizer steps; the kernel reads k from
         the device-side step count, so a gated (skipped) step does not advance the ramp.  0: constant lr."""
-        import ctypes
-        from . import _lib
         self.trainer, self.lr, self.betas, self.eps, self.weight_decay = trainer, lr, betas, eps, weight_decay
         self.group_of = group_of
         assert warmup_steps >= 0, "PackedAdamW: warmup_steps"
         self.warmup_steps = warmup_steps
-        entries = []                                   # (parameter, bf16 shadow or None)
-        for e in trainer.gemms.values():
-            entries.append((e.P, e.pw.w))
-            if e.Pb is not None:
-                entries.append((e.Pb, None))
-        for a in trainer.affines.values():
-            entries += [(a.Pg, None), (a.Pb, None)]
-        entries = [(p, sh) for p, sh in entries if p.grad is not None]      # (entries no backward reaches have nothing to apply)
+        entries = [(p, sh) for p, sh in PackedTrainer.entries(trainer) if p.grad is not None]   # (entries no backward reaches have nothing to apply)
         assert entries, "PackedAdamW: run one backward first (the gradient addresses go into the kernel's table)"
         dev = entries[0][0].device
         self.entries = entries
@@ -329,12 +350,9 @@ class PackedAdamW:
     def rebind_(self):
         """(re)build the kernel's table from the parameters' CURRENT gradient tensors (state is kept): once for a captured
         backward, whose replays re-write the same addresses; before every step of an eager loop, whose backward allocates"""
-        from . import _lib
         lib = _lib.load()
-        dev = self.params[0].device
         self.grads = [p.grad for p in self.params]      # keeps the addresses in the table alive
         items = (_lib.AdamWItem * len(self.entries))()
-        starts = [0]
         for i, ((p, sh), m, v) in enumerate(zip(self.entries, self.m, self.v)):
             g = p.grad
             assert g is not None, f"PackedAdamW.rebind_: {self.names[i]} has no gradient (every tensor of the table needs one)"
@@ -345,35 +363,20 @@ class PackedAdamW:
             if sh is not None:
                 assert sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() == p.numel() and sh.data_ptr() % 8 == 0
                 it.shadow = sh.data_ptr()
-            starts.append(starts[-1] + lib.aptp_adamw_blocks(p.numel()))
-        self.items = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(dev)
-        self.starts = torch.tensor(starts, dtype=torch.int32).to(dev)
-        self.n, self.total = len(self.entries), starts[-1]
+        self.table = _lib.BlockTable(items, [lib.aptp_adamw_blocks(p.numel()) for p in self.params], self.params[0].device)
         # per-group tables (bucketed data-parallel exchange): the same descriptors, regrouped, with block prefixes of their own
         self.groups = None
         if self.group_of is not None:
-            import ctypes
-            isz = ctypes.sizeof(_lib.AdamWItem)
-            raw = bytes(items)
             by = {}
             for i, p in enumerate(self.params):
                 by.setdefault(int(self.group_of(p)), []).append(i)
-            self.groups = {}
-            for gi, idx in sorted(by.items()):
-                st = [0]
-                for i in idx:
-                    st.append(st[-1] + (starts[i + 1] - starts[i]))
-                blob = b"".join(raw[i * isz:(i + 1) * isz] for i in idx)
-                self.groups[gi] = (torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev),
-                                   torch.tensor(st, dtype=torch.int32).to(dev), len(idx), st[-1])
+            self.groups = {gi: self.table.subset(idx) for gi, idx in sorted(by.items())}
         return self
 
-    def _launch(self, items, starts, n, total, gate, grad_scale):
-        import ctypes
-        from . import _lib
+    def _launch(self, table, gate, grad_scale):
         lib = _lib.load()
         q = _lib.AdamWParams()
-        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = items.data_ptr(), starts.data_ptr(), n, total
+        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = table.args()
         q.lr, q.beta1, q.beta2, q.eps, q.weight_decay = self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay
         q.step_dev = self.step_t.data_ptr()
         q.gate_dev = None if gate is None else gate.data_ptr()
@@ -391,15 +394,14 @@ class PackedAdamW:
         -- parameters, moments, operands and the step count -- is skipped unless it is finite (reference: the batch skip of
         pdm/training/trainer.py:921-929); grad_scale multiplies the gradients first (1 / world after a summed exchange)."""
         self._check_grads()
-        self._launch(self.items, self.starts, self.n, self.total, gate, grad_scale)
+        self._launch(self.table, gate, grad_scale)
         self.finish_step(gate)
 
     @torch.no_grad()
     def step_group(self, gi: int, gate: torch.Tensor = None, grad_scale: float = 1.0):
         """the tensors of group gi only (no step-count update: call finish_step() after the last group)"""
         if gi in self.groups:
-            items, starts, n, total = self.groups[gi]
-            self._launch(items, starts, n, total, gate, grad_scale)
+            self._launch(self.groups[gi], gate, grad_scale)
 
     @torch.no_grad()
     def finish_step(self, gate: torch.Tensor = None):
@@ -423,12 +425,7 @@ class PackedAdamW:
             assert len(sd["exp_avg"]) == len(self.m), "PackedAdamW: different tensor list"
             order = list(range(len(self.m)))
         else:
-            pos = {n: i for i, n in enumerate(names)}
-            missing = [n for n in self.names if n not in pos]
-            assert not missing and len(pos) == len(names) == len(self.names), \
-                f"PackedAdamW: the saved state belongs to another expert / tensor list (missing {missing[:3]}, " \
-                f"{len(names)} saved vs {len(self.names)} here)"
-            order = [pos[n] for n in self.names]
+            order = _order_by_name(names, self.names, "PackedAdamW")
         for i, j in enumerate(order):
             ma, va = sd["exp_avg"][j], sd["exp_avg_sq"][j]
             assert self.m[i].shape == ma.shape and self.v[i].shape == va.shape, \
@@ -449,20 +446,13 @@ class PackedEMA:
 
     def __init__(self, trainer: PackedTrainer, optimizer: Optional[PackedAdamW] = None, decay: float = 0.9999, min_decay: float = 0.0,
                  update_after_step: int = 0, use_ema_warmup: bool = False, inv_gamma: float = 1.0, power: float = 2.0 / 3.0):
-        from . import _lib
         lib = _lib.load()
         assert 0.0 <= decay <= 1.0 and 0.0 <= min_decay <= decay and int(update_after_step) >= 0 and inv_gamma > 0 and power > 0, \
             "PackedEMA: hyper-parameters"
         self.trainer, self.optimizer = trainer, optimizer
         self.decay, self.min_decay, self.update_after_step = float(decay), float(min_decay), int(update_after_step)
         self.use_ema_warmup, self.inv_gamma, self.power = bool(use_ema_warmup), float(inv_gamma), float(power)
-        entries = []                                   # (master, bf16 shadow or None)
-        for e in trainer.gemms.values():
-            entries.append((e.P, e.pw.w))
-            if e.Pb is not None:
-                entries.append((e.Pb, None))
-        for a in trainer.affines.values():
-            entries += [(a.Pg, None), (a.Pb, None)]
+        entries = PackedTrainer.entries(trainer)
         assert entries, "PackedEMA: the trainer has no packed tensors yet (PackedTrainer.materialize)"
         by_id = {id(p): n for n, p in trainer.named_parameters()}
         self.entries = entries
@@ -474,7 +464,6 @@ class PackedEMA:
         self._cur_decay = torch.zeros((), dtype=torch.float32, device=dev)
         self.swapped = False
         items = (_lib.EmaItem * len(entries))()
-        starts = [0]
         for i, ((p, sh), a) in enumerate(zip(entries, self.ema)):
             assert p.dtype == torch.float32 and p.data.is_contiguous() and a.is_contiguous() and p.numel() >= 1
             assert p.data_ptr() % 16 == 0 and a.data_ptr() % 16 == 0
@@ -483,20 +472,15 @@ class PackedEMA:
             if sh is not None:
                 assert sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() == p.numel() and sh.data_ptr() % 8 == 0
                 it.shadow = sh.data_ptr()
-            starts.append(starts[-1] + lib.aptp_adamw_blocks(p.numel()))
-        self.items = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(dev)
-        self.starts = torch.tensor(starts, dtype=torch.int32).to(dev)
-        self.n, self.total = len(entries), starts[-1]
+        self.table = _lib.BlockTable(items, [lib.aptp_adamw_blocks(p.numel()) for p in self.params], dev)
 
     def n_elements(self) -> int:
         return sum(p.numel() for p in self.params)
 
     def _launch(self, mode: int, gate: Optional[torch.Tensor] = None):
-        import ctypes
-        from . import _lib
         lib = _lib.load()
         q = _lib.EmaParams()
-        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = self.items.data_ptr(), self.starts.data_ptr(), self.n, self.total
+        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = self.table.args()
         q.mode = mode
         q.count_dev = self.count.data_ptr()
         q.gate_dev = None if gate is None else gate.data_ptr()
@@ -510,7 +494,6 @@ class PackedEMA:
         """one EMA update over every tensor (one launch), then the count on the device.  gate: optional fp32 device scalar (the
         step's loss): averages, decay and count stay as they are unless it is finite -- PackedAdamW's predicate.  No host sync."""
         assert not self.swapped, "PackedEMA.step: the masters hold the average (swap_() back first)"
-        from . import _lib
         self._launch(_lib.EMA_UPDATE, gate)
         if gate is None:
             self.count += 1.0
@@ -522,10 +505,7 @@ class PackedEMA:
         """masters <-> averages in one launch; the bf16 forward operands follow the masters.  The data-gradient operands (pwb)
         are NOT rewritten: only a backward reads them, no step runs while swapped, and the swap back returns the masters bit for
         bit, so they are valid again."""
-        from . import _lib
-        sync = getattr(self.trainer, "sync", None)
-        if sync is not None:
-            sync()                                # (a graphed step's optimizer tail runs on its own stream)
+        PackedTrainer._sync(self.trainer)
         self._launch(_lib.EMA_SWAP)
         self.swapped = not self.swapped
         return self
@@ -554,9 +534,7 @@ class PackedEMA:
     def state_dict(self):
         """count and averages, keyed by the stable names of PackedTrainer.named_parameters()"""
         assert not self.swapped, "PackedEMA.state_dict: swapped (the averages sit in the masters)"
-        sync = getattr(self.trainer, "sync", None)
-        if sync is not None:
-            sync()
+        PackedTrainer._sync(self.trainer)
         return {"count": self.count.clone(), "cur_decay": self._cur_decay.clone(), "names": list(self.names),
                 "ema": [a.clone() for a in self.ema]}
 
@@ -565,18 +543,11 @@ class PackedEMA:
         assert not self.swapped, "PackedEMA.load_state_dict: swapped (the averages sit in the masters)"
         names = sd["names"]
         assert len(sd["ema"]) == len(names), "PackedEMA: malformed state"
-        pos = {n: i for i, n in enumerate(names)}
-        missing = [n for n in self.names if n not in pos]
-        assert not missing and len(pos) == len(names) == len(self.names), \
-            f"PackedEMA: the saved state belongs to another expert / tensor list (missing {missing[:3]}, " \
-            f"{len(names)} saved vs {len(self.names)} here)"
-        order = [pos[n] for n in self.names]
+        order = _order_by_name(names, self.names, "PackedEMA")
         for i, j in enumerate(order):
             assert self.ema[i].shape == sd["ema"][j].shape, \
                 f"PackedEMA: {self.names[i]}: saved average {tuple(sd['ema'][j].shape)} vs {tuple(self.ema[i].shape)}"
-        sync = getattr(self.trainer, "sync", None)
-        if sync is not None:
-            sync()
+        PackedTrainer._sync(self.trainer)
         self.count.copy_(sd["count"])
         if "cur_decay" in sd:
             self._cur_decay.copy_(sd["cur_decay"])

@@ -200,15 +200,11 @@ class RouterAdamW:
                 "RouterAdamW.add_table: parameters that share a buffer (the hyper-net's heads) go into a table together"
         assert runs, "RouterAdamW.add_table: no parameters"
         items = (_lib.GroupAdamWItem * len(runs))()
-        starts = [0]
         for it, ri in zip(items, runs):
             r = self.runs[ri]
             it.p, it.g, it.m, it.v, it.n = r["ptr"], r["g"].data_ptr(), r["m"].data_ptr(), r["v"].data_ptr(), r["n"]
             it.step, it.group = self.run_steps.data_ptr() + 4 * ri, r["group"]
-            starts.append(starts[-1] + lib.aptp_group_adamw_blocks(r["n"]))
-        self.tables[key] = dict(host=items, n=len(runs), total=starts[-1],
-                                items=torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.device),
-                                starts=torch.tensor(starts, dtype=torch.int32).to(self.device))
+        self.tables[key] = _lib.BlockTable(items, [lib.aptp_group_adamw_blocks(self.runs[ri]["n"]) for ri in runs], self.device)
 
     def add_table(self, key, params):
         """a descriptor table over a subset of the parameters (device memory; built once, before any capture)"""
@@ -244,13 +240,13 @@ class RouterAdamW:
         self._check()
         tb = self.tables[table]
         q = _lib.GroupAdamWParams()
-        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = tb["items"].data_ptr(), tb["starts"].data_ptr(), tb["n"], tb["total"]
+        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = tb.args()
         q.groups_dev, q.n_groups, q.counters_dev = self.groups_dev.data_ptr(), len(self.param_groups), self.counters.data_ptr()
         q.beta1, q.beta2, q.eps, q.grad_scale, q.zero_grad = self.betas[0], self.betas[1], self.eps, float(grad_scale), 1
         if gate is not None:
             assert gate.dtype == torch.float32 and gate.device == self.device and gate.numel() == 1
             q.gate_dev = gate.data_ptr()
-        q.items_host = ctypes.cast(tb["host"], ctypes.c_void_p)
+        q.items_host = ctypes.cast(tb.host, ctypes.c_void_p)
         _lib.check(_lib.load().aptp_group_adamw(ctypes.byref(q), ops._stream()), "aptp_group_adamw")
 
     @torch.no_grad()

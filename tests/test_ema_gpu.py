@@ -132,8 +132,8 @@ def test_update_kernel_against_fp64_model(cuda, ns):
                     k += 1
 
 
-@pytest.mark.parametrize("gate,applied", [(0.25, True), (-3.0e38, True), (float("nan"), False), (float("inf"), False),
-                                          (float("-inf"), False)])
+@pytest.mark.parametrize("gate,applied", [(0.25, True), (-3.0e38, True), (3.2e38, True), (-3.2e38, True), (float("nan"), False),
+                                          (float("inf"), False), (float("-inf"), False)])
 def test_update_kernel_gate(cuda, gate, applied):
     from diffusion_pruning_amd import _lib
     t = _Table((5, 4097, 1), cuda, seed=7)

@@ -359,6 +359,34 @@ def test_adamw_gate_grad_scale_and_groups(cuda):
     assert torch.equal(sh2[1], sh0[1])
 
 
+def test_adamw_gate_just_below_float_max_applies_the_step(cuda):
+    """finite means |gate| <= FLT_MAX in the kernel as in PackedAdamW.finish_step (torch.isfinite): a gate of 3.2e38 applies the
+    step -- parameters, moments and operand bit for bit those of the ungated step -- and the step count advances with it (the
+    kernel used to skip above 3.0e38 while the count advanced)."""
+    from types import SimpleNamespace
+    from diffusion_pruning_amd.packed_train import PackedAdamW
+    shapes = [(8, 1, 8), (5,), (4097,)]
+
+    def stepped(gate):
+        ps = [torch.nn.Parameter(torch.randn(*s, generator=torch.Generator().manual_seed(21 + i)).to(cuda)) for i, s in enumerate(shapes)]
+        sh = [torch.zeros(shapes[i], dtype=torch.bfloat16, device=cuda) for i in (0, 2)]
+        gemms = {0: SimpleNamespace(P=ps[0], Pb=ps[1], pw=SimpleNamespace(w=sh[0])), 1: SimpleNamespace(P=ps[2], Pb=None, pw=SimpleNamespace(w=sh[1]))}
+        tr = SimpleNamespace(gemms=gemms, affines={}, refresh_=lambda shadows_done=False: None)
+        for i, p in enumerate(ps):
+            p.grad = torch.randn(*p.shape, generator=torch.Generator().manual_seed(31 + i)).to(cuda)
+        opt = PackedAdamW(tr, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+        opt.step(gate=None if gate is None else torch.tensor(gate, dtype=torch.float32, device=cuda))
+        return ps, sh, opt
+    ps0, sh0, o0 = stepped(None)
+    ps1, sh1, o1 = stepped(3.2e38)
+    assert float(o0.step_t) == 1.0 and float(o1.step_t) == 1.0
+    assert all(float((p.detach() - torch.randn(*p.shape, generator=torch.Generator().manual_seed(21 + i)).to(cuda)).abs().max()) > 0
+               for i, p in enumerate(ps0))                                   # (the ungated step moved every tensor)
+    assert all(torch.equal(a.detach(), b.detach()) for a, b in zip(ps1, ps0))
+    assert all(torch.equal(a, b) for a, b in zip(o1.m + o1.v + sh1, o0.m + o0.v + sh0))
+    assert torch.equal(sh1[0], ps1[0].detach().to(torch.bfloat16)) and torch.equal(sh1[1], ps1[2].detach().to(torch.bfloat16))
+
+
 def test_graphed_finetune_step_skips_a_batch_with_nan_loss(cuda):
     """GraphedFineTunerStep(nan_guard=True): a batch that makes the loss NaN (here: a NaN in the target) is skipped on the
     device -- parameters, AdamW moments and step count keep their values -- and the following clean batch trains normally
