@@ -195,7 +195,17 @@ class GroupAdamWParams(Structure):
     _fields_ = [("items_dev", c_void_p), ("starts_dev", c_void_p), ("n_items", c_int32), ("total_blocks", c_int32),
                 ("groups_dev", c_void_p), ("n_groups", c_int32), ("counters_dev", c_void_p),
                 ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("grad_scale", c_float), ("zero_grad", c_int32),
-                ("gate_dev", c_void_p), ("items_host", c_void_p)]
+                ("gate_dev", c_void_p), ("items_host", c_void_p), ("grad_scale_dev", c_void_p)]
+
+
+class GradNormItem(Structure):
+    _fields_ = [("g", c_void_p), ("n", c_int64)]
+
+
+class GradNormParams(Structure):
+    _fields_ = [("items_dev", c_void_p), ("starts_dev", c_void_p), ("n_items", c_int32), ("total_blocks", c_int32),
+                ("partials_dev", c_void_p), ("grad_scale", c_float), ("max_norm_dev", c_void_p), ("gate_dev", c_void_p),
+                ("out_dev", c_void_p)]
 
 
 EMA_UPDATE, EMA_SWAP = 0, 1
@@ -604,9 +614,12 @@ EXPORTS = [
     ("aptp_pack_dgrad_many", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("aptp_adamw_blocks", c_int, [c_int64]),
     ("aptp_adamw_many", c_int, [POINTER(AdamWParams), c_void_p]),
+    ("aptp_adamw_many_scaled", c_int, [POINTER(AdamWParams), c_void_p, c_void_p]),
     ("aptp_ema_many", c_int, [POINTER(EmaParams), c_void_p]),
     ("aptp_group_adamw_blocks", c_int, [c_int64]),
     ("aptp_group_adamw", c_int, [POINTER(GroupAdamWParams), c_void_p]),
+    ("aptp_grad_norm_blocks", c_int, [c_int64]),
+    ("aptp_grad_norm", c_int, [POINTER(GradNormParams), c_void_p]),
     ("aptp_grad_accumulate_blocks", c_int, [c_int64]),
     ("aptp_grad_accumulate", c_int, [POINTER(GradAccumParams), c_void_p]),
     ("aptp_mse_nblocks", c_int, [c_int64, c_int32]),

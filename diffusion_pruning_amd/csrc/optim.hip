@@ -23,6 +23,7 @@ struct AdamK {
   const float* gate;                            // optional device scalar: the step is applied only when it is finite
   float gscale;                                 // gradients are multiplied by this first (1 / world size of a summed exchange)
   float warmup;                                 // 0 = off; else the rate ramps linearly over this many optimizer steps
+  const float* gscale_dev;                      // optional device scalar (the clip coefficient of grad_norm.hip): one more factor of gscale
 };
 
 __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
@@ -33,8 +34,9 @@ __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
   // the same predicate.  Uniform over the grid: one scalar load.
   if (k.gate && non_finite(k.gate[0])) return;
   const AptpAdamWItem it = k.items[lo];
-  // the warm-up is counted in optimizer steps.  Uniform; W = 0 leaves lr as passed.
-  const AdamCoef c = adam_coef(warmup_lr(k.lr, k.step[0], k.warmup), k.wd, k.beta1, k.beta2, k.eps, k.gscale, k.step[0] + 1.0f);
+  // the warm-up is counted in optimizer steps.  Uniform; W = 0 leaves lr as passed.  So is the clip: one scalar load, one product.
+  const float gscale = k.gscale_dev ? k.gscale * k.gscale_dev[0] : k.gscale;
+  const AdamCoef c = adam_coef(warmup_lr(k.lr, k.step[0], k.warmup), k.wd, k.beta1, k.beta2, k.eps, gscale, k.step[0] + 1.0f);
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   __bf16* sh = (__bf16*)it.shadow;
 #pragma unroll
@@ -68,13 +70,16 @@ __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
 
 extern "C" int aptp_adamw_blocks(int64_t n) { return blocks_of(n); }
 
-extern "C" int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream) {
+extern "C" int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream) { return aptp_adamw_many_scaled(p, nullptr, stream); }
+
+extern "C" int aptp_adamw_many_scaled(const AptpAdamWParams* p, const float* grad_scale_dev, aptp_stream_t stream) {
   APTP_CHECK(p && p->items_dev && p->starts_dev && p->step_dev && p->n_items >= 1 && p->total_blocks >= 1, "adamw_many: bad arguments");
   APTP_CHECK(p->lr >= 0.f && p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f && p->eps > 0.f, "adamw_many: hyper-parameters");
   APTP_CHECK(p->grad_scale >= 0.f, "adamw_many: grad_scale");
   APTP_CHECK(p->warmup_steps >= 0.f, "adamw_many: warmup_steps");
+  APTP_CHECK(((uintptr_t)grad_scale_dev & 3) == 0, "adamw_many: misaligned grad_scale_dev");
   AdamK k{p->items_dev, p->starts_dev, p->n_items, p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->step_dev,
-          p->gate_dev, p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->warmup_steps};
+          p->gate_dev, p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->warmup_steps, grad_scale_dev};
   hipLaunchKernelGGL(adamw_many_kernel, dim3((unsigned)p->total_blocks), dim3(256), 0, (hipStream_t)stream, k);
   APTP_LAUNCH_CHECK();
   return APTP_OK;

@@ -28,6 +28,7 @@ struct GroupAdamK {
   float beta1, beta2, eps, gscale;
   int zero_grad;
   const float* gate;                            // optional device scalar: the step is applied only when it is finite
+  const float* gscale_dev;                      // optional device scalar (the clip coefficient of grad_norm.hip): one more factor of gscale
 };
 
 __global__ __launch_bounds__(256) void group_adamw_scan_kernel(const GroupAdamK k) {
@@ -60,7 +61,8 @@ __global__ __launch_bounds__(256) void group_adamw_update_kernel(const GroupAdam
   const bool skip = k.counters[2] != 0.0f;      // uniform over the grid: written by the scan, cleared by the advance launch
   if (skip && !k.zero_grad) return;
   const AptpAdamWGroup gr = k.groups[it.group];
-  const AdamCoef c = adam_coef(warmup_lr(gr.lr, k.counters[0], gr.warmup_steps), gr.weight_decay, k.beta1, k.beta2, k.eps, k.gscale,
+  const float gscale = k.gscale_dev ? k.gscale * k.gscale_dev[0] : k.gscale;      // uniform: one scalar load, one product
+  const AdamCoef c = adam_coef(warmup_lr(gr.lr, k.counters[0], gr.warmup_steps), gr.weight_decay, k.beta1, k.beta2, k.eps, gscale,
                                it.step[0] + 1.0f);
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -117,7 +119,8 @@ extern "C" int aptp_group_adamw(const AptpGroupAdamWParams* p, aptp_stream_t str
   APTP_CHECK(p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f && p->eps > 0.f, "group_adamw: hyper-parameters");
   APTP_CHECK(p->grad_scale >= 0.f, "group_adamw: grad_scale");
   APTP_CHECK(((uintptr_t)p->items_dev & 7) == 0 && ((uintptr_t)p->starts_dev & 3) == 0 && ((uintptr_t)p->groups_dev & 3) == 0 &&
-             ((uintptr_t)p->counters_dev & 15) == 0 && ((uintptr_t)p->gate_dev & 3) == 0, "group_adamw: misaligned table");
+             ((uintptr_t)p->counters_dev & 15) == 0 && ((uintptr_t)p->gate_dev & 3) == 0 && ((uintptr_t)p->grad_scale_dev & 3) == 0,
+             "group_adamw: misaligned table");
   if (p->items_host) {                          // the host's copy of the table: what the kernels will dereference is checked here
     int64_t blocks = 0;
     for (int i = 0; i < p->n_items; ++i) {
@@ -132,7 +135,8 @@ extern "C" int aptp_group_adamw(const AptpGroupAdamWParams* p, aptp_stream_t str
     APTP_CHECK(blocks == p->total_blocks, "group_adamw: total_blocks %d, the items need %lld", (int)p->total_blocks, (long long)blocks);
   }
   GroupAdamK k{p->items_dev, p->starts_dev, p->n_items, p->groups_dev, p->n_groups, p->counters_dev, p->beta1, p->beta2, p->eps,
-               p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->zero_grad != 0, p->gate_dev};
+               p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->zero_grad != 0, p->gate_dev,
+               p->grad_scale_dev};
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)p->total_blocks), block(256);
   hipLaunchKernelGGL(group_adamw_scan_kernel, grid, block, 0, s, k);

@@ -2154,6 +2154,59 @@ def grad_accumulate(acc: torch.Tensor, g: torch.Tensor, mode) -> None:
     _lib.check(_lib.load().aptp_grad_accumulate(ctypes.byref(q), _stream()), "aptp_grad_accumulate")
 
 
+class GradNorm:
+    """The global L2 norm of a fixed list of gradient tensors and the clip coefficient of torch.nn.utils.clip_grad_norm_, computed
+    and kept on the device (csrc/grad_norm.hip: two launches, fp64 accumulation in a fixed order, the same bits at every replay).
+    grads: contiguous, 16-byte aligned fp32 tensors whose addresses stay put (they go into a device table, built here once).
+    ``run`` is one call and is capturable; ``out`` = {total_norm, clip_coef, verdict, clipped_count}, with views
+      norm     the norm of grad_scale * gradients
+      coef     min(1, max_norm / (norm + 1e-6)), exactly 1 without a threshold: what grad_scale_dev of the AdamW passes reads
+      verdict  the norm when it and the gate are finite, else NaN: the gate of the optimizer and the EMA
+      clipped  calls so far with a finite verdict and coef < 1
+    share: another GradNorm whose ``out`` and threshold this one uses (tables over subsets of one optimizer's gradients)."""
+
+    def __init__(self, grads, device=None, max_norm: Optional[float] = None, share: Optional["GradNorm"] = None):
+        lib = _lib.load()
+        grads = list(grads)
+        assert grads, "GradNorm: no gradient tensors"
+        device = torch.device(device) if device is not None else grads[0].device
+        items = (_lib.GradNormItem * len(grads))()
+        for it, g in zip(items, grads):
+            assert g.device == device and g.dtype == torch.float32 and g.is_contiguous() and g.numel() >= 1 and g.data_ptr() % 16 == 0, \
+                "GradNorm: contiguous, 16-byte aligned fp32 tensors on one device"
+            it.g, it.n = g.data_ptr(), g.numel()
+        self.grads = grads                        # keeps the addresses in the table alive
+        self.table = _lib.BlockTable(items, [lib.aptp_grad_norm_blocks(g.numel()) for g in grads], device)
+        self.partials = torch.zeros(self.table.total, dtype=torch.float64, device=device)
+        self.out = torch.zeros(4, dtype=torch.float32, device=device) if share is None else share.out
+        self.norm, self.coef, self.verdict, self.clipped = self.out[0:1], self.out[1:2], self.out[2:3], self.out[3:4]
+        if share is None:
+            self.max_norm_dev = torch.full((1,), float("inf"), dtype=torch.float32, device=device)
+            self.set_max_norm(max_norm)
+        else:
+            self.max_norm_dev, self.max_norm = share.max_norm_dev, share.max_norm
+
+    def set_max_norm(self, value: Optional[float]):
+        """the threshold, written into device memory: replays of a captured run read it (no recapture).  None: measure only."""
+        assert value is None or float(value) > 0.0, "GradNorm: max_norm must be > 0 (None: measure only)"
+        self.max_norm = None if value is None else float(value)
+        self.max_norm_dev.fill_(float("inf") if value is None else float(value))
+        return self
+
+    def run(self, grad_scale: float = 1.0, gate: Optional[torch.Tensor] = None):
+        """grad_scale: the scale the optimizer will apply to the gradients (the norm is that of the scaled gradients); gate:
+        optional fp32 device scalar (the step's loss).  Returns ``out``."""
+        q = _lib.GradNormParams()
+        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = self.table.args()
+        q.partials_dev, q.grad_scale, q.out_dev = self.partials.data_ptr(), float(grad_scale), self.out.data_ptr()
+        q.max_norm_dev = self.max_norm_dev.data_ptr()
+        if gate is not None:
+            assert gate.dtype == torch.float32 and gate.device == self.out.device and gate.numel() == 1
+            q.gate_dev = gate.data_ptr()
+        _lib.check(_lib.load().aptp_grad_norm(ctypes.byref(q), _stream()), "aptp_grad_norm")
+        return self.out
+
+
 class FoldBatch:
     def __init__(self, records):
         lib = _lib.load()

@@ -324,17 +324,23 @@ class PackedAdamW:
     captured backward of GraphedFineTunerStep: the graph re-writes the same addresses at every replay)."""
 
     def __init__(self, trainer: PackedTrainer, lr: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 group_of=None, warmup_steps: int = 0):
+                 group_of=None, warmup_steps: int = 0, max_grad_norm: Optional[float] = None, log_grad_norm: bool = False):
         """group_of: optional map parameter -> group index (e.g. the gradient bucket that completes it, ArenaGradReducer.bucket_of):
         the table is built per group and ``step_group(i)`` applies one group per launch, so the optimizer can follow a
         bucketed gradient exchange bucket by bucket; ``step()`` applies all groups.
         warmup_steps W > 0: the rate of the step that follows k applied steps is lr * min(1, k / W) -- `constant_with_warmup` of
         the fine-tune recipe (configs/finetuning/sd-2-1_cc3m.yaml:108-109) counted in optimizer steps; the kernel reads k from
-        the device-side step count, so a gated (skipped) step does not advance the ramp.  0: constant lr."""
+        the device-side step count, so a gated (skipped) step does not advance the ramp.  0: constant lr.
+        max_grad_norm X: torch.nn.utils.clip_grad_norm_(parameters, X) in front of every ``step()``, on the device (ops.GradNorm over
+        the gradients of the table: two launches; the kernel multiplies the gradients by the coefficient it reads from device
+        memory, they are not rewritten), and a non-finite norm skips the step as a non-finite gate does.  log_grad_norm=True: the
+        norm is taken (and gates) without a threshold.  Neither: no GradNorm, no extra launch."""
         self.trainer, self.lr, self.betas, self.eps, self.weight_decay = trainer, lr, betas, eps, weight_decay
         self.group_of = group_of
         assert warmup_steps >= 0, "PackedAdamW: warmup_steps"
         self.warmup_steps = warmup_steps
+        assert max_grad_norm is None or max_grad_norm > 0, "PackedAdamW: max_grad_norm"
+        self.max_grad_norm, self._want_norm, self.grad_norm = max_grad_norm, (max_grad_norm is not None or log_grad_norm), None
         entries = [(p, sh) for p, sh in PackedTrainer.entries(trainer) if p.grad is not None]   # (entries no backward reaches have nothing to apply)
         assert entries, "PackedAdamW: run one backward first (the gradient addresses go into the kernel's table)"
         dev = entries[0][0].device
@@ -371,9 +377,14 @@ class PackedAdamW:
             for i, p in enumerate(self.params):
                 by.setdefault(int(self.group_of(p)), []).append(i)
             self.groups = {gi: self.table.subset(idx) for gi, idx in sorted(by.items())}
+        if self._want_norm:
+            clipped = None if self.grad_norm is None else self.grad_norm.clipped.clone()
+            self.grad_norm = ops.GradNorm(self.grads, self.params[0].device, max_norm=self.max_grad_norm)
+            if clipped is not None:
+                self.grad_norm.clipped.copy_(clipped)
         return self
 
-    def _launch(self, table, gate, grad_scale):
+    def _launch(self, table, gate, grad_scale, grad_scale_dev=None):
         lib = _lib.load()
         q = _lib.AdamWParams()
         q.items_dev, q.starts_dev, q.n_items, q.total_blocks = table.args()
@@ -382,7 +393,10 @@ class PackedAdamW:
         q.gate_dev = None if gate is None else gate.data_ptr()
         q.grad_scale = float(grad_scale)
         q.warmup_steps = float(self.warmup_steps)
-        _lib.check(lib.aptp_adamw_many(ctypes.byref(q), ops._stream()), "aptp_adamw_many")
+        if grad_scale_dev is None:
+            _lib.check(lib.aptp_adamw_many(ctypes.byref(q), ops._stream()), "aptp_adamw_many")
+        else:       # (the clip coefficient of ops.GradNorm, read from device memory as one more factor of grad_scale)
+            _lib.check(lib.aptp_adamw_many_scaled(ctypes.byref(q), grad_scale_dev.data_ptr(), ops._stream()), "aptp_adamw_many_scaled")
 
     def _check_grads(self):
         for p, g in zip(self.params, self.grads):
@@ -392,14 +406,42 @@ class PackedAdamW:
     def step(self, gate: torch.Tensor = None, grad_scale: float = 1.0):
         """one AdamW step over every tensor (one launch).  gate: optional fp32 device scalar (the step's loss): the whole step
         -- parameters, moments, operands and the step count -- is skipped unless it is finite (reference: the batch skip of
-        pdm/training/trainer.py:921-929); grad_scale multiplies the gradients first (1 / world after a summed exchange)."""
+        pdm/training/trainer.py:921-929); grad_scale multiplies the gradients first (1 / world after a summed exchange).
+        With a gradient norm (max_grad_norm, log_grad_norm): the norm of the scaled gradients first, then AdamW with the clip
+        coefficient as one more factor, gated by the norm's verdict (finite norm and finite gate).  Returns the gate the step
+        ran under -- that verdict, else `gate` -- for whatever follows the optimizer under the same predicate (PackedEMA.step)."""
         self._check_grads()
-        self._launch(self.table, gate, grad_scale)
+        coef = None
+        if self.grad_norm is not None:
+            self.grad_norm.run(grad_scale, gate)
+            gate, coef = self.grad_norm.verdict, self.grad_norm.coef
+        self._launch(self.table, gate, grad_scale, coef)
         self.finish_step(gate)
+        return gate
+
+    def set_max_grad_norm(self, value: Optional[float]):
+        """another threshold for the steps to come, captured ones included (a device scalar); None: measure only"""
+        assert self.grad_norm is not None, "PackedAdamW.set_max_grad_norm: built without max_grad_norm / log_grad_norm"
+        self.max_grad_norm = value
+        self.grad_norm.set_max_norm(value)
+
+    def last_grad_norm(self) -> float:
+        """the norm the last step() measured, before clipping (host read: logging only)"""
+        assert self.grad_norm is not None, "PackedAdamW.last_grad_norm: built without max_grad_norm / log_grad_norm"
+        PackedTrainer._sync(self.trainer)
+        return float(self.grad_norm.norm)
+
+    def clipped_steps(self) -> int:
+        """applied steps whose gradients were scaled down (host read: logging only)"""
+        assert self.grad_norm is not None, "PackedAdamW.clipped_steps: built without max_grad_norm / log_grad_norm"
+        PackedTrainer._sync(self.trainer)
+        return int(self.grad_norm.clipped)
 
     @torch.no_grad()
     def step_group(self, gi: int, gate: torch.Tensor = None, grad_scale: float = 1.0):
-        """the tensors of group gi only (no step-count update: call finish_step() after the last group)"""
+        """the tensors of group gi only (no step-count update: call finish_step() after the last group).  No clip: the norm needs
+        every group's gradients (a caller with a norm configured exchanges first and calls step())"""
+        assert self.grad_norm is None, "PackedAdamW.step_group: a gradient norm covers all groups -- exchange first, then step()"
         if gi in self.groups:
             self._launch(self.groups[gi], gate, grad_scale)
 

@@ -98,9 +98,16 @@ class RouterAdamW:
 
     A step is skipped -- parameters, moments, step counts and the warm-up untouched, ``skipped_steps()`` + 1 -- when ``gate`` is
     non-finite or any gradient element of the table is NaN or +-Inf (reference: trainer.py:921-929 under anomaly detection, which
-    raises on NaN; Inf is skipped here as well)."""
+    raises on NaN; Inf is skipped here as well).
 
-    def __init__(self, param_groups, betas=(0.9, 0.999), eps: float = 1e-8, warmup_steps: int = 0):
+    max_grad_norm X: torch.nn.utils.clip_grad_norm_(all parameters of the table, X) in front of the step, on the device: ONE norm
+    over both groups (ops.GradNorm, csrc/grad_norm.hip: two more launches inside step(), so a captured step holds them); the
+    update kernel multiplies the gradients by the coefficient it reads from device memory.  A zero-filled gradient (the codebook's
+    during the pre-training) contributes nothing.  The threshold is a device scalar (set_max_grad_norm: no recapture); the
+    clip has no state beyond a counter, so state_dict() is what it was.  log_grad_norm=True: the norm without a threshold."""
+
+    def __init__(self, param_groups, betas=(0.9, 0.999), eps: float = 1e-8, warmup_steps: int = 0, max_grad_norm=None,
+                 log_grad_norm: bool = False):
         param_groups = list(param_groups)
         assert param_groups and all(isinstance(g, dict) and "params" in g for g in param_groups), \
             "RouterAdamW: param_groups = [{'params': [...], 'lr': ..., 'weight_decay': ...}, ...]"
@@ -127,6 +134,9 @@ class RouterAdamW:
                                        dtype=torch.float32).to(dev)
         self.before_access = None      # GraphedPrunerStep.finish: orders the current stream behind a step pending on the router's stream
         self.grads = self.m = self.v = None
+        assert max_grad_norm is None or max_grad_norm > 0, "RouterAdamW: max_grad_norm"
+        self.max_grad_norm, self._want_norm = max_grad_norm, (max_grad_norm is not None or bool(log_grad_norm))
+        self.grad_norm, self.norms = None, {}     # the GradNorm whose out / threshold every table's GradNorm shares; one per table
         self.table_keys = {None: list(range(len(self.params)))}
         self.rebind_()
 
@@ -180,7 +190,7 @@ class RouterAdamW:
         self.run_steps = torch.tensor([r["step"] for r in runs], dtype=torch.float32).to(self.device)
         self._gather = torch.tensor(self.run_of, dtype=torch.int64).to(self.device)
         self.ptrs = [p.data_ptr() for p in self.params]
-        self.tables = {}
+        self.tables, self.norms = {}, {}
         for key, idx in self.table_keys.items():
             self._build_table(key, idx)
         return self
@@ -205,6 +215,12 @@ class RouterAdamW:
             it.p, it.g, it.m, it.v, it.n = r["ptr"], r["g"].data_ptr(), r["m"].data_ptr(), r["v"].data_ptr(), r["n"]
             it.step, it.group = self.run_steps.data_ptr() + 4 * ri, r["group"]
         self.tables[key] = _lib.BlockTable(items, [lib.aptp_group_adamw_blocks(self.runs[ri]["n"]) for ri in runs], self.device)
+        if self._want_norm:
+            from . import ops
+            self.norms[key] = ops.GradNorm([self.runs[ri]["g"] for ri in runs], self.device, max_norm=self.max_grad_norm,
+                                           share=self.grad_norm)
+            if self.grad_norm is None:
+                self.grad_norm = self.norms[key]
 
     def add_table(self, key, params):
         """a descriptor table over a subset of the parameters (device memory; built once, before any capture)"""
@@ -234,7 +250,8 @@ class RouterAdamW:
     @torch.no_grad()
     def step(self, table=None, gate: torch.Tensor = None, grad_scale: float = 1.0):
         """one AdamW step over the tensors of `table` (default: all): ONE call, three launches on the current stream, nothing on
-        the host.  gate: optional fp32 device scalar (the step's total loss).  The gradients are zero afterwards."""
+        the host.  gate: optional fp32 device scalar (the step's total loss).  The gradients are zero afterwards.  With a
+        gradient norm: two launches in front, over the gradients of this table; the step runs under the norm's verdict."""
         from . import _lib, ops
         assert self.device.type == "cuda", "RouterAdamW.step: the kernel runs on the GPU"
         self._check()
@@ -247,6 +264,10 @@ class RouterAdamW:
             assert gate.dtype == torch.float32 and gate.device == self.device and gate.numel() == 1
             q.gate_dev = gate.data_ptr()
         q.items_host = ctypes.cast(tb.host, ctypes.c_void_p)
+        if self._want_norm:
+            gn = self.norms[table]
+            gn.run(grad_scale, gate)
+            q.gate_dev, q.grad_scale_dev = gn.verdict.data_ptr(), gn.coef.data_ptr()
         _lib.check(_lib.load().aptp_group_adamw(ctypes.byref(q), ops._stream()), "aptp_group_adamw")
 
     @torch.no_grad()
@@ -285,6 +306,25 @@ class RouterAdamW:
         self.param_groups[group]["weight_decay"] = float(value)
         self.groups_dev[group, 1] = float(value)
 
+    @torch.no_grad()
+    def set_max_grad_norm(self, value):
+        """the clip threshold, written into device memory: replays of a captured step read it.  None: measure only."""
+        assert self.grad_norm is not None, "RouterAdamW.set_max_grad_norm: built without max_grad_norm / log_grad_norm"
+        self._wait()
+        self.max_grad_norm = value
+        self.grad_norm.set_max_norm(value)
+
+    def last_grad_norm(self) -> float:
+        """the norm the last step measured, before clipping (waits for the device: logging)"""
+        assert self.grad_norm is not None, "RouterAdamW.last_grad_norm: built without max_grad_norm / log_grad_norm"
+        self._wait()
+        return float(self.grad_norm.norm)
+
+    def clipped_steps(self) -> int:
+        assert self.grad_norm is not None, "RouterAdamW.clipped_steps: built without max_grad_norm / log_grad_norm"
+        self._wait()
+        return int(self.grad_norm.clipped)
+
     def applied_steps(self) -> int:
         """(waits for the device: logging and checkpoints)"""
         self._wait()
@@ -304,7 +344,8 @@ class RouterAdamW:
         """everything a step changes, for GraphedPrunerStep's capture warm-up (restored in place by _restore)"""
         self._wait()
         return dict(p=[p.detach().clone() for p in self.params], m=[m.clone() for m in self.m], v=[v.clone() for v in self.v],
-                    steps=self.steps.clone(), counters=self.counters.clone())
+                    steps=self.steps.clone(), counters=self.counters.clone(),
+                    norm=None if self.grad_norm is None else self.grad_norm.out.clone())
 
     @torch.no_grad()
     def _restore(self, snap):
@@ -313,6 +354,8 @@ class RouterAdamW:
             dst.copy_(src)
         self._install_steps(snap["steps"])
         self.counters.copy_(snap["counters"])
+        if snap.get("norm") is not None:
+            self.grad_norm.out.copy_(snap["norm"])
         self.zero_grad()
 
     def _install_steps(self, steps):

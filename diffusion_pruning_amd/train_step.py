@@ -636,6 +636,8 @@ class PrunerStep:
             before = optimizer.counters[0:1].clone()
             optimizer.step(table=key, gate=gate)
             out["applied"] = optimizer.counters[0:1] - before
+            if optimizer.grad_norm is not None:
+                out["grad_norm"] = optimizer.grad_norm.norm.clone()
         return out
 
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
@@ -1049,6 +1051,8 @@ class GraphedPrunerStep(PrunerStep):
             rs.wait_event(rt["ev_bwd"])
             ph["g_bwd"].replay()                              # d(router losses + U-Net terms)/d(router), optimizer step
             applied = ph["applied"].clone() if "applied" in ph else None
+            gn = rt["optimizer"].grad_norm if rt["hip"] else None
+            grad_norm = gn.norm.clone() if gn is not None else None
             rt["ev_tail"].record(rs)
         rt["pending"] = rs is not main
         r = ph["out"]
@@ -1060,6 +1064,9 @@ class GraphedPrunerStep(PrunerStep):
         if applied is not None:
             applied.record_stream(main)
             out["applied"] = applied
+        if grad_norm is not None:
+            grad_norm.record_stream(main)
+            out["grad_norm"] = grad_norm
         return out
 
     def finish(self):
@@ -1404,14 +1411,23 @@ class GraphedFineTunerStep(FineTunerStep):
     lr_warmup_steps=W > 0: `constant_with_warmup` over W optimizer steps (PackedAdamW(warmup_steps=W)).
     ema=True or a dict of PackedEMA's arguments: an exponential moving average of the packed state (`use_ema` of the reference's
     interface), one launch behind AdamW on the call that closes a window, under the same gate; validate(use_ema=True),
-    export_ema_() and save_ema_pretrained() read it through a swap of masters and averages."""
+    export_ema_() and save_ema_pretrained() read it through a swap of masters and averages.
+    max_grad_norm=X: clip_grad_norm_(X) on the device in front of AdamW (ops.GradNorm: two launches); the dict gains
+    "grad_norm" and a window whose norm is not finite is skipped like one whose loss is not; log_grad_norm=True: the norm alone."""
 
     def __init__(self, student, teacher, cfg: Optional[FinetuneLossConfig] = None, schedule: Optional[NoiseSchedule] = None,
                  lr: float = 1e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  data_parallel: bool = False, bucket_bytes: int = 256 << 20, reduce_mode: str = "rs_ag", nan_guard: bool = True,
-                 accumulation_steps: int = 1, lr_warmup_steps: int = 0, ema=None):
+                 accumulation_steps: int = 1, lr_warmup_steps: int = 0, ema=None, max_grad_norm: Optional[float] = None,
+                 log_grad_norm: bool = False):
         super().__init__(student, teacher, cfg, schedule)
         assert int(accumulation_steps) >= 1 and lr_warmup_steps >= 0
+        # max_grad_norm X: clip_grad_norm_(X) of the diffusers training scripts, on the device, where AdamW reads the gradients
+        # (after the FINAL accumulate and any exchange); log_grad_norm: the norm without a threshold.  Either adds two launches
+        # (ops.GradNorm), a "grad_norm" entry to train_step's dict and the skip of a window whose norm is not finite.  Neither:
+        # nothing is built and nothing launched.  DESIGN 6t.
+        assert max_grad_norm is None or max_grad_norm > 0, "GraphedFineTunerStep: max_grad_norm"
+        self.max_grad_norm, self.log_grad_norm = max_grad_norm, bool(log_grad_norm)
         # ema: None = no average (no allocation, no launch); True = packed_train.PackedEMA with its defaults; a dict = its keyword
         # arguments (decay, min_decay, update_after_step, use_ema_warmup, inv_gamma, power).  Built by capture() as self.ema.
         assert ema is None or ema is True or isinstance(ema, dict), "GraphedFineTunerStep: ema is None, True or a dict of PackedEMA's arguments"
@@ -1547,7 +1563,8 @@ class GraphedFineTunerStep(FineTunerStep):
             group_of = lambda p_: self.reducer.bucket_of(off[id(p_)], p_.numel())          # noqa: E731
         self.optimizer = PackedAdamW(self.trainer, lr=self.opt_kw["lr"], betas=self.opt_kw["betas"], eps=self.opt_kw["eps"],
                                      weight_decay=self.opt_kw["weight_decay"], group_of=group_of,
-                                     warmup_steps=self.lr_warmup_steps)
+                                     warmup_steps=self.lr_warmup_steps, max_grad_norm=self.max_grad_norm,
+                                     log_grad_norm=self.log_grad_norm)
         if self._ema_kw is not None:
             from .packed_train import PackedEMA
             self.ema = PackedEMA(self.trainer, self.optimizer, **self._ema_kw)
@@ -1775,15 +1792,23 @@ class GraphedFineTunerStep(FineTunerStep):
                     arena[0:1].copy_(cap["total"].reshape(1))
                 gate = arena[0:1] if self.nan_guard else None
                 scale = 1.0 / (N * self.reducer.world)       # mean over the window's micro-batches and the ranks
-                self.reducer.exchange(lambda i: self.optimizer.step_group(i, gate, scale))
-                self.optimizer.finish_step(gate)
+                if self.optimizer.grad_norm is None:
+                    self.reducer.exchange(lambda i: self.optimizer.step_group(i, gate, scale))
+                    self.optimizer.finish_step(gate)
+                else:
+                    # the norm needs every bucket's sum: the whole exchange first, then the norm over the summed arena and ONE
+                    # AdamW launch -- the bucket-by-bucket overlap of exchange and optimizer is what the clip costs here
+                    self.reducer.exchange()
+                    gate = self.optimizer.step(gate, grad_scale=scale)
             elif N > 1:
                 # slot 0 = sum of the window's losses: one non-finite micro-batch skips the window
                 gate = self.trainer.grad_arena[0:1] if self.nan_guard else None
-                self.optimizer.step(gate, grad_scale=1.0 / N)
+                gate = self.optimizer.step(gate, grad_scale=1.0 / N)
             else:
                 gate = cap["total"] if self.nan_guard else None
-                self.optimizer.step(gate)
+                gate = self.optimizer.step(gate)
+            # (with a gradient norm, `gate` is now its verdict: finite norm and finite loss)
+            grad_norm = self.optimizer.grad_norm.norm.clone() if (applied and self.optimizer.grad_norm is not None) else None
             if applied and self.ema is not None:
                 # the average follows the optimizer on its stream, under its gate: one launch + the device-side count.  Local to
                 # the rank in data-parallel mode (identical masters give identical averages: no collective)
@@ -1794,5 +1819,10 @@ class GraphedFineTunerStep(FineTunerStep):
         # (clones: the graph's static outputs are overwritten by the next replay, and callers accumulate losses over steps)
         # the four losses are this micro-batch's; applied: this call ran the exchange and the optimizer (always, without
         # accumulation; whether the step took effect is the device-side NaN verdict); accum_index: its place in the window
-        return {"loss": cap["total"].clone(), "diff_loss": cap["diff"].clone(), "distillation_loss": cap["dist"].clone(),
-                "block_loss": cap["blk"].clone(), "applied": applied, "accum_index": idx}
+        out = {"loss": cap["total"].clone(), "diff_loss": cap["diff"].clone(), "distillation_loss": cap["dist"].clone(),
+               "block_loss": cap["blk"].clone(), "applied": applied, "accum_index": idx}
+        if self.optimizer.grad_norm is not None:
+            # the norm of the mean gradient the optimizer saw, before clipping (device scalar; NaN-free only when the window
+            # was applied: compare ops.GradNorm.verdict); None inside an open window
+            out["grad_norm"] = grad_norm
+        return out

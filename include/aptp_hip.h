@@ -695,6 +695,11 @@ typedef struct {
 } AptpAdamWParams;
 int aptp_adamw_blocks(int64_t n);
 int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream);
+/* The same launch with one more factor on the gradients, read from DEVICE memory: grad_scale_dev is an optional fp32 device scalar
+ * (4-byte aligned), e.g. the clip coefficient aptp_grad_norm left in out_dev[1]; the gradients are multiplied by
+ * grad_scale * grad_scale_dev[0], one fp32 product, uniform over the grid.  Null: aptp_adamw_many itself, bit for bit.  (An
+ * argument, not a field: the layout of AptpAdamWParams ends with warmup_steps and stays as it is.) */
+int aptp_adamw_many_scaled(const AptpAdamWParams* p, const float* grad_scale_dev, aptp_stream_t stream);
 
 /* Gradient accumulation over the micro-batches of one optimizer window (gradient_accumulation_steps of the fine-tune recipe,
  * configs/finetuning/sd-2-1_cc3m.yaml): ONE launch over a contiguous fp32 range (the gradient arena of
@@ -764,9 +769,40 @@ typedef struct {
   int32_t zero_grad;
   const float* gate_dev;  /* optional fp32 device scalar, e.g. the step's total loss */
   const AptpGroupAdamWItem* items_host;
+  const float* grad_scale_dev; /* optional fp32 device scalar (4-byte aligned), e.g. the clip coefficient aptp_grad_norm left in
+                           * out_dev[1]: the gradients are multiplied by grad_scale * grad_scale_dev[0], one fp32 product, uniform
+                           * over the grid; null: by grad_scale alone, every bit as without the field */
 } AptpGroupAdamWParams;
 int aptp_group_adamw_blocks(int64_t n);
 int aptp_group_adamw(const AptpGroupAdamWParams* p, aptp_stream_t stream);
+
+/* Global L2 norm of the gradients of a table and the clip coefficient of torch.nn.utils.clip_grad_norm_ (max_grad_norm), both left
+ * in device memory (csrc/grad_norm.hip): what grad_scale_dev of aptp_adamw_many_scaled and aptp_group_adamw reads.  items_dev: n_items
+ * descriptors in DEVICE memory, g fp32 [n], 16-byte aligned.  starts_dev: int32 [n_items + 1] prefix sums of
+ * aptp_grad_norm_blocks(n) (= aptp_adamw_blocks(n)); total_blocks = starts[n_items].  Two launches on `stream`, no atomics, fp64
+ * accumulation in a FIXED order, so the four floats are the same bits at every replay:
+ *   partial   one block of 256 threads per 4096 elements of an item; thread t, trips i = 0..3 at e = base + (i * 256 + t) * 4:
+ *             s += (double)g * (double)g over g[e], g[e+1], g[e+2], g[e+3] (or the item's last 1..3 elements) in index order;
+ *             per wave of 64 a butterfly s = s + s[lane ^ off], off = 32, 16, 8, 4, 2, 1; then ((w0 + w1) + w2) + w3 -> partials[b]
+ *   finalise  one block: thread j adds partials[j], partials[j + 256], ... in that order, the same tree gives S; then in fp64
+ *             total = sqrt(S) * grad_scale;  r = max_norm / (total + 1e-6);  coef = r < 1 ? max(r, 0) : 1, rounded to fp32
+ *             (so 1.0f for a null max_norm_dev, +inf, or total <= max_norm - 1e-6)
+ *             verdict = (float)total when it and gate_dev[0] (when given) are finite, else NaN -- and then coef = 1.0f
+ *             clipped_count += 1 when the verdict is finite and coef < 1
+ * out_dev: fp32 [4] = {total_norm, clip_coef, verdict, clipped_count}; the caller zeroes clipped_count once.
+ * APTP_EINVAL and nothing launched for: null items_dev / starts_dev / partials_dev / out_dev, n_items or total_blocks < 1,
+ * grad_scale < 0, out_dev not 16-byte or partials_dev not 8-byte aligned. */
+typedef struct { const float* g; int64_t n; } AptpGradNormItem;
+typedef struct {
+  const AptpGradNormItem* items_dev; const int32_t* starts_dev; int32_t n_items, total_blocks;
+  double* partials_dev;        /* [total_blocks] scratch; every slot is written */
+  float   grad_scale;          /* 0 = 1: the scale the optimizer will apply (1 / micro-batches, 1 / world) */
+  const float* max_norm_dev;   /* optional fp32 device scalar > 0; null or +inf = measure only, coef = 1 */
+  const float* gate_dev;       /* optional fp32 device scalar (the loss) */
+  float* out_dev;
+} AptpGradNormParams;
+int aptp_grad_norm_blocks(int64_t n);
+int aptp_grad_norm(const AptpGradNormParams* p, aptp_stream_t stream);
 
 /* Mean squared error of two equally shaped activations, read where they lie (the loss terms of Pruner.step / FineTuner.step:
  * pdm/training/trainer.py:1197-1225 diffusion MSE, output distillation, block distillation; :1729-1752 for the fine-tune step).

@@ -80,18 +80,19 @@ class LaunchTimer:
     """HIP events around every call of obj._launch while `on` (the one-launch AdamW / EMA passes of the optimizer tail): the
     events go onto the stream the launch goes to, so a pair brackets that kernel alone"""
 
-    def __init__(self, obj):
-        self.pairs, self.on, inner = [], False, obj._launch
+    def __init__(self, obj, name="_launch"):
+        self.pairs, self.on, inner = [], False, getattr(obj, name)
 
         def timed(*a, **k):
             if not self.on:
                 return inner(*a, **k)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            inner(*a, **k)
+            r = inner(*a, **k)
             e1.record()
             self.pairs.append((e0, e1))
-        obj._launch = timed
+            return r
+        setattr(obj, name, timed)
 
     def ms(self):
         """median over the recorded launches (call after a synchronize)"""
@@ -119,8 +120,12 @@ def main():
     ap.add_argument("--ema", action="store_true",
                     help="keep an EMA of the trained weights (graphed mode, PackedEMA defaults); adds the EMA and AdamW launch times "
                          "(HIP events over the timed steps) and, with --validate, the validation means of the averaged weights")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the global gradient norm at this value on the device (graphed mode, GraphedFineTunerStep(max_grad_norm=)); "
+                         "adds max_grad_norm, grad_norm_last, clipped_steps and the norm pass's time (HIP events) to the JSON line")
     args = ap.parse_args()
     assert args.validate == 0 or args.mode == "graphed", "--validate belongs to the graphed step"
+    assert args.max_grad_norm is None or args.mode == "graphed", "--max-grad-norm belongs to the graphed step"
     assert not args.ema or args.mode == "graphed", "--ema belongs to the graphed step"
     assert args.accum >= 1 and (args.mode == "graphed" or (args.accum == 1 and args.lr_warmup == 0)), \
         "--accum / --lr-warmup belong to the graphed step"
@@ -146,11 +151,14 @@ def main():
     if args.mode == "graphed":
         from diffusion_pruning_amd.train_step import GraphedFineTunerStep
         step = GraphedFineTunerStep(student, teacher, lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup,
-                                    **({"ema": True} if args.ema else {}))
+                                    **({"ema": True} if args.ema else {}),
+                                    **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}))
         step.capture(batch, offload_masters=True)
         opt, n_train = None, step.trainer.n_trainable()
+        if args.max_grad_norm is not None:
+            timers = {"grad_norm_ms": LaunchTimer(step.optimizer.grad_norm, "run")}
         if args.ema:
-            timers = {"adamw_ms": LaunchTimer(step.optimizer), "ema_update_ms": LaunchTimer(step.ema)}
+            timers.update({"adamw_ms": LaunchTimer(step.optimizer), "ema_update_ms": LaunchTimer(step.ema)})
     elif args.mode == "packed-eager":
         from diffusion_pruning_amd.packed_train import PackedTrainer
         step = FineTunerStep(student, teacher)
@@ -180,6 +188,14 @@ def main():
         val.update({"ema_bytes": 12 * n_el, "ema_steps": step.ema.steps(), "ema_cur_decay": step.ema.cur_decay(),
                     "ema_gb_per_s": round(12 * n_el / val["ema_update_ms"] * 1e-6, 1),
                     "adamw_gb_per_s": round(30 * n_el / val["adamw_ms"] * 1e-6, 1)})
+    if args.max_grad_norm is not None:
+        # the pass reads every gradient element once: 4 B per trainable element
+        for t in timers.values():
+            t.on = False
+        gn_ms = timers["grad_norm_ms"].ms()
+        val.update({"max_grad_norm": args.max_grad_norm, "grad_norm_last": step.optimizer.last_grad_norm(),
+                    "clipped_steps": step.optimizer.clipped_steps(), "grad_norm_ms": round(gn_ms, 4),
+                    "grad_norm_gb_per_s": round(4 * n_train / gn_ms * 1e-6, 1)})
     if args.validate:
         batches = [synthetic_batch(args.val_batch, 64, dev, seed=100 + i) for i in range(args.validate)]
         val.update(time_validation(step, batches, args.validate_baseline))

@@ -27,6 +27,8 @@ def main():
                          "captured for both phases with its schedule in device memory (DESIGN 6p)")
     ap.add_argument("--lr-warmup", type=int, default=0, help="hip: constant_with_warmup over this many applied steps")
     ap.add_argument("--pretrain-steps", type=int, default=0, help="hip: the first P steps run the hyper-net pre-training phase")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="hip: clip the global gradient norm of the router at this value on the device (RouterAdamW(max_grad_norm=))")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     unet = UNet2DConditionModelGated().init_synthetic(seed=0).to(dev)
@@ -41,8 +43,8 @@ def main():
     step = (PrunerStep if args.eager else GraphedPrunerStep)(unet, hn, qz)
     step.count_macs(args.latent)
     hip = args.router_optimizer == "hip"
-    if not hip and (args.lr_warmup or args.pretrain_steps):
-        ap.error("--lr-warmup and --pretrain-steps need --router-optimizer hip")
+    if not hip and (args.lr_warmup or args.pretrain_steps or args.max_grad_norm is not None):
+        ap.error("--lr-warmup, --pretrain-steps and --max-grad-norm need --router-optimizer hip")
     batch = synthetic_batch(args.batch, args.latent, dev)
     done = 0
     if hip:
@@ -51,7 +53,7 @@ def main():
         graph_utils.KEEP_GRAPHS = True                      # (graph_nodes() below)
         opt = RouterAdamW([{"params": [p for p in hn.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0},
                            {"params": [p for p in qz.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0}],
-                          warmup_steps=args.lr_warmup)
+                          warmup_steps=args.lr_warmup, max_grad_norm=args.max_grad_norm)
         if not args.eager:
             step.capture(batch, optimizer=opt, pretrain=args.pretrain_steps > 0)
             if args.pretrain_steps > 0:
@@ -83,6 +85,8 @@ def main():
             step.finish()
             extra["graph_nodes"] = step.graph_nodes()
         extra.update(router_optimizer="hip", applied_steps=opt.applied_steps(), skipped_steps=opt.skipped_steps(), last_lr=opt.last_lr())
+        if args.max_grad_norm is not None:
+            extra.update(max_grad_norm=args.max_grad_norm, grad_norm_last=opt.last_grad_norm(), clipped_steps=opt.clipped_steps())
     print(json.dumps({"metric": "pruning-train-steps/s (SD-2.1, 64x64 latents, teacher fwd + student fwd/bwd + router)",
                       "value": round(1.0 / dt, 3), "unit": "steps/s", "ms_per_step": round(dt * 1e3, 2),
                       "batch": args.batch, "loss": float(out["loss"].detach()),
