@@ -182,6 +182,15 @@ class AdamWParams(Structure):
                 ("step_dev", c_void_p), ("gate_dev", c_void_p), ("grad_scale", c_float), ("warmup_steps", c_float)]
 
 
+class AdamW8Item(Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m8", c_void_p), ("v8", c_void_p), ("absmax_m", c_void_p), ("absmax_v", c_void_p),
+                ("shadow", c_void_p), ("n", c_int64)]
+
+
+class AdamW8Params(Structure):
+    _fields_ = AdamWParams._fields_ + [("qmap_signed_dev", c_void_p), ("qmap_unsigned_dev", c_void_p), ("items_host", c_void_p)]
+
+
 class GroupAdamWItem(Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("step", c_void_p), ("n", c_int64),
                 ("group", c_int32)]
@@ -615,6 +624,8 @@ EXPORTS = [
     ("aptp_adamw_blocks", c_int, [c_int64]),
     ("aptp_adamw_many", c_int, [POINTER(AdamWParams), c_void_p]),
     ("aptp_adamw_many_scaled", c_int, [POINTER(AdamWParams), c_void_p, c_void_p]),
+    ("aptp_adamw8_blocks", c_int, [c_int64]),
+    ("aptp_adamw8_many", c_int, [POINTER(AdamW8Params), c_void_p, c_void_p]),
     ("aptp_ema_many", c_int, [POINTER(EmaParams), c_void_p]),
     ("aptp_group_adamw_blocks", c_int, [c_int64]),
     ("aptp_group_adamw", c_int, [POINTER(GroupAdamWParams), c_void_p]),

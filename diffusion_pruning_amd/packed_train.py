@@ -318,13 +318,51 @@ class PackedTrainer:
         return self.model
 
 
+ADAM8_BLOCK = 256           # elements per quantisation block of the 8-bit state (csrc/optim8.hip)
+ADAM8_MIN_SIZE = 4096       # tensors below this keep fp32 moments: bitsandbytes' rule, and one workgroup of the kernel
+
+
+def adam8_code_map(signed: bool) -> torch.Tensor:
+    """The 256 ascending fp32 values a code of the 8-bit AdamW state stands for (times its block's absmax): the block-wise
+    "dynamic" map in its published construction -- per decade i = 0..6 the midpoints of 2^i (signed; 2^(i+1) unsigned) equal
+    steps of [0.1, 1] times 10^(i-6), with both signs for the signed map, plus 0 and 1.  Built in fp64, rounded to fp32, sorted.
+    tests/adamw8_model.py is the definition; DESIGN 6u."""
+    vals = [0.0, 1.0]
+    for i in range(7):
+        k = 2 ** i if signed else 2 ** (i + 1)
+        step = (1.0 - 0.1) / k
+        edges = [0.1 + j * step for j in range(k)] + [1.0]
+        for a, b in zip(edges[:-1], edges[1:]):
+            mid = (a + b) / 2.0 * 10.0 ** (i - 6)
+            vals += [mid, -mid] if signed else [mid]
+    out = torch.tensor(vals, dtype=torch.float64).to(torch.float32).sort().values
+    assert out.numel() == 256
+    return out
+
+
+def adam8_uses_8bit(numel: int, optim_bits: int = 8, min_8bit_size: int = ADAM8_MIN_SIZE) -> bool:
+    """the partition rule of PackedAdamW(optim_bits=8): a tensor of at least min_8bit_size elements keeps 8-bit moments"""
+    return optim_bits == 8 and int(numel) >= int(min_8bit_size)
+
+
+def adam_state_bytes(sizes, optim_bits: int = 32, min_8bit_size: int = ADAM8_MIN_SIZE) -> int:
+    """bytes of both moments of tensors of these sizes, the scales of the 8-bit ones included (fp32: 8 B per element; 8-bit:
+    2 B per element + 8 B per block of 256)"""
+    total = 0
+    for n in sizes:
+        n = int(n)
+        total += 2 * n + 8 * ((n + ADAM8_BLOCK - 1) // ADAM8_BLOCK) if adam8_uses_8bit(n, optim_bits, min_8bit_size) else 8 * n
+    return total
+
+
 class PackedAdamW:
     """torch.optim.AdamW's arithmetic over a PackedTrainer's state as ONE launch that also writes the bf16 operands
     (csrc/optim.hip).  The gradient tensors must exist and stay where they are (``.grad`` of every parameter as left by the
     captured backward of GraphedFineTunerStep: the graph re-writes the same addresses at every replay)."""
 
     def __init__(self, trainer: PackedTrainer, lr: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 group_of=None, warmup_steps: int = 0, max_grad_norm: Optional[float] = None, log_grad_norm: bool = False):
+                 group_of=None, warmup_steps: int = 0, max_grad_norm: Optional[float] = None, log_grad_norm: bool = False,
+                 optim_bits: int = 32, min_8bit_size: int = ADAM8_MIN_SIZE):
         """group_of: optional map parameter -> group index (e.g. the gradient bucket that completes it, ArenaGradReducer.bucket_of):
         the table is built per group and ``step_group(i)`` applies one group per launch, so the optimizer can follow a
         bucketed gradient exchange bucket by bucket; ``step()`` applies all groups.
@@ -334,7 +372,14 @@ class PackedAdamW:
         max_grad_norm X: torch.nn.utils.clip_grad_norm_(parameters, X) in front of every ``step()``, on the device (ops.GradNorm over
         the gradients of the table: two launches; the kernel multiplies the gradients by the coefficient it reads from device
         memory, they are not rewritten), and a non-finite norm skips the step as a non-finite gate does.  log_grad_norm=True: the
-        norm is taken (and gates) without a threshold.  Neither: no GradNorm, no extra launch."""
+        norm is taken (and gates) without a threshold.  Neither: no GradNorm, no extra launch.
+        optim_bits=8 (`use_8bit_adam` of the reference's recipe): tensors of at least min_8bit_size elements keep both
+        moments as uint8 codes with one fp32 absmax per moment and 256 elements (``self.m`` / ``self.v`` hold the codes,
+        ``self.absmax1`` / ``self.absmax2`` the scales) and take their step in a second launch (csrc/optim8.hip) under the same
+        gate and factors; smaller tensors keep fp32 moments and the fp32 kernel.  32: nothing of this exists."""
+        assert optim_bits in (32, 8), "PackedAdamW: optim_bits is 32 or 8"
+        assert int(min_8bit_size) >= 1, "PackedAdamW: min_8bit_size"
+        self.optim_bits, self.min_8bit_size = int(optim_bits), int(min_8bit_size)
         self.trainer, self.lr, self.betas, self.eps, self.weight_decay = trainer, lr, betas, eps, weight_decay
         self.group_of = group_of
         assert warmup_steps >= 0, "PackedAdamW: warmup_steps"
@@ -348,8 +393,17 @@ class PackedAdamW:
         self.params = [p for p, _ in entries]
         by_id = {id(p): n for n, p in trainer.named_parameters()} if hasattr(trainer, "named_parameters") else {}
         self.names = [by_id.get(id(p), f"#{i}") for i, p in enumerate(self.params)]
-        self.m = [torch.zeros_like(p.data) for p in self.params]
-        self.v = [torch.zeros_like(p.data) for p in self.params]
+        self.is8 = [adam8_uses_8bit(p.numel(), self.optim_bits, self.min_8bit_size) for p in self.params]
+        self.m = [torch.full((p.numel(),), 127, dtype=torch.uint8, device=dev) if q else torch.zeros_like(p.data)
+                  for p, q in zip(self.params, self.is8)]         # (the first moment's zero is code 127)
+        self.v = [torch.zeros(p.numel(), dtype=torch.uint8, device=dev) if q else torch.zeros_like(p.data)
+                  for p, q in zip(self.params, self.is8)]
+        nqb = [(p.numel() + ADAM8_BLOCK - 1) // ADAM8_BLOCK for p in self.params]
+        self.absmax1 = [torch.zeros(b, dtype=torch.float32, device=dev) if q else None for b, q in zip(nqb, self.is8)]
+        self.absmax2 = [torch.zeros(b, dtype=torch.float32, device=dev) if q else None for b, q in zip(nqb, self.is8)]
+        self.qmap1 = self.qmap2 = None
+        if self.optim_bits == 8:                                  # both maps, uploaded once
+            self.qmap1, self.qmap2 = adam8_code_map(True).to(dev), adam8_code_map(False).to(dev)
         self.step_t = torch.zeros((), dtype=torch.float32, device=dev)
         self.rebind_()
 
@@ -358,25 +412,38 @@ class PackedAdamW:
         backward, whose replays re-write the same addresses; before every step of an eager loop, whose backward allocates"""
         lib = _lib.load()
         self.grads = [p.grad for p in self.params]      # keeps the addresses in the table alive
-        items = (_lib.AdamWItem * len(self.entries))()
-        for i, ((p, sh), m, v) in enumerate(zip(self.entries, self.m, self.v)):
+        idx32 = [i for i, q in enumerate(self.is8) if not q]         # (optim_bits = 32: every tensor, in order)
+        idx8 = [i for i, q in enumerate(self.is8) if q]
+        items, items8 = (_lib.AdamWItem * len(idx32))(), (_lib.AdamW8Item * len(idx8))()
+        for it, i in list(zip(items, idx32)) + list(zip(items8, idx8)):
+            (p, sh), m, v = self.entries[i], self.m[i], self.v[i]
             g = p.grad
             assert g is not None, f"PackedAdamW.rebind_: {self.names[i]} has no gradient (every tensor of the table needs one)"
             assert g.is_contiguous() and p.data.is_contiguous() and g.dtype == torch.float32 and p.dtype == torch.float32
             assert p.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and m.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0
-            it = items[i]
-            it.p, it.g, it.m, it.v, it.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+            it.p, it.g, it.n = p.data_ptr(), g.data_ptr(), p.numel()
+            if self.is8[i]:
+                a1, a2 = self.absmax1[i], self.absmax2[i]
+                assert m.dtype == v.dtype == torch.uint8 and a1.data_ptr() % 4 == 0 and a2.data_ptr() % 4 == 0
+                it.m8, it.v8, it.absmax_m, it.absmax_v = m.data_ptr(), v.data_ptr(), a1.data_ptr(), a2.data_ptr()
+            else:
+                it.m, it.v = m.data_ptr(), v.data_ptr()
             if sh is not None:
                 assert sh.dtype == torch.bfloat16 and sh.is_contiguous() and sh.numel() == p.numel() and sh.data_ptr() % 8 == 0
                 it.shadow = sh.data_ptr()
-        self.table = _lib.BlockTable(items, [lib.aptp_adamw_blocks(p.numel()) for p in self.params], self.params[0].device)
+        dev = self.params[0].device
+        self.table = _lib.BlockTable(items, [lib.aptp_adamw_blocks(self.params[i].numel()) for i in idx32], dev) if idx32 else None
+        self.table8 = _lib.BlockTable(items8, [lib.aptp_adamw8_blocks(self.params[i].numel()) for i in idx8], dev) if idx8 else None
         # per-group tables (bucketed data-parallel exchange): the same descriptors, regrouped, with block prefixes of their own
-        self.groups = None
+        self.groups, self.groups8 = None, None
         if self.group_of is not None:
-            by = {}
-            for i, p in enumerate(self.params):
-                by.setdefault(int(self.group_of(p)), []).append(i)
+            by, by8 = {}, {}
+            for k, i in enumerate(idx32):
+                by.setdefault(int(self.group_of(self.params[i])), []).append(k)
+            for k, i in enumerate(idx8):
+                by8.setdefault(int(self.group_of(self.params[i])), []).append(k)
             self.groups = {gi: self.table.subset(idx) for gi, idx in sorted(by.items())}
+            self.groups8 = {gi: self.table8.subset(idx) for gi, idx in sorted(by8.items())}
         if self._want_norm:
             clipped = None if self.grad_norm is None else self.grad_norm.clipped.clone()
             self.grad_norm = ops.GradNorm(self.grads, self.params[0].device, max_norm=self.max_grad_norm)
@@ -398,6 +465,21 @@ class PackedAdamW:
         else:       # (the clip coefficient of ops.GradNorm, read from device memory as one more factor of grad_scale)
             _lib.check(lib.aptp_adamw_many_scaled(ctypes.byref(q), grad_scale_dev.data_ptr(), ops._stream()), "aptp_adamw_many_scaled")
 
+    def _launch8(self, table, gate, grad_scale, grad_scale_dev=None):
+        """the 8-bit tensors of `table`: the same step under the same gate and factors (csrc/optim8.hip)"""
+        lib = _lib.load()
+        q = _lib.AdamW8Params()
+        q.items_dev, q.starts_dev, q.n_items, q.total_blocks = table.args()
+        q.lr, q.beta1, q.beta2, q.eps, q.weight_decay = self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay
+        q.step_dev = self.step_t.data_ptr()
+        q.gate_dev = None if gate is None else gate.data_ptr()
+        q.grad_scale = float(grad_scale)
+        q.warmup_steps = float(self.warmup_steps)
+        q.qmap_signed_dev, q.qmap_unsigned_dev = self.qmap1.data_ptr(), self.qmap2.data_ptr()
+        q.items_host = ctypes.cast(table.host, ctypes.c_void_p)
+        _lib.check(lib.aptp_adamw8_many(ctypes.byref(q), None if grad_scale_dev is None else grad_scale_dev.data_ptr(), ops._stream()),
+                   "aptp_adamw8_many")
+
     def _check_grads(self):
         for p, g in zip(self.params, self.grads):
             assert p.grad is g, "PackedAdamW: a gradient tensor was replaced (its address is part of the kernel's table)"
@@ -415,7 +497,10 @@ class PackedAdamW:
         if self.grad_norm is not None:
             self.grad_norm.run(grad_scale, gate)
             gate, coef = self.grad_norm.verdict, self.grad_norm.coef
-        self._launch(self.table, gate, grad_scale, coef)
+        if self.table is not None:
+            self._launch(self.table, gate, grad_scale, coef)
+        if self.table8 is not None:
+            self._launch8(self.table8, gate, grad_scale, coef)
         self.finish_step(gate)
         return gate
 
@@ -444,6 +529,8 @@ class PackedAdamW:
         assert self.grad_norm is None, "PackedAdamW.step_group: a gradient norm covers all groups -- exchange first, then step()"
         if gi in self.groups:
             self._launch(self.groups[gi], gate, grad_scale)
+        if gi in self.groups8:
+            self._launch8(self.groups8[gi], gate, grad_scale)
 
     @torch.no_grad()
     def finish_step(self, gate: torch.Tensor = None):
@@ -456,8 +543,12 @@ class PackedAdamW:
     def state_dict(self):
         """step count and both moments, keyed by the stable names of PackedTrainer.named_parameters() (resume:
         load_state_dict on an optimizer built over the same expert, whatever order its modules first ran in)"""
+        clone = lambda ts: [None if t is None else t.clone() for t in ts]       # noqa: E731
         return {"step": self.step_t.clone(), "names": list(self.names),
-                "exp_avg": [m.clone() for m in self.m], "exp_avg_sq": [v.clone() for v in self.v]}
+                "exp_avg": [m.clone() for m in self.m], "exp_avg_sq": [v.clone() for v in self.v],
+                # optim_bits = 8: uint8 codes above for the 8-bit tensors, their scales and both maps here (None: fp32 moments)
+                "optim_bits": self.optim_bits, "absmax1": clone(self.absmax1), "absmax2": clone(self.absmax2),
+                "qmap1": None if self.qmap1 is None else self.qmap1.clone(), "qmap2": None if self.qmap2 is None else self.qmap2.clone()}
 
     @torch.no_grad()
     def load_state_dict(self, sd):
@@ -468,6 +559,18 @@ class PackedAdamW:
             order = list(range(len(self.m)))
         else:
             order = _order_by_name(names, self.names, "PackedAdamW")
+        bits = int(sd.get("optim_bits", 32))
+        assert bits == self.optim_bits, \
+            f"PackedAdamW: the saved state holds {bits}-bit moments, this optimizer {self.optim_bits}-bit ones (no conversion on load)"
+        if self.optim_bits == 8:
+            for key, own in (("qmap1", self.qmap1), ("qmap2", self.qmap2)):
+                assert sd.get(key) is not None and torch.equal(sd[key].to(own.device), own), \
+                    f"PackedAdamW: the saved state's code map {key} is not this optimizer's: its codes mean other values"
+            for i, j in enumerate(order):
+                saved8 = sd["exp_avg"][j].dtype == torch.uint8
+                assert saved8 == self.is8[i] and (sd["absmax1"][j] is not None) == self.is8[i], \
+                    f"PackedAdamW: {self.names[i]}: saved with {'8-bit' if saved8 else 'fp32'} moments, {'8-bit' if self.is8[i] else 'fp32'} " \
+                    f"here -- another partition (min_8bit_size = {self.min_8bit_size} here)"
         for i, j in enumerate(order):
             ma, va = sd["exp_avg"][j], sd["exp_avg_sq"][j]
             assert self.m[i].shape == ma.shape and self.v[i].shape == va.shape, \
@@ -476,6 +579,31 @@ class PackedAdamW:
         for i, j in enumerate(order):
             self.m[i].copy_(sd["exp_avg"][j])    # in place: the moments' addresses are part of the kernel's table
             self.v[i].copy_(sd["exp_avg_sq"][j])
+            if self.is8[i]:
+                self.absmax1[i].copy_(sd["absmax1"][j])
+                self.absmax2[i].copy_(sd["absmax2"][j])
+
+    @torch.no_grad()
+    def dequantized_state(self):
+        """both moments of every tensor as fp32 in the tensor's shape, in torch.optim.AdamW's layout -- {"names": [...], "state":
+        {i: {"step", "exp_avg", "exp_avg_sq"}}} in the order of ``self.params`` -- for whoever continues with another
+        optimizer.  torch ops only: map[code] * absmax of the element's block (fp32 moments: clones)."""
+        PackedTrainer._sync(self.trainer)
+        state = {}
+        for i, p in enumerate(self.params):
+            if self.is8[i]:
+                scale = lambda a: a.repeat_interleave(ADAM8_BLOCK)[:p.numel()]      # noqa: E731
+                m = (self.qmap1[self.m[i].long()] * scale(self.absmax1[i])).view_as(p)
+                v = (self.qmap2[self.v[i].long()] * scale(self.absmax2[i])).view_as(p)
+            else:
+                m, v = self.m[i].clone(), self.v[i].clone()
+            state[i] = {"step": self.step_t.clone(), "exp_avg": m, "exp_avg_sq": v}
+        return {"names": list(self.names), "state": state}
+
+    def state_bytes(self) -> int:
+        """bytes of the moment state: both moments of every tensor, the scales of the 8-bit ones included"""
+        ts = self.m + self.v + [a for a in self.absmax1 + self.absmax2 if a is not None]
+        return sum(t.numel() * t.element_size() for t in ts)
 
 
 class PackedEMA:

@@ -1413,15 +1413,20 @@ class GraphedFineTunerStep(FineTunerStep):
     interface), one launch behind AdamW on the call that closes a window, under the same gate; validate(use_ema=True),
     export_ema_() and save_ema_pretrained() read it through a swap of masters and averages.
     max_grad_norm=X: clip_grad_norm_(X) on the device in front of AdamW (ops.GradNorm: two launches); the dict gains
-    "grad_norm" and a window whose norm is not finite is skipped like one whose loss is not; log_grad_norm=True: the norm alone."""
+    "grad_norm" and a window whose norm is not finite is skipped like one whose loss is not; log_grad_norm=True: the norm alone.
+    use_8bit_adam=True: both AdamW moments as block-wise 8-bit codes (PackedAdamW(optim_bits=8), csrc/optim8.hip)."""
 
     def __init__(self, student, teacher, cfg: Optional[FinetuneLossConfig] = None, schedule: Optional[NoiseSchedule] = None,
                  lr: float = 1e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  data_parallel: bool = False, bucket_bytes: int = 256 << 20, reduce_mode: str = "rs_ag", nan_guard: bool = True,
                  accumulation_steps: int = 1, lr_warmup_steps: int = 0, ema=None, max_grad_norm: Optional[float] = None,
-                 log_grad_norm: bool = False):
+                 log_grad_norm: bool = False, use_8bit_adam: bool = False):
         super().__init__(student, teacher, cfg, schedule)
         assert int(accumulation_steps) >= 1 and lr_warmup_steps >= 0
+        # use_8bit_adam (training.optim.use_8bit_adam of the reference's configs): PackedAdamW(optim_bits=8) -- block-wise 8-bit
+        # moments for the tensors of at least 4096 elements, a second launch for them; parameters, operands and gradients keep
+        # their type and address, so everything else of the step is as without it.  DESIGN 6u.
+        self.use_8bit_adam = bool(use_8bit_adam)
         # max_grad_norm X: clip_grad_norm_(X) of the diffusers training scripts, on the device, where AdamW reads the gradients
         # (after the FINAL accumulate and any exchange); log_grad_norm: the norm without a threshold.  Either adds two launches
         # (ops.GradNorm), a "grad_norm" entry to train_step's dict and the skip of a window whose norm is not finite.  Neither:
@@ -1564,7 +1569,7 @@ class GraphedFineTunerStep(FineTunerStep):
         self.optimizer = PackedAdamW(self.trainer, lr=self.opt_kw["lr"], betas=self.opt_kw["betas"], eps=self.opt_kw["eps"],
                                      weight_decay=self.opt_kw["weight_decay"], group_of=group_of,
                                      warmup_steps=self.lr_warmup_steps, max_grad_norm=self.max_grad_norm,
-                                     log_grad_norm=self.log_grad_norm)
+                                     log_grad_norm=self.log_grad_norm, optim_bits=8 if self.use_8bit_adam else 32)
         if self._ema_kw is not None:
             from .packed_train import PackedEMA
             self.ema = PackedEMA(self.trainer, self.optimizer, **self._ema_kw)

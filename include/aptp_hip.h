@@ -701,6 +701,34 @@ int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream);
  * argument, not a field: the layout of AptpAdamWParams ends with warmup_steps and stays as it is.) */
 int aptp_adamw_many_scaled(const AptpAdamWParams* p, const float* grad_scale_dev, aptp_stream_t stream);
 
+/* The same step with both moments kept as block-wise 8-bit codes (csrc/optim8.hip; `use_8bit_adam` of the fine-tune recipe,
+ * configs/finetuning/sd-2-1_cc3m.yaml:102; the format is defined by tests/adamw8_model.py).  A quantisation block is
+ * 256 consecutive elements of one tensor (the last may be short) with one fp32 absmax per moment; a moment is
+ * map[code] * absmax, the first through qmap_signed_dev, the second through qmap_unsigned_dev (256 ascending fp32 each, device
+ * memory).  One launch: dequantise, the AdamW element of aptp_adamw_many on p (from the unquantised new moments) and the bf16
+ * operand, then absmax = max |.| per block and a nearest code of x / absmax per element.  absmax == 0 stores the zero code
+ * throughout; a block with a non-finite new moment stores a NaN absmax.  m8, v8: uint8 [n], 4-byte aligned; absmax_m, absmax_v:
+ * fp32 [ceil(n / 256)], 4-byte aligned; p, g, shadow, starts_dev, step_dev, gate_dev, grad_scale, warmup_steps and grad_scale_dev
+ * as in aptp_adamw_many_scaled; aptp_adamw8_blocks(n) == aptp_adamw_blocks(n).  items_host: optional host copy of the table;
+ * when given, every item is checked (non-null, n >= 1, alignment, block count) before anything is launched.  APTP_EINVAL and
+ * nothing launched for: null table, maps or step_dev, n_items / total_blocks < 1, bad hyper-parameters, a misaligned item. */
+typedef struct {
+  float* p; const float* g; uint8_t* m8; uint8_t* v8; float* absmax_m; float* absmax_v; void* shadow; int64_t n;
+} AptpAdamW8Item;
+typedef struct {
+  const AptpAdamW8Item* items_dev; const int32_t* starts_dev; int32_t n_items, total_blocks;
+  float lr, beta1, beta2, eps, weight_decay;
+  const float* step_dev;
+  const float* gate_dev;
+  float grad_scale;
+  float warmup_steps;
+  const float* qmap_signed_dev;    /* 256 ascending fp32 in [-1, 1], zero at code 127: the first moment's map */
+  const float* qmap_unsigned_dev;  /* 256 ascending fp32 in [0, 1], zero at code 0: the second moment's map */
+  const AptpAdamW8Item* items_host;
+} AptpAdamW8Params;
+int aptp_adamw8_blocks(int64_t n);
+int aptp_adamw8_many(const AptpAdamW8Params* p, const float* grad_scale_dev, aptp_stream_t stream);
+
 /* Gradient accumulation over the micro-batches of one optimizer window (gradient_accumulation_steps of the fine-tune recipe,
  * configs/finetuning/sd-2-1_cc3m.yaml): ONE launch over a contiguous fp32 range (the gradient arena of
  * PackedTrainer.ensure_grad_buffers(arena=True)).  acc, g: fp32 [n], 16-byte aligned; plain fp32 addition, no gate: a

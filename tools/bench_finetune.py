@@ -10,7 +10,12 @@ FineTunerStep.step under the attached trainer as well (what validation cost befo
 
 --ema (graphed mode) keeps an EMA of the trained weights (packed_train.PackedEMA) and adds `adamw_ms` / `ema_update_ms` (HIP
 events around the two launches, median over the timed steps), `ema_bytes` = 12 x trainable elements and the two rates; with
---validate also `validate_losses_ema`, the means of the averaged weights from the same graphs."""
+--validate also `validate_losses_ema`, the means of the averaged weights from the same graphs.
+
+--adam8bit (graphed mode) keeps both AdamW moments as block-wise 8-bit codes (GraphedFineTunerStep(use_8bit_adam=True),
+csrc/optim8.hip) and adds `optimizer_state_bytes`, `adamw_ms` (the fp32 launch over the small tensors) and `adamw8_ms` (the 8-bit
+launch), HIP events around each, median over the timed steps, with `optimizer_pass_ms` their sum; --optimizer-times adds the same
+fields for the fp32 state (no `adamw8_ms`), for the comparison."""
 import argparse
 import json
 import os
@@ -123,7 +128,14 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="clip the global gradient norm at this value on the device (graphed mode, GraphedFineTunerStep(max_grad_norm=)); "
                          "adds max_grad_norm, grad_norm_last, clipped_steps and the norm pass's time (HIP events) to the JSON line")
+    ap.add_argument("--adam8bit", action="store_true",
+                    help="block-wise 8-bit AdamW moments (graphed mode, GraphedFineTunerStep(use_8bit_adam=True)); adds "
+                         "optimizer_state_bytes and the optimizer launches' times (HIP events) to the JSON line")
+    ap.add_argument("--optimizer-times", action="store_true",
+                    help="the same fields without the 8-bit state (graphed mode): what --adam8bit is compared with")
     args = ap.parse_args()
+    args.optimizer_times = args.optimizer_times or args.adam8bit
+    assert not args.optimizer_times or args.mode == "graphed", "--adam8bit / --optimizer-times belong to the graphed step"
     assert args.validate == 0 or args.mode == "graphed", "--validate belongs to the graphed step"
     assert args.max_grad_norm is None or args.mode == "graphed", "--max-grad-norm belongs to the graphed step"
     assert not args.ema or args.mode == "graphed", "--ema belongs to the graphed step"
@@ -151,7 +163,7 @@ def main():
     if args.mode == "graphed":
         from diffusion_pruning_amd.train_step import GraphedFineTunerStep
         step = GraphedFineTunerStep(student, teacher, lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup,
-                                    **({"ema": True} if args.ema else {}),
+                                    **({"ema": True} if args.ema else {}), **({"use_8bit_adam": True} if args.adam8bit else {}),
                                     **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}))
         step.capture(batch, offload_masters=True)
         opt, n_train = None, step.trainer.n_trainable()
@@ -159,6 +171,11 @@ def main():
             timers = {"grad_norm_ms": LaunchTimer(step.optimizer.grad_norm, "run")}
         if args.ema:
             timers.update({"adamw_ms": LaunchTimer(step.optimizer), "ema_update_ms": LaunchTimer(step.ema)})
+        if args.optimizer_times:
+            if "adamw_ms" not in timers:
+                timers["adamw_ms"] = LaunchTimer(step.optimizer)
+            if args.adam8bit:
+                timers["adamw8_ms"] = LaunchTimer(step.optimizer, "_launch8")
     elif args.mode == "packed-eager":
         from diffusion_pruning_amd.packed_train import PackedTrainer
         step = FineTunerStep(student, teacher)
@@ -188,6 +205,21 @@ def main():
         val.update({"ema_bytes": 12 * n_el, "ema_steps": step.ema.steps(), "ema_cur_decay": step.ema.cur_decay(),
                     "ema_gb_per_s": round(12 * n_el / val["ema_update_ms"] * 1e-6, 1),
                     "adamw_gb_per_s": round(30 * n_el / val["adamw_ms"] * 1e-6, 1)})
+    if args.optimizer_times:
+        # bytes of the pass by the model of csrc/optim.hip / optim8.hip: 30 B per element with fp32 moments (26 without an
+        # operand); 18 B + 16 B per 256 elements with 8-bit ones
+        for t in timers.values():
+            t.on = False
+        o = step.optimizer
+        ms = {k: timers[k].ms() for k in ("adamw_ms", "adamw8_ms") if k in timers and timers[k].ms() is not None}
+        n8 = sum(p.numel() for p, q in zip(o.params, o.is8) if q)
+        val.update({k: round(v, 4) for k, v in ms.items()})
+        val.update({"optimizer_state_bytes": o.state_bytes(), "optim_bits": o.optim_bits, "elements_8bit": n8,
+                    "elements_fp32": n_train - n8, "optimizer_pass_ms": round(sum(ms.values()), 4)})
+        if "adamw8_ms" in ms:
+            val["adamw8_gb_per_s"] = round((18 + 16 / 256) * n8 / ms["adamw8_ms"] * 1e-6, 1)
+        elif "adamw_ms" in ms:
+            val["adamw_gb_per_s"] = round(30 * n_train / ms["adamw_ms"] * 1e-6, 1)
     if args.max_grad_norm is not None:
         # the pass reads every gradient element once: 4 B per trainable element
         for t in timers.values():
