@@ -15,7 +15,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, scratch
 from ._lib import ImageInParams, LatentDistParams, UnetEpilogueParams, UnetPrologueParams
 from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F401
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
@@ -206,9 +206,6 @@ def pack_weight_cat(pw: PackedWeight, w2: torch.Tensor, bias2: Optional[torch.Te
     return PackedWeight(flat, bias, pw.N, pw.Cin, pw.KH, pw.KW, False, None, c2_live, c2_pad, pw.cin_pad)
 
 
-_ws_cache = {}
-_ws_capture_keep = []      # see _workspace
-
 # Optional launch recorder used by bench.py's roofline leg: when a list, every aptp_conv_gemm launch appends
 # {"params": ConvGemmParams, "flops": algorithmic FLOPs, "keep": tensors referenced by the params}.
 LAUNCH_LOG = None
@@ -219,64 +216,15 @@ ATTN_LAUNCH_LOG = None      # bench.py: the attention launches of ONE forward (r
 # Split-K launches combine their K-slices inside the kernel (AptpConvGemmParams.tile_counters) instead of launching
 # splitk_reduce_kernel; False restores the two-launch form (A/B timing, tests of both forms)
 SPLITK_IN_KERNEL = True
-_counters = {}
-_N_COUNTERS = 1 << 16
 
-
-_N_SLABS = int(os.environ.get("APTP_N_SLABS", "16"))
-_counters_lock = threading.Lock()
-
-
-class scratch_domain:
-    """``with ops.scratch_domain("teacher"): ...`` -- launches issued (or CAPTURED) inside use their own split-K counters and
-    scratch buffers.  Scratch is keyed by the launching stream, which is enough for eager concurrency; but every
-    ``torch.cuda.graph`` capture runs on the same capture stream, so two graphs that will REPLAY concurrently on different
-    streams (the pruning step's teacher next to the student forward) must be captured under different domains."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        self.prev = getattr(_tls, "domain", None)
-        _tls.domain = self.name
-        return self
-
-    def __exit__(self, *exc):
-        _tls.domain = self.prev
-        return False
-
-
-def _domain():
-    return getattr(_tls, "domain", None)
-
-
-def _tile_counters(device):
-    """Zero-initialised arrival counters of the split-K launches issued on the CURRENT stream (every launch leaves them
-    zero).  One pool of _N_SLABS slabs per device, created on first use outside stream capture (a fill recorded into a
-    graph would only run at replay); each stream that launches split-K work is handed its own slab on first use -- a
-    host-side table lookup, legal during capture -- so forwards running concurrently on different streams never share
-    counters.  Returns None (= use the separate reduce launch) when the pool cannot be created yet or is exhausted."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    pool = _counters.get(key)
-    if pool is None:
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        with _counters_lock:
-            pool = _counters.get(key)
-            if pool is None:
-                pool = {"buf": torch.zeros(_N_SLABS, _N_COUNTERS, dtype=torch.int32, device=device), "slab": {}}
-                _counters[key] = pool
-    sid = (torch.cuda.current_stream().cuda_stream, _domain())
-    i = pool["slab"].get(sid)
-    if i is None:
-        with _counters_lock:
-            i = pool["slab"].get(sid)
-            if i is None:
-                if len(pool["slab"]) >= _N_SLABS:
-                    return None
-                i = pool["slab"][sid] = len(pool["slab"])
-    return pool["buf"][i]
-
+# Launch scratch -- the split-K arrival counters, the grow-only workspaces, the unit-statistics arena of a forward and the
+# domain that keeps concurrently replaying graphs apart -- lives in scratch.py; these are the same objects under the names the
+# models, tools and tests use.
+scratch_domain, _domain = scratch.scratch_domain, scratch.domain
+_tile_counters, _N_COUNTERS = scratch.counters, scratch.N_COUNTERS
+_workspace, _ws_capture_keep = scratch.workspace, scratch.capture_keep
+ustat_begin, ustat_end, _ustat_alloc = scratch.ustat_begin, scratch.ustat_end, scratch.ustat_alloc
+USTAT, USTAT_NREP = scratch.USTAT, scratch.USTAT_NREP
 
 # AptpGroupNormParams.variant used when the caller asks for "auto" (0).  0 = the library's own choice (small maps in one
 # launch, large maps in three).  3 (large maps in two launches: <= 16 coarse statistics chunks folded by the apply
@@ -298,30 +246,6 @@ GN_FUSED_FINALIZE = False
 EPILOGUE = 0
 
 
-def _workspace(nbytes: int, device) -> torch.Tensor:
-    """Grow-only scratch buffer per (device, stream): stream-ordered reuse, kernels on one stream serialise; forwards that
-    run concurrently on different streams must not share split-K slabs or GroupNorm partials."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.is_current_stream_capturing(),
-           torch.cuda.current_stream().cuda_stream, _domain())
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        size = max(nbytes, 1 << 20)
-        if key[1] and buf is not None:
-            size = max(size, buf.numel() + buf.numel() // 2)      # (kept forever, below: grow geometrically so the kept set stays small)
-        buf = torch.empty(size, dtype=torch.uint8, device=device)
-        if key[1]:
-            # Allocated while a stream is capturing: the block comes from that graph's private pool and its address is baked into
-            # every launch captured with it -- possibly into graphs captured LATER on the same stream, which may outlive the graph
-            # that owns the pool.  torch.cuda.graph.__enter__ empties the cache, so once the owning graph is gone and a larger
-            # request has replaced the buffer here, the block would be returned to the device while a younger graph still
-            # writes to it (seen as "Memory access fault ... write access to a read-only page" when a code object was mapped
-            # there, and only for some test orders).  A capture-time scratch buffer is therefore never released: a few grow
-            # steps per (stream, domain), bounded by the largest request.
-            _ws_capture_keep.append(buf)
-        _ws_cache[key] = buf
-    return buf
-
-
 # GroupNorm statistics emitted by the GEMM that produces a tensor (AptpConvGemmParams.colstat_out) travel with the
 # tensor: they are recorded on its root storage owner (the tensor itself, or the concat buffer it is a channel slice of)
 # under the view's storage offset, so the consumer finds them through any permute / reshape view, and the two halves of
@@ -332,63 +256,6 @@ COLSTATS_MIN_HW = 1024
 
 def _root(t: torch.Tensor) -> torch.Tensor:
     return t._base if t._base is not None else t
-
-
-# Round 4: GroupNorm statistics WITHOUT a finalise launch.  A producer that emits column statistics also adds per-(sample, channel
-# unit) fixed-point sums to a slice of a zeroed arena (AptpConvGemmParams.ustat_out: 64-bit integer atomics, order-independent);
-# when every producer of a GroupNorm's input left them, the apply pass finishes mean / rstd itself (AptpGroupNormColStats.ustats).
-# The arena belongs to ONE forward: the model calls ustat_begin() at the top of its forward (that zeroes it: one fill launch, also
-# inside a captured graph) and ustat_end() at the end; outside such a bracket nothing is emitted.  USTAT_UNIT = channels per unit:
-# it must divide every GroupNorm group size of the model (SD-2.1: 320 / 32 = 10); 0 = off.
-USTAT = os.environ.get("APTP_USTAT", "1") != "0"
-USTAT_NREP = int(os.environ.get("APTP_USTAT_NREP", "8"))
-_USTAT_WORDS = 1 << 17            # int64 words per arena (1 MiB): ~35 producers x 8 replicas x 4 samples x <= 128 units x 2
-_ustat_arenas = {}
-
-
-def ustat_begin(device, unit: int):
-    """open the unit-statistics arena of the forward that starts now on the current stream (zeroed here); unit <= 0 or
-    APTP_USTAT=0: no arena, producers emit column statistics only"""
-    if not USTAT or unit <= 0 or torch.device(device).type != "cuda":
-        _tls.ustat = None
-        return
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (torch.device(device).index, torch.cuda.current_stream().cuda_stream, _domain(), capturing)
-    ent = _ustat_arenas.get(key)
-    if ent is None:
-        # (allocated inside a capture, the zero fill is part of the graph: every replay starts from a clean arena; such a buffer is
-        #  never released -- its address is baked into the graph, see _workspace)
-        ent = _ustat_arenas[key] = {"buf": torch.zeros(_USTAT_WORDS, dtype=torch.int64, device=device), "used": 0}
-        if capturing:
-            _ws_capture_keep.append(ent["buf"])
-            ent["used"] = _USTAT_WORDS          # a second capture on this stream zeroes everything: it cannot know what the first used
-    elif ent["used"]:
-        ent["buf"][:ent["used"]].zero_()        # what the previous forward on this arena added to
-    _tls.ustat = {"buf": ent["buf"], "off": 0, "unit": int(unit), "ent": ent}
-
-
-def ustat_end():
-    st = getattr(_tls, "ustat", None)
-    if st is not None and not st.get("closed"):
-        st["closed"] = True
-        st["ent"]["used"] = max(st["ent"]["used"], st["off"])
-
-
-def _ustat_alloc(B: int, nout: int):
-    st = getattr(_tls, "ustat", None)
-    if st is None or st.get("closed"):
-        return None
-    unit = st["unit"]
-    units = (nout + unit - 1) // unit
-    nrep = USTAT_NREP                 # replicas spread the same-address contention; more samples already spread it
-    while nrep > 1 and nrep * B > 4 * USTAT_NREP:
-        nrep //= 2
-    n = nrep * B * units * 2
-    if st["off"] + n > st["buf"].numel():
-        return None
-    u = st["buf"][st["off"]:st["off"] + n]
-    st["off"] += n
-    return u, unit, units, nrep
 
 
 def _colstats_drop(out: torch.Tensor):
@@ -606,7 +473,7 @@ def conv_gemm(x: torch.Tensor, pw: PackedWeight, *, stride: int = 1, pad: Option
             if cnt is not None:
                 p.tile_counters = cnt.data_ptr()
         if sk_tile and cnt is None:
-            p.split_k = 1                     # no counters at hand (pool exhausted / first use under capture): whole tiles only
+            p.split_k = 1                     # no counters at hand (a new key under capture and no free slab): whole tiles only
         else:
             ws = _workspace(lib.aptp_conv_gemm_workspace_bytes(ctypes.byref(p)), x.device)
             p.workspace = ws.data_ptr()

@@ -8,9 +8,10 @@ are states an optimizer can have produced: per block absmax_v = absmax_m^2 and e
 the square of the first moment's value, so m^2 <= v before the step and |m| / sqrt(v) <= 10 after it (the update stays a small
 fraction of |p|, as in training, and the margin on p -- relative to max |p| -- keeps its meaning).
 
-(The file is named after csrc/optim8.hip so that it runs after the other captured-step tests: every GraphedFineTunerStep takes
-split-K counter slabs of ops' fixed pool for its streams, and tests/test_clip_score_gpu.py compares an eager run with a replay
-bit for bit while both still find a slab.)"""
+(The file is named after csrc/optim8.hip.  The name once mattered: it sorts after the other captured-step tests because every
+GraphedFineTunerStep takes split-K counter slabs for its streams, the pool was fixed at 16, and tests/test_clip_score_gpu.py
+compares an eager run with a replay bit for bit, which needs a slab for both.  The pool grows now, scratch.py, and the order of
+the files no longer decides a launch's form.)"""
 import ctypes
 from types import SimpleNamespace
 

@@ -49,7 +49,8 @@ _stream = None
 
 
 def time_graph(fn, reps=10):
-    # ONE stream for every measurement: split-K counters are handed out per launching stream (ops._tile_counters: 16 slabs)
+    # ONE stream for every measurement: split-K counters are handed out per launching stream (ops._tile_counters: a slab per
+    # stream, never handed back), and every measurement then sees the same slab and workspace
     global _stream
     if _stream is None:
         _stream = torch.cuda.Stream()

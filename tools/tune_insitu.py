@@ -75,7 +75,7 @@ def main():
     def fwd():
         return model(sample, t, ehs, return_dict=False)[0]
 
-    side = torch.cuda.Stream()          # ONE warm-up stream: split-K counter slabs are handed out per launching stream
+    side = torch.cuda.Stream()          # ONE warm-up stream: split-K counter slabs are handed out per launching stream and never handed back
 
     def measure(replays):
         """steps/s of the forward captured NOW (with whatever ops.TUNING holds)"""
