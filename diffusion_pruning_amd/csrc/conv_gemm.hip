@@ -836,28 +836,6 @@ __global__ __launch_bounds__(GN_RED_NT) void splitk_reduce_gn_kernel(const KPara
   }
 }
 
-struct TileCfg { int bm, bn, wn, nw; };   // tile extents, the wave grid's N extent and the wave count (launch table below)
-const TileCfg kTiles[] = {
-    {0, 0, 0, 0}, {128, 128, 2, 4}, {128, 160, 2, 4}, {64, 128, 2, 4}, {64, 160, 2, 4}, {128, 64, 2, 4},
-    {64, 64, 2, 4}, {128, 128, 2, 4}, {128, 160, 2, 4}, {64, 128, 2, 4}, {64, 160, 2, 4}, {128, 64, 2, 4},
-    {64, 64, 2, 4}, {128, 128, 2, 4}, {128, 160, 2, 4}, {64, 128, 2, 4}, {64, 160, 2, 4}, {128, 64, 2, 4},
-    {64, 64, 2, 4}, {128, 160, 2, 8}, {256, 160, 2, 8}, {128, 128, 4, 8}, {256, 128, 2, 8}, {64, 160, 2, 4},
-    {64, 128, 2, 4}, {64, 64, 2, 4}, {128, 64, 2, 4}, {128, 128, 2, 4}, {128, 160, 2, 8}, {128, 160, 2, 8},
-    {128, 128, 4, 8}, {128, 128, 4, 8}, {256, 128, 2, 8}, {128, 160, 2, 8}, {128, 160, 2, 8}, {128, 128, 4, 8},
-    {128, 128, 4, 8}, {64, 160, 2, 8}, {64, 128, 4, 8}, {64, 160, 2, 8}, {128, 64, 2, 8}, {256, 128, 2, 8},
-    {128, 256, 4, 8},
-    {128, 160, 2, 8}, {128, 128, 2, 8},       // 43, 44: 3x3 halo-in-LDS kernel (conv3x3_halo_kernel)
-    {64, 64, 2, 4}, {64, 64, 2, 4}, {64, 128, 2, 4}, {128, 64, 2, 4},   // 45-48: deep rings for latency-bound small-M launches
-    {64, 64, 2, 4}, {64, 64, 2, 4}, {64, 128, 2, 4}, {64, 128, 2, 4}, {128, 64, 2, 4}, {128, 128, 2, 4}, {64, 160, 2, 4},
-    {128, 160, 2, 8}, {128, 128, 4, 8},                                  // 49-57: two K-tiles per barrier
-    {64, 64, 2, 4}, {64, 64, 2, 4}, {64, 128, 2, 4}, {64, 128, 2, 4}, {128, 64, 2, 4}, {128, 128, 2, 4},   // 58-63: intra-workgroup K split (compute grid 2 x 2)
-    {256, 160, 2, 8}, {256, 128, 2, 8}, {128, 256, 4, 8},               // 64-66: persistent stream-K macro-tiles (conv_gemm_sk.hip)
-    {256, 160, 2, 8}, {256, 128, 2, 8}, {128, 256, 4, 8},               // 67-69: the same, fragment reads in the load slot
-    {128, 160, 2, 8}, {128, 160, 2, 8}, {128, 128, 2, 8}, {128, 128, 2, 8}};   // 70-73: stream-K on 128-row tiles (round 4)
-constexpr int kNumTiles = 74;
-inline bool is_sk_tile(int t) { return t >= APTP_TILE_SK_256x160 && t <= APTP_TILE_SKL_128x128; }
-static_assert(sizeof(kTiles) / sizeof(kTiles[0]) == kNumTiles, "tile table");
-
 int pick_tile(const AptpConvGemmParams* p, int M) {
   if (p->tile != APTP_TILE_AUTO) return p->tile;
   const bool geglu = p->act == APTP_ACT_GEGLU;
@@ -973,51 +951,43 @@ int fill_kparams(const AptpConvGemmParams* p, KParams& k) {
   return APTP_OK;
 }
 
+// One launcher per kernel; launch_row gives each row of conv_gemm_tiles.h the one of its family.
 template <int BM, int BN>
+dim3 tile_grid(const KParams& k) { return dim3(((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN) * k.split_k, 1, 1); }
+template <int BM, int BN, int WM, int WN>
 void launch_tile(const KParams& k, hipStream_t s) {
-  const int tiles = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN);
-  dim3 grid(tiles * k.split_k, 1, 1);
-  if (k.io_f32) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, 2, 2, float>), grid, dim3(256), 0, s, k);
-  else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, 2, 2>), grid, dim3(256), 0, s, k);
+  if (k.io_f32) hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, float>), (tile_grid<BM, BN>(k)), dim3(256), 0, s, k);
+  else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN>), (tile_grid<BM, BN>(k)), dim3(256), 0, s, k);
+}
+
+// LDS-DMA ring on KS copies of WM x WN waves; PP: ping-pong schedule, KU = 2: two K-tiles per barrier (see the kernel)
+template <int BM, int BN, int WM, int WN, int STAGES, bool PP, int KU, int KS>
+void launch_dma(const KParams& k, hipStream_t s) {
+  hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, WM, WN, STAGES, PP, KU, KS>), (tile_grid<BM, BN>(k)), dim3(WM * WN * KS * 64), 0, s, k);
 }
 
 template <int BM, int BN, int STAGES>
-void launch_tile_dma(const KParams& k, hipStream_t s) {
-  const int tiles = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN);
-  dim3 grid(tiles * k.split_k, 1, 1);
-  hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 2, 2, STAGES>), grid, dim3(256), 0, s, k);
+int launch_halo(const AptpConvGemmParams* p, const KParams& k, hipStream_t s) {
+  static_assert(BM == 128, "conv3x3_halo_kernel: 128 output pixels per tile");
+  // whole image rows per tile, the patch (R+2) x (W+2) must fit the 264-row LDS image, no second operand
+  const int W = p->Wout;
+  if (!(p->KH == 3 && p->KW == 3 && p->stride == 1 && p->pad == 1 && p->pad_end == 0 && p->ups == 0 && !p->x2 && W > 0 && 128 % W == 0 &&
+        (p->Hout * W) % 128 == 0 && (128 / W + 2) * (W + 2) <= 264)) {
+    aptp_set_error("conv_gemm: the halo tiles need a 3x3 / stride-1 / pad-1 convolution without x2 whose width divides 128 (16, 32 or 64)");
+    return APTP_EINVAL;
+  }
+  hipLaunchKernelGGL((conv3x3_halo_kernel<BN, STAGES>), (tile_grid<BM, BN>(k)), dim3(512), 0, s, k);
+  return APTP_OK;
 }
 
-// 8-wave workgroups (512 threads, wave grid WM x WN): one weight tile shared by twice the rows
-template <int BM, int BN, int WM, int WN, int STAGES = 2>
-void launch_tile_dma8(const KParams& k, hipStream_t s) {
-  const int tiles = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN);
-  dim3 grid(tiles * k.split_k, 1, 1);
-  hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, WM, WN, STAGES>), grid, dim3(512), 0, s, k);
-}
-
-// two K-tiles per barrier (KU = 2, see the kernel): 4 waves (2 x 2) or 8 waves
-template <int BM, int BN, int WM, int WN, int STAGES>
-void launch_tile_ku2(const KParams& k, hipStream_t s) {
-  const int tiles = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN);
-  dim3 grid(tiles * k.split_k, 1, 1);
-  hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, WM, WN, STAGES, false, 2>), grid, dim3(WM * WN * 64), 0, s, k);
-}
-
-// intra-workgroup K split (KS = 2, see the kernel): 2 x (2 x 2) waves
-template <int BM, int BN, int STAGES>
-void launch_tile_ks2(const KParams& k, hipStream_t s) {
-  const int tiles = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN);
-  dim3 grid(tiles * k.split_k, 1, 1);
-  hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, 2, 2, STAGES, false, 1, 2>), grid, dim3(512), 0, s, k);
-}
-
-// 8-wave ping-pong schedule (see the kernel): wave grid WM x WN, STAGES-deep ring
-template <int BM, int BN, int WM, int WN, int STAGES>
-void launch_tile_pp(const KParams& k, hipStream_t s) {
-  const int tiles = ((k.M + BM - 1) / BM) * ((k.N + BN - 1) / BN);
-  dim3 grid(tiles * k.split_k, 1, 1);
-  hipLaunchKernelGGL((conv_gemm_dma_kernel<BM, BN, WM, WN, STAGES, true>), grid, dim3(512), 0, s, k);
+template <TileFamily F, int BM, int BN, int WM, int WN, int STAGES, int KU, int KS>
+int launch_row(const AptpConvGemmParams* p, const KParams& k, int t, hipStream_t s) {
+  if constexpr (F == TileFamily::REG) launch_tile<BM, BN, WM, WN>(k, s);
+  else if constexpr (F == TileFamily::DMA || F == TileFamily::PP) launch_dma<BM, BN, WM, WN, STAGES, F == TileFamily::PP, KU, KS>(k, s);
+  else if constexpr (F == TileFamily::HALO) return launch_halo<BM, BN, STAGES>(p, k, s);
+  else if (k.split_k > 1 && !k.counters) { aptp_set_error("conv_gemm: the stream-K tiles combine in-kernel: split_k > 1 needs tile_counters"); return APTP_EINVAL; }
+  else return aptp_launch_sk(k, t, s);
+  return APTP_OK;
 }
 
 }  // namespace
@@ -1091,11 +1061,11 @@ extern "C" int aptp_conv_gemm(const AptpConvGemmParams* p, aptp_stream_t stream)
   hipStream_t s = (hipStream_t)stream;
   int t = pick_tile(p, k.M);
   if (t < 0 || t >= kNumTiles) { aptp_set_error("conv_gemm: unknown tile %d", t); return APTP_EINVAL; }
-  if (k.io_f32 && t >= APTP_TILE_DMA_128x128) {
+  if (k.io_f32 && !is_reg_tile(t)) {
     aptp_set_error("conv_gemm: io_f32 (fp32 parity path) runs on the register-staged tiles 1..6 only (got tile %d)", t);
     return APTP_EINVAL;
   }
-  if (t >= APTP_TILE_DMA_128x128 && !is_sk_tile(t) && (p->cin_pad * 2 > 8064 || (p->x2 && p->cin2_pad * 2 > 8064))) {
+  if (is_dma_tile(t) && (p->cin_pad * 2 > 8064 || (p->x2 && p->cin2_pad * 2 > 8064))) {
     // the LDS-DMA variants stream padding lanes from an 8 KiB zero page that must cover one channel row
     aptp_set_error("conv_gemm: LDS-DMA tiles need Cin <= 4032 (got cin_pad %d)", p->cin_pad);
     return APTP_EINVAL;
@@ -1144,96 +1114,16 @@ extern "C" int aptp_conv_gemm(const AptpConvGemmParams* p, aptp_stream_t stream)
   }
   // 3x3 convolutions take the lean kernel of the same tile (conv_lean.hip); APTP_CONV_LEAN=0 keeps them here (A/B timing, tests)
   static const bool lean_on = !(getenv("APTP_CONV_LEAN") && getenv("APTP_CONV_LEAN")[0] == '0');
-  if (lean_on && p->epilogue == 0 && p->pad_end == 0 && aptp_conv_lean_eligible(k, t)) {
-    const int rc2 = aptp_launch_conv_lean(k, t, s);
-    if (rc2 != APTP_OK) return rc2;
-  } else
-  switch (t) {
-    case APTP_TILE_128x128: launch_tile<128, 128>(k, s); break;
-    case APTP_TILE_128x160: launch_tile<128, 160>(k, s); break;
-    case APTP_TILE_64x128: launch_tile<64, 128>(k, s); break;
-    case APTP_TILE_64x160: launch_tile<64, 160>(k, s); break;
-    case APTP_TILE_128x64: launch_tile<128, 64>(k, s); break;
-    case APTP_TILE_64x64: launch_tile<64, 64>(k, s); break;
-    case APTP_TILE_DMA_128x128: launch_tile_dma<128, 128, 2>(k, s); break;
-    case APTP_TILE_DMA_128x160: launch_tile_dma<128, 160, 2>(k, s); break;
-    case APTP_TILE_DMA_64x128: launch_tile_dma<64, 128, 2>(k, s); break;
-    case APTP_TILE_DMA_64x160: launch_tile_dma<64, 160, 2>(k, s); break;
-    case APTP_TILE_DMA_128x64: launch_tile_dma<128, 64, 2>(k, s); break;
-    case APTP_TILE_DMA_64x64: launch_tile_dma<64, 64, 2>(k, s); break;
-    case APTP_TILE_DMA3_128x128: launch_tile_dma<128, 128, 3>(k, s); break;
-    case APTP_TILE_DMA3_128x160: launch_tile_dma<128, 160, 3>(k, s); break;
-    case APTP_TILE_DMA3_64x128: launch_tile_dma<64, 128, 3>(k, s); break;
-    case APTP_TILE_DMA3_64x160: launch_tile_dma<64, 160, 3>(k, s); break;
-    case APTP_TILE_DMA3_128x64: launch_tile_dma<128, 64, 3>(k, s); break;
-    case APTP_TILE_DMA3_64x64: launch_tile_dma<64, 64, 3>(k, s); break;
-    case APTP_TILE_DMA8_128x160: launch_tile_dma8<128, 160, 4, 2>(k, s); break;
-    case APTP_TILE_DMA8_256x160: launch_tile_dma8<256, 160, 4, 2>(k, s); break;
-    case APTP_TILE_DMA8_128x128: launch_tile_dma8<128, 128, 2, 4>(k, s); break;
-    case APTP_TILE_DMA8_256x128: launch_tile_dma8<256, 128, 4, 2>(k, s); break;
-    case APTP_TILE_DMA4_64x160: launch_tile_dma<64, 160, 4>(k, s); break;
-    case APTP_TILE_DMA4_64x128: launch_tile_dma<64, 128, 4>(k, s); break;
-    case APTP_TILE_DMA4_64x64: launch_tile_dma<64, 64, 4>(k, s); break;
-    case APTP_TILE_DMA4_128x64: launch_tile_dma<128, 64, 4>(k, s); break;
-    case APTP_TILE_DMA4_128x128: launch_tile_dma<128, 128, 4>(k, s); break;
-    case APTP_TILE_DMA8R3_128x160: launch_tile_dma8<128, 160, 4, 2, 3>(k, s); break;
-    case APTP_TILE_DMA8R4_128x160: launch_tile_dma8<128, 160, 4, 2, 4>(k, s); break;
-    case APTP_TILE_DMA8R3_128x128: launch_tile_dma8<128, 128, 2, 4, 3>(k, s); break;
-    case APTP_TILE_DMA8R4_128x128: launch_tile_dma8<128, 128, 2, 4, 4>(k, s); break;
-    case APTP_TILE_DMA8R3_256x128: launch_tile_dma8<256, 128, 4, 2, 3>(k, s); break;
-    case APTP_TILE_PP3_128x160: launch_tile_pp<128, 160, 4, 2, 3>(k, s); break;
-    case APTP_TILE_PP4_128x160: launch_tile_pp<128, 160, 4, 2, 4>(k, s); break;
-    case APTP_TILE_PP3_128x128: launch_tile_pp<128, 128, 2, 4, 3>(k, s); break;
-    case APTP_TILE_PP4_128x128: launch_tile_pp<128, 128, 2, 4, 4>(k, s); break;
-    case APTP_TILE_PP4_64x160: launch_tile_pp<64, 160, 4, 2, 4>(k, s); break;
-    case APTP_TILE_PP4_64x128: launch_tile_pp<64, 128, 2, 4, 4>(k, s); break;
-    case APTP_TILE_PP5_64x160: launch_tile_pp<64, 160, 4, 2, 5>(k, s); break;
-    case APTP_TILE_PP4_128x64: launch_tile_pp<128, 64, 4, 2, 4>(k, s); break;
-    case APTP_TILE_PP3_256x128: launch_tile_pp<256, 128, 4, 2, 3>(k, s); break;
-    case APTP_TILE_PP3_128x256: launch_tile_pp<128, 256, 2, 4, 3>(k, s); break;
-    case APTP_TILE_DMA6_64x64: launch_tile_dma<64, 64, 6>(k, s); break;
-    case APTP_TILE_DMA8S_64x64: launch_tile_dma<64, 64, 8>(k, s); break;
-    case APTP_TILE_DMA6_64x128: launch_tile_dma<64, 128, 6>(k, s); break;
-    case APTP_TILE_DMA6_128x64: launch_tile_dma<128, 64, 6>(k, s); break;
-    case APTP_TILE_KU2S4_64x64: launch_tile_ku2<64, 64, 2, 2, 4>(k, s); break;
-    case APTP_TILE_KU2S6_64x64: launch_tile_ku2<64, 64, 2, 2, 6>(k, s); break;
-    case APTP_TILE_KU2S4_64x128: launch_tile_ku2<64, 128, 2, 2, 4>(k, s); break;
-    case APTP_TILE_KU2S6_64x128: launch_tile_ku2<64, 128, 2, 2, 6>(k, s); break;
-    case APTP_TILE_KU2S4_128x64: launch_tile_ku2<128, 64, 2, 2, 4>(k, s); break;
-    case APTP_TILE_KU2S4_128x128: launch_tile_ku2<128, 128, 2, 2, 4>(k, s); break;
-    case APTP_TILE_KU2S4_64x160: launch_tile_ku2<64, 160, 2, 2, 4>(k, s); break;
-    case APTP_TILE_KU2S4_128x160: launch_tile_ku2<128, 160, 4, 2, 4>(k, s); break;
-    case APTP_TILE_KU2S4_128x128W8: launch_tile_ku2<128, 128, 2, 4, 4>(k, s); break;
-    case APTP_TILE_KS2S3_64x64: launch_tile_ks2<64, 64, 3>(k, s); break;
-    case APTP_TILE_KS2S4_64x64: launch_tile_ks2<64, 64, 4>(k, s); break;
-    case APTP_TILE_KS2S3_64x128: launch_tile_ks2<64, 128, 3>(k, s); break;
-    case APTP_TILE_KS2S4_64x128: launch_tile_ks2<64, 128, 4>(k, s); break;
-    case APTP_TILE_KS2S3_128x64: launch_tile_ks2<128, 64, 3>(k, s); break;
-    case APTP_TILE_KS2S3_128x128: launch_tile_ks2<128, 128, 3>(k, s); break;
-    case APTP_TILE_SK_256x160: case APTP_TILE_SK_256x128: case APTP_TILE_SK_128x256:
-    case APTP_TILE_SKL_256x160: case APTP_TILE_SKL_256x128: case APTP_TILE_SKL_128x256:
-    case APTP_TILE_SK_128x160: case APTP_TILE_SKL_128x160: case APTP_TILE_SK_128x128: case APTP_TILE_SKL_128x128: {
-      if (k.split_k > 1 && !k.counters) { aptp_set_error("conv_gemm: the stream-K tiles combine in-kernel: split_k > 1 needs tile_counters"); return APTP_EINVAL; }
-      const int rc2 = aptp_launch_sk(k, t, s);
-      if (rc2 != APTP_OK) return rc2;
-      break;
-    }
-    case APTP_TILE_HALO_128x160:
-    case APTP_TILE_HALO_128x128: {
-      // whole image rows per tile, the patch (R+2) x (W+2) must fit the 264-row LDS image, no second operand
-      const int W = p->Wout;
-      if (!(p->KH == 3 && p->KW == 3 && p->stride == 1 && p->pad == 1 && p->pad_end == 0 && p->ups == 0 && !p->x2 && W > 0 && 128 % W == 0 &&
-            (p->Hout * W) % 128 == 0 && (128 / W + 2) * (W + 2) <= 264)) {
-        aptp_set_error("conv_gemm: the halo tiles need a 3x3 / stride-1 / pad-1 convolution without x2 whose width divides 128 (16, 32 or 64)");
-        return APTP_EINVAL;
-      }
-      const int tiles = ((k.M + 127) / 128) * ((k.N + kTiles[t].bn - 1) / kTiles[t].bn);
-      if (t == APTP_TILE_HALO_128x160) hipLaunchKernelGGL((conv3x3_halo_kernel<160, 4>), dim3(tiles * k.split_k), dim3(512), 0, s, k);
-      else hipLaunchKernelGGL((conv3x3_halo_kernel<128, 4>), dim3(tiles * k.split_k), dim3(512), 0, s, k);
-      break;
-    }
+  int rc2 = APTP_OK;
+  if (lean_on && p->epilogue == 0 && p->pad_end == 0 && aptp_conv_lean_eligible(k, t)) rc2 = aptp_launch_conv_lean(k, t, s);
+  else switch (t) {
+#define X(NAME, FAMILY, BM, BN, WM, WN, STAGES, KU, KS, LIN, C3) \
+    case APTP_TILE_##NAME: rc2 = launch_row<TileFamily::FAMILY, BM, BN, WM, WN, STAGES, KU, KS>(p, k, t, s); break;
+    APTP_CONV_GEMM_TILES(X)
+#undef X
     default: aptp_set_error("conv_gemm: unknown tile %d", t); return APTP_EINVAL;
   }
+  if (rc2 != APTP_OK) return rc2;
   APTP_LAUNCH_CHECK();
   if (k.split_k > 1 && !k.counters) {
     if (k.gn_gamma) {

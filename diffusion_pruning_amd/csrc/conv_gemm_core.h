@@ -894,4 +894,5 @@ int aptp_launch_conv_lean(const KParams& k, int tile, hipStream_t s);
 
 }  // namespace aptp_cg
 
+#include "conv_gemm_tiles.h"      // the one table of tile ids: geometry, families, and the rows the launch switches expand
 #include "conv_gemm_kloop.h"      // the K loop the LDS-DMA kernels share: MFMA block, counted wait, ring schedules

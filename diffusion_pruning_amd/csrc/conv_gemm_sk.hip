@@ -424,20 +424,21 @@ int aptp_sk_cus() {
   return g_sk_cus;
 }
 
+// The kernel of an SK / SKL row (RDC, fragment reads one phase ahead: SK).  Rows of the other families instantiate nothing.
+template <TileFamily F, int BM, int BN, int WM, int WN>
+static int launch_sk_row(const KParams& k, int tile, hipStream_t s) {
+  if constexpr (F == TileFamily::SK || F == TileFamily::SKL) return launch_sk<BM, BN, WM, WN, F == TileFamily::SK>(k, s);
+  aptp_set_error("conv_gemm: unknown stream-K tile %d", tile); return APTP_EINVAL;
+}
+
 int aptp_launch_sk(const KParams& k, int tile, hipStream_t s) {
   switch (tile) {
-    case APTP_TILE_SK_256x160: return launch_sk<256, 160, 4, 2, true>(k, s);
-    case APTP_TILE_SK_256x128: return launch_sk<256, 128, 4, 2, true>(k, s);
-    case APTP_TILE_SK_128x256: return launch_sk<128, 256, 2, 4, true>(k, s);
-    case APTP_TILE_SKL_256x160: return launch_sk<256, 160, 4, 2, false>(k, s);
-    case APTP_TILE_SKL_256x128: return launch_sk<256, 128, 4, 2, false>(k, s);
-    case APTP_TILE_SKL_128x256: return launch_sk<128, 256, 2, 4, false>(k, s);
-    case APTP_TILE_SK_128x160: return launch_sk<128, 160, 4, 2, true>(k, s);
-    case APTP_TILE_SKL_128x160: return launch_sk<128, 160, 4, 2, false>(k, s);
-    case APTP_TILE_SK_128x128: return launch_sk<128, 128, 4, 2, true>(k, s);
-    case APTP_TILE_SKL_128x128: return launch_sk<128, 128, 4, 2, false>(k, s);
-    default: aptp_set_error("conv_gemm: unknown stream-K tile %d", tile); return APTP_EINVAL;
+#define X(NAME, FAMILY, BM, BN, WM, WN, STAGES, KU, KS, LIN, C3) \
+    case APTP_TILE_##NAME: return launch_sk_row<TileFamily::FAMILY, BM, BN, WM, WN>(k, tile, s);
+    APTP_CONV_GEMM_TILES(X)
+#undef X
   }
+  return launch_sk_row<TileFamily::NONE, 0, 0, 0, 0>(k, tile, s);
 }
 
 }  // namespace aptp_cg

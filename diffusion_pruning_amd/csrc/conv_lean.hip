@@ -230,25 +230,24 @@ bool aptp_conv_lean_eligible(const KParams& k, int tile) {
   if (k.io_f32 || k.out_f32 || !k.epi16 || k.ln_stats || k.rstat_out || k.depth) return false;
   if (k.act != APTP_ACT_NONE && k.act != APTP_ACT_SILU) return false;
   if (k.Nout < 8 || k.ncc < 1) return false;
-  switch (tile) {
-    case APTP_TILE_PP4_128x160: case APTP_TILE_PP4_128x64: case APTP_TILE_DMA8R3_128x160:
-    case APTP_TILE_DMA8R3_128x128: case APTP_TILE_DMA3_64x64: case APTP_TILE_KU2S4_128x160:
-      return true;
-    default: return false;
-  }
+  return tile_known(tile) && kTiles[tile].c3;        // the rows of conv_gemm_tiles.h flagged C3
+}
+
+// The lean kernel of a C3 row, with the row's own geometry, ring and schedule.  A row without the flag instantiates nothing.
+template <bool C3, int BM, int BN, int WM, int WN, int STAGES, bool PP, int KU>
+static bool launch_lean_row(const KParams& k, hipStream_t s) {
+  if constexpr (C3) launch_lean<BM, BN, WM, WN, STAGES, PP, KU>(k, s);
+  return C3;
 }
 
 int aptp_launch_conv_lean(const KParams& k, int tile, hipStream_t s) {
   switch (tile) {
-    case APTP_TILE_PP4_128x160: launch_lean<128, 160, 4, 2, 4, true, 1>(k, s); break;
-    case APTP_TILE_PP4_128x64: launch_lean<128, 64, 4, 2, 4, true, 1>(k, s); break;
-    case APTP_TILE_DMA8R3_128x160: launch_lean<128, 160, 4, 2, 3, false, 1>(k, s); break;
-    case APTP_TILE_DMA8R3_128x128: launch_lean<128, 128, 2, 4, 3, false, 1>(k, s); break;
-    case APTP_TILE_DMA3_64x64: launch_lean<64, 64, 2, 2, 3, false, 1>(k, s); break;
-    case APTP_TILE_KU2S4_128x160: launch_lean<128, 160, 4, 2, 4, false, 2>(k, s); break;
-    default: aptp_set_error("conv_lean: tile %d has no lean instantiation", tile); return APTP_EINVAL;
+#define X(NAME, FAMILY, BM, BN, WM, WN, STAGES, KU, KS, LIN, C3) case APTP_TILE_##NAME: \
+    if (launch_lean_row<C3 != 0, BM, BN, WM, WN, STAGES, TileFamily::FAMILY == TileFamily::PP, KU>(k, s)) return APTP_OK; break;
+    APTP_CONV_GEMM_TILES(X)
+#undef X
   }
-  return APTP_OK;
+  aptp_set_error("conv_lean: tile %d has no lean instantiation", tile); return APTP_EINVAL;
 }
 
 }  // namespace aptp_cg

@@ -415,34 +415,26 @@ bool aptp_lin_eligible(const KParams& k, int tile) {
   if (k.colgate || k.corr || k.rowbias || k.depth) return false;
   if (k.act == APTP_ACT_GEGLU && (k.residual || k.rstat_out || k.cstat_out || k.N % 32 != 0)) return false;
   if (k.Nout < 8 || k.ncc < 1) return false;
-  switch (tile) {
-    case APTP_TILE_DMA_64x64: case APTP_TILE_DMA3_64x64: case APTP_TILE_DMA4_64x64: case APTP_TILE_DMA6_64x64: case APTP_TILE_DMA8S_64x64:
-    case APTP_TILE_KU2S4_64x64: case APTP_TILE_KU2S6_64x64:
-    case APTP_TILE_DMA_64x128: case APTP_TILE_DMA3_64x128: case APTP_TILE_DMA4_64x128: case APTP_TILE_DMA6_64x128:
-    case APTP_TILE_KU2S4_64x128: case APTP_TILE_KU2S6_64x128:
-    case APTP_TILE_DMA_128x64: case APTP_TILE_DMA3_128x64: case APTP_TILE_DMA4_128x64: case APTP_TILE_DMA6_128x64: case APTP_TILE_KU2S4_128x64:
-      return true;
-    default: return false;
-  }
+  return tile_known(tile) && kTiles[tile].lin;       // the rows of conv_gemm_tiles.h flagged LIN
+}
+
+// The lean kernel of a LIN row: the row's tile on 2 x 2 waves, its ring capped at LIN_MAX_STAGES (the deeper rings of the general
+// kernel share the 4-stage instantiation).  A row without the flag instantiates nothing and answers false.
+constexpr int LIN_MAX_STAGES = 4;
+template <bool LIN, int BM, int BN, int STAGES, int KU>
+static bool launch_lin_row(const KParams& k, hipStream_t s) {
+  if constexpr (LIN) launch_lin<BM, BN, 2, 2, (STAGES < LIN_MAX_STAGES ? STAGES : LIN_MAX_STAGES), KU>(k, s);
+  return LIN;
 }
 
 int aptp_launch_lin(const KParams& k, int tile, hipStream_t s) {
   switch (tile) {
-    case APTP_TILE_DMA_64x64: launch_lin<64, 64, 2, 2, 2, 1>(k, s); break;
-    case APTP_TILE_DMA3_64x64: launch_lin<64, 64, 2, 2, 3, 1>(k, s); break;
-    case APTP_TILE_DMA4_64x64: case APTP_TILE_DMA6_64x64: case APTP_TILE_DMA8S_64x64: launch_lin<64, 64, 2, 2, 4, 1>(k, s); break;
-    case APTP_TILE_KU2S4_64x64: case APTP_TILE_KU2S6_64x64: launch_lin<64, 64, 2, 2, 4, 2>(k, s); break;
-    case APTP_TILE_DMA_64x128: launch_lin<64, 128, 2, 2, 2, 1>(k, s); break;
-    case APTP_TILE_DMA3_64x128: launch_lin<64, 128, 2, 2, 3, 1>(k, s); break;
-    case APTP_TILE_DMA4_64x128: case APTP_TILE_DMA6_64x128: launch_lin<64, 128, 2, 2, 4, 1>(k, s); break;
-    case APTP_TILE_KU2S4_64x128: case APTP_TILE_KU2S6_64x128: launch_lin<64, 128, 2, 2, 4, 2>(k, s); break;
-    case APTP_TILE_DMA_128x64: launch_lin<128, 64, 2, 2, 2, 1>(k, s); break;
-    case APTP_TILE_DMA3_128x64: launch_lin<128, 64, 2, 2, 3, 1>(k, s); break;
-    case APTP_TILE_DMA4_128x64: case APTP_TILE_DMA6_128x64: launch_lin<128, 64, 2, 2, 4, 1>(k, s); break;
-    case APTP_TILE_KU2S4_128x64: launch_lin<128, 64, 2, 2, 4, 2>(k, s); break;
-    default: aptp_set_error("lin_gemm: tile %d has no lean instantiation", tile); return APTP_EINVAL;
+#define X(NAME, FAMILY, BM, BN, WM, WN, STAGES, KU, KS, LIN, C3) \
+    case APTP_TILE_##NAME: if (launch_lin_row<LIN != 0, BM, BN, STAGES, KU>(k, s)) return APTP_OK; break;
+    APTP_CONV_GEMM_TILES(X)
+#undef X
   }
-  return APTP_OK;
+  aptp_set_error("lin_gemm: tile %d has no lean instantiation", tile); return APTP_EINVAL;
 }
 
 }  // namespace aptp_cg

@@ -15,7 +15,7 @@ DMA_MAX_CHANNELS = 4032             # ... whose channel steps address at most th
 SK_TILE_FIRST = L.TILE_SK_256x160   # APTP_TILE_SK_*: persistent stream-K macro-tiles (csrc/conv_gemm_sk.hip)
 SK_MAX_CHANNELS = 32704             # channels per tap of a stream-K tile
 _HALO_TILES = (L.TILE_HALO_128x160, L.TILE_HALO_128x128)
-# tiles csrc/lin_gemm.hip instantiates (the switch of aptp_lin_eligible; tests/test_host_logic.py compares the two)
+# tiles csrc/lin_gemm.hip instantiates (the LIN rows of csrc/conv_gemm_tiles.h; tests/test_host_logic.py compares the two)
 _LEAN_TILES = frozenset(getattr(L, "TILE_" + t) for t in (
     "DMA_64x128 DMA_128x64 DMA_64x64 DMA3_64x128 DMA3_128x64 DMA3_64x64 DMA4_64x128 DMA4_64x64 DMA4_128x64 DMA6_64x64 DMA8S_64x64 "
     "DMA6_64x128 DMA6_128x64 KU2S4_64x64 KU2S6_64x64 KU2S4_64x128 KU2S6_64x128 KU2S4_128x64").split())

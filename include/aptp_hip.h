@@ -171,6 +171,8 @@ typedef struct {
   int32_t pad_end;
 } AptpConvGemmParams;
 
+/* The documented numbering.  Each id's geometry, kernel family and lean instantiations are its row of csrc/conv_gemm_tiles.h,
+ * which fails the build when a row's position and the value here disagree. */
 enum { APTP_TILE_AUTO = 0, APTP_TILE_128x128 = 1, APTP_TILE_128x160 = 2, APTP_TILE_64x128 = 3, APTP_TILE_64x160 = 4,
        APTP_TILE_128x64 = 5, APTP_TILE_64x64 = 6,
        /* same tiles, operands copied global->LDS by LDS-DMA instead of through registers */

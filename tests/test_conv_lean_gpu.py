@@ -11,10 +11,10 @@ import pytest
 import torch
 
 from oracle import unet_oracle as O
+from tests.tiles import C3 as LEAN_TILES               # the tiles csrc/conv_lean.hip instantiates
 
 pytestmark = pytest.mark.gpu
 
-LEAN_TILES = (34, 40, 28, 30, 18, 56)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 

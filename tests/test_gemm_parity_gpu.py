@@ -12,12 +12,13 @@ import torch
 
 from tests import gemm_model as GM
 from tests import margins
+from tests import tiles
 
 pytestmark = pytest.mark.gpu
 
-HALO_TILES = (43, 44)
-WIDE160_TILES = (2, 4, 8, 10, 14, 16, 19, 20, 23, 28, 29, 33, 34, 37, 39, 43, 55, 56, 64, 67, 70, 71)   # GEGLU refuses them
-SK_FIRST = 64
+HALO_TILES = tiles.HALO
+WIDE160_TILES = tiles.WIDE160                          # GEGLU refuses them
+SK_TILES = tiles.SK
 # (family, tile id of include/aptp_hip.h, split_k or None = the case's own, ops.EPILOGUE)
 FAMILIES = [
     ("staged", 2, None, 0), ("staged", 6, None, 0),
@@ -37,6 +38,10 @@ FAMILIES = [
 # plain linear layers: the tiles csrc/lin_gemm.hip instantiates (LIN_TILES of tests/test_ops_gpu.py), one per tile shape and ring
 LIN_FAMILIES = [("lean-linear 64x64", 12, None, 0), ("lean-linear 64x64 ku2", 49, None, 0), ("lean-linear 64x128", 15, None, 0),
                 ("lean-linear 128x64", 26, None, 0)]
+# (both are hand-picked: one id per kernel family; what must hold is that the table knows them)
+assert {t for _, t, _, _ in FAMILIES} <= {0, *tiles.ALL} and {t for _, t, _, _ in LIN_FAMILIES} <= set(tiles.LIN)
+assert {t for f, t, _, _ in FAMILIES if f.startswith("streamk")} <= set(SK_TILES)
+assert {t for f, t, _, _ in FAMILIES if "lean3x3" in f} <= set(tiles.C3)
 
 
 def _statically_refused(case, tile):
@@ -61,8 +66,8 @@ def _params():
         for fam, tile, fsplit, fepi in fams:
             if _statically_refused(case, tile):
                 continue
-            split = fsplit if tile >= SK_FIRST else case.split_k
-            both = tile < SK_FIRST and split != 1 and (split is not None or case.name.startswith("largestK"))
+            split = fsplit if tile in SK_TILES else case.split_k
+            both = tile not in SK_TILES and split != 1 and (split is not None or case.name.startswith("largestK"))
             for epi in epis:
                 if epi is not None and fepi == 1:
                     continue                      # (the epilogue cases sweep EPILOGUE themselves)

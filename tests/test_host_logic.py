@@ -5,6 +5,7 @@ import torch
 
 from oracle import unet_oracle as O
 from tests import hip_emulator
+from tests import tiles
 
 TOL = 2e-2
 
@@ -555,22 +556,59 @@ def test_the_tile_ids_of_the_policy_are_the_library_s():
     header = open(os.path.join(root, "include", "aptp_hip.h")).read()
     enum = {n: int(v) for n, v in re.findall(r"APTP_TILE_(\w+)\s*=\s*(\d+)", header)}
     assert enum["AUTO"] == 0 and len(set(enum.values())) == len(enum)
-    n_tiles = int(re.search(r"constexpr int kNumTiles = (\d+);", open(os.path.join(root, "diffusion_pruning_amd", "csrc", "conv_gemm.hip")).read()).group(1))
+    n_tiles = len(tiles.TILES) + 1                                                     # (kNumTiles: the rows and id 0 = auto)
     assert sorted(enum.values()) == list(range(n_tiles))
+    assert {t.name: t.id for t in tiles.TILES} == {n: v for n, v in enum.items() if n != "AUTO"}   # (csrc static_asserts the same)
     named = {n[5:]: v for n, v in vars(_lib).items() if n.startswith("TILE_")}
     assert named and all(enum[n] == v for n, v in named.items())                       # no second numbering
-    lin = open(os.path.join(root, "diffusion_pruning_amd", "csrc", "lin_gemm.hip")).read()
-    body = lin[lin.index("bool aptp_lin_eligible("):]
-    body = body[:body.index("default:")]
-    cases = {enum[n] for n in re.findall(r"case APTP_TILE_(\w+):", body)}
-    assert cases == set(lp._LEAN_TILES) == {9, 11, 12, 15, 17, 18, 24, 25, 26} | set(range(45, 54))
-    assert set(lp._HALO_TILES) == {enum["HALO_128x160"], enum["HALO_128x128"]}
+    assert set(tiles.LIN) == set(lp._LEAN_TILES) == {9, 11, 12, 15, 17, 18, 24, 25, 26} | set(range(45, 54))
+    assert set(lp._HALO_TILES) == set(tiles.HALO) == {enum["HALO_128x160"], enum["HALO_128x128"]}
+    assert lp.DMA_TILE_FIRST == max(tiles.REG) + 1 == len(tiles.REG) + 1 and lp.SK_TILE_FIRST == min(tiles.SK)
+    assert tiles.SK == tuple(range(min(tiles.SK), n_tiles))                            # (ops and the policy test `tile >= SK_TILE_FIRST`)
     assert lp.DMA_TILE_FIRST == enum["DMA_128x128"] == enum["64x64"] + 1 and lp.SK_TILE_FIRST == enum["SK_256x160"]
     policy_tiles = set(lp._LEAN_TILES) | set(lp._HALO_TILES) | {lp.DMA_TILE_FIRST, lp.SK_TILE_FIRST, _lib.TILE_SK_256x160, _lib.TILE_SK_256x128}
     policy_tiles |= {lp._lean_tile(M) for M in (1, 2048, 8192)}
     assert {lp._lean_tile(M) for M in (1, 2048, 8192)} <= set(lp._LEAN_TILES)
     assert all(0 < t < n_tiles for t in policy_tiles)
     assert all(0 < e["tile"] < n_tiles for e in lp.TUNING.values())
+
+
+def test_the_compiled_tile_geometry_is_the_table_s():
+    """The host helpers that size a launch's workspace, arrival counters and statistics buffers index the compiled tile table by id:
+    a wrong extent there is a slab that is too small, not a failing number.  For every id the library's answers equal the ones
+    recorded from the last library with a hand-written table (tests/golden/conv_gemm_tile_helpers.json) AND what the id's row of
+    csrc/conv_gemm_tiles.h predicts.  The problem's extents (M = 407, N = 328) are multiples of no tile size and tell every
+    (bm, bn, wn, waves) combination apart.  The stream-K workspace scales with the CU count the runtime reports: a positive
+    multiple of two fp32 tiles, whatever the machine."""
+    import ctypes
+    import json
+    import os
+    from diffusion_pruning_amd import _lib
+    lib = _lib.load()
+    rec = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_gemm_tile_helpers.json")))
+    prob = rec["problem"]
+    M, N, split_k = prob["B"] * prob["Hout"] * prob["Wout"], prob["N"], prob["split_k"]
+    assert (M, N, split_k) == (407, 328, 3) and rec["columns"] == ["tiles", "colstat_rows", "rowstat_slots", "workspace_bytes"]
+    assert sorted(map(int, rec["rows"])) == list(tiles.ALL) + [len(tiles.ALL) + 1]
+    assert [rec["rows"][i] for i in ("1", "6")] == [[12, 64, 6, 2359296], [42, 32, 12, 2064384]]
+    assert rec["rows"]["66"][:3] == [8, 64, 8] and rec["rows"]["72"][:3] == [12, 32, 6]
+
+    def ask(tile):
+        p = _lib.ConvGemmParams(tile=tile, **prob)
+        r = ctypes.byref(p)
+        return [lib.aptp_conv_gemm_tiles(r), lib.aptp_conv_gemm_colstat_rows(r), lib.aptp_conv_gemm_rowstat_slots(r),
+                lib.aptp_conv_gemm_workspace_bytes(r)]
+
+    for t in tiles.TILES:
+        got, want = ask(t.id), rec["rows"][str(t.id)]
+        tm, tn = -(-M // t.bm), -(-N // t.bn)
+        row = [tm * tn, t.bm // t.wm, tn * t.wn, split_k * tm * t.bm * tn * t.bn * 4]
+        if t.id in tiles.SK:
+            assert got[3] > 0 and got[3] % (2 * t.bm * t.bn * 4) == 0 and want[3] % (2 * t.bm * t.bn * 4) == 0, (t, got, want)
+            got, want, row = got[:3], want[:3], row[:3]
+        assert got == want == row, (t, got, want, row)
+    past = len(tiles.TILES) + 1                                                        # no such tile: no tiles, no statistics rows
+    assert ask(past)[:3] == rec["rows"][str(past)][:3] == [0, 0, 0] and ask(past)[3] == rec["rows"][str(past)][3] == split_k * M * N * 4
 
 
 # ---- the same host logic without any rounding: fp32 storage end to end (emulator exact mode) vs the fp32 oracle -------------

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from tests import clip_vision_oracle as O
+from tests import tiles
 from tests.helpers import rel_l2
 from tests.margins import check
 
@@ -26,7 +27,7 @@ ENC_F32_TOL = 1e-4
 # absolute bound of the MMD statistic: the granularity of the reference's own fp32 result -- three fp32 means of values just
 # under 1 (ulp 2^-24 below 1, so 2^-23 after the subtraction), weighted 1, 1, 2 and scaled by 1000
 MMD_BOUND = 1000 * 4 * 2.0 ** -23
-HALO_TILES = (43, 44)
+HALO_TILES = tiles.HALO
 TINY = dict(hidden_size=128, intermediate_size=128, num_hidden_layers=2, num_attention_heads=2, patch_size=14, image_size=56,
             projection_dim=64)
 VISION_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clip_vision_tiny.npz")
@@ -58,7 +59,7 @@ def test_quick_gelu_linear_every_tile_bf16(cuda, monkeypatch, general):
     monkeypatch.setattr(ops, "EPILOGUE", 2 if general else 0)
     x, w, b, res, ref = _qgelu_case(cuda, torch.bfloat16, 21)
     pw = ops.pack_weight(w, b, device=cuda)
-    for tile in range(1, 74):
+    for tile in tiles.ALL:
         if tile in HALO_TILES:
             with pytest.raises(AptpError):
                 ops.linear(x, pw, act=ops.ACT_QUICK_GELU, residual=res, tile=tile)
@@ -81,7 +82,7 @@ def test_quick_gelu_linear_split_k_bf16(cuda, monkeypatch, split_k, in_kernel):
     monkeypatch.setattr(ops, "SPLITK_IN_KERNEL", in_kernel)
     x, w, b, res, ref = _qgelu_case(cuda, torch.bfloat16, 22, K=1024)
     pw = ops.pack_weight(w, b, device=cuda)
-    for tile in (t for t in range(1, 74) if t not in HALO_TILES):
+    for tile in (t for t in tiles.ALL if t not in HALO_TILES):
         y = ops.linear(x, pw, act=ops.ACT_QUICK_GELU, residual=res, tile=tile, split_k=split_k)
         torch.cuda.synchronize()
         check(rel_l2(y, ref), LIN_BF16_TOL, f"QuickGELU linear bf16 tile {tile} split_k {split_k} in_kernel {in_kernel}")

@@ -32,12 +32,13 @@ import torch
 
 from tests import margins
 from tests import norm_model as NM
+from tests import tiles
 
 pytestmark = pytest.mark.gpu
 
 GPU_SHAPES = [i for i, s in enumerate(NM.GN_SHAPES) if s.gpu]
 FEW_KINDS = ("plain", "offset16", "offset32", "offset64", "tiny", "mixed")      # variants 2, 3, 4 (1 and 0 take every kind)
-WAVE_COLUMNS = {9: 64, 18: 32, 34: 80, 64: 80}              # bn / wn of the tiles asked for by id (kTiles, conv_gemm.hip:840-856)
+WAVE_COLUMNS = {t: tiles.BY_ID[t].bn // tiles.BY_ID[t].wn for t in (9, 18, 34, 64)}    # bn / wn of the tiles asked for by id
 SENTINEL = 0x5A5B
 
 

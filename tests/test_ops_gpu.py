@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import tiles
+
 pytestmark = pytest.mark.gpu
 
 REL_L2_TOL = 4e-3
@@ -1028,7 +1030,8 @@ def test_capture_time_scratch_buffers_are_never_released(ops, cuda):
     assert bool((kept[0][:1 << 10] == 7).all())
 
 
-LIN_TILES = [12, 18, 25, 49, 9, 15, 24, 51, 11, 17, 26, 53]
+LIN_TILES = [12, 18, 25, 49, 9, 15, 24, 51, 11, 17, 26, 53]       # hand-picked: each tile shape at rings 2, 3, 4 and KU = 2
+assert set(LIN_TILES) <= set(tiles.LIN)                          # ... of the tiles csrc/lin_gemm.hip instantiates
 
 
 @pytest.mark.parametrize("tile", LIN_TILES)

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import tiles
 from tests.clip_text_oracle import clip_text_forward
 from tests.helpers import rel_l2
 from tests.margins import check
@@ -97,7 +98,7 @@ def test_attention_causal_refuses_long_sequences(cuda):
 # ---------------------------------------------------------------------------------------------------------------------
 # GELU epilogue (APTP_ACT_GELU)
 # ---------------------------------------------------------------------------------------------------------------------
-HALO_TILES = (43, 44)
+HALO_TILES = tiles.HALO
 
 
 def _gelu_case(cuda, dtype, seed, M=154, K=256, N=512):
@@ -121,7 +122,7 @@ def test_gelu_linear_every_tile_bf16(cuda, monkeypatch, general):
     monkeypatch.setattr(ops, "EPILOGUE", 2 if general else 0)
     x, w, b, res, ref = _gelu_case(cuda, torch.bfloat16, 11)
     pw = ops.pack_weight(w, b, device=cuda)
-    for tile in range(1, 74):
+    for tile in tiles.ALL:
         if tile in HALO_TILES:
             with pytest.raises(AptpError):
                 ops.linear(x, pw, act=ops.ACT_GELU, residual=res, tile=tile)
@@ -142,7 +143,7 @@ def test_gelu_linear_split_k_bf16(cuda, monkeypatch, split_k, in_kernel):
     monkeypatch.setattr(ops, "SPLITK_IN_KERNEL", in_kernel)
     x, w, b, res, ref = _gelu_case(cuda, torch.bfloat16, 12, K=1024)
     pw = ops.pack_weight(w, b, device=cuda)
-    for tile in (t for t in range(1, 74) if t not in HALO_TILES):
+    for tile in (t for t in tiles.ALL if t not in HALO_TILES):
         y = ops.linear(x, pw, act=ops.ACT_GELU, residual=res, tile=tile, split_k=split_k)
         torch.cuda.synchronize()
         check(rel_l2(y, ref), LIN_BF16_TOL, f"GELU linear bf16 tile {tile} split_k {split_k} in_kernel {in_kernel}")
@@ -154,11 +155,11 @@ def test_gelu_linear_fp32_parity(cuda, monkeypatch, split_k):
     monkeypatch.setattr(ops, "ACT_DTYPE", torch.float32)
     x, w, b, res, ref = _gelu_case(cuda, torch.float32, 13, K=512)
     pw = ops.pack_weight(w, b, device=cuda)
-    for tile in range(0, 7):
+    for tile in (0,) + tiles.REG:
         y = ops.linear(x, pw, act=ops.ACT_GELU, residual=res, tile=tile, split_k=split_k)
         torch.cuda.synchronize()
         check(rel_l2(y, ref), LIN_F32_TOL, f"GELU linear fp32 tile {tile} split_k {split_k}")
-    for tile in range(7, 74):                                 # the parity path runs on the register-staged tiles only
+    for tile in (t for t in tiles.ALL if t not in tiles.REG):     # the parity path runs on the register-staged tiles only
         with pytest.raises(ValueError):
             ops.linear(x, pw, act=ops.ACT_GELU, residual=res, tile=tile, split_k=split_k)
 

@@ -2,6 +2,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from diffusion_pruning_amd import ops
+from tests.tiles import HALO
 dev = torch.device("cuda:0")
 def timeit(fn, reps=10):
     fn(); torch.cuda.synchronize()
@@ -22,7 +23,7 @@ for (H, Cin, N) in [(64, 160, 320), (64, 320, 160), (64, 640, 160), (64, 960, 16
     y = ops.conv_gemm(x, pw)
     t0 = timeit(lambda: ops.conv_gemm(x, pw, out=y))
     row = []
-    for tile in (43, 44):
+    for tile in HALO:
         for sk in (1, 2, 3, 4):
             for order in (2, 3):
                 try:

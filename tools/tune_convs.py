@@ -17,6 +17,7 @@ from bench import fixed_half_mask, ones_mask  # noqa: E402
 from diffusion_pruning_amd import ops  # noqa: E402
 from diffusion_pruning_amd._lib import ACT_GEGLU, ConvGemmParams  # noqa: E402
 from diffusion_pruning_amd.unet import UNet2DConditionModelGated  # noqa: E402
+from tests.tiles import ALL as ALL_TILES  # noqa: E402
 
 dev = torch.device("cuda:0")
 
@@ -166,7 +167,7 @@ def tune(args, lib, log):
         else:
             timer = lambda q: time_launch(lib, q)
         t_base = timer(base)
-        tiles = [1, 3, 5, 6, 7, 9, 11, 12, 13, 15, 17, 18, 21, 22, 24, 25, 26, 27, 30, 31, 32, 35, 36, 38, 40] if p0.act == ACT_GEGLU else list(range(1, 70))
+        tiles = [1, 3, 5, 6, 7, 9, 11, 12, 13, 15, 17, 18, 21, 22, 24, 25, 26, 27, 30, 31, 32, 35, 36, 38, 40] if p0.act == ACT_GEGLU else list(ALL_TILES)
         if p0.act == ACT_GEGLU:
             tiles += [45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 57, 58, 59, 60, 61, 62, 63, 65, 66, 68, 69]
         if args.tiles:

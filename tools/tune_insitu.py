@@ -24,6 +24,7 @@ sys.path.insert(0, ROOT)
 from bench import expert_mask, fixed_half_mask, ones_mask  # noqa: E402
 from diffusion_pruning_amd import ops  # noqa: E402
 from diffusion_pruning_amd.unet import UNet2DConditionModelGated, UNet2DConditionModelPruned  # noqa: E402
+from tests import tiles as tile_table  # noqa: E402
 
 dev = torch.device("cuda:0")
 
@@ -114,7 +115,8 @@ def main():
         key = ops.key_of(p)
         s = shapes.setdefault(key, {"count": 0, "flops": rec["flops"], "params": p})
         s["count"] += 1
-    LEAN_TILES = (12, 18, 25, 49, 9, 15, 24, 51, 11, 17, 26, 53)
+    # one id per lean linear instantiation (csrc/conv_gemm_tiles.h): the rings deeper than 4 share the 4-stage kernel
+    LEAN_TILES = tile_table.ids(lambda t: t.lin and t.stages <= 4)
     order = sorted(shapes, key=lambda k: -shapes[k]["flops"] * shapes[k]["count"] ** 0.5)
     if args.lean:
         order = [k for k in order if ops.parse_key(k)[3] == 1 and ops.parse_key(k)[4] == 1 and ops.parse_key(k)[0] >= 256]
