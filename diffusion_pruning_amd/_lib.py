@@ -270,6 +270,35 @@ class LossTermsParams(Structure):
     ]
 
 
+class LossStageTerm(Structure):
+    _fields_ = [
+        ("a", c_void_p), ("lda", c_int64), ("b", c_void_p), ("ldb", c_int64),
+        ("rows", c_int64), ("rows_per_sample", c_int64),
+        ("C", c_int32), ("a_f32", c_int32), ("b_f32", c_int32), ("group", c_int32),
+        ("scale", c_float), ("weighted", c_int32),
+    ]
+
+
+class LossStageGrad(Structure):
+    _fields_ = [("grad_out", c_void_p), ("ldg", c_int64), ("term0", c_int32), ("term1", c_int32)]
+
+
+LOSS_STAGE_MAX_B = 1024
+
+
+class LossStageParams(Structure):
+    _fields_ = [
+        ("terms", LossStageTerm * LOSS_TERMS_MAX),
+        ("n_terms", c_int32), ("n_groups", c_int32),
+        ("group_coef", c_float * LOSS_TERMS_MAX), ("group_div", c_float * LOSS_TERMS_MAX),
+        ("valid", c_void_p), ("w", c_void_p),
+        ("partial", c_void_p), ("out", c_void_p), ("sample_out", c_void_p),
+        ("grads", LossStageGrad * LOSS_TERMS_MAX),
+        ("n_grads", c_int32), ("reserved", c_int32),
+        ("g", c_void_p),
+    ]
+
+
 class GroupNormBwdParams(Structure):
     _fields_ = [
         ("x", c_void_p), ("ldx", c_int64), ("dy", c_void_p), ("lddy", c_int64), ("dx", c_void_p), ("lddx", c_int64),
@@ -638,6 +667,11 @@ EXPORTS = [
     ("aptp_loss_terms_nblocks", c_int, [POINTER(LossTermsParams)]),
     ("aptp_loss_terms_scratch_floats", c_int, [POINTER(LossTermsParams)]),
     ("aptp_loss_terms", c_int, [POINTER(LossTermsParams), c_void_p]),
+    ("aptp_loss_stage_nblocks", c_int, [POINTER(LossStageParams)]),
+    ("aptp_loss_stage_scratch_floats", c_int, [POINTER(LossStageParams)]),
+    ("aptp_loss_stage", c_int, [POINTER(LossStageParams), c_void_p]),
+    ("aptp_loss_stage_bwd_nblocks", c_int, [POINTER(LossStageParams)]),
+    ("aptp_loss_stage_bwd", c_int, [POINTER(LossStageParams), c_void_p]),
     ("aptp_groupnorm_bwd", c_int, [POINTER(GroupNormBwdParams), c_void_p]),
     ("aptp_layernorm_bwd", c_int, [POINTER(LayerNormBwdParams), c_void_p]),
     ("aptp_attention_bwd", c_int, [POINTER(AttentionBwdParams), c_void_p]),

@@ -262,6 +262,30 @@ def mse(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return MseFn.apply(a, b)
 
 
+class LossStageFn(Function):
+    """total = ops.LossStage(...).run()[G] as ONE autograd node: the inputs are the stage's `grad_inputs` (the prediction and the
+    student's block activations), the output is the total, and backward hands every gradient back from the stage's one launch.
+    Targets, teacher tensors, weights and the valid mask are operands of the stage only: they receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, stage, *inputs):
+        srcs = stage.grad_inputs
+        assert len(inputs) == len(srcs) and all(x is s for x, s in zip(inputs, srcs)), \
+            "LossStageFn: the inputs are the stage's grad_inputs, in its order"
+        ctx.stage = stage
+        return stage.run()[stage.n_groups].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = ctx.stage.backward(g.to(torch.float32))
+        return (None, *[gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[1:])])
+
+
+def loss_stage(stage) -> torch.Tensor:
+    """the total of an ops.LossStage with the gradient flowing into its first operands"""
+    return LossStageFn.apply(stage, *stage.grad_inputs)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Fine-tuning variants (SURVEY a20): the same ops with WEIGHT gradients.  The trainable tensors are the fp32 masters in
 # diffusers' layout; a pruned expert computes on compacted packs, so parameter gradients are produced in the compact

@@ -21,7 +21,7 @@ from ._lib import ACT_GELU, AttentionCausalParams, TokenEmbedParams  # noqa: F40
 from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
-from ._lib import GuidedStepParams, LossTermsParams, PhiloxNormalParams, TrainNoiseParams
+from ._lib import GuidedStepParams, LossStageParams, LossTermsParams, PhiloxNormalParams, TrainNoiseParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -1844,19 +1844,7 @@ class LossTerms:
             q = p.terms[i]
             if t.per_sample:
                 B = a.shape[0]
-                order = (0,) + tuple(d + 1 for d in _mse_order(a[0]))       # the samples, each in the order ops.mse(a[i], b[i]) walks
-                ap, bp = a.permute(order), b.permute(order)
-                v = self._pair(ap[0], bp[0], stage=False)
-                ok = v is not None
-                for s in range(1, B if ok else 0):         # sample s lies rows * ld elements behind sample s - 1, in the same view?
-                    vs = self._pair(ap[s], bp[s], stage=False)
-                    ok = ok and vs is not None and vs[2:] == v[2:] \
-                        and vs[0].data_ptr() == v[0].data_ptr() + s * v[2] * v[4] * a.element_size() \
-                        and vs[1].data_ptr() == v[1].data_ptr() + s * v[2] * v[5] * b.element_size()
-                if not ok:                                  # stage both whole batches: sample s = rows s * rows .. of the staging
-                    ap, bp = self._stage(ap), self._stage(bp)
-                    v = self._pair(ap[0], bp[0], stage=False)
-                a2, b2, rows, C, lda, ldb = v
+                _, ap, bp, (a2, b2, rows, C, lda, ldb) = self._per_sample_pair(a, b)
                 assert weights is not None and weights.dtype == torch.float32 and weights.is_contiguous() \
                     and weights.numel() >= B and weights.device == a.device, "LossTerms: weights = fp32 [B] on the operands' device"
                 q.rows, q.rows_per_sample, self.n_samples = rows * B, rows, B
@@ -1895,6 +1883,25 @@ class LossTerms:
             self.copies.append((self._staged[key], src))
         return self._staged[key]
 
+    def _per_sample_pair(self, a: torch.Tensor, b: torch.Tensor):
+        """the view of a per-sample term: (order, a permuted, b permuted, _pair of sample 0), every sample in the order
+        ops.mse(a[i], b[i]) walks and sample s lying s * rows rows behind sample 0 -- in place where the operands allow it, else
+        both whole batches are staged"""
+        B = a.shape[0]
+        order = (0,) + tuple(d + 1 for d in _mse_order(a[0]))
+        ap, bp = a.permute(order), b.permute(order)
+        v = self._pair(ap[0], bp[0], stage=False)
+        ok = v is not None
+        for s in range(1, B if ok else 0):         # sample s lies rows * ld elements behind sample s - 1, in the same view?
+            vs = self._pair(ap[s], bp[s], stage=False)
+            ok = ok and vs is not None and vs[2:] == v[2:] \
+                and vs[0].data_ptr() == v[0].data_ptr() + s * v[2] * v[4] * a.element_size() \
+                and vs[1].data_ptr() == v[1].data_ptr() + s * v[2] * v[5] * b.element_size()
+        if not ok:                                  # stage both whole batches: sample s = rows s * rows .. of the staging
+            ap, bp = self._stage(ap), self._stage(bp)
+            v = self._pair(ap[0], bp[0], stage=False)
+        return order, ap, bp, v
+
     def _pair(self, a: torch.Tensor, b: torch.Tensor, stage: bool):
         """_mse_operands for a pair already permuted into the first operand's memory order: (a2, b2, rows, C, lda, ldb) with the
         same row shapes.  Where _mse_operands would copy an operand, `stage` puts a staging tensor in its place; without
@@ -1929,6 +1936,143 @@ def loss_terms(terms, group_coef, weights: Optional[torch.Tensor] = None, runnin
     """one-off LossTerms(...).run(): (out [G + 1], per-sample means of the weighted term or None)"""
     lt = LossTerms(terms, group_coef, weights, running, group_div)
     return lt.run(), lt.sample_out
+
+
+class LossStage(LossTerms):
+    """The loss stage of a TRAINING step whose batch may be short (csrc/loss_stage.hip): every term per sample, a 0 / 1 mask over
+    the samples, the mean over the samples present, and every gradient from one launch.
+
+    terms: LossTerm objects or (a, b, group[, scale[, per_sample]]) tuples, at most 16, all [B, ...] with the same B <= 1024.
+    Every term is taken per sample here; `per_sample=True` marks the terms that use `weights` (the min-SNR term), the others
+    have weight 1.  The views are the ones ops.mse(a[i], b[i]) chooses (LossTerms' rules, its staging included), so every unit
+    has ops.mse's bits.  valid: fp32 [B] of 0 and 1 in any pattern (None: all ones); weights: fp32 [B].
+      term_t = (1/n) sum_b valid[b] * w_or_1[b] * mse(a_t[b], b_t[b]),  n = sum_b valid[b];  groups and total as in LossTerms
+      out = [G + 2]: the groups, the total, n.  n = 0: zeros.  Samples that are not valid are skipped, whatever their rows hold.
+    run() is the staging copies and three launches; backward(g) ONE launch that writes the gradient of `g * total` w.r.t. every
+    distinct first operand (a tensor that is the first operand of two terms -- the prediction of the diffusion and of the
+    distillation term -- gets one gradient, not two to be summed); rows of samples that are not valid are written as zeros.
+    Everything either reads at launch time -- valid, weights, n, g -- is device memory: both are safe to capture and replay while
+    the operands stay where they are.  `grad_inputs` are the first operands in the order of `backward`'s list."""
+
+    def __init__(self, terms, group_coef, weights: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None,
+                 group_div=None, dense_grads: bool = True):
+        lib = _lib.load()
+        terms = [t if isinstance(t, LossTerm) else LossTerm(*t) for t in terms]
+        assert 1 <= len(terms) <= _lib.LOSS_TERMS_MAX, f"LossStage takes 1..{_lib.LOSS_TERMS_MAX} terms"
+        G = len(group_coef)
+        assert 1 <= G <= _lib.LOSS_TERMS_MAX
+        p = LossStageParams()
+        p.n_terms, p.n_groups = len(terms), G
+        for g in range(G):
+            p.group_coef[g] = float(group_coef[g])
+            p.group_div[g] = float(group_div[g]) if group_div is not None else 0.0
+        dev, B = terms[0].a.device, int(terms[0].a.shape[0])
+        assert 1 <= B <= _lib.LOSS_STAGE_MAX_B, f"LossStage: 1..{_lib.LOSS_STAGE_MAX_B} samples (got {B})"
+        if valid is None:
+            valid = torch.ones(B, dtype=torch.float32, device=dev)
+        for name, v in (("valid", valid), ("weights", weights)):
+            assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == B and v.device == dev), \
+                f"LossStage: {name} = fp32 [B] on the operands' device"
+        self._keep, self.n_samples = [weights, valid], B
+        self._staged, self.copies = {}, []
+        self.items, by_a = [], {}                          # gradient items: one per distinct first-operand view
+        for i, t in enumerate(terms):
+            a, b = t.a.detach(), t.b.detach()
+            assert a.shape == b.shape and a.is_cuda and b.device == a.device and a.dim() >= 2 and a.shape[0] == B, \
+                "LossStage: operands are [B, ...] pairs of one shape"
+            assert a.dtype in (torch.bfloat16, torch.float32) and b.dtype in (torch.bfloat16, torch.float32)
+            assert not t.per_sample or weights is not None, "LossStage: a per_sample term needs weights"
+            order, ap, bp, (a2, b2, rows, C, lda, ldb) = self._per_sample_pair(a, b)
+            q = p.terms[i]
+            q.a, q.lda, q.b, q.ldb, q.C = a2.data_ptr(), lda, b2.data_ptr(), ldb, C
+            q.rows, q.rows_per_sample = rows * B, rows
+            q.a_f32, q.b_f32 = int(a.dtype == torch.float32), int(b.dtype == torch.float32)
+            q.group, q.scale, q.weighted = int(t.group), float(t.scale), int(bool(t.per_sample))
+            self._keep += [a, b, ap, bp, a2, b2]
+            key = (a2.data_ptr(), lda, rows, C, a.dtype)
+            item = by_a.get(key)
+            if item is None:
+                assert all(it["src"] is not t.a for it in self.items), \
+                    "LossStage: one tensor is read through two different views as a first operand"
+                item = by_a[key] = dict(src=t.a, order=order, shape=tuple(ap.shape), dtype=a.dtype, rows=rows * B, C=C, lda=lda, terms=[])
+                self.items.append(item)
+            assert len(item["terms"]) < 2, "LossStage: a first operand appears in at most two terms"
+            item["terms"].append(i)
+        p.valid, p.w = valid.data_ptr(), _ptr(weights)
+        n_scratch = lib.aptp_loss_stage_scratch_floats(ctypes.byref(p))
+        if n_scratch <= 0:
+            _lib.check(lib.aptp_loss_stage(ctypes.byref(p), None), "aptp_loss_stage")      # (refuses the table with its reason)
+        self.n_groups, self.nblocks = G, lib.aptp_loss_stage_nblocks(ctypes.byref(p))
+        self.partial = self._alloc(n_scratch, dev)
+        self.out = self._alloc(G + 2, dev)
+        self.sample_out = self._alloc(B, dev)
+        p.partial, p.out, p.sample_out = self.partial.data_ptr(), self.out.data_ptr(), self.sample_out.data_ptr()
+        self.valid, self.weights, self.running = valid, weights, None
+        self.dense_grads, self.grads, self._grad_bufs, self._g = bool(dense_grads), None, [], None
+        self._p, self._lib = p, lib
+
+    @staticmethod
+    def _alloc(n: int, device) -> torch.Tensor:
+        return scratch._alloc(n, torch.float32, device, zero=False)
+
+    @staticmethod
+    def _alloc_grad(n: int, dtype, device) -> torch.Tensor:
+        return scratch._alloc(n, dtype, device, zero=False)
+
+    @property
+    def grad_inputs(self):
+        return [it["src"] for it in self.items]
+
+    @property
+    def total(self) -> torch.Tensor:
+        return self.out[self.n_groups]
+
+    @property
+    def n_valid(self) -> torch.Tensor:
+        """fp32 device scalar: the number of samples the last run() counted"""
+        return self.out[self.n_groups + 1]
+
+    def run(self) -> torch.Tensor:
+        """the staging copies (none for operands ops.mse reads in place) and three launches on the current stream; returns `out`
+        ([G + 2]: the groups, their weighted sum, n), which the next run() overwrites"""
+        for dst, src in self.copies:
+            dst.copy_(src)
+        _lib.check(self._lib.aptp_loss_stage(ctypes.byref(self._p), _stream()), "aptp_loss_stage")
+        return self.out
+
+    @property
+    def units(self) -> torch.Tensor:
+        """fp32 [n_terms, B] view of the scratch: mean((a_t[b] - b_t[b])^2) as the last run() left it, samples that are not valid
+        included (whatever their rows gave)"""
+        return self.partial[self.nblocks:self.nblocks + self._p.n_terms * self.n_samples].view(self._p.n_terms, self.n_samples)
+
+    def _build_grads(self):
+        """the gradient buffers, allocated once: rows of C elements at pitch C (dense_grads) or at the operand's pitch, handed
+        out in the first operand's shape and memory order"""
+        p, self.grads = self._p, []
+        p.n_grads = len(self.items)
+        for i, it in enumerate(self.items):
+            ld = it["C"] if self.dense_grads else it["lda"]
+            buf = self._alloc_grad(it["rows"] * ld, it["dtype"], self.out.device)
+            self._grad_bufs.append(buf)
+            q = p.grads[i]
+            q.grad_out, q.ldg = buf.data_ptr(), ld
+            q.term0, q.term1 = it["terms"][0], (it["terms"][1] if len(it["terms"]) > 1 else -1)
+            inv = [0] * len(it["order"])
+            for j, d in enumerate(it["order"]):
+                inv[d] = j
+            self.grads.append(buf.view(it["rows"], ld)[:, :it["C"]].view(it["shape"]).permute(inv))
+
+    def backward(self, g: torch.Tensor):
+        """ONE launch after run(): the gradients of g * total w.r.t. `grad_inputs`, in that order, each in its operand's dtype, shape
+        and memory order; the same tensors on every call.  g: fp32 device scalar."""
+        assert g.is_cuda and g.dtype == torch.float32 and g.numel() == 1, "LossStage.backward: g is an fp32 device scalar"
+        if self.grads is None:
+            self._build_grads()
+        self._g = g.detach().reshape(1)
+        self._p.g = self._g.data_ptr()
+        _lib.check(self._lib.aptp_loss_stage_bwd(ctypes.byref(self._p), _stream()), "aptp_loss_stage_bwd")
+        return self.grads
 
 
 def fold_rows(partials: torch.Tensor, n_rows: int, C: int, out: Optional[torch.Tensor] = None,

@@ -392,6 +392,37 @@ def _stage_batch(st: dict, batch) -> None:
             st[k].copy_(batch[k])
 
 
+def _stage_short_batch(st: dict, batch, data_parallel: bool = False) -> int:
+    """_stage_batch for a batch of 0 <= n <= B rows (B: the rows of the static tensors): rows [0, n) are the batch, rows [n, B)
+    are filled with row 0 of THIS batch -- finite whenever the batch is, and never what an earlier batch left there -- and
+    st["valid"] becomes 1 for the first n rows and 0 behind them, or the batch's own "valid" vector where it carries one (samples
+    masked without compacting them).  No host sync.  Returns n; nothing is staged for n = 0."""
+    if not isinstance(batch, dict):
+        batch = dict(zip(_BATCH_KEYS, batch))
+    B, n = int(st["valid"].shape[0]), int(batch[_BATCH_KEYS[0]].shape[0])
+    if n > B:
+        raise ValueError(f"a batch of {n} samples does not fit the step captured for {B}")
+    if n == 0:
+        if data_parallel:
+            raise ValueError("an empty batch under data_parallel=True: a rank cannot leave the gradient exchange; drop the batch on every rank")
+        return 0
+    with torch.no_grad():
+        for k in _BATCH_KEYS:
+            assert int(batch[k].shape[0]) == n, f"batch[{k!r}] has {int(batch[k].shape[0])} rows, {_BATCH_KEYS[0]} has {n}"
+            st[k][:n].copy_(batch[k])
+            if n < B:
+                st[k][n:].copy_(batch[k][0:1])           # (broadcast over the missing rows)
+        given = batch.get("valid")
+        if given is not None:
+            assert int(given.shape[0]) == n, "batch['valid'] has one entry per sample of the batch"
+            st["valid"][:n].copy_(given)
+        else:
+            st["valid"][:n].fill_(1.0)
+        if n < B:
+            st["valid"][n:].zero_()
+    return n
+
+
 @contextlib.contextmanager
 def _launch_log_off():
     """ops.LAUNCH_LOG (bench.py: the contractions of ONE step, re-timed for the family roofline) is filled by an eager warm-up pass,
@@ -1334,6 +1365,20 @@ class FineTunerStep:
         loss, diff_loss, distillation_loss, block_loss = self._losses(model_pred, full_pred, w, target)
         return {"loss": loss, "diff_loss": diff_loss.clone(), "distillation_loss": distillation_loss, "block_loss": block_loss}
 
+    def _loss_stage(self, model_pred, full_pred, w, target, valid) -> "ops.LossStage":
+        """_losses as ONE ops.LossStage over the samples `valid` marks: group 0 the diffusion term (min-SNR weighted unless
+        snr_gamma is None), group 1 the mean of the block terms (skipped without a block weight), group 2 the output
+        distillation, with _losses' coefficients; every term a per-sample mean, averaged over the samples present"""
+        cfg = self.cfg
+        weighted = cfg.snr_gamma is not None
+        terms = [ops.LossTerm(model_pred, target.detach(), 0, 1.0, weighted)]
+        n_blocks = len(self.acts_s) if cfg.block_weight > 0 else 0
+        if n_blocks:
+            terms += [ops.LossTerm(self.acts_s[k], self.acts_t[k].detach(), 1) for k in self.acts_s]
+        terms.append(ops.LossTerm(model_pred, full_pred.detach(), 2))
+        return ops.LossStage(terms, self._group_coef(), weights=w if weighted else None, valid=valid,
+                             group_div=(0.0, float(n_blocks), 0.0))
+
     def _group_coef(self):
         cfg = self.cfg
         return (cfg.diffusion_weight, cfg.block_weight if cfg.block_weight > 0 else 0.0, cfg.distillation_weight)
@@ -1414,15 +1459,24 @@ class GraphedFineTunerStep(FineTunerStep):
     export_ema_() and save_ema_pretrained() read it through a swap of masters and averages.
     max_grad_norm=X: clip_grad_norm_(X) on the device in front of AdamW (ops.GradNorm: two launches); the dict gains
     "grad_norm" and a window whose norm is not finite is skipped like one whose loss is not; log_grad_norm=True: the norm alone.
-    use_8bit_adam=True: both AdamW moments as block-wise 8-bit codes (PackedAdamW(optim_bits=8), csrc/optim8.hip)."""
+    use_8bit_adam=True: both AdamW moments as block-wise 8-bit codes (PackedAdamW(optim_bits=8), csrc/optim8.hip).
+    short_batches=True: capture(batch) fixes the LARGEST batch; train_step then takes any 0 <= n <= B samples (or a full batch
+    with a "valid" vector) through the same graphs: the losses are means over the samples present, the dict gains "n_valid" and
+    "skipped", and an empty batch touches nothing."""
 
     def __init__(self, student, teacher, cfg: Optional[FinetuneLossConfig] = None, schedule: Optional[NoiseSchedule] = None,
                  lr: float = 1e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  data_parallel: bool = False, bucket_bytes: int = 256 << 20, reduce_mode: str = "rs_ag", nan_guard: bool = True,
                  accumulation_steps: int = 1, lr_warmup_steps: int = 0, ema=None, max_grad_norm: Optional[float] = None,
-                 log_grad_norm: bool = False, use_8bit_adam: bool = False):
+                 log_grad_norm: bool = False, use_8bit_adam: bool = False, short_batches: bool = False):
         super().__init__(student, teacher, cfg, schedule)
         assert int(accumulation_steps) >= 1 and lr_warmup_steps >= 0
+        # short_batches: the captured batch size is a MAXIMUM; train_step takes 0 <= n <= B samples (the loader drops samples
+        # it cannot decode and ends every epoch on a short batch).  The loss terms become ONE autograd node over the fused
+        # masked loss stage (ops.LossStage, csrc/loss_stage.hip) whose mean runs over the samples present; the rows behind them
+        # are finite padding with loss weight, hence gradient, exactly zero.  False: nothing is allocated or launched and the
+        # captured graphs are the ones without the argument.  DESIGN 6x.
+        self.short_batches = bool(short_batches)
         # use_8bit_adam (training.optim.use_8bit_adam of the reference's configs): PackedAdamW(optim_bits=8) -- block-wise 8-bit
         # moments for the tensors of at least 4096 elements, a second launch for them; parameters, operands and gradients keep
         # their type and address, so everything else of the step is as without it.  DESIGN 6u.
@@ -1468,6 +1522,8 @@ class GraphedFineTunerStep(FineTunerStep):
         if self.schedule.alphas_cumprod.device != dev:
             self.schedule.alphas_cumprod = self.schedule.alphas_cumprod.to(dev)
         st["snr_w"] = _min_snr_weights(self.cfg, self.schedule, st["timesteps"])
+        if self.short_batches:
+            st["valid"] = torch.ones(int(st["noisy_latents"].shape[0]), dtype=torch.float32, device=dev)
         self.trainer.materialize(st["noisy_latents"], st["timesteps"], st["encoder_hidden_states"])
         # the block-output hooks kept the materialising forward's autograd graph (and through it every AccumulateGrad node)
         # alive: drop it before the warm-up builds the graphs the capture will re-use
@@ -1503,6 +1559,12 @@ class GraphedFineTunerStep(FineTunerStep):
             self.acts_s.update(student_acts)
             self.acts_t.clear()
             self.acts_t.update(teacher_acts)
+            if self.short_batches:
+                stage = self._loss_stage(pred, full_pred, st["snr_w"], st["target"], st["valid"])
+                AG.loss_stage(stage).backward()
+                o = stage.out                    # [diffusion, block, distillation, total, n]
+                out.update(total=o[3], diff=o[0], dist=o[2], blk=o[1], n_valid=o[4], stage=stage)
+                return
             total, diff, dist_l, blk = self._losses(pred, full_pred, st["snr_w"], st["target"])
             total.backward()
             out.update(total=total.detach(), diff=diff, dist=dist_l, blk=blk)
@@ -1759,7 +1821,14 @@ class GraphedFineTunerStep(FineTunerStep):
         assert cap is not None, "call capture(batch) first"
         if self.ema is not None and self.ema.swapped:
             raise RuntimeError("GraphedFineTunerStep.train_step: the masters hold the EMA (swap_() back first): a step would train it")
-        _stage_batch(cap["st"], batch)
+        if self.short_batches:
+            if _stage_short_batch(cap["st"], batch, self._dp_graphed) == 0:
+                # nothing to learn from: no replay, no accumulation, no optimizer; the window stays where it is
+                zero = torch.zeros((), dtype=torch.float32, device=cap["st"]["valid"].device)
+                return {"loss": zero, "diff_loss": zero.clone(), "distillation_loss": zero.clone(), "block_loss": zero.clone(),
+                        "applied": False, "accum_index": self.accum_index, "n_valid": zero.clone(), "skipped": True}
+        else:
+            _stage_batch(cap["st"], batch)
         main = torch.cuda.current_stream()       # (the min-SNR weights are computed from the staged timesteps inside g_teacher)
         side = cap["side"] if self.overlap_teacher else main
         side.wait_stream(main)                   # (the batch copies above)
@@ -1830,4 +1899,6 @@ class GraphedFineTunerStep(FineTunerStep):
             # the norm of the mean gradient the optimizer saw, before clipping (device scalar; NaN-free only when the window
             # was applied: compare ops.GradNorm.verdict); None inside an open window
             out["grad_norm"] = grad_norm
+        if self.short_batches:
+            out["n_valid"], out["skipped"] = cap["n_valid"].clone(), False          # (device scalar: the samples the losses average)
         return out

@@ -887,6 +887,62 @@ int aptp_loss_terms_nblocks(const AptpLossTermsParams* p);          /* workgroup
 int aptp_loss_terms_scratch_floats(const AptpLossTermsParams* p);   /* those partials plus one value per term / sample */
 int aptp_loss_terms(const AptpLossTermsParams* p, aptp_stream_t stream);
 
+/* The loss stage of a TRAINING step whose batch may be short (FineTuner.step, pdm/training/trainer.py:1736-1763, on a batch
+ * from which collate_fn dropped samples, pdm/utils/data_utils.py:175-179): every term per sample, a 0 / 1 mask over the
+ * samples, the mean over the samples PRESENT, and every gradient from one launch.
+ * A term is AptpLossTerm's (operand rules of AptpMseParams, a dtype flag per operand) with rows_per_sample > 0 required:
+ * B = rows / rows_per_sample is the same for all terms, 1 <= B <= APTP_LOSS_STAGE_MAX_B.  Unit (t, b) = mean((a - b)^2) over
+ * sample b of term t has the workgroups, the grid stride and the folds aptp_mse gives that sample's view: the same bits.
+ *   valid: fp32 [B] of 0 and 1 in any pattern; w: fp32 [B], may be null when no term has `weighted` set
+ *   n        = sum_b valid[b]
+ *   term_t   = (1/n) sum_b valid[b] * (weighted ? w[b] : 1) * unit[t][b], in sample order; samples with valid[b] = 0 are
+ *              SKIPPED, not multiplied by 0: what their rows hold (NaN included) reaches no output
+ *   out[g]   = (sum over the terms of group g, in index order, of term * scale), / group_div[g] where that is not 0
+ *   out[G]   = sum_g group_coef[g] * out[g];  out[G + 1] = n      (out: fp32 [G + 2]; n = 0: all of it 0)
+ *   sample_out (optional): fp32 [B], unit[t][b] of the first weighted term (term 0 without one), 0 where valid[b] = 0
+ * aptp_loss_stage: three launches (partial, finish, combine), no atomics; partial: fp32 [aptp_loss_stage_scratch_floats(p)].
+ * aptp_loss_stage_bwd: ONE launch for the gradients w.r.t. the first operands.  Gradient item i names one or two terms with
+ * the SAME first operand (pointer, lda, rows, C, dtype; term1 = -1: one term) and receives
+ *   grad_out[b, e] = c_0[b] * (a - b_0) + c_1[b] * (a - b_1),
+ *   c_t[b] = g[0] * 2 * group_coef[group_t] * scale_t * valid[b] * (weighted_t ? w[b] : 1) / (n * E_t * gdiv_t)
+ * (E_t elements per sample; gdiv_t = group_div[group_t], 1 where that is 0; g: fp32 device scalar, the upstream gradient;
+ * c_t is formed in fp64 and rounded once).  grad_out has a's element type, rows of C elements at pitch ldg (0 = lda).  Rows of
+ * samples with valid[b] = 0 are WRITTEN as zeros without reading the operands; n = 0 writes zeros everywhere.  n is read from
+ * out[G + 1]: call after aptp_loss_stage on the same block.  Nothing outside the C columns of the B * rows_per_sample rows is
+ * written.
+ * APTP_EINVAL and nothing launched for: null pointers, n_terms / n_groups / n_grads outside 1..16, C no positive multiple of
+ * 8, pitches below C or no multiples of 8, operands or grad_out not 16-byte aligned, rows no multiple of rows_per_sample,
+ * differing B, B above APTP_LOSS_STAGE_MAX_B, a weighted term with w null, a group or a term index out of range, two terms
+ * of an item with different first operands. */
+#define APTP_LOSS_STAGE_MAX_B 1024
+typedef struct {
+  const void* a; int64_t lda;
+  const void* b; int64_t ldb;
+  int64_t rows; int64_t rows_per_sample;
+  int32_t C; int32_t a_f32; int32_t b_f32; int32_t group;
+  float scale; int32_t weighted;
+} AptpLossStageTerm;
+typedef struct {
+  void* grad_out; int64_t ldg;
+  int32_t term0; int32_t term1;
+} AptpLossStageGrad;
+typedef struct {
+  AptpLossStageTerm terms[APTP_LOSS_TERMS_MAX];
+  int32_t n_terms; int32_t n_groups;
+  float group_coef[APTP_LOSS_TERMS_MAX];
+  float group_div[APTP_LOSS_TERMS_MAX];
+  const float* valid; const float* w;
+  float* partial; float* out; float* sample_out;
+  AptpLossStageGrad grads[APTP_LOSS_TERMS_MAX];
+  int32_t n_grads; int32_t reserved;
+  const float* g;
+} AptpLossStageParams;
+int aptp_loss_stage_nblocks(const AptpLossStageParams* p);          /* workgroups of the first launch; 0 for a refused table */
+int aptp_loss_stage_scratch_floats(const AptpLossStageParams* p);   /* those partials plus n_terms * B unit values */
+int aptp_loss_stage(const AptpLossStageParams* p, aptp_stream_t stream);
+int aptp_loss_stage_bwd_nblocks(const AptpLossStageParams* p);      /* workgroups of the gradient launch; 0 for a refused table */
+int aptp_loss_stage_bwd(const AptpLossStageParams* p, aptp_stream_t stream);
+
 /* Data-gradient operand from the forward operand of the same contraction (both in packed bf16 layout):
  * dst[c][taps-1-t][n] = src[n][t][c] for n < N, c < C, zero in the rest of dst's [dst_rows][taps][dst_ld] image.
  * (ops.pack_weight_dgrad of the same weights, without going through the diffusers layout.) */

@@ -15,7 +15,12 @@ events around the two launches, median over the timed steps), `ema_bytes` = 12 x
 --adam8bit (graphed mode) keeps both AdamW moments as block-wise 8-bit codes (GraphedFineTunerStep(use_8bit_adam=True),
 csrc/optim8.hip) and adds `optimizer_state_bytes`, `adamw_ms` (the fp32 launch over the small tensors) and `adamw8_ms` (the 8-bit
 launch), HIP events around each, median over the timed steps, with `optimizer_pass_ms` their sum; --optimizer-times adds the same
-fields for the fp32 state (no `adamw8_ms`), for the comparison."""
+fields for the fp32 state (no `adamw8_ms`), for the comparison.
+
+--short-batches (graphed mode) runs the step with GraphedFineTunerStep(short_batches=True) -- the fused masked loss stage, batches of
+up to --batch samples -- and, in the same process, the default step on a second copy of the expert: `short_batches` in the line holds
+both rates (alternating rounds of --steps steps, the faster round of each) and the nodes of both loss-and-backward graphs.
+--valid N hands the switched step batches of N samples (default: the full batch)."""
 import argparse
 import json
 import os
@@ -133,7 +138,13 @@ def main():
                          "optimizer_state_bytes and the optimizer launches' times (HIP events) to the JSON line")
     ap.add_argument("--optimizer-times", action="store_true",
                     help="the same fields without the 8-bit state (graphed mode): what --adam8bit is compared with")
+    ap.add_argument("--short-batches", action="store_true",
+                    help="GraphedFineTunerStep(short_batches=True) (graphed mode), timed against the default step in the same run; adds "
+                         "both rates and the node counts of both loss-and-backward graphs to the JSON line")
+    ap.add_argument("--valid", type=int, default=None, help="with --short-batches: samples per timed batch, 1..--batch (default: all)")
     args = ap.parse_args()
+    assert not args.short_batches or args.mode == "graphed", "--short-batches belongs to the graphed step"
+    assert args.valid is None or (args.short_batches and 1 <= args.valid <= args.batch), "--valid N needs --short-batches and 1 <= N <= --batch"
     args.optimizer_times = args.optimizer_times or args.adam8bit
     assert not args.optimizer_times or args.mode == "graphed", "--adam8bit / --optimizer-times belong to the graphed step"
     assert args.validate == 0 or args.mode == "graphed", "--validate belongs to the graphed step"
@@ -159,13 +170,27 @@ def main():
     student.to(dev)
     student.prune(expert_mask(st, args.expert, dev))
     batch = synthetic_batch(args.batch, 64, dev)
-    n_train, timers = None, {}
+    n_train, timers, base = None, {}, None
+    timed_batch = batch if args.valid is None else {k: v[:args.valid].clone() for k, v in batch.items()}
     if args.mode == "graphed":
+        from diffusion_pruning_amd import graph_utils
         from diffusion_pruning_amd.train_step import GraphedFineTunerStep
-        step = GraphedFineTunerStep(student, teacher, lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup,
-                                    **({"ema": True} if args.ema else {}), **({"use_8bit_adam": True} if args.adam8bit else {}),
-                                    **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}))
+        kw = dict(lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup,
+                  **({"ema": True} if args.ema else {}), **({"use_8bit_adam": True} if args.adam8bit else {}),
+                  **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}))
+        if args.short_batches:
+            # the default step on a second copy of the same expert, for the comparison; graphs kept so that their nodes can be counted
+            graph_utils.KEEP_GRAPHS = True
+            student2 = UNet2DConditionModelPruned()
+            student2.load_state_dict(teacher.state_dict())
+            student2.to(dev)
+            student2.prune(expert_mask(st, args.expert, dev))
+            base = GraphedFineTunerStep(student2, teacher, **kw)
+            base.capture(batch, offload_masters=True)
+            kw["short_batches"] = True
+        step = GraphedFineTunerStep(student, teacher, **kw)
         step.capture(batch, offload_masters=True)
+        graph_utils.KEEP_GRAPHS = False
         opt, n_train = None, step.trainer.n_trainable()
         if args.max_grad_norm is not None:
             timers = {"grad_norm_ms": LaunchTimer(step.optimizer.grad_norm, "run")}
@@ -185,16 +210,36 @@ def main():
         step = FineTunerStep(student, teacher)
         opt = torch.optim.AdamW([p for p in student.parameters() if p.requires_grad], lr=1e-5, fused=True)
     for _ in range(args.warmup):
-        out = step.train_step(opt, batch)
+        out = step.train_step(opt, timed_batch)
     torch.cuda.synchronize()
     for t in timers.values():
         t.on = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        out = step.train_step(opt, batch)
+        out = step.train_step(opt, timed_batch)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     peak_train, val = torch.cuda.max_memory_allocated(), {}
+    if base is not None:
+        for t in timers.values():
+            t.on = False
+
+        def per_step(s, b):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                s.train_step(None, b)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t1) / args.steps
+        for _ in range(args.warmup):
+            base.train_step(None, batch)
+        rounds = [(per_step(base, batch), per_step(step, timed_batch)) for _ in range(2)]
+        dt_off, dt_on = min(r[0] for r in rounds), min(r[1] for r in rounds)
+        val["short_batches"] = {"valid": args.batch if args.valid is None else args.valid, "steps_per_s": round(1.0 / dt_on, 3),
+                                "default_steps_per_s": round(1.0 / dt_off, 3), "ratio_to_default": round(dt_off / dt_on, 4),
+                                "loss_bwd_graph_nodes": step.graph_nodes()["student_bwd"],
+                                "default_loss_bwd_graph_nodes": base.graph_nodes()["student_bwd"],
+                                "n_valid_last": float(out["n_valid"])}
     if args.ema:
         # both passes stream the same tensors in the same geometry: 30 B per element (AdamW: p, g, m, v read; p, m, v and the
         # bf16 operand of a weight written) against 12 B (EMA: p, ema read; ema written)
