@@ -207,6 +207,17 @@ class GroupAdamWParams(Structure):
                 ("gate_dev", c_void_p), ("items_host", c_void_p), ("grad_scale_dev", c_void_p)]
 
 
+# kinds of aptp_lr_schedule, by the names of the recipes' `lr_scheduler` (transformers.optimization.SchedulerType)
+LR_KINDS = {"constant": 0, "constant_with_warmup": 1, "linear": 2, "cosine": 3, "cosine_with_restarts": 4, "polynomial": 5}
+
+
+class LrScheduleParams(Structure):
+    _fields_ = [("kind", c_int32), ("warmup_steps", c_int32), ("training_steps", c_int32), ("n", c_int32),
+                ("num_cycles", ctypes.c_double), ("power", ctypes.c_double), ("lr_end", ctypes.c_double), ("lr_init", ctypes.c_double),
+                ("count_dev", c_void_p), ("base_dev", c_void_p), ("out_dev", c_void_p), ("out_stride", c_int32),
+                ("mult_dev", c_void_p)]
+
+
 class GradNormItem(Structure):
     _fields_ = [("g", c_void_p), ("n", c_int64)]
 
@@ -653,8 +664,11 @@ EXPORTS = [
     ("aptp_adamw_blocks", c_int, [c_int64]),
     ("aptp_adamw_many", c_int, [POINTER(AdamWParams), c_void_p]),
     ("aptp_adamw_many_scaled", c_int, [POINTER(AdamWParams), c_void_p, c_void_p]),
+    ("aptp_adamw_many_lr", c_int, [POINTER(AdamWParams), c_void_p, c_void_p, c_void_p]),
     ("aptp_adamw8_blocks", c_int, [c_int64]),
     ("aptp_adamw8_many", c_int, [POINTER(AdamW8Params), c_void_p, c_void_p]),
+    ("aptp_adamw8_many_lr", c_int, [POINTER(AdamW8Params), c_void_p, c_void_p, c_void_p]),
+    ("aptp_lr_schedule", c_int, [POINTER(LrScheduleParams), c_void_p]),
     ("aptp_ema_many", c_int, [POINTER(EmaParams), c_void_p]),
     ("aptp_group_adamw_blocks", c_int, [c_int64]),
     ("aptp_group_adamw", c_int, [POINTER(GroupAdamWParams), c_void_p]),

@@ -24,8 +24,11 @@ struct AdamK {
   float gscale;                                 // gradients are multiplied by this first (1 / world size of a summed exchange)
   float warmup;                                 // 0 = off; else the rate ramps linearly over this many optimizer steps
   const float* gscale_dev;                      // optional device scalar (the clip coefficient of grad_norm.hip): one more factor of gscale
+  const float* lr_dev;                          // LR_DEV only: the rate itself (what aptp_lr_schedule stored); lr and warmup are not read
 };
 
+// LR_DEV: the rate is one more uniform scalar load instead of warmup_lr; the instantiation without it is the kernel as it was
+template <bool LR_DEV>
 __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
   const int b = blockIdx.x;
   const int lo = item_of_block(k.starts, k.n_items, b);
@@ -36,7 +39,8 @@ __global__ __launch_bounds__(256) void adamw_many_kernel(const AdamK k) {
   const AptpAdamWItem it = k.items[lo];
   // the warm-up is counted in optimizer steps.  Uniform; W = 0 leaves lr as passed.  So is the clip: one scalar load, one product.
   const float gscale = k.gscale_dev ? k.gscale * k.gscale_dev[0] : k.gscale;
-  const AdamCoef c = adam_coef(warmup_lr(k.lr, k.step[0], k.warmup), k.wd, k.beta1, k.beta2, k.eps, gscale, k.step[0] + 1.0f);
+  const float lr = LR_DEV ? k.lr_dev[0] : warmup_lr(k.lr, k.step[0], k.warmup);
+  const AdamCoef c = adam_coef(lr, k.wd, k.beta1, k.beta2, k.eps, gscale, k.step[0] + 1.0f);
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   __bf16* sh = (__bf16*)it.shadow;
 #pragma unroll
@@ -73,14 +77,22 @@ extern "C" int aptp_adamw_blocks(int64_t n) { return blocks_of(n); }
 extern "C" int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream) { return aptp_adamw_many_scaled(p, nullptr, stream); }
 
 extern "C" int aptp_adamw_many_scaled(const AptpAdamWParams* p, const float* grad_scale_dev, aptp_stream_t stream) {
+  return aptp_adamw_many_lr(p, grad_scale_dev, nullptr, stream);
+}
+
+extern "C" int aptp_adamw_many_lr(const AptpAdamWParams* p, const float* grad_scale_dev, const float* lr_dev, aptp_stream_t stream) {
   APTP_CHECK(p && p->items_dev && p->starts_dev && p->step_dev && p->n_items >= 1 && p->total_blocks >= 1, "adamw_many: bad arguments");
-  APTP_CHECK(p->lr >= 0.f && p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f && p->eps > 0.f, "adamw_many: hyper-parameters");
+  APTP_CHECK((lr_dev || p->lr >= 0.f) && p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f && p->eps > 0.f, "adamw_many: hyper-parameters");
   APTP_CHECK(p->grad_scale >= 0.f, "adamw_many: grad_scale");
   APTP_CHECK(p->warmup_steps >= 0.f, "adamw_many: warmup_steps");
   APTP_CHECK(((uintptr_t)grad_scale_dev & 3) == 0, "adamw_many: misaligned grad_scale_dev");
+  APTP_CHECK(((uintptr_t)lr_dev & 3) == 0, "adamw_many: misaligned lr_dev");
+  APTP_CHECK(!lr_dev || p->warmup_steps == 0.f, "adamw_many: lr_dev and warmup_steps > 0 (the schedule that writes lr_dev owns the warm-up)");
   AdamK k{p->items_dev, p->starts_dev, p->n_items, p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->step_dev,
-          p->gate_dev, p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->warmup_steps, grad_scale_dev};
-  hipLaunchKernelGGL(adamw_many_kernel, dim3((unsigned)p->total_blocks), dim3(256), 0, (hipStream_t)stream, k);
+          p->gate_dev, p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->warmup_steps, grad_scale_dev, lr_dev};
+  const dim3 grid((unsigned)p->total_blocks), block(256);
+  if (lr_dev) hipLaunchKernelGGL(adamw_many_kernel<true>, grid, block, 0, (hipStream_t)stream, k);
+  else hipLaunchKernelGGL(adamw_many_kernel<false>, grid, block, 0, (hipStream_t)stream, k);
   APTP_LAUNCH_CHECK();
   return APTP_OK;
 }

@@ -23,6 +23,7 @@ struct Adam8K {
   float lr, beta1, beta2, eps, wd;
   const float* step; const float* gate; float gscale; float warmup; const float* gscale_dev;      // as AdamK of optim.hip
   const float* qs; const float* qu;             // signed map (first moment), unsigned map (second moment)
+  const float* lr_dev;                          // LR_DEV only, as AdamK of optim.hip
 };
 
 // a nearest code of x in the ascending map q[0..255] (LDS): the last value <= x by bisection, then the closer of it and its
@@ -55,6 +56,7 @@ __device__ __forceinline__ float4 dequant_quad(const float* q, uint32_t c, float
   return float4{q[c & 255] * absmax, q[(c >> 8) & 255] * absmax, q[(c >> 16) & 255] * absmax, q[c >> 24] * absmax};
 }
 
+template <bool LR_DEV>                          // as adamw_many_kernel of optim.hip
 __global__ __launch_bounds__(256) void adamw8_many_kernel(const Adam8K k) {
   __shared__ float qs[256], qu[256];
   const int b = blockIdx.x;
@@ -64,7 +66,8 @@ __global__ __launch_bounds__(256) void adamw8_many_kernel(const Adam8K k) {
   qu[threadIdx.x] = k.qu[threadIdx.x];
   const AptpAdamW8Item it = k.items[lo];
   const float gscale = k.gscale_dev ? k.gscale * k.gscale_dev[0] : k.gscale;
-  const AdamCoef c = adam_coef(warmup_lr(k.lr, k.step[0], k.warmup), k.wd, k.beta1, k.beta2, k.eps, gscale, k.step[0] + 1.0f);
+  const float lr = LR_DEV ? k.lr_dev[0] : warmup_lr(k.lr, k.step[0], k.warmup);
+  const AdamCoef c = adam_coef(lr, k.wd, k.beta1, k.beta2, k.eps, gscale, k.step[0] + 1.0f);
   const int64_t base = (int64_t)(b - k.starts[lo]) * ELEMS_PER_BLOCK;
   __bf16* sh = (__bf16*)it.shadow;
   const int wave = threadIdx.x / APTP_WAVE;
@@ -140,12 +143,18 @@ __global__ __launch_bounds__(256) void adamw8_many_kernel(const Adam8K k) {
 extern "C" int aptp_adamw8_blocks(int64_t n) { return blocks_of(n); }
 
 extern "C" int aptp_adamw8_many(const AptpAdamW8Params* p, const float* grad_scale_dev, aptp_stream_t stream) {
+  return aptp_adamw8_many_lr(p, grad_scale_dev, nullptr, stream);
+}
+
+extern "C" int aptp_adamw8_many_lr(const AptpAdamW8Params* p, const float* grad_scale_dev, const float* lr_dev, aptp_stream_t stream) {
   APTP_CHECK(p && p->items_dev && p->starts_dev && p->step_dev && p->n_items >= 1 && p->total_blocks >= 1, "adamw8_many: bad arguments");
   APTP_CHECK(p->qmap_signed_dev && p->qmap_unsigned_dev, "adamw8_many: null code map");
-  APTP_CHECK(p->lr >= 0.f && p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f && p->eps > 0.f, "adamw8_many: hyper-parameters");
+  APTP_CHECK((lr_dev || p->lr >= 0.f) && p->beta1 >= 0.f && p->beta1 < 1.f && p->beta2 >= 0.f && p->beta2 < 1.f && p->eps > 0.f, "adamw8_many: hyper-parameters");
   APTP_CHECK(p->grad_scale >= 0.f, "adamw8_many: grad_scale");
   APTP_CHECK(p->warmup_steps >= 0.f, "adamw8_many: warmup_steps");
   APTP_CHECK(((uintptr_t)grad_scale_dev & 3) == 0, "adamw8_many: misaligned grad_scale_dev");
+  APTP_CHECK(((uintptr_t)lr_dev & 3) == 0, "adamw8_many: misaligned lr_dev");
+  APTP_CHECK(!lr_dev || p->warmup_steps == 0.f, "adamw8_many: lr_dev and warmup_steps > 0 (the schedule that writes lr_dev owns the warm-up)");
   APTP_CHECK((((uintptr_t)p->qmap_signed_dev | (uintptr_t)p->qmap_unsigned_dev) & 3) == 0, "adamw8_many: misaligned code map");
   if (p->items_host) {                          // the host's copy of the table: what the kernel will dereference is checked here
     int64_t blocks = 0;
@@ -163,8 +172,10 @@ extern "C" int aptp_adamw8_many(const AptpAdamW8Params* p, const float* grad_sca
   }
   Adam8K k{p->items_dev, p->starts_dev, p->n_items, p->lr, p->beta1, p->beta2, p->eps, p->weight_decay, p->step_dev,
            p->gate_dev, p->grad_scale == 0.f ? 1.0f : p->grad_scale, p->warmup_steps, grad_scale_dev,
-           p->qmap_signed_dev, p->qmap_unsigned_dev};
-  hipLaunchKernelGGL(adamw8_many_kernel, dim3((unsigned)p->total_blocks), dim3(256), 0, (hipStream_t)stream, k);
+           p->qmap_signed_dev, p->qmap_unsigned_dev, lr_dev};
+  const dim3 grid((unsigned)p->total_blocks), block(256);
+  if (lr_dev) hipLaunchKernelGGL(adamw8_many_kernel<true>, grid, block, 0, (hipStream_t)stream, k);
+  else hipLaunchKernelGGL(adamw8_many_kernel<false>, grid, block, 0, (hipStream_t)stream, k);
   APTP_LAUNCH_CHECK();
   return APTP_OK;
 }

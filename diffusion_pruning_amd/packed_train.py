@@ -355,6 +355,126 @@ def adam_state_bytes(sizes, optim_bits: int = 32, min_8bit_size: int = ADAM8_MIN
     return total
 
 
+class LrSchedule:
+    """The curve `lr_scheduler` names in the recipes (training.optim.lr_scheduler -> get_scheduler, pdm/training/trainer.py:376-383)
+    as a function of the count k of APPLIED optimizer steps: the step that follows k applied ones runs at lr * m(k), the first at
+    m(0), and a skipped step does not advance k.  warmup_steps W and training_steps T are optimizer steps (the single-process
+    curve: DESIGN 6n).  The expressions are transformers.optimization's (csrc/lr_schedule.h holds them for the device):
+    constant, constant_with_warmup, linear, cosine (num_cycles, default 0.5), cosine_with_restarts (num_cycles an integer,
+    default 1), polynomial (power, lr_end; lr_init is the OPTIMIZER's default rate, which the library divides by -- the reference
+    builds its optimizers from groups, so torch.optim.AdamW's 1e-3 -- not the rate the curve is applied to).
+    ``multiplier(k)`` is m(k) in host fp64, ``rate(lr, k)`` the fp32 value aptp_lr_schedule stores; ``launch`` is that kernel."""
+
+    KINDS = tuple(_lib.LR_KINDS)
+    NEEDS_T = ("linear", "cosine", "cosine_with_restarts", "polynomial")
+    MAX_STEPS = 1 << 24         # the count is an fp32 scalar: every integer below 2^24 is exact
+
+    def __init__(self, name: str, warmup_steps: int = 0, training_steps: Optional[int] = None, num_cycles=None, power: float = 1.0,
+                 lr_end: float = 1e-7, lr_init: float = 1e-3):
+        name = str(getattr(name, "value", name))
+        if name == "piecewise_constant":
+            raise ValueError("LrSchedule: piecewise_constant is diffusers-only and takes a rule string; it is not built here "
+                             "(DESIGN 6y) -- use one of " + ", ".join(self.KINDS))
+        if name not in _lib.LR_KINDS:
+            raise ValueError(f"LrSchedule: unknown lr_scheduler {name!r}; one of " + ", ".join(self.KINDS))
+        self.name, self.kind = name, _lib.LR_KINDS[name]
+        W = int(warmup_steps)
+        if W != warmup_steps or not 0 <= W < self.MAX_STEPS:
+            raise ValueError("LrSchedule: warmup_steps is an integer in [0, 2^24)")
+        if name in self.NEEDS_T:
+            if training_steps is None:
+                raise ValueError(f"LrSchedule: {name} needs training_steps")
+            T = int(training_steps)
+            if T != training_steps or not 0 <= T < self.MAX_STEPS:
+                raise ValueError("LrSchedule: training_steps is an integer in [0, 2^24)")
+            if T < W or (name == "polynomial" and T == W):
+                raise ValueError(f"LrSchedule: {name} with training_steps {T} and warmup_steps {W} (polynomial divides by T - W)")
+        else:
+            T = 0 if training_steps is None else int(training_steps)
+            if not 0 <= T < self.MAX_STEPS:
+                raise ValueError("LrSchedule: training_steps is an integer in [0, 2^24)")
+        self.warmup_steps, self.training_steps = W, T
+        if num_cycles is None:
+            num_cycles = 1 if name == "cosine_with_restarts" else 0.5
+        if name == "cosine_with_restarts" and int(num_cycles) != num_cycles:
+            raise ValueError("LrSchedule: cosine_with_restarts takes an integer num_cycles")
+        self.num_cycles, self.power, self.lr_end, self.lr_init = float(num_cycles), float(power), float(lr_end), float(lr_init)
+        if name in ("cosine", "cosine_with_restarts") and not self.num_cycles > 0:
+            raise ValueError("LrSchedule: num_cycles must be > 0")
+        if name == "polynomial":
+            if not self.power > 0:
+                raise ValueError("LrSchedule: power must be > 0")
+            if not self.lr_init > self.lr_end:
+                raise ValueError(f"LrSchedule: lr_end ({lr_end}) must be smaller than lr_init ({lr_init}), the optimizer's default rate")
+
+    def as_dict(self):
+        return {"name": self.name, "warmup_steps": self.warmup_steps, "training_steps": self.training_steps,
+                "num_cycles": self.num_cycles, "power": self.power, "lr_end": self.lr_end, "lr_init": self.lr_init}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(**d)
+
+    def __eq__(self, other):
+        return isinstance(other, LrSchedule) and self.as_dict() == other.as_dict()
+
+    def __repr__(self):
+        return "LrSchedule(" + ", ".join(f"{k}={v!r}" for k, v in self.as_dict().items()) + ")"
+
+    def multiplier(self, k) -> float:
+        """m(k), host fp64, expression by expression as the library evaluates it"""
+        import math
+        k, W, T, name = float(k), float(self.warmup_steps), float(self.training_steps), self.name
+        if name == "constant":
+            return 1.0
+        if k < W:
+            return k / max(1.0, W)
+        if name == "constant_with_warmup":
+            return 1.0
+        if name == "linear":
+            return max(0.0, (T - k) / max(1.0, T - W))
+        if name == "polynomial":
+            if k > T:
+                return self.lr_end / self.lr_init
+            pct = 1.0 - (k - W) / (T - W)
+            return ((self.lr_init - self.lr_end) * pct ** self.power + self.lr_end) / self.lr_init
+        prog = (k - W) / max(1.0, T - W)
+        if name == "cosine":
+            return max(0.0, 0.5 * (1.0 + math.cos(math.pi * self.num_cycles * 2.0 * prog)))
+        if prog >= 1.0:
+            return 0.0
+        return max(0.0, 0.5 * (1.0 + math.cos(math.pi * ((self.num_cycles * prog) % 1.0))))
+
+    def rate(self, lr: float, k) -> float:
+        """what the kernel stores for base rate lr (as fp32) after k applied steps: (float)((double)lr * m(k)), except that constant
+        stores lr itself and constant_with_warmup the fp32 expression of ``warmup_steps=W``, lr * min(1, k / W)"""
+        f32 = lambda x: torch.tensor(x, dtype=torch.float64).to(torch.float32)      # noqa: E731
+        lr32 = f32(float(lr))
+        if self.name == "constant":
+            return float(lr32)
+        if self.name == "constant_with_warmup":
+            W = self.warmup_steps
+            return float(lr32 * torch.clamp(f32(float(k)) / f32(float(W)), max=1.0)) if W > 0 else float(lr32)
+        return float(f32(float(lr32) * self.multiplier(k)))
+
+    def launch(self, count: torch.Tensor, base: torch.Tensor, out: torch.Tensor, out_stride: int = 1, mult: Optional[torch.Tensor] = None):
+        """one aptp_lr_schedule launch on the current stream: out[i * out_stride] <- rate(base[i], count) for every base rate"""
+        assert count.dtype == base.dtype == out.dtype == torch.float32 and base.is_contiguous() and count.numel() == 1
+        n = base.numel()
+        assert out.numel() >= (n - 1) * out_stride + 1, "LrSchedule.launch: out is too small"
+        q = _lib.LrScheduleParams()
+        q.kind, q.warmup_steps, q.training_steps, q.n = self.kind, self.warmup_steps, self.training_steps, n
+        q.num_cycles, q.power, q.lr_end, q.lr_init = self.num_cycles, self.power, self.lr_end, self.lr_init
+        q.count_dev, q.base_dev, q.out_dev, q.out_stride = count.data_ptr(), base.data_ptr(), out.data_ptr(), int(out_stride)
+        q.mult_dev = None if mult is None else mult.data_ptr()
+        _lib.check(_lib.load().aptp_lr_schedule(ctypes.byref(q), ops._stream()), "aptp_lr_schedule")
+
+
+def as_lr_schedule(s) -> Optional[LrSchedule]:
+    """None, an LrSchedule or its as_dict()"""
+    return s if (s is None or isinstance(s, LrSchedule)) else LrSchedule.from_dict(s)
+
+
 class PackedAdamW:
     """torch.optim.AdamW's arithmetic over a PackedTrainer's state as ONE launch that also writes the bf16 operands
     (csrc/optim.hip).  The gradient tensors must exist and stay where they are (``.grad`` of every parameter as left by the
@@ -362,7 +482,7 @@ class PackedAdamW:
 
     def __init__(self, trainer: PackedTrainer, lr: float = 1e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
                  group_of=None, warmup_steps: int = 0, max_grad_norm: Optional[float] = None, log_grad_norm: bool = False,
-                 optim_bits: int = 32, min_8bit_size: int = ADAM8_MIN_SIZE):
+                 optim_bits: int = 32, min_8bit_size: int = ADAM8_MIN_SIZE, lr_schedule=None):
         """group_of: optional map parameter -> group index (e.g. the gradient bucket that completes it, ArenaGradReducer.bucket_of):
         the table is built per group and ``step_group(i)`` applies one group per launch, so the optimizer can follow a
         bucketed gradient exchange bucket by bucket; ``step()`` applies all groups.
@@ -376,7 +496,11 @@ class PackedAdamW:
         optim_bits=8 (`use_8bit_adam` of the reference's recipe): tensors of at least min_8bit_size elements keep both
         moments as uint8 codes with one fp32 absmax per moment and 256 elements (``self.m`` / ``self.v`` hold the codes,
         ``self.absmax1`` / ``self.absmax2`` the scales) and take their step in a second launch (csrc/optim8.hip) under the same
-        gate and factors; smaller tensors keep fp32 moments and the fp32 kernel.  32: nothing of this exists."""
+        gate and factors; smaller tensors keep fp32 moments and the fp32 kernel.  32: nothing of this exists.
+        lr_schedule: an LrSchedule (or its as_dict()): the rate follows that curve over the applied steps.  ``lr`` becomes
+        a base rate in device memory (``lr_base_t``; set_lr rewrites it) and one aptp_lr_schedule launch in front of every step's
+        AdamW launches writes ``lr_t`` from ``step_t``; the AdamW kernels read it (aptp_adamw_many_lr).  Not together with
+        warmup_steps > 0: the schedule has its own.  None: neither tensor exists, nothing more is launched."""
         assert optim_bits in (32, 8), "PackedAdamW: optim_bits is 32 or 8"
         assert int(min_8bit_size) >= 1, "PackedAdamW: min_8bit_size"
         self.optim_bits, self.min_8bit_size = int(optim_bits), int(min_8bit_size)
@@ -384,6 +508,9 @@ class PackedAdamW:
         self.group_of = group_of
         assert warmup_steps >= 0, "PackedAdamW: warmup_steps"
         self.warmup_steps = warmup_steps
+        self.lr_schedule = as_lr_schedule(lr_schedule)
+        assert self.lr_schedule is None or warmup_steps == 0, \
+            "PackedAdamW: lr_schedule and warmup_steps > 0 (give the warm-up to the schedule: LrSchedule(name, warmup_steps=W, ...))"
         assert max_grad_norm is None or max_grad_norm > 0, "PackedAdamW: max_grad_norm"
         self.max_grad_norm, self._want_norm, self.grad_norm = max_grad_norm, (max_grad_norm is not None or log_grad_norm), None
         entries = [(p, sh) for p, sh in PackedTrainer.entries(trainer) if p.grad is not None]   # (entries no backward reaches have nothing to apply)
@@ -405,6 +532,10 @@ class PackedAdamW:
         if self.optim_bits == 8:                                  # both maps, uploaded once
             self.qmap1, self.qmap2 = adam8_code_map(True).to(dev), adam8_code_map(False).to(dev)
         self.step_t = torch.zeros((), dtype=torch.float32, device=dev)
+        self.lr_base_t = self.lr_t = None
+        if self.lr_schedule is not None:
+            self.lr_base_t = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
+            self.lr_t = torch.zeros(1, dtype=torch.float32, device=dev)
         self.rebind_()
 
     def rebind_(self):
@@ -451,6 +582,11 @@ class PackedAdamW:
                 self.grad_norm.clipped.copy_(clipped)
         return self
 
+    def _launch_rate(self):
+        """lr_t <- the rate of the step that follows step_t applied ones (one small launch; nothing without a schedule)"""
+        if self.lr_schedule is not None:
+            self.lr_schedule.launch(self.step_t, self.lr_base_t, self.lr_t)
+
     def _launch(self, table, gate, grad_scale, grad_scale_dev=None):
         lib = _lib.load()
         q = _lib.AdamWParams()
@@ -460,7 +596,10 @@ class PackedAdamW:
         q.gate_dev = None if gate is None else gate.data_ptr()
         q.grad_scale = float(grad_scale)
         q.warmup_steps = float(self.warmup_steps)
-        if grad_scale_dev is None:
+        if self.lr_t is not None:     # (the rate from device memory: what _launch_rate stored for this step)
+            _lib.check(lib.aptp_adamw_many_lr(ctypes.byref(q), None if grad_scale_dev is None else grad_scale_dev.data_ptr(),
+                                              self.lr_t.data_ptr(), ops._stream()), "aptp_adamw_many_lr")
+        elif grad_scale_dev is None:
             _lib.check(lib.aptp_adamw_many(ctypes.byref(q), ops._stream()), "aptp_adamw_many")
         else:       # (the clip coefficient of ops.GradNorm, read from device memory as one more factor of grad_scale)
             _lib.check(lib.aptp_adamw_many_scaled(ctypes.byref(q), grad_scale_dev.data_ptr(), ops._stream()), "aptp_adamw_many_scaled")
@@ -477,8 +616,11 @@ class PackedAdamW:
         q.warmup_steps = float(self.warmup_steps)
         q.qmap_signed_dev, q.qmap_unsigned_dev = self.qmap1.data_ptr(), self.qmap2.data_ptr()
         q.items_host = ctypes.cast(table.host, ctypes.c_void_p)
-        _lib.check(lib.aptp_adamw8_many(ctypes.byref(q), None if grad_scale_dev is None else grad_scale_dev.data_ptr(), ops._stream()),
-                   "aptp_adamw8_many")
+        gs = None if grad_scale_dev is None else grad_scale_dev.data_ptr()
+        if self.lr_t is not None:
+            _lib.check(lib.aptp_adamw8_many_lr(ctypes.byref(q), gs, self.lr_t.data_ptr(), ops._stream()), "aptp_adamw8_many_lr")
+        else:
+            _lib.check(lib.aptp_adamw8_many(ctypes.byref(q), gs, ops._stream()), "aptp_adamw8_many")
 
     def _check_grads(self):
         for p, g in zip(self.params, self.grads):
@@ -497,6 +639,7 @@ class PackedAdamW:
         if self.grad_norm is not None:
             self.grad_norm.run(grad_scale, gate)
             gate, coef = self.grad_norm.verdict, self.grad_norm.coef
+        self._launch_rate()
         if self.table is not None:
             self._launch(self.table, gate, grad_scale, coef)
         if self.table8 is not None:
@@ -509,6 +652,21 @@ class PackedAdamW:
         assert self.grad_norm is not None, "PackedAdamW.set_max_grad_norm: built without max_grad_norm / log_grad_norm"
         self.max_grad_norm = value
         self.grad_norm.set_max_norm(value)
+
+    @torch.no_grad()
+    def set_lr(self, value: float):
+        """another (base) rate for the steps to come.  With a schedule it is rewritten in device memory, behind a pending step"""
+        self.lr = float(value)
+        if self.lr_base_t is not None:
+            PackedTrainer._sync(self.trainer)
+            self.lr_base_t.fill_(float(value))
+
+    def last_lr(self) -> float:
+        """the rate of the NEXT step, as get_last_lr() reports it after scheduler.step() (host read of the step count: logging only)"""
+        PackedTrainer._sync(self.trainer)
+        k = float(self.step_t)
+        sched = self.lr_schedule if self.lr_schedule is not None else LrSchedule("constant_with_warmup", self.warmup_steps)
+        return sched.rate(self.lr, k)
 
     def last_grad_norm(self) -> float:
         """the norm the last step() measured, before clipping (host read: logging only)"""
@@ -527,6 +685,7 @@ class PackedAdamW:
         """the tensors of group gi only (no step-count update: call finish_step() after the last group).  No clip: the norm needs
         every group's gradients (a caller with a norm configured exchanges first and calls step())"""
         assert self.grad_norm is None, "PackedAdamW.step_group: a gradient norm covers all groups -- exchange first, then step()"
+        self._launch_rate()         # (step_t moves in finish_step only: every group launch of a step stores the same bits)
         if gi in self.groups:
             self._launch(self.groups[gi], gate, grad_scale)
         if gi in self.groups8:
@@ -545,6 +704,9 @@ class PackedAdamW:
         load_state_dict on an optimizer built over the same expert, whatever order its modules first ran in)"""
         clone = lambda ts: [None if t is None else t.clone() for t in ts]       # noqa: E731
         return {"step": self.step_t.clone(), "names": list(self.names),
+                # the curve this optimizer was built with (None: none), for the record: load_state_dict keeps the constructed
+                # optimizer's schedule, and the position on it is "step"
+                "lr_schedule": None if self.lr_schedule is None else self.lr_schedule.as_dict(),
                 "exp_avg": [m.clone() for m in self.m], "exp_avg_sq": [v.clone() for v in self.v],
                 # optim_bits = 8: uint8 codes above for the 8-bit tensors, their scales and both maps here (None: fp32 moments)
                 "optim_bits": self.optim_bits, "absmax1": clone(self.absmax1), "absmax2": clone(self.absmax2),

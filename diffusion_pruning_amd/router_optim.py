@@ -104,10 +104,16 @@ class RouterAdamW:
     over both groups (ops.GradNorm, csrc/grad_norm.hip: two more launches inside step(), so a captured step holds them); the
     update kernel multiplies the gradients by the coefficient it reads from device memory.  A zero-filled gradient (the codebook's
     during the pre-training) contributes nothing.  The threshold is a device scalar (set_max_grad_norm: no recapture); the
-    clip has no state beyond a counter, so state_dict() is what it was.  log_grad_norm=True: the norm without a threshold."""
+    clip has no state beyond a counter, so state_dict() is what it was.  log_grad_norm=True: the norm without a threshold.
+
+    lr_schedule: a packed_train.LrSchedule (or its as_dict()): every group's rate follows that curve over the APPLIED steps (DESIGN
+    6y).  The groups' rates become base rates in a table of their own next to ``groups_dev`` (``base_lr_dev``; set_lr writes it),
+    and one aptp_lr_schedule launch inside step(), in front of the norm and the scan, rewrites the lr column of ``groups_dev``
+    from counters[0] -- so a captured step holds it; the warm-up column stays 0.  Not together with warmup_steps > 0.  None: no
+    base table, no launch."""
 
     def __init__(self, param_groups, betas=(0.9, 0.999), eps: float = 1e-8, warmup_steps: int = 0, max_grad_norm=None,
-                 log_grad_norm: bool = False):
+                 log_grad_norm: bool = False, lr_schedule=None):
         param_groups = list(param_groups)
         assert param_groups and all(isinstance(g, dict) and "params" in g for g in param_groups), \
             "RouterAdamW: param_groups = [{'params': [...], 'lr': ..., 'weight_decay': ...}, ...]"
@@ -132,6 +138,13 @@ class RouterAdamW:
         self.counters = torch.zeros(4, dtype=torch.float32, device=dev)      # applied, skipped, bad-gradient flag, reserved
         self.groups_dev = torch.tensor([[g["lr"], g["weight_decay"], self.warmup_steps] for g in self.param_groups],
                                        dtype=torch.float32).to(dev)
+        from .packed_train import as_lr_schedule
+        self.lr_schedule, self.base_lr_dev = as_lr_schedule(lr_schedule), None
+        if self.lr_schedule is not None:
+            assert warmup_steps == 0, \
+                "RouterAdamW: lr_schedule and warmup_steps > 0 (give the warm-up to the schedule: LrSchedule(name, warmup_steps=W, ...))"
+            assert len(self.param_groups) <= 16, "RouterAdamW: lr_schedule serves at most 16 parameter groups (aptp_lr_schedule)"
+            self.base_lr_dev = self.groups_dev[:, 0].clone()
         self.before_access = None      # GraphedPrunerStep.finish: orders the current stream behind a step pending on the router's stream
         self.grads = self.m = self.v = None
         assert max_grad_norm is None or max_grad_norm > 0, "RouterAdamW: max_grad_norm"
@@ -264,6 +277,8 @@ class RouterAdamW:
             assert gate.dtype == torch.float32 and gate.device == self.device and gate.numel() == 1
             q.gate_dev = gate.data_ptr()
         q.items_host = ctypes.cast(tb.host, ctypes.c_void_p)
+        if self.lr_schedule is not None:      # the lr column of groups_dev <- base rates x m(applied): read by this step's update launch
+            self.lr_schedule.launch(self.counters[0:1], self.base_lr_dev, self.groups_dev, out_stride=3)
         if self._want_norm:
             gn = self.norms[table]
             gn.run(grad_scale, gate)
@@ -298,7 +313,10 @@ class RouterAdamW:
         """the rate of one group, written into the device table: replays of a captured step read it (no recapture, no host wait)"""
         self._wait()
         self.param_groups[group]["lr"] = float(value)
-        self.groups_dev[group, 0] = float(value)
+        if self.base_lr_dev is not None:      # (with a schedule the lr column is what the rate launch derives from this)
+            self.base_lr_dev[group] = float(value)
+        else:
+            self.groups_dev[group, 0] = float(value)
 
     @torch.no_grad()
     def set_weight_decay(self, group: int, value: float):
@@ -337,6 +355,8 @@ class RouterAdamW:
     def last_lr(self):
         """the rate of each group for the NEXT step, as LambdaLR.get_last_lr() reports it after scheduler.step()"""
         k, W = self.applied_steps(), self.warmup_steps
+        if self.lr_schedule is not None:
+            return [self.lr_schedule.rate(g["lr"], k) for g in self.param_groups]
         return [g["lr"] * (min(1.0, k / W) if W > 0 else 1.0) for g in self.param_groups]
 
     # ---- state ------------------------------------------------------------------------------------------------------------------
@@ -344,7 +364,7 @@ class RouterAdamW:
         """everything a step changes, for GraphedPrunerStep's capture warm-up (restored in place by _restore)"""
         self._wait()
         return dict(p=[p.detach().clone() for p in self.params], m=[m.clone() for m in self.m], v=[v.clone() for v in self.v],
-                    steps=self.steps.clone(), counters=self.counters.clone(),
+                    steps=self.steps.clone(), counters=self.counters.clone(), groups=self.groups_dev.clone(),
                     norm=None if self.grad_norm is None else self.grad_norm.out.clone())
 
     @torch.no_grad()
@@ -354,6 +374,8 @@ class RouterAdamW:
             dst.copy_(src)
         self._install_steps(snap["steps"])
         self.counters.copy_(snap["counters"])
+        if snap.get("groups") is not None:      # (the lr column a scheduled warm-up step rewrote)
+            self.groups_dev.copy_(snap["groups"])
         if snap.get("norm") is not None:
             self.grad_norm.out.copy_(snap["norm"])
         self.zero_grad()
@@ -366,15 +388,21 @@ class RouterAdamW:
         else:
             self.run_steps.copy_(torch.tensor([per[r["idx"][0]] for r in self.runs], dtype=torch.float32))
 
+    def _extra(self, c):
+        ex = {"applied": c[0], "skipped": c[1], "warmup_steps": self.warmup_steps}
+        if self.lr_schedule is not None:      # (for the record: load_state_dict keeps the constructed optimizer's schedule)
+            ex["lr_schedule"] = self.lr_schedule.as_dict()
+        return ex
+
     def state_dict(self):
         """torch.optim.AdamW.state_dict()'s layout (state[i] = {step, exp_avg, exp_avg_sq}, param_groups) plus one key,
-        "router_adamw": {applied, skipped, warmup_steps}"""
+        "router_adamw": {applied, skipped, warmup_steps[, lr_schedule]}; param_groups hold the BASE rates"""
         groups = [{"n": len(g["params"]), "lr": g["lr"], "weight_decay": g["weight_decay"], "betas": self.betas, "eps": self.eps}
                   for g in self.param_groups]
         self._wait()
         c = self.counters.tolist()
         return export_state_dict(list(self.steps.unbind(0)), self.m, self.v, groups,
-                                 extra={"applied": c[0], "skipped": c[1], "warmup_steps": self.warmup_steps})
+                                 extra=self._extra(c))
 
     @torch.no_grad()
     def load_state_dict(self, sd):

@@ -1109,6 +1109,13 @@ class GraphedPrunerStep(PrunerStep):
             rt["pending"] = False
 
 
+def scaled_lr(lr: float, batch: int, accumulation: int = 1, world: int = 1) -> float:
+    """`scale_lr` of the recipes (pdm/training/trainer.py:806-812, 1521-1527): the configured rate times the square root of the
+    effective batch, lr * sqrt(accumulation * batch * world)"""
+    import math
+    return lr * math.sqrt(accumulation * batch * world)
+
+
 def synthetic_batch(batch: int, latent: int, device, seed: int = 1234, cross_dim: int = 1024, text_dim: int = 768):
     """SURVEY §8d synthetic CC3M-shape batch: latents/target N(0,1), text states N(0,1), MPNet embeddings 0.05*N(0,1),
     random integer timesteps."""
@@ -1454,6 +1461,10 @@ class GraphedFineTunerStep(FineTunerStep):
     checkpoint taken in the middle of a window drops the micro-batches accumulated so far (``accum_index`` tells where a
     window stands: save at 0).
     lr_warmup_steps=W > 0: `constant_with_warmup` over W optimizer steps (PackedAdamW(warmup_steps=W)).
+    lr_scheduler=NAME (training.optim.lr_scheduler of the recipes: constant, constant_with_warmup, linear, cosine,
+    cosine_with_restarts, polynomial) with max_train_steps=T, lr_num_cycles, lr_power: the rate follows that curve over the applied
+    optimizer steps, W = lr_warmup_steps (packed_train.LrSchedule; one small launch in front of AdamW on the call that closes a
+    window).  log_lr=True: the dict gains "lr", the rate that step ran at (device scalar; None inside an open window).
     ema=True or a dict of PackedEMA's arguments: an exponential moving average of the packed state (`use_ema` of the reference's
     interface), one launch behind AdamW on the call that closes a window, under the same gate; validate(use_ema=True),
     export_ema_() and save_ema_pretrained() read it through a swap of masters and averages.
@@ -1468,9 +1479,21 @@ class GraphedFineTunerStep(FineTunerStep):
                  lr: float = 1e-5, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  data_parallel: bool = False, bucket_bytes: int = 256 << 20, reduce_mode: str = "rs_ag", nan_guard: bool = True,
                  accumulation_steps: int = 1, lr_warmup_steps: int = 0, ema=None, max_grad_norm: Optional[float] = None,
-                 log_grad_norm: bool = False, use_8bit_adam: bool = False, short_batches: bool = False):
-        super().__init__(student, teacher, cfg, schedule)
+                 log_grad_norm: bool = False, use_8bit_adam: bool = False, short_batches: bool = False,
+                 lr_scheduler: Optional[str] = None, max_train_steps: Optional[int] = None, lr_num_cycles=None, lr_power: float = 1.0,
+                 log_lr: bool = False):
         assert int(accumulation_steps) >= 1 and lr_warmup_steps >= 0
+        # lr_scheduler: the curve of get_scheduler(name, num_warmup_steps=lr_warmup_steps, num_training_steps=max_train_steps), both in
+        # optimizer steps, evaluated on the device from the count of applied steps (PackedAdamW(lr_schedule=)).  None: nothing is
+        # allocated or launched and lr_warmup_steps is the warm-up of PackedAdamW(warmup_steps=).  DESIGN 6y.
+        self.lr_schedule = None
+        if lr_scheduler is not None:
+            from .packed_train import LrSchedule
+            self.lr_schedule = LrSchedule(lr_scheduler, warmup_steps=lr_warmup_steps, training_steps=max_train_steps,
+                                          num_cycles=lr_num_cycles, power=lr_power)
+        assert not log_lr or self.lr_schedule is not None, "GraphedFineTunerStep: log_lr reads the device-side rate of an lr_scheduler"
+        self.log_lr = bool(log_lr)
+        super().__init__(student, teacher, cfg, schedule)       # (registers hooks: after everything that can refuse the arguments)
         # short_batches: the captured batch size is a MAXIMUM; train_step takes 0 <= n <= B samples (the loader drops samples
         # it cannot decode and ends every epoch on a short batch).  The loss terms become ONE autograd node over the fused
         # masked loss stage (ops.LossStage, csrc/loss_stage.hip) whose mean runs over the samples present; the rows behind them
@@ -1630,8 +1653,9 @@ class GraphedFineTunerStep(FineTunerStep):
             group_of = lambda p_: self.reducer.bucket_of(off[id(p_)], p_.numel())          # noqa: E731
         self.optimizer = PackedAdamW(self.trainer, lr=self.opt_kw["lr"], betas=self.opt_kw["betas"], eps=self.opt_kw["eps"],
                                      weight_decay=self.opt_kw["weight_decay"], group_of=group_of,
-                                     warmup_steps=self.lr_warmup_steps, max_grad_norm=self.max_grad_norm,
-                                     log_grad_norm=self.log_grad_norm, optim_bits=8 if self.use_8bit_adam else 32)
+                                     warmup_steps=0 if self.lr_schedule is not None else self.lr_warmup_steps,
+                                     max_grad_norm=self.max_grad_norm, log_grad_norm=self.log_grad_norm,
+                                     optim_bits=8 if self.use_8bit_adam else 32, lr_schedule=self.lr_schedule)
         if self._ema_kw is not None:
             from .packed_train import PackedEMA
             self.ema = PackedEMA(self.trainer, self.optimizer, **self._ema_kw)
@@ -1826,7 +1850,8 @@ class GraphedFineTunerStep(FineTunerStep):
                 # nothing to learn from: no replay, no accumulation, no optimizer; the window stays where it is
                 zero = torch.zeros((), dtype=torch.float32, device=cap["st"]["valid"].device)
                 return {"loss": zero, "diff_loss": zero.clone(), "distillation_loss": zero.clone(), "block_loss": zero.clone(),
-                        "applied": False, "accum_index": self.accum_index, "n_valid": zero.clone(), "skipped": True}
+                        "applied": False, "accum_index": self.accum_index, "n_valid": zero.clone(), "skipped": True,
+                        **({"lr": None} if self.log_lr else {})}
         else:
             _stage_batch(cap["st"], batch)
         main = torch.cuda.current_stream()       # (the min-SNR weights are computed from the staged timesteps inside g_teacher)
@@ -1883,6 +1908,7 @@ class GraphedFineTunerStep(FineTunerStep):
                 gate = self.optimizer.step(gate)
             # (with a gradient norm, `gate` is now its verdict: finite norm and finite loss)
             grad_norm = self.optimizer.grad_norm.norm.clone() if (applied and self.optimizer.grad_norm is not None) else None
+            lr_now = self.optimizer.lr_t.reshape(()).clone() if (applied and self.log_lr) else None
             if applied and self.ema is not None:
                 # the average follows the optimizer on its stream, under its gate: one launch + the device-side count.  Local to
                 # the rank in data-parallel mode (identical masters give identical averages: no collective)
@@ -1899,6 +1925,9 @@ class GraphedFineTunerStep(FineTunerStep):
             # the norm of the mean gradient the optimizer saw, before clipping (device scalar; NaN-free only when the window
             # was applied: compare ops.GradNorm.verdict); None inside an open window
             out["grad_norm"] = grad_norm
+        if self.log_lr:
+            # the rate the optimizer step of this call ran at -- or would have: a skipped window leaves it for the next one
+            out["lr"] = lr_now
         if self.short_batches:
             out["n_valid"], out["skipped"] = cap["n_valid"].clone(), False          # (device scalar: the samples the losses average)
         return out

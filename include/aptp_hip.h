@@ -702,6 +702,11 @@ int aptp_adamw_many(const AptpAdamWParams* p, aptp_stream_t stream);
  * grad_scale * grad_scale_dev[0], one fp32 product, uniform over the grid.  Null: aptp_adamw_many itself, bit for bit.  (An
  * argument, not a field: the layout of AptpAdamWParams ends with warmup_steps and stays as it is.) */
 int aptp_adamw_many_scaled(const AptpAdamWParams* p, const float* grad_scale_dev, aptp_stream_t stream);
+/* The same launch with the RATE read from device memory: lr_dev is an optional fp32 device scalar (4-byte aligned), what
+ * aptp_lr_schedule stored for this step.  With it the kernel uses lr_dev[0] where it otherwise forms lr * min(1, step / W): p->lr
+ * is ignored, p->warmup_steps != 0 is APTP_EINVAL (the schedule owns the warm-up), one more uniform scalar load and no bytes per
+ * element.  Null: aptp_adamw_many_scaled itself, bit for bit (it forwards here).  An argument, not a field, for the same reason. */
+int aptp_adamw_many_lr(const AptpAdamWParams* p, const float* grad_scale_dev, const float* lr_dev, aptp_stream_t stream);
 
 /* The same step with both moments kept as block-wise 8-bit codes (csrc/optim8.hip; `use_8bit_adam` of the fine-tune recipe,
  * configs/finetuning/sd-2-1_cc3m.yaml:102; the format is defined by tests/adamw8_model.py).  A quantisation block is
@@ -730,6 +735,8 @@ typedef struct {
 } AptpAdamW8Params;
 int aptp_adamw8_blocks(int64_t n);
 int aptp_adamw8_many(const AptpAdamW8Params* p, const float* grad_scale_dev, aptp_stream_t stream);
+/* lr_dev as in aptp_adamw_many_lr; null: aptp_adamw8_many itself, bit for bit (it forwards here) */
+int aptp_adamw8_many_lr(const AptpAdamW8Params* p, const float* grad_scale_dev, const float* lr_dev, aptp_stream_t stream);
 
 /* Gradient accumulation over the micro-batches of one optimizer window (gradient_accumulation_steps of the fine-tune recipe,
  * configs/finetuning/sd-2-1_cc3m.yaml): ONE launch over a contiguous fp32 range (the gradient arena of
@@ -779,7 +786,8 @@ int aptp_ema_many(const AptpEmaParams* p, aptp_stream_t stream);
  *   lr_eff = lr_g * min(1, applied / warmup_steps_g)  when warmup_steps_g > 0: `constant_with_warmup` counted in applied steps
  * items_dev: n_items descriptors in device memory; p, g, m, v fp32 [n], 16-byte aligned; step: fp32 device scalar; group: index
  * into groups_dev.  starts_dev: int32 [n_items + 1] prefix sums of aptp_group_adamw_blocks(n); total_blocks = starts[n_items].
- * groups_dev: n_groups entries the host may rewrite between replays of a captured launch.
+ * groups_dev: n_groups entries the host may rewrite between replays of a captured launch -- or aptp_lr_schedule, launched in
+ * front with out_stride = 3, rewrites the lr column from counters_dev[0] at every step (warmup_steps_g is then 0).
  * counters_dev: fp32 [4], 16-byte aligned = {applied steps, skipped steps, bad-gradient flag (0 outside the call), reserved}.
  * The step is SKIPPED when gate_dev[0] is non-finite or any gradient element of any item is non-finite (NaN or +-Inf; the
  * reference's anomaly mode raises on NaN only): p, m, v, every step[0] and applied keep their bits and skipped advances by 1;
@@ -805,6 +813,43 @@ typedef struct {
 } AptpGroupAdamWParams;
 int aptp_group_adamw_blocks(int64_t n);
 int aptp_group_adamw(const AptpGroupAdamWParams* p, aptp_stream_t stream);
+
+/* The rate of the next optimizer step from the count of applied steps, on the device (csrc/lr_schedule.hip): the
+ * `lr_scheduler` family of the recipes (transformers.optimization.get_scheduler) for the three AdamW kernels above.  ONE launch of
+ * one small block; put it in front of the AdamW launch(es) of the step.  With k = count_dev[0], W = warmup_steps, T = training_steps
+ * (optimizer steps), the step that follows k applied ones runs at base * m(k); m in fp64:
+ *   every kind but CONSTANT, k < W:  m = k / max(1, W)
+ *   CONSTANT                         m = 1
+ *   CONSTANT_WITH_WARMUP             m = 1 for k >= W
+ *   LINEAR                           m = max(0, (T - k) / max(1, T - W))
+ *   COSINE                           m = max(0, 0.5 (1 + cos(pi num_cycles 2 prog))), prog = (k - W) / max(1, T - W); it rises again past T
+ *   COSINE_WITH_RESTARTS             m = 0 for prog >= 1, else max(0, 0.5 (1 + cos(pi ((num_cycles prog) mod 1))))
+ *   POLYNOMIAL                       m = lr_end / lr_init for k > T, else ((lr_init - lr_end) (1 - (k - W) / (T - W))^power + lr_end) / lr_init
+ * out_dev[i * out_stride] = (float)((double)base_dev[i] * m) for i < n, except that CONSTANT stores base_dev[i] itself and
+ * CONSTANT_WITH_WARMUP the fp32 expression of AptpAdamWParams.warmup_steps, base * min(1, k / W): the same bits as the paths
+ * without this launch.  out_stride = 3 writes the lr column of an AptpAdamWGroup table in place (its warmup_steps column must
+ * then be 0).  mult_dev: optional, receives (float)m.  lr_init is the OPTIMIZER's default rate, not a group's (the library divides
+ * by optimizer.defaults["lr"]; the reference builds its optimizers from groups, so that is torch.optim.AdamW's 1e-3).
+ * APTP_EINVAL and nothing launched for: null or misaligned count_dev / base_dev / out_dev, a misaligned mult_dev, an unknown kind,
+ * negative steps or steps >= 2^24 (k is an fp32 count), T < W for the four decaying kinds (T <= W for POLYNOMIAL), n outside
+ * 1..16, out_stride < 1, and for the kinds that read them num_cycles <= 0, power <= 0, lr_init <= lr_end. */
+enum {
+  APTP_LR_CONSTANT = 0, APTP_LR_CONSTANT_WITH_WARMUP = 1, APTP_LR_LINEAR = 2, APTP_LR_COSINE = 3,
+  APTP_LR_COSINE_WITH_RESTARTS = 4, APTP_LR_POLYNOMIAL = 5
+};
+typedef struct {
+  int32_t kind;
+  int32_t warmup_steps, training_steps;
+  int32_t n;                   /* rates to write: 1 <= n <= 16 */
+  double num_cycles;           /* COSINE (0.5 = half a wave down to 0 at T), COSINE_WITH_RESTARTS (an integer) */
+  double power, lr_end, lr_init; /* POLYNOMIAL */
+  const float* count_dev;      /* fp32 device scalar: applied steps (PackedAdamW.step_t, RouterAdamW.counters[0]) */
+  const float* base_dev;       /* n base rates */
+  float* out_dev;              /* element i at out_dev[i * out_stride] */
+  int32_t out_stride;
+  float* mult_dev;             /* optional */
+} AptpLrScheduleParams;
+int aptp_lr_schedule(const AptpLrScheduleParams* p, aptp_stream_t stream);
 
 /* Global L2 norm of the gradients of a table and the clip coefficient of torch.nn.utils.clip_grad_norm_ (max_grad_norm), both left
  * in device memory (csrc/grad_norm.hip): what grad_scale_dev of aptp_adamw_many_scaled and aptp_group_adamw reads.  items_dev: n_items

@@ -20,7 +20,11 @@ fields for the fp32 state (no `adamw8_ms`), for the comparison.
 --short-batches (graphed mode) runs the step with GraphedFineTunerStep(short_batches=True) -- the fused masked loss stage, batches of
 up to --batch samples -- and, in the same process, the default step on a second copy of the expert: `short_batches` in the line holds
 both rates (alternating rounds of --steps steps, the faster round of each) and the nodes of both loss-and-backward graphs.
---valid N hands the switched step batches of N samples (default: the full batch)."""
+--valid N hands the switched step batches of N samples (default: the full batch).
+
+--lr-scheduler NAME --max-train-steps T [--lr-num-cycles C] [--lr-power P] (graphed mode) runs the step under
+GraphedFineTunerStep(lr_scheduler=NAME, max_train_steps=T, ...) with --lr-warmup as its warm-up -- one more small launch per optimizer
+step (csrc/lr_schedule.hip) -- and adds `lr_scheduler`, `max_train_steps` and `last_lr`, the rate of the next step."""
 import argparse
 import json
 import os
@@ -142,7 +146,14 @@ def main():
                     help="GraphedFineTunerStep(short_batches=True) (graphed mode), timed against the default step in the same run; adds "
                          "both rates and the node counts of both loss-and-backward graphs to the JSON line")
     ap.add_argument("--valid", type=int, default=None, help="with --short-batches: samples per timed batch, 1..--batch (default: all)")
+    ap.add_argument("--lr-scheduler", default=None,
+                    help="the curve of the rate over the applied optimizer steps (graphed mode, GraphedFineTunerStep(lr_scheduler=)): "
+                         "constant, constant_with_warmup, linear, cosine, cosine_with_restarts, polynomial")
+    ap.add_argument("--max-train-steps", type=int, default=None, help="with --lr-scheduler: num_training_steps, in optimizer steps")
+    ap.add_argument("--lr-num-cycles", type=float, default=None, help="with --lr-scheduler cosine / cosine_with_restarts")
+    ap.add_argument("--lr-power", type=float, default=1.0, help="with --lr-scheduler polynomial")
     args = ap.parse_args()
+    assert args.lr_scheduler is None or args.mode == "graphed", "--lr-scheduler belongs to the graphed step"
     assert not args.short_batches or args.mode == "graphed", "--short-batches belongs to the graphed step"
     assert args.valid is None or (args.short_batches and 1 <= args.valid <= args.batch), "--valid N needs --short-batches and 1 <= N <= --batch"
     args.optimizer_times = args.optimizer_times or args.adam8bit
@@ -177,7 +188,9 @@ def main():
         from diffusion_pruning_amd.train_step import GraphedFineTunerStep
         kw = dict(lr=1e-5, accumulation_steps=args.accum, lr_warmup_steps=args.lr_warmup,
                   **({"ema": True} if args.ema else {}), **({"use_8bit_adam": True} if args.adam8bit else {}),
-                  **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}))
+                  **({"max_grad_norm": args.max_grad_norm} if args.max_grad_norm is not None else {}),
+                  **({"lr_scheduler": args.lr_scheduler, "max_train_steps": args.max_train_steps, "lr_num_cycles": args.lr_num_cycles,
+                      "lr_power": args.lr_power} if args.lr_scheduler is not None else {}))
         if args.short_batches:
             # the default step on a second copy of the same expert, for the comparison; graphs kept so that their nodes can be counted
             graph_utils.KEEP_GRAPHS = True
@@ -273,6 +286,8 @@ def main():
         val.update({"max_grad_norm": args.max_grad_norm, "grad_norm_last": step.optimizer.last_grad_norm(),
                     "clipped_steps": step.optimizer.clipped_steps(), "grad_norm_ms": round(gn_ms, 4),
                     "grad_norm_gb_per_s": round(4 * n_train / gn_ms * 1e-6, 1)})
+    if args.lr_scheduler is not None:
+        val.update({"lr_scheduler": args.lr_scheduler, "max_train_steps": args.max_train_steps, "last_lr": step.optimizer.last_lr()})
     if args.validate:
         batches = [synthetic_batch(args.val_batch, 64, dev, seed=100 + i) for i in range(args.validate)]
         val.update(time_validation(step, batches, args.validate_baseline))

@@ -29,6 +29,10 @@ def main():
     ap.add_argument("--pretrain-steps", type=int, default=0, help="hip: the first P steps run the hyper-net pre-training phase")
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="hip: clip the global gradient norm of the router at this value on the device (RouterAdamW(max_grad_norm=))")
+    ap.add_argument("--lr-scheduler", default=None,
+                    help="hip: the curve of both groups' rates over the applied steps (RouterAdamW(lr_schedule=), DESIGN 6y), with "
+                         "--lr-warmup as its warm-up: constant, constant_with_warmup, linear, cosine, cosine_with_restarts, polynomial")
+    ap.add_argument("--max-train-steps", type=int, default=None, help="with --lr-scheduler: num_training_steps, in optimizer steps")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     unet = UNet2DConditionModelGated().init_synthetic(seed=0).to(dev)
@@ -43,17 +47,21 @@ def main():
     step = (PrunerStep if args.eager else GraphedPrunerStep)(unet, hn, qz)
     step.count_macs(args.latent)
     hip = args.router_optimizer == "hip"
-    if not hip and (args.lr_warmup or args.pretrain_steps or args.max_grad_norm is not None):
-        ap.error("--lr-warmup, --pretrain-steps and --max-grad-norm need --router-optimizer hip")
+    if not hip and (args.lr_warmup or args.pretrain_steps or args.max_grad_norm is not None or args.lr_scheduler is not None):
+        ap.error("--lr-warmup, --pretrain-steps, --max-grad-norm and --lr-scheduler need --router-optimizer hip")
     batch = synthetic_batch(args.batch, args.latent, dev)
     done = 0
     if hip:
         from diffusion_pruning_amd import graph_utils
         from diffusion_pruning_amd.router_optim import RouterAdamW
+        sched = None
+        if args.lr_scheduler is not None:
+            from diffusion_pruning_amd.packed_train import LrSchedule
+            sched = LrSchedule(args.lr_scheduler, warmup_steps=args.lr_warmup, training_steps=args.max_train_steps)
         graph_utils.KEEP_GRAPHS = True                      # (graph_nodes() below)
         opt = RouterAdamW([{"params": [p for p in hn.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0},
                            {"params": [p for p in qz.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0}],
-                          warmup_steps=args.lr_warmup, max_grad_norm=args.max_grad_norm)
+                          warmup_steps=0 if sched is not None else args.lr_warmup, max_grad_norm=args.max_grad_norm, lr_schedule=sched)
         if not args.eager:
             step.capture(batch, optimizer=opt, pretrain=args.pretrain_steps > 0)
             if args.pretrain_steps > 0:
@@ -85,6 +93,8 @@ def main():
             step.finish()
             extra["graph_nodes"] = step.graph_nodes()
         extra.update(router_optimizer="hip", applied_steps=opt.applied_steps(), skipped_steps=opt.skipped_steps(), last_lr=opt.last_lr())
+        if args.lr_scheduler is not None:
+            extra.update(lr_scheduler=args.lr_scheduler, max_train_steps=args.max_train_steps)
         if args.max_grad_norm is not None:
             extra.update(max_grad_norm=args.max_grad_norm, grad_norm_last=opt.last_grad_norm(), clipped_steps=opt.clipped_steps())
     print(json.dumps({"metric": "pruning-train-steps/s (SD-2.1, 64x64 latents, teacher fwd + student fwd/bwd + router)",
