@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (APTP_LIB=<file> loads another build of the same ABI: A/B timing of kernel changes on one box)
@@ -307,6 +307,31 @@ class LossStageParams(Structure):
         ("grads", LossStageGrad * LOSS_TERMS_MAX),
         ("n_grads", c_int32), ("reserved", c_int32),
         ("g", c_void_p),
+    ]
+
+
+ROUTER_STAGE_MAX_B, ROUTER_STAGE_MAX_FEATURES, SINKHORN_MAX_K = 1024, 4096, 64
+RESOURCE_TYPES = {"log": 0, "mae": 1, "mse": 2}
+
+
+class SinkhornParams(Structure):
+    _fields_ = [
+        ("scores", c_void_p), ("ld", c_int64),
+        ("valid", c_void_p), ("idx", c_void_p), ("q", c_void_p),
+        ("B", c_int32), ("K", c_int32), ("iters", c_int32),
+        ("eps", c_float),
+    ]
+
+
+class RouterStageParams(Structure):
+    _fields_ = [
+        ("text", c_void_p), ("ld_text", c_int64), ("arch", c_void_p), ("ld_arch", c_int64),
+        ("ratios", c_void_p), ("valid", c_void_p), ("g", c_void_p),
+        ("work", c_void_p), ("out", c_void_p),
+        ("d_arch", c_void_p), ("ld_darch", c_int64), ("d_ratios", c_void_p),
+        ("B", c_int32), ("E", c_int32), ("D", c_int32), ("resource_type", c_int32),
+        ("tau_arch", c_float), ("tau_text", c_float), ("p", c_double),
+        ("w_resource", c_float), ("w_contrastive", c_float), ("w_std", c_float), ("w_max", c_float),
     ]
 
 
@@ -686,6 +711,10 @@ EXPORTS = [
     ("aptp_loss_stage", c_int, [POINTER(LossStageParams), c_void_p]),
     ("aptp_loss_stage_bwd_nblocks", c_int, [POINTER(LossStageParams)]),
     ("aptp_loss_stage_bwd", c_int, [POINTER(LossStageParams), c_void_p]),
+    ("aptp_sinkhorn_assign", c_int, [POINTER(SinkhornParams), c_void_p]),
+    ("aptp_router_stage_work_floats", c_int64, [c_int32, c_int32, c_int32]),
+    ("aptp_router_stage", c_int, [POINTER(RouterStageParams), c_void_p]),
+    ("aptp_router_stage_bwd", c_int, [POINTER(RouterStageParams), c_void_p]),
     ("aptp_groupnorm_bwd", c_int, [POINTER(GroupNormBwdParams), c_void_p]),
     ("aptp_layernorm_bwd", c_int, [POINTER(LayerNormBwdParams), c_void_p]),
     ("aptp_attention_bwd", c_int, [POINTER(AttentionBwdParams), c_void_p]),

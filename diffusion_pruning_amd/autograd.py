@@ -286,6 +286,30 @@ def loss_stage(stage) -> torch.Tensor:
     return LossStageFn.apply(stage, *stage.grad_inputs)
 
 
+class RouterStageFn(Function):
+    """router_loss = ops.RouterStage(...).run()[4] as ONE autograd node: the inputs are the stage's `arch` and `ratios`, the output
+    is the router loss, and backward hands both gradients back from the stage's two launches.  The prompt embeddings and the
+    valid mask are operands of the stage only: they receive no gradient."""
+
+    @staticmethod
+    def forward(ctx, stage, arch, ratios):
+        assert arch.data_ptr() == stage.arch.data_ptr() and ratios.data_ptr() == stage.ratios.data_ptr(), \
+            "RouterStageFn: the inputs are the stage's own arch and ratios"
+        ctx.stage = stage
+        return stage.run()[4].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        d_arch, d_ratios = ctx.stage.backward(g.to(torch.float32))
+        return None, (d_arch if ctx.needs_input_grad[1] else None), (d_ratios if ctx.needs_input_grad[2] else None)
+
+
+def router_stage(stage) -> torch.Tensor:
+    """the router loss of an ops.RouterStage with the gradient flowing into the `arch` and `ratios` it was built on"""
+    assert not stage.text_requires_grad, "router_stage: text must not require grad (the stage has no gradient for it)"
+    return RouterStageFn.apply(stage, *stage.grad_inputs)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Fine-tuning variants (SURVEY a20): the same ops with WEIGHT gradients.  The trainable tensors are the fp32 masters in
 # diffusers' layout; a pruned expert computes on compacted packs, so parameter gradients are produced in the compact

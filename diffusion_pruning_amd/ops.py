@@ -22,6 +22,7 @@ from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
 from ._lib import GuidedStepParams, LossStageParams, LossTermsParams, PhiloxNormalParams, TrainNoiseParams
+from ._lib import RouterStageParams, SinkhornParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -2073,6 +2074,108 @@ class LossStage(LossTerms):
         self._p.g = self._g.data_ptr()
         _lib.check(self._lib.aptp_loss_stage_bwd(ctypes.byref(self._p), _stream()), "aptp_loss_stage_bwd")
         return self.grads
+
+
+def _check_valid(valid: torch.Tensor, B: int, device, what: str):
+    assert valid.dtype == torch.float32 and valid.is_contiguous() and valid.numel() == B and valid.device == device, \
+        f"{what}: valid = fp32 [B] on the operands' device"
+
+
+def sinkhorn_assign(scores: torch.Tensor, valid: torch.Tensor, eps: float, iters: int, out: Optional[torch.Tensor] = None,
+                    q: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The quantiser's Sinkhorn assignment over the valid samples of a batch in ONE launch (csrc/router_stage.hip):
+    scores fp32 [B, K] (rows at any pitch), valid fp32 [B] of 0 and 1 -> idx int64 [B] (`out` when given).  A sample that is not
+    valid gets the argmax of its own raw scores.  q: fp32 [B, K] contiguous, the kernel's workspace and, afterwards, the
+    transport plan (zeros on the rows that are not valid); allocated when not given.  Everything is read at launch time: safe to
+    capture and replay while scores, valid, out and q stay where they are."""
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2 and scores.stride(1) == 1, \
+        "sinkhorn_assign: scores = fp32 [B, K] with contiguous rows on the GPU"
+    B, K = scores.shape
+    _check_valid(valid, B, scores.device, "sinkhorn_assign")
+    if out is None:
+        out = torch.empty(B, dtype=torch.int64, device=scores.device)
+    if q is None:
+        q = torch.empty((B, K), dtype=torch.float32, device=scores.device)
+    assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == B and out.device == scores.device
+    assert q.dtype == torch.float32 and q.is_contiguous() and q.shape == (B, K) and q.device == scores.device
+    p = SinkhornParams()
+    p.scores, p.ld, p.valid, p.idx, p.q = scores.data_ptr(), (scores.stride(0) if B > 1 else K), valid.data_ptr(), out.data_ptr(), q.data_ptr()
+    p.B, p.K, p.iters, p.eps = B, K, int(iters), float(eps)
+    _lib.check(_lib.load().aptp_sinkhorn_assign(ctypes.byref(p), _stream()), "aptp_sinkhorn_assign")
+    return out
+
+
+class RouterStage:
+    """The router's batch-coupled losses of a pruning step whose batch may be short (csrc/router_stage.hip): the contrastive loss
+    and the three MAC losses over the samples present, and their gradients.
+
+    text fp32 [B, D] (no gradient), arch fp32 [B, E] (the width_depth_normalize'd architecture vectors), ratios fp32 [B] (the
+    per-sample prunable-MAC ratios), valid fp32 [B] of 0 and 1 in any pattern (None: all ones); B <= 1024, E and D <= 4096.
+    The constants are baked in at construction: the two temperatures, the resource target `p` and type ("log" | "mae" | "mse"),
+    the four weights.  run() is three launches and returns `out` (fp32 [8]: contrastive, resource, max_loss, std_loss,
+    router_loss, mean ratio, n, the number of samples at the maximum); backward(g) two launches that write the gradient of
+    g * router_loss as (d_arch [B, E], d_ratios [B]) -- the same tensors on every call, rows of samples that are not valid as
+    zeros.  Everything either reads at launch time -- the operands, valid, n, g -- is device memory, and all buffers are allocated
+    here, once per object (a captured router builds one per phase; an eager router one per step, on that step's tensors): both are
+    safe to capture and replay while the operands stay where they are."""
+
+    def __init__(self, text: torch.Tensor, arch: torch.Tensor, ratios: torch.Tensor, valid: Optional[torch.Tensor] = None, *,
+                 arch_temperature: float = 1.0, text_temperature: float = 1.0, p: float = 0.9, resource_type: str = "log",
+                 resource_weight: float = 1.0, contrastive_weight: float = 1.0, std_weight: float = 0.0, max_weight: float = 0.0):
+        lib = _lib.load()
+        self.grad_inputs = [arch, ratios]                  # with their autograd history: what autograd.router_stage applies to
+        self.text_requires_grad = bool(text.requires_grad)
+        text, arch, ratios = text.detach(), arch.detach(), ratios.detach()
+        for name, t in (("text", text), ("arch", arch)):
+            assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1, \
+                f"RouterStage: {name} = fp32 [B, features] with contiguous rows on the GPU"
+        B, E = arch.shape
+        D = text.shape[1]
+        dev = arch.device
+        assert text.shape[0] == B and text.device == dev, "RouterStage: text and arch have one row per sample"
+        assert ratios.dtype == torch.float32 and ratios.is_contiguous() and ratios.numel() == B and ratios.device == dev, \
+            "RouterStage: ratios = fp32 [B] on the operands' device"
+        assert resource_type in _lib.RESOURCE_TYPES, f"RouterStage: unknown resource type {resource_type!r}"
+        if valid is None:
+            valid = torch.ones(B, dtype=torch.float32, device=dev)
+        _check_valid(valid, B, dev, "RouterStage")
+        q = RouterStageParams()
+        q.text, q.ld_text = text.data_ptr(), (text.stride(0) if B > 1 else D)
+        q.arch, q.ld_arch = arch.data_ptr(), (arch.stride(0) if B > 1 else E)
+        q.ratios, q.valid = ratios.data_ptr(), valid.data_ptr()
+        q.B, q.E, q.D, q.resource_type = B, E, D, _lib.RESOURCE_TYPES[resource_type]
+        q.tau_arch, q.tau_text, q.p = float(arch_temperature), float(text_temperature), float(p)
+        q.w_resource, q.w_contrastive, q.w_std, q.w_max = float(resource_weight), float(contrastive_weight), float(std_weight), float(max_weight)
+        n_work = lib.aptp_router_stage_work_floats(B, E, D)
+        self.work = scratch._alloc(max(int(n_work), 1), torch.float32, dev, zero=False)
+        self.out = scratch._alloc(8, torch.float32, dev, zero=False)
+        self.d_arch = scratch._alloc(B * E, torch.float32, dev, zero=False).view(B, E)
+        self.d_ratios = scratch._alloc(B, torch.float32, dev, zero=False).view(ratios.shape)
+        q.work, q.out, q.d_arch, q.ld_darch, q.d_ratios = self.work.data_ptr(), self.out.data_ptr(), self.d_arch.data_ptr(), E, self.d_ratios.data_ptr()
+        self.text, self.arch, self.ratios, self.valid = text, arch, ratios, valid
+        self.B, self.E, self.D = B, E, D
+        self._g, self._p, self._lib = None, q, lib
+
+    contrastive = property(lambda self: self.out[0])
+    resource = property(lambda self: self.out[1])
+    max_loss = property(lambda self: self.out[2])
+    std_loss = property(lambda self: self.out[3])
+    router_loss = property(lambda self: self.out[4])
+    mean_ratio = property(lambda self: self.out[5])
+    n_valid = property(lambda self: self.out[6])
+
+    def run(self) -> torch.Tensor:
+        """three launches on the current stream; returns `out`, which the next run() overwrites"""
+        _lib.check(self._lib.aptp_router_stage(ctypes.byref(self._p), _stream()), "aptp_router_stage")
+        return self.out
+
+    def backward(self, g: torch.Tensor):
+        """two launches after run(): (d_arch, d_ratios) of g * router_loss.  g: fp32 device scalar."""
+        assert g.is_cuda and g.dtype == torch.float32 and g.numel() == 1, "RouterStage.backward: g is an fp32 device scalar"
+        self._g = g.detach().reshape(1)
+        self._p.g = self._g.data_ptr()
+        _lib.check(self._lib.aptp_router_stage_bwd(ctypes.byref(self._p), _stream()), "aptp_router_stage_bwd")
+        return self.d_arch, self.d_ratios
 
 
 def fold_rows(partials: torch.Tensor, n_rows: int, C: int, out: Optional[torch.Tensor] = None,

@@ -68,14 +68,16 @@ class StructureVectorQuantizer(nn.Module):
         self.fused_sinkhorn_allreduce = fused_sinkhorn_allreduce
 
     # ---- forward (quantizer.py:136-169) ---------------------------------------------------------------------------
-    def forward(self, z: torch.Tensor) -> Tuple[torch.Tensor, Tuple]:
+    def forward(self, z: torch.Tensor, valid: torch.Tensor = None) -> Tuple[torch.Tensor, Tuple]:
+        """valid: fp32 [B] of 0 and 1 on z's device (a short batch staged into a full one): the optimal-transport assignment then
+        couples the valid samples only, and a sample that is not valid gets the code nearest to it (the eval branch's rule)"""
         z = z.contiguous()
         z_flat = z.view(-1, self.vq_embed_dim)
         if self.training:
             codes = self.gumbel_sigmoid_trick(self.embedding.weight)      # gradient reaches the codebook
             self.embedding_gs.data = codes.detach()
             if self.optimal_transport:
-                idx = self.get_optimal_transport_min_encoding_indices(z_flat)
+                idx = self.get_optimal_transport_min_encoding_indices(z_flat, valid)
             else:
                 idx = self.get_cosine_sim_min_encoding_indices(z_flat)
         else:
@@ -239,10 +241,18 @@ class StructureVectorQuantizer(nn.Module):
         return full[rank * n:(rank + 1) * n]
 
     @torch.no_grad()
-    def get_optimal_transport_min_encoding_indices(self, a: torch.Tensor) -> torch.Tensor:
+    def get_optimal_transport_min_encoding_indices(self, a: torch.Tensor, valid: torch.Tensor = None) -> torch.Tensor:
         a = self._unit(self.gumbel_sigmoid_trick(a))
         codes = self._unit(self.embedding_gs)
         out = a @ codes.t()
+        if valid is not None:
+            # the masked assignment is one HIP launch that reads `valid` on the device; there is no other implementation of it
+            if dist.is_available() and dist.is_initialized():
+                raise NotImplementedError("a valid mask under a process group: the distributed Sinkhorn does not gather it")
+            if not out.is_cuda:
+                raise NotImplementedError("a valid mask needs the GPU: the masked Sinkhorn assignment is a HIP kernel")
+            from . import ops
+            return ops.sinkhorn_assign(out.float().contiguous(), valid, self.sinkhorn_epsilon, self.sinkhorn_iterations)
         if dist.is_available() and dist.is_initialized():
             Q = self._sinkhorn_fused(out) if self.fused_sinkhorn_allreduce else self._sinkhorn(out, True)
         else:

@@ -412,14 +412,34 @@ def _stage_short_batch(st: dict, batch, data_parallel: bool = False) -> int:
             st[k][:n].copy_(batch[k])
             if n < B:
                 st[k][n:].copy_(batch[k][0:1])           # (broadcast over the missing rows)
-        given = batch.get("valid")
+        _stage_valid(st["valid"], batch.get("valid"), n)
+    return n
+
+
+def _stage_valid(valid: torch.Tensor, given: Optional[torch.Tensor], n: int) -> None:
+    """the mask of a batch of 1 <= n <= B rows on the current stream: 1 for the first n entries (or the batch's own vector), 0 behind"""
+    with torch.no_grad():
         if given is not None:
             assert int(given.shape[0]) == n, "batch['valid'] has one entry per sample of the batch"
-            st["valid"][:n].copy_(given)
+            valid[:n].copy_(given)
         else:
-            st["valid"][:n].fill_(1.0)
+            valid[:n].fill_(1.0)
+        if n < int(valid.shape[0]):
+            valid[n:].zero_()
+
+
+def _stage_short_rows(static: torch.Tensor, rows: torch.Tensor) -> int:
+    """_stage_short_batch's rule for one more per-sample tensor (the pruning step's prompt embeddings): rows [0, n) are `rows`,
+    the rows behind them its own first row.  Returns n; nothing is staged for n = 0."""
+    B, n = int(static.shape[0]), int(rows.shape[0])
+    if n > B:
+        raise ValueError(f"a batch of {n} samples does not fit the step captured for {B}")
+    if n == 0:
+        return 0
+    with torch.no_grad():
+        static[:n].copy_(rows)
         if n < B:
-            st["valid"][n:].zero_()
+            static[n:].copy_(rows[0:1])
     return n
 
 
@@ -511,16 +531,29 @@ class PrunerStep:
         self.resource.p = float(1 - (1 - p) * info["total_macs"] / float(torch.as_tensor(info["cur_prunable_macs"]).flatten()[0]))
 
     # ---- the router head and the MAC losses: one definition for the eager, the validation and the captured paths ----------------
-    def _route(self, text_embeddings, pretrain: bool):
-        """hyper-net -> quantiser -> Gumbel-sigmoid relaxation -> cross-rank gather -> contrastive loss (trainer.py:1129-1171).
-        Returns (arch_vector, arch_vector_quantized, arch_used, contrastive_loss); arch_used is the code the student runs under."""
+    def _route_head(self, text_embeddings, pretrain: bool, valid: Optional[torch.Tensor] = None):
+        """hyper-net -> quantiser -> Gumbel-sigmoid relaxation -> normalisation (trainer.py:1129-1138, 1165-1168).  Returns
+        (arch_vector, arch_vector_quantized, arch_used, arch_wdn): arch_used is the code the student runs under, arch_wdn the
+        width_depth_normalize'd vectors the contrastive loss reads.  valid (fp32 [B] of 0 and 1 on the device: a short batch
+        staged into a full one, no process group): the quantiser's assignment couples the valid samples only."""
         arch_vector = self.hyper_net(text_embeddings)                                           # :1129
-        arch_vector_quantized, _ = self.quantizer(arch_vector)                                  # :1130
+        if valid is None:
+            arch_vector_quantized, _ = self.quantizer(arch_vector)                              # :1130
+        else:
+            arch_vector_quantized, _ = self.quantizer(arch_vector, valid=valid)
         arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)                          # :1132
         arch_vector = self._single_arch_repeat(arch_vector, text_embeddings.shape[0])           # :1134-1136
         arch_wdn = self.quantizer.width_depth_normalize(arch_vector)                            # :1138
-        text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)                  # :1147-1162 (one collective)
         arch_used = arch_vector if pretrain else arch_vector_quantized                          # :1165-1168
+        return arch_vector, arch_vector_quantized, arch_used, arch_wdn
+
+    def _route(self, text_embeddings, pretrain: bool):
+        """_route_head -> cross-rank gather -> contrastive loss (trainer.py:1129-1171).
+        Returns (arch_vector, arch_vector_quantized, arch_used, contrastive_loss).  A masked step does not come through here: it
+        takes _route_head(valid=) and forms the contrastive loss with the MAC losses in one ops.RouterStage
+        (_masked_router_losses, GraphedPrunerStep._router_forward)."""
+        arch_vector, arch_vector_quantized, arch_used, arch_wdn = self._route_head(text_embeddings, pretrain)
+        text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)                  # :1147-1162 (one collective)
         contrastive_loss = self.contrastive(text_all, arch_all)                                 # :1170-1171
         return arch_vector, arch_vector_quantized, arch_used, contrastive_loss
 
@@ -531,6 +564,17 @@ class PrunerStep:
         max_loss = 1.0 - torch.max(ratios)
         std_loss = -torch.std(ratios)
         return ratios, resource_loss, max_loss, std_loss
+
+    def _masked_router_losses(self, text_embeddings, arch_wdn, macs, valid) -> "ops.RouterStage":
+        """the contrastive loss, _mac_losses and the router's weighted sum over the samples `valid` marks as ONE ops.RouterStage
+        (csrc/router_stage.hip), with this step's constants baked in (count_macs comes first: it sets the resource target)"""
+        cfg = self.cfg
+        ratios = macs["cur_prunable_macs"] / self.unet.resource_info_dict["cur_prunable_macs"].squeeze()
+        return ops.RouterStage(text_embeddings, arch_wdn, ratios.float().contiguous(), valid,
+                               arch_temperature=cfg.arch_vector_temperature, text_temperature=cfg.prompt_embedding_temperature,
+                               p=float(self.resource.p), resource_type=self.resource.loss_type,
+                               resource_weight=cfg.resource_weight, contrastive_weight=cfg.contrastive_weight,
+                               std_weight=cfg.std_weight, max_weight=cfg.max_weight)
 
     def _unet_losses(self, model_pred, student_acts, full_pred, teacher_acts, w, target):
         """the three U-Net terms in the pruner's order -- diffusion, output distillation, block distillation (trainer.py:1197-1225);
@@ -653,8 +697,7 @@ class PrunerStep:
         out = {}
 
         def run():
-            out.update(self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
-                                 batch["mpnet_embeddings"], batch["target"], pretrain=pretrain))
+            out.update(self._step_on(batch, pretrain))
             self.backward(out)
         key, probed = self._probe_phase_table(optimizer, pretrain, run)
         if not probed:
@@ -670,6 +713,10 @@ class PrunerStep:
             if optimizer.grad_norm is not None:
                 out["grad_norm"] = optimizer.grad_norm.norm.clone()
         return out
+
+    def _step_on(self, batch: dict, pretrain: bool):
+        return self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
+                         batch["mpnet_embeddings"], batch["target"], pretrain=pretrain)
 
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
         """forward + backward + fused gradient all-reduce + optimizer step (trainer.py:913-933)"""
@@ -698,10 +745,22 @@ class GraphedPrunerStep(PrunerStep):
     Each step the router runs eagerly (it draws host-side Gumbel noise, quirk Q6, and is tiny), its architecture code is
     copied into the static buffer the 84 gate views alias, the graphs are replayed, and the chain rule is closed eagerly:
     ``autograd.backward([router-only losses, arch code], [None, captured gradient w.r.t. the code])``.
-    Losses and router gradients equal the eager step's (tests/test_train_step_gpu.py)."""
+    Losses and router gradients equal the eager step's (tests/test_train_step_gpu.py).
 
-    def __init__(self, *a, **k):
+    short_batches=True: capture(batch) fixes the LARGEST batch; step / train_step then take any 0 <= n <= B samples (or B samples
+    with a "valid" vector) through the same graphs.  The three U-Net terms come from one masked ops.LossStage, the router's
+    batch-coupled pieces -- Sinkhorn assignment, contrastive loss, MAC losses -- from ops.sinkhorn_assign and one ops.RouterStage,
+    all reading `valid` on the device; the rows behind a short batch are its own first row and reach nothing.  The dict gains
+    "n_valid" and "skipped"; an empty batch replays nothing, draws no noise and touches no state.  The Gumbel draws stay B rows
+    per call from the host generator: the host stream advances by the same amount whatever n is, which is NOT the stream an eager
+    n-row step would consume.  Not under a process group."""
+
+    def __init__(self, *a, short_batches: bool = False, **k):
+        if short_batches and torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise NotImplementedError("GraphedPrunerStep(short_batches=True) under a process group: the router runs eagerly there, "
+                                      "its collectives are not captured and `valid` is not gathered")
         super().__init__(*a, **k)
+        self.short_batches = bool(short_batches)
         self._cap = None
         self.stream_probe = []          # what graph_utils.concurrent_stream measured when it chose the teacher's / router's side streams
         self.overlap_router = os.environ.get("APTP_OVERLAP_ROUTER", "1") != "0"
@@ -744,6 +803,10 @@ class GraphedPrunerStep(PrunerStep):
         self._schedule_on(dev)
         st["snr_w"] = _min_snr_weights(cfg, self.schedule, st["timesteps"])
         B = st["noisy_latents"].shape[0]
+        short = self.short_batches
+        if short:
+            st["valid"] = torch.ones(int(B), dtype=torch.float32, device=dev)
+            st["text"] = batch["mpnet_embeddings"].clone()         # what the eager router reads; a captured phase has its own
         ones = torch.ones((B, self.quantizer.vq_embed_dim), device=dev)
         full = self.hyper_net.transform_structure_vector(ones)
         # ONE static buffer holds the student's architecture code, SEGMENT-MAJOR: gate j's [B, w_j] block is contiguous, so
@@ -779,6 +842,8 @@ class GraphedPrunerStep(PrunerStep):
         from .macs import VectorizedMacs
         vmacs = VectorizedMacs(self.unet, device=dev)
 
+        keep_stage = []                                    # the masked loss stage of the last student_bwd call (short_batches)
+
         def teacher():
             # own split-K counters / scratch: this graph replays NEXT TO the student's forward (ops.scratch_domain)
             with torch.no_grad(), ops.scratch_domain("teacher"):
@@ -793,6 +858,18 @@ class GraphedPrunerStep(PrunerStep):
             return pred, dict(self.block_activations)
 
         def student_bwd(pred, acts, full_pred, teacher_acts):
+            if short:
+                # _unet_losses and _unet_loss as ONE masked stage, in the pruner's term order: diffusion, distillation, blocks
+                weighted = cfg.snr_gamma is not None
+                terms = [ops.LossTerm(pred, st["target"], 0, 1.0, weighted), ops.LossTerm(pred, full_pred.detach(), 1)]
+                terms += [ops.LossTerm(acts[k], teacher_acts[k].detach(), 2) for k in acts]
+                stage = ops.LossStage(terms, (1.0, cfg.distillation_weight, cfg.block_weight), weights=st["snr_w"] if weighted else None,
+                                      valid=st["valid"], group_div=(0.0, 0.0, float(len(acts))))
+                grads = torch.autograd.grad(AG.loss_stage(stage), gw + gd, allow_unused=True)
+                flat = torch.cat([(torch.zeros_like(t) if g is None else g).reshape(-1) for g, t in zip(grads, gw + gd)])
+                o = stage.out                              # [diffusion, distillation, block, total, n]
+                keep_stage.append(stage)
+                return o[0], o[1], o[2], flat[inv].view(B, E)
             loss, dist, blk = self._unet_losses(pred, acts, full_pred, teacher_acts, st["snr_w"], st["target"])
             grads = torch.autograd.grad(self._unet_loss(loss, dist, blk), gw + gd, allow_unused=True)
             flat = torch.cat([(torch.zeros_like(t) if g is None else g).reshape(-1) for g, t in zip(grads, gw + gd)])
@@ -832,13 +909,24 @@ class GraphedPrunerStep(PrunerStep):
         self._cap = dict(st=st, ga=ga, install_code=install_code, perm=perm, inv=inv, full=full, pred=pred, acts=acts, teacher_acts=teacher_acts, gw=gw, gd=gd, g_teacher=g_teacher, g_student=g_student, g_student_bwd=g_student_bwd,
                          loss=loss, dist=dist, blk=blk, grad=grad, full_pred=full_pred, side=concurrent_stream(log=self.stream_probe), vmacs=vmacs,
                          launch_log=launch_log, router=None)
+        if short:
+            self._cap["loss_stage"] = keep_stage[-1]
+            self._cap["n_valid"] = keep_stage[-1].out[4]
         if optimizer is not None and not (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self._capture_router(batch, optimizer, pretrain)           # (`dist` is the distillation loss in this scope)
         return self
 
     # ---- the router as two more graphs per training phase -------------------------------------------
-    def _router_forward(self, text_embeddings, pretrain: bool):
-        """the router head and its own losses, MACs from the router-connected code (step() up to the student's code)"""
+    def _router_forward(self, text_embeddings, pretrain: bool, valid: Optional[torch.Tensor] = None):
+        """the router head and its own losses, MACs from the router-connected code (step() up to the student's code); with
+        `valid` everything that couples the samples of the batch runs masked (quantiser, one ops.RouterStage)"""
+        if valid is not None:
+            _, arch_vector_quantized, arch_used, arch_wdn = self._route_head(text_embeddings, pretrain, valid)
+            stage = self._masked_router_losses(text_embeddings, arch_wdn, self._cap["vmacs"](arch_used), valid)
+            router_loss = AG.router_stage(stage)
+            return dict(arch_used=arch_used, arch_vector_quantized=arch_vector_quantized, contrastive_loss=stage.contrastive,
+                        resource_loss=stage.resource, ratios=stage.grad_inputs[1], resource_ratio=stage.mean_ratio,
+                        std_loss=stage.std_loss, router_loss=router_loss, stage=stage)
         _, arch_vector_quantized, arch_used, contrastive_loss = self._route(text_embeddings, pretrain)
         # MAC accounting is differentiable in the gates (calc_macs family): VectorizedMacs evaluates it on the router-connected
         # architecture vector directly (same numbers as unet.calc_macs() after set_structure, tests/test_macs_pinned.py) in
@@ -882,15 +970,18 @@ class GraphedPrunerStep(PrunerStep):
             assert optimizer.defaults.get("capturable", False), "GraphedPrunerStep.capture(optimizer=): the optimizer must be capturable"
             rt = None
         text = batch["mpnet_embeddings"].clone()
+        # a phase's router graphs replay on the router's stream next to the NEXT step's staging on the caller's: they read a mask of
+        # their own, staged on that stream like `text` (st["valid"] belongs to the loss stage and the eager router, on the caller's)
+        valid = torch.ones_like(cap["st"]["valid"]) if self.short_batches else None
         tape = EU.NoiseTape()
         host_rng = torch.get_rng_state()
-        ph = dict(text=text, tape=tape)
+        ph = dict(text=text, tape=tape, valid=valid)
 
         def fwd():
             tape.begin()
             EU.NOISE_TAPE = tape
             try:
-                r = self._router_forward(text, pretrain)
+                r = self._router_forward(text, pretrain) if valid is None else self._router_forward(text, pretrain, valid)
             finally:
                 EU.NOISE_TAPE = None
             with torch.no_grad():
@@ -990,15 +1081,29 @@ class GraphedPrunerStep(PrunerStep):
         return n
 
     # ---- one step -------------------------------------------------------------------------------------------------------
-    def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False):
+    def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False,
+             valid: Optional[torch.Tensor] = None):
+        """valid: short_batches only -- one entry per sample of this batch (samples masked without compacting them)"""
         if self._cap is None:
+            assert valid is None and not self.short_batches, "GraphedPrunerStep(short_batches=True): call capture(batch) first"
             return super().step(noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain)
         cap = self._cap
+        assert valid is None or self.short_batches, "step(valid=): only under short_batches=True"
         # The teacher depends on the batch only: its graph replays on a side stream WHILE the router (launch-bound kernels of a
         # few microseconds each, during which the GPU is mostly idle) is being issued on this stream.
         # Order on the device: batch copies -> [teacher graph || router] -> student graph.
-        self._stage_batch_and_launch_teacher(noisy_latents, timesteps, encoder_hidden_states, target)
-        r = self._router_forward(text_embeddings, pretrain)
+        if self.short_batches:
+            batch = dict(zip(_BATCH_KEYS, (noisy_latents, timesteps, encoder_hidden_states, target)))
+            if valid is not None:
+                batch["valid"] = valid
+            if _stage_short_batch(cap["st"], batch) == 0:
+                return self._skipped_step()
+            _stage_short_rows(cap["st"]["text"], text_embeddings)
+            self._launch_teacher()
+            r = self._router_forward(cap["st"]["text"], pretrain, cap["st"]["valid"])
+        else:
+            self._stage_batch_and_launch_teacher(noisy_latents, timesteps, encoder_hidden_states, target)
+            r = self._router_forward(text_embeddings, pretrain)
         with torch.no_grad():
             cap["install_code"](r["arch_used"])
         cap["g_student"].replay()                                     # forward: needs the code only
@@ -1006,8 +1111,25 @@ class GraphedPrunerStep(PrunerStep):
         cap["g_student_bwd"].replay()                                 # losses against the teacher + backward to the code
         return {**self._captured_losses(r["router_loss"]),
                 "contrastive_loss": r["contrastive_loss"].detach(), "resource_loss": r["resource_loss"].detach(),
-                "resource_ratio": r["ratios"].mean().detach(), "arch_vector_quantized": r["arch_vector_quantized"].detach(),
-                "_router_loss": r["router_loss"], "_gate_tensors": [r["arch_used"]], "_gate_grads": [cap["grad"]]}
+                "resource_ratio": self._resource_ratio(r), "arch_vector_quantized": r["arch_vector_quantized"].detach(),
+                "_router_loss": r["router_loss"], "_gate_tensors": [r["arch_used"]], "_gate_grads": [cap["grad"]],
+                **self._short_batch_report(r)}
+
+    @staticmethod
+    def _resource_ratio(r):
+        """the mean prunable-MAC ratio a step reports: over the samples present where the router ran masked"""
+        return r["resource_ratio"].detach().clone() if "stage" in r else r["ratios"].mean().detach()
+
+    def _short_batch_report(self, r):
+        if not self.short_batches:
+            return {}
+        return {"n_valid": self._cap["n_valid"].clone(), "skipped": False, "std_loss": r["std_loss"].detach().clone()}
+
+    def _skipped_step(self):
+        """an empty batch under short_batches: nothing was staged, replayed or drawn"""
+        zero = torch.zeros((), dtype=torch.float32, device=self._cap["st"]["valid"].device)
+        keys = ("loss", "diff_loss", "distillation_loss", "block_loss", "contrastive_loss", "resource_loss", "resource_ratio", "n_valid")
+        return {**{k: zero.clone() for k in keys}, "applied": zero.reshape(1).clone(), "skipped": True}
 
     def _captured_losses(self, router_loss):
         """the step's total and the three U-Net terms as clones of g_student_bwd's static outputs (the next replay overwrites them)"""
@@ -1016,8 +1138,11 @@ class GraphedPrunerStep(PrunerStep):
                 "diff_loss": cap["loss"].clone(), "distillation_loss": cap["dist"].clone(), "block_loss": cap["blk"].clone()}
 
     def _stage_batch_and_launch_teacher(self, noisy_latents, timesteps, encoder_hidden_states, target):
+        _stage_batch(self._cap["st"], (noisy_latents, timesteps, encoder_hidden_states, target))
+        self._launch_teacher()
+
+    def _launch_teacher(self):
         cap = self._cap
-        _stage_batch(cap["st"], (noisy_latents, timesteps, encoder_hidden_states, target))
         side = cap["side"]                       # (the min-SNR weights are computed from the staged timesteps inside g_teacher)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -1033,7 +1158,19 @@ class GraphedPrunerStep(PrunerStep):
         gs = [g for t, g in zip(out["_gate_tensors"], out["_gate_grads"]) if t.requires_grad]
         torch.autograd.backward([out["_router_loss"]] + ts, [None] + gs)
 
+    def _step_on(self, batch: dict, pretrain: bool):
+        return self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
+                         batch["mpnet_embeddings"], batch["target"], pretrain=pretrain,
+                         valid=batch.get("valid") if self.short_batches else None)
+
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
+        if self.short_batches:
+            assert self._cap is not None, "GraphedPrunerStep(short_batches=True): call capture(batch) first"
+            B, n = int(self._cap["st"]["valid"].shape[0]), int(batch["noisy_latents"].shape[0])
+            if n > B:
+                raise ValueError(f"a batch of {n} samples does not fit the step captured for {B}")
+            if n == 0:
+                return self._skipped_step()              # before anything: no probe, no zero_grad, no noise, no replay
         rt = self._cap.get("router") if self._cap is not None else None
         ph = rt.get(bool(pretrain)) if rt and rt["optimizer"] is optimizer else None
         if ph is not None and self.hyper_net.training:
@@ -1042,8 +1179,7 @@ class GraphedPrunerStep(PrunerStep):
             return self._train_step_eager_router_hip(optimizer, batch, bool(pretrain))
         self.finish()
         optimizer.zero_grad(set_to_none=True)
-        out = self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
-                        batch["mpnet_embeddings"], batch["target"], pretrain=pretrain)
+        out = self._step_on(batch, pretrain)
         self.backward(out)
         allreduce_mean_grads(self.trainable_parameters())
         optimizer.step()
@@ -1065,11 +1201,21 @@ class GraphedPrunerStep(PrunerStep):
         main = torch.cuda.current_stream()
         rs = rt["stream"] if self.overlap_router else main
         rt["ev_entry"].record(main)                           # the batch tensors were produced on the caller's stream
-        self._stage_batch_and_launch_teacher(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"], batch["target"])
+        if self.short_batches:
+            _stage_short_batch(cap["st"], batch)              # (train_step returned before this for an empty batch)
+            self._launch_teacher()
+        else:
+            self._stage_batch_and_launch_teacher(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"], batch["target"])
         with torch.cuda.stream(rs):
             rs.wait_event(rt["ev_entry"])
-            with torch.no_grad():
-                ph["text"].copy_(batch["mpnet_embeddings"])
+            if self.short_batches:
+                # both operands of the router graphs are written HERE, on the stream that replays them: behind the previous step's
+                # g_bwd (same stream), ahead of this step's g_fwd, and behind ev_entry (the batch's own tensors)
+                _stage_short_rows(ph["text"], batch["mpnet_embeddings"])
+                _stage_valid(ph["valid"], batch.get("valid"), int(batch["mpnet_embeddings"].shape[0]))
+            else:
+                with torch.no_grad():
+                    ph["text"].copy_(batch["mpnet_embeddings"])
             ph["tape"].refill()                               # host-RNG stream, consumed exactly as the eager calls consume it
             ph["g_fwd"].replay()                              # router -> architecture code installed for the student
             rt["ev_code"].record(rs)
@@ -1088,10 +1234,12 @@ class GraphedPrunerStep(PrunerStep):
         rt["pending"] = rs is not main
         r = ph["out"]
         # (the router graph's outputs were complete at ev_code; the next router forward, which overwrites them, waits for the next
-        #  step's ev_entry, i.e. for these clones)
+        #  step's ev_entry, i.e. for these clones.  Under short_batches nothing the router graphs read is written on this stream:
+        #  ph["text"] and ph["valid"] are staged on the router's stream, st["valid"] is read by g_student_bwd on this one only)
         out = {**self._captured_losses(r["router_loss"]),
                "contrastive_loss": r["contrastive_loss"].detach().clone(), "resource_loss": r["resource_loss"].detach().clone(),
-               "resource_ratio": r["ratios"].mean().detach(), "arch_vector_quantized": r["arch_vector_quantized"].detach().clone()}
+               "resource_ratio": self._resource_ratio(r), "arch_vector_quantized": r["arch_vector_quantized"].detach().clone(),
+               **self._short_batch_report(r)}
         if applied is not None:
             applied.record_stream(main)
             out["applied"] = applied

@@ -988,6 +988,69 @@ int aptp_loss_stage(const AptpLossStageParams* p, aptp_stream_t stream);
 int aptp_loss_stage_bwd_nblocks(const AptpLossStageParams* p);      /* workgroups of the gradient launch; 0 for a refused table */
 int aptp_loss_stage_bwd(const AptpLossStageParams* p, aptp_stream_t stream);
 
+/* The router's batch-coupled stage of a PRUNING step whose batch may be short (Pruner.step, pdm/training/trainer.py:1129-1249):
+ * what couples the samples of a batch outside the U-Net terms, over the samples present.  valid: fp32 [B] of 0 and 1 in any
+ * pattern, read at launch time; V = {b: valid[b] != 0}, n = sum_b valid[b].  fp32 throughout, every sum in one fixed order, no
+ * atomics: the same bits at every replay.  A sample outside V is skipped, not multiplied by 0: a NaN in its rows reaches nothing.
+ *
+ * aptp_sinkhorn_assign, ONE launch: the quantiser's Sinkhorn assignment (pdm/models/vq/quantizer.py:263-340) over V.
+ *   scores fp32 [B, K] at pitch ld -> idx int64 [B]; q: fp32 [B, K] contiguous, workspace AND output (the transport plan, for
+ *   tests).  q = exp(scores / eps) on the rows of V; q /= sum(q); `iters` times: columns (codes) /= their sum over V, /= K, rows
+ *   (samples) /= their sum, /= n; q *= n; idx[b] = first argmax_k q[b][k].  A sample outside V -- every sample when n = 0 -- gets
+ *   the first argmax of its own raw score row (the quantiser's eval branch: a real code that depends on no other sample) and a
+ *   q row of zeros.  A NaN counts as the maximum, as torch.argmax has it.
+ *
+ * aptp_router_stage, three launches: the contrastive loss (pdm/losses/contrastive_loss.py:5-22) and the MAC losses
+ * (trainer.py:1227-1238, pdm/losses/resource_loss.py:5-23) over V.  text fp32 [B, D], arch fp32 [B, E] (row pitches ld_*),
+ * ratios fp32 [B].  With Â_i = arch_i / |arch_i|, Ẑ_i = text_i / |text_i|, P = softmax_row(Â Â^T / tau_arch) and
+ * T = softmax_row(Ẑ Ẑ^T / tau_text) over V x V, rbar / rmax / sd the mean, maximum and unbiased deviation of ratios over V:
+ *   out[0] contrastive = -(1/n^2) sum_{i,j in V} [T_ij log P_ij + (1 - T_ij) log(1 - P_ij)], each log clamped at -100; where
+ *          P_ij > 1/2, 1 - P_ij is formed from the other exponentials of the row
+ *   out[1] resource    = LOG: log(rbar > p ? rbar / p : p / rbar);  MAE: |rbar - p|;  MSE: (rbar - p)^2
+ *   out[2] max_loss    = 1 - rmax
+ *   out[3] std_loss    = -sd          (n = 1: NaN, as torch.std)
+ *   out[4] router_loss = w_resource * out[1] + w_contrastive * out[0] + w_std * out[3] + w_max * out[2], in this order
+ *   out[5] rbar;  out[6] n;  out[7] the number of samples of V with ratios == rmax.        n = 0: all eight are 0.
+ * aptp_router_stage_bwd, two launches, after aptp_router_stage on the same block: the gradient of g[0] * router_loss (g: fp32
+ * device scalar) as d_arch fp32 [B, E] at pitch ld_darch and d_ratios fp32 [B].  BCE backward as torch has it,
+ * dP_ij = (P_ij - T_ij) / max(P_ij (1 - P_ij), 1e-12) / n^2; the row-softmax backward; dÂ = (dS + dS^T) Â / tau_arch; the
+ * normalisation.  The maximum's gradient is shared evenly among the samples that attain it, the deviation's is 0 where sd is
+ * exactly 0 (torch.max, torch.std).  Rows of samples outside V are WRITTEN as zeros without reading the operands.
+ * The statistics of the ratios (rbar, sd, the resource term against the fp64 target p) are accumulated in fp64 and rounded once.
+ * work: fp32 [aptp_router_stage_work_floats(B, E, D)], written by the forward and read by the backward.
+ * APTP_EINVAL and nothing launched (no HIP call is made) for: a null block or pointer, B outside 1..1024, K outside 1..64, E or
+ * D outside 1..4096, a pitch below the row length, iters outside 0..1000, eps or a temperature <= 0, an unknown resource type. */
+#define APTP_ROUTER_STAGE_MAX_B 1024
+#define APTP_ROUTER_STAGE_MAX_FEATURES 4096
+#define APTP_SINKHORN_MAX_K 64
+enum { APTP_RESOURCE_LOG = 0, APTP_RESOURCE_MAE = 1, APTP_RESOURCE_MSE = 2 };
+typedef struct {
+  const float* scores; int64_t ld;
+  const float* valid;
+  int64_t* idx;
+  float* q;
+  int32_t B, K, iters;
+  float eps;
+} AptpSinkhornParams;
+int aptp_sinkhorn_assign(const AptpSinkhornParams* p, aptp_stream_t stream);
+typedef struct {
+  const float* text; int64_t ld_text;
+  const float* arch; int64_t ld_arch;
+  const float* ratios;
+  const float* valid;
+  const float* g;
+  float* work; float* out;
+  float* d_arch; int64_t ld_darch;
+  float* d_ratios;
+  int32_t B, E, D, resource_type;
+  float tau_arch, tau_text;
+  double p;
+  float w_resource, w_contrastive, w_std, w_max;
+} AptpRouterStageParams;
+int64_t aptp_router_stage_work_floats(int32_t B, int32_t E, int32_t D);    /* 0 for sizes out of range */
+int aptp_router_stage(const AptpRouterStageParams* p, aptp_stream_t stream);
+int aptp_router_stage_bwd(const AptpRouterStageParams* p, aptp_stream_t stream);
+
 /* Data-gradient operand from the forward operand of the same contraction (both in packed bf16 layout):
  * dst[c][taps-1-t][n] = src[n][t][c] for n < N, c < C, zero in the rest of dst's [dst_rows][taps][dst_ld] image.
  * (ops.pack_weight_dgrad of the same weights, without going through the diffusers layout.) */

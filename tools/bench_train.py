@@ -15,6 +15,57 @@ from diffusion_pruning_amd.train_step import GraphedPrunerStep, PrunerStep, synt
 from diffusion_pruning_amd.unet import UNet2DConditionModelGated  # noqa: E402
 
 
+def short_batches_ab(args, dev, unet, hn, qz):
+    """--short-batches: the default captured step and GraphedPrunerStep(short_batches=True), each with its own copy of the router
+    under a RouterAdamW with the router captured, in ONE process and in alternating rounds (the clocks of two processes differ by
+    more than these two steps do).  The switched step runs `--valid` samples of the batch (default: all but one)."""
+    import copy
+    from diffusion_pruning_amd import graph_utils
+    from diffusion_pruning_amd.router_optim import RouterAdamW
+    graph_utils.KEEP_GRAPHS = True
+    batch = synthetic_batch(args.batch, args.latent, dev)
+    n_valid = args.batch - 1 if args.valid is None else args.valid
+    assert 1 <= n_valid <= args.batch, "--valid: 1..batch"
+    short = {k: v[:n_valid] for k, v in batch.items()}
+    sides = {}
+    for name, kw, b in (("default", {}, batch), ("short_batches", {"short_batches": True}, short)):
+        h, q = copy.deepcopy(hn), copy.deepcopy(qz)
+        step = GraphedPrunerStep(unet, h, q, **kw)
+        step.count_macs(args.latent)
+        opt = RouterAdamW([{"params": [p for p in h.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0},
+                           {"params": [p for p in q.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0}])
+        step.capture(batch, optimizer=opt)
+        sides[name] = dict(step=step, opt=opt, batch=b, ms=[])
+    rounds = 4
+    for r in range(rounds + 1):                               # round 0 warms both up
+        for name, sd in sides.items():
+            for _ in range(args.warmup if r == 0 else 0):
+                sd["step"].train_step(sd["opt"], sd["batch"])
+            sd["step"].finish()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                out = sd["step"].train_step(sd["opt"], sd["batch"])
+            sd["step"].finish()
+            torch.cuda.synchronize()
+            if r:
+                sd["ms"].append((time.perf_counter() - t0) / args.steps * 1e3)
+            sd["loss"] = float(out["loss"])
+    res = {"metric": "pruning-train-steps/s, default captured step vs short_batches=True (same process, alternating rounds)",
+           "batch": args.batch, "latent": args.latent, "valid": n_valid, "steps_per_round": args.steps, "rounds": rounds}
+    for name, sd in sides.items():
+        best = min(sd["ms"])
+        res[name] = {"steps_per_s": round(1e3 / best, 3), "ms_per_step_best": round(best, 3), "ms_per_step_rounds": [round(m, 3) for m in sd["ms"]],
+                     "graph_nodes": sd["step"].graph_nodes(), "loss": sd["loss"], "applied_steps": sd["opt"].applied_steps(),
+                     "skipped_steps": sd["opt"].skipped_steps()}
+    line = json.dumps(res)
+    out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "bench_train_short_batches.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4)
@@ -33,6 +84,10 @@ def main():
                     help="hip: the curve of both groups' rates over the applied steps (RouterAdamW(lr_schedule=), DESIGN 6y), with "
                          "--lr-warmup as its warm-up: constant, constant_with_warmup, linear, cosine, cosine_with_restarts, polynomial")
     ap.add_argument("--max-train-steps", type=int, default=None, help="with --lr-scheduler: num_training_steps, in optimizer steps")
+    ap.add_argument("--short-batches", action="store_true",
+                    help="A/B of the default captured step and GraphedPrunerStep(short_batches=True) in one process; writes "
+                         "profiles/bench_train_short_batches.json")
+    ap.add_argument("--valid", type=int, default=None, help="with --short-batches: samples per step of the switched side (default batch - 1)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     unet = UNet2DConditionModelGated().init_synthetic(seed=0).to(dev)
@@ -44,6 +99,8 @@ def main():
                                   depth_order=[-1, -2, 0, 1, -3, -4, 2, 3, -5, -6, 4, 5, -7, 6],
                                   resource_aware_normalization=False, optimal_transport=True).to(dev)
     hn.train(); qz.train()
+    if args.short_batches:
+        return short_batches_ab(args, dev, unet, hn, qz)
     step = (PrunerStep if args.eager else GraphedPrunerStep)(unet, hn, qz)
     step.count_macs(args.latent)
     hip = args.router_optimizer == "hip"
