@@ -335,6 +335,30 @@ class RouterStageParams(Structure):
     ]
 
 
+GUMBEL_RELAX_MAX_R, GUMBEL_RELAX_MAX_E, GUMBEL_RELAX_MAX_SEG, GUMBEL_RELAX_MAX_ND = 65535, 4096, 1024, 64
+ROUTER_ASSIGN_SUBDRAW, ROUTER_RELAX_SUBDRAW = 6, 7          # csrc/gumbel_relax.h: APTP_TN_ROUTER_ASSIGN / _RELAX
+
+
+class GumbelRelaxParams(Structure):
+    _fields_ = [
+        ("z", c_void_p), ("out", c_void_p), ("dout", c_void_p), ("dz", c_void_p),
+        ("seeds", c_void_p), ("draw", c_void_p),
+        ("seg_start", c_void_p), ("depth_order", c_void_p),
+        ("seg_start_host", c_void_p), ("depth_order_host", c_void_p),
+        ("R", c_int32), ("nw", c_int32), ("nd", c_int32), ("n_seg", c_int32),
+        ("sub", c_int32), ("codebook", c_int32), ("non_zero_width", c_int32), ("reserved", c_int32),
+        ("T", c_float), ("base", c_float),
+    ]
+
+
+class PhiloxGumbelParams(Structure):
+    _fields_ = [
+        ("out", c_void_p), ("words", c_void_p), ("seeds", c_void_p), ("draw", c_void_p),
+        ("n", c_int64), ("offset", c_int64),
+        ("R", c_int32), ("sub", c_int32), ("codebook", c_int32), ("reserved", c_int32),
+    ]
+
+
 class GroupNormBwdParams(Structure):
     _fields_ = [
         ("x", c_void_p), ("ldx", c_int64), ("dy", c_void_p), ("lddy", c_int64), ("dx", c_void_p), ("lddx", c_int64),
@@ -715,6 +739,9 @@ EXPORTS = [
     ("aptp_router_stage_work_floats", c_int64, [c_int32, c_int32, c_int32]),
     ("aptp_router_stage", c_int, [POINTER(RouterStageParams), c_void_p]),
     ("aptp_router_stage_bwd", c_int, [POINTER(RouterStageParams), c_void_p]),
+    ("aptp_gumbel_relax", c_int, [POINTER(GumbelRelaxParams), c_void_p]),
+    ("aptp_gumbel_relax_bwd", c_int, [POINTER(GumbelRelaxParams), c_void_p]),
+    ("aptp_philox_gumbel", c_int, [POINTER(PhiloxGumbelParams), c_void_p]),
     ("aptp_groupnorm_bwd", c_int, [POINTER(GroupNormBwdParams), c_void_p]),
     ("aptp_layernorm_bwd", c_int, [POINTER(LayerNormBwdParams), c_void_p]),
     ("aptp_attention_bwd", c_int, [POINTER(AttentionBwdParams), c_void_p]),

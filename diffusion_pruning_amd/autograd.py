@@ -310,6 +310,30 @@ def router_stage(stage) -> torch.Tensor:
     return RouterStageFn.apply(stage, *stage.grad_inputs)
 
 
+class GumbelRelaxFn(Function):
+    """out = ops.GumbelRelax(...).run(z, ...) as ONE autograd node with the single input z: the seeds, the draw and the stage's
+    tables are operands only.  The output is the stage's own `out` buffer (the next run() of that stage overwrites it); backward
+    is the stage's one launch, on this node's operands."""
+
+    @staticmethod
+    def forward(ctx, stage, z, seeds_dev, draw_dev, sub, codebook):
+        ctx.stage = stage
+        out = stage.run(z, seeds_dev, draw_dev, sub, codebook)
+        ctx.operands = stage._keep
+        return out.view_as(out)
+
+    @staticmethod
+    def backward(ctx, dout):
+        z, seeds_dev, draw_dev, sub, codebook = ctx.operands
+        ctx.stage.bind(z, seeds_dev, draw_dev, sub, codebook)
+        return None, ctx.stage.backward(dout.to(torch.float32).contiguous()), None, None, None, None
+
+
+def gumbel_relax(stage, z: torch.Tensor, seeds_dev: torch.Tensor, draw_dev: torch.Tensor, sub: int, codebook: bool = False) -> torch.Tensor:
+    """the seeded Gumbel-sigmoid relaxation of z (fp32 [R, E], contiguous) through an ops.GumbelRelax, the gradient flowing into z"""
+    return GumbelRelaxFn.apply(stage, z, seeds_dev, draw_dev, int(sub), bool(codebook))
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Fine-tuning variants (SURVEY a20): the same ops with WEIGHT gradients.  The trainable tensors are the fp32 masters in
 # diffusers' layout; a pruned expert computes on compacted packs, so parameter gradients are produced in the compact

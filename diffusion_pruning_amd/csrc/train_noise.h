@@ -8,6 +8,8 @@
 //   k = 3  offset noise           element c (one block: the four channels)
 //   k = 4  input perturbation     same indexing as k = 1
 //   k = 5  timestep               word x0 of block 0: t = (x0 T) >> 32 in uint64, T = max_scheduler_steps
+//   k = 6  router assignment      Gumbel noise of the optimal-transport assignment (gumbel_relax.h): element = column
+//   k = 7  router relaxation      Gumbel noise of the relaxation itself (gumbel_relax.h): same indexing
 // fp32, contraction off, in this order (z_k the normal of sub-draw k, s the scale, (sa, so) row t of the [T, 2] table of
 // sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)):
 //   x0     = s fmaf(expf(0.5f clamp(logvar, -30, 20)), z1, mean)   (moments given)   |   x0 = latents_in   (latents given)

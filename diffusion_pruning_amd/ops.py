@@ -22,7 +22,7 @@ from ._lib import AttentionBiasParams, EmbedLnParams, MaskedMeanParams
 from ._lib import ACT_QUICK_GELU, ImagePatchesParams, L2NormalizeParams, MmdRbfParams, VitEmbedLnParams  # noqa: F401
 from ._lib import EOS_ARGMAX, EOS_FIRST, EosPoolLnParams, ImagePatchesPilParams, PairedCosineParams
 from ._lib import GuidedStepParams, LossStageParams, LossTermsParams, PhiloxNormalParams, TrainNoiseParams
-from ._lib import RouterStageParams, SinkhornParams
+from ._lib import GumbelRelaxParams, PhiloxGumbelParams, RouterStageParams, SinkhornParams
 from ._lib import (ACT_GEGLU, ACT_NONE, ACT_SILU, AttentionBwdParams, AttentionParams, ConvGemmParams, DepthLerpParams, GateBwdParams, WgradParams, FfTailParams, FoldRowsParams, PackDgradParams, MseParams,
                    GegluParams, GroupNormBwdParams, GroupNormParams, LayerNormBwdParams, LayerNormParams,
                    ColsumParams, LayerNormPgradParams, AttentionWideParams, ImageOutParams)
@@ -2176,6 +2176,125 @@ class RouterStage:
         self._p.g = self._g.data_ptr()
         _lib.check(self._lib.aptp_router_stage_bwd(ctypes.byref(self._p), _stream()), "aptp_router_stage_bwd")
         return self.d_arch, self.d_ratios
+
+
+def _check_noise_source(what: str, R: int, seeds_dev, draw_dev, sub, device):
+    if not isinstance(seeds_dev, torch.Tensor) or not isinstance(draw_dev, torch.Tensor):
+        raise ValueError(f"{what}: seeds_dev and draw_dev must be device tensors")
+    _seed_tensor(seeds_dev, R, device, what)
+    if draw_dev.dtype != torch.int64 or draw_dev.numel() != 1 or draw_dev.device != device:
+        raise ValueError(f"{what}: draw_dev must be an int64 tensor of one element on {device}")
+    if sub not in (_lib.ROUTER_ASSIGN_SUBDRAW, _lib.ROUTER_RELAX_SUBDRAW):
+        raise ValueError(f"{what}: sub must be {_lib.ROUTER_ASSIGN_SUBDRAW} (assignment) or {_lib.ROUTER_RELAX_SUBDRAW} (relaxation), got {sub!r}")
+
+
+def philox_gumbel(shape, seeds, draw, sub: int, offset: int = 0, *, codebook: bool = False, words: bool = False,
+                  out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """The router's seeded Gumbel noise on its own (csrc/gumbel_relax.hip, the stream in csrc/gumbel_relax.h): fp32 [R, n] with
+    ``G[r, i] = -log(1e-20 - log(u))``, u the (0, 1] uniform of word ``offset + i`` of (seeds[r], Philox draw), where the Philox
+    draw is ``8 * draw + sub`` (sub 6: the assignment's noise, 7: the relaxation's) or, with ``codebook=True``, ``2^63 | draw``.
+    seeds as ``randn`` takes them; draw an int in [0, 2^59) or a device int64 [1] tensor (the capturable form).  ``words=True``
+    returns the uint32 words behind the values instead, as an int32 tensor holding their bits."""
+    shape, out, dev = _philox_out("philox_gumbel", shape, torch.int32 if words else torch.float32, out, device, seeds)
+    if len(shape) != 2:
+        raise ValueError(f"philox_gumbel: shape must be [R, n], got {shape}")
+    R, n = shape
+    sd = _seed_tensor(seeds, R, dev, "philox_gumbel")
+    if not isinstance(draw, torch.Tensor):
+        if not isinstance(draw, int) or isinstance(draw, bool) or not 0 <= draw < (1 << 59):
+            raise ValueError(f"philox_gumbel: draw must be an int in [0, 2^59) or a device int64 [1] tensor, got {draw!r}")
+        draw = torch.tensor([draw], dtype=torch.int64, device=dev)
+    _check_noise_source("philox_gumbel", R, sd, draw, sub, dev)
+    if not isinstance(offset, int) or offset < 0 or offset > (1 << 62):
+        raise ValueError(f"philox_gumbel: offset must be an int in [0, 2^62], got {offset!r}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int32 if words else torch.float32, device=dev)
+    p = PhiloxGumbelParams()
+    p.out, p.words = (None, out.data_ptr()) if words else (out.data_ptr(), None)
+    p.seeds, p.draw, p.n, p.offset = sd.data_ptr(), draw.data_ptr(), n, offset
+    p.R, p.sub, p.codebook = R, int(sub), int(bool(codebook))
+    _lib.check(_lib.load().aptp_philox_gumbel(ctypes.byref(p), _stream()), "aptp_philox_gumbel")
+    return out
+
+
+class GumbelRelax:
+    """The router's training-mode Gumbel-sigmoid relaxation on seeded device noise, one launch forward and one backward
+    (csrc/gumbel_relax.hip; formulas and draw map in csrc/gumbel_relax.h).
+
+    widths: the width segments (their sum nw); depth_order: a permutation of range(nd) (entries are taken mod nd, as the quantiser
+    normalises them); rows: R.  The tables, `out` and `dz` (fp32 [R, nw + nd]) are allocated here, once.  run(z, seeds_dev,
+    draw_dev, sub, codebook=False) returns `out` = [w | d] of ``gumbel_sigmoid_trick(z)`` with row r's noise a function of
+    (seeds_dev[r], draw_dev[0], sub / codebook) alone; backward(dout) returns `dz` for the operands of the last run().  Both read
+    z, the seeds and the draw at launch time: safe to capture and replay while those tensors stay where they are."""
+
+    def __init__(self, widths, depth_order, temperature: float, base: float, non_zero_width: bool, rows: int, device):
+        self._lib = _lib.load()
+        widths = [int(w) for w in widths]
+        nd = len(list(depth_order))
+        order = [int(o) % nd for o in depth_order]
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError(f"GumbelRelax: the stage runs on the GPU, got device {device}")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        starts = [0]
+        for w in widths:
+            starts.append(starts[-1] + w)
+        self.nw, self.nd, self.R, self.E, self.device = starts[-1], nd, int(rows), starts[-1] + nd, device
+        self._seg_host = (ctypes.c_int32 * len(starts))(*starts)
+        self._order_host = (ctypes.c_int32 * max(nd, 1))(*(order or [0]))
+        p = GumbelRelaxParams()
+        p.R, p.nw, p.nd, p.n_seg = self.R, self.nw, nd, len(widths)
+        p.non_zero_width, p.T, p.base = int(bool(non_zero_width)), float(temperature), float(base)
+        p.sub = _lib.ROUTER_RELAX_SUBDRAW
+        p.seg_start_host = ctypes.cast(self._seg_host, ctypes.c_void_p)
+        p.depth_order_host = ctypes.cast(self._order_host, ctypes.c_void_p)
+        # refuse a bad geometry before anything is allocated for it: the limits are the library's
+        if not (1 <= self.R <= _lib.GUMBEL_RELAX_MAX_R and 1 <= self.E <= _lib.GUMBEL_RELAX_MAX_E and nd <= _lib.GUMBEL_RELAX_MAX_ND
+                and len(widths) <= _lib.GUMBEL_RELAX_MAX_SEG and all(w >= 1 for w in widths) and sorted(order) == list(range(nd))
+                and float(temperature) > 0):
+            raise ValueError(f"GumbelRelax: R in 1..{_lib.GUMBEL_RELAX_MAX_R}, nw + nd in 1..{_lib.GUMBEL_RELAX_MAX_E}, at most "
+                             f"{_lib.GUMBEL_RELAX_MAX_SEG} non-empty segments, depth_order a permutation of at most "
+                             f"{_lib.GUMBEL_RELAX_MAX_ND} entries and a positive temperature; got R = {self.R}, nw = {self.nw}, "
+                             f"nd = {nd}, {len(widths)} segments, depth_order = {order}, temperature = {temperature}")
+        self.seg_start = torch.tensor(starts, dtype=torch.int32, device=device)
+        self.depth_order = torch.tensor(order or [0], dtype=torch.int32, device=device)
+        self.out = scratch._alloc(self.R * self.E, torch.float32, device, zero=False).view(self.R, self.E)
+        self.dz = scratch._alloc(self.R * self.E, torch.float32, device, zero=False).view(self.R, self.E)
+        p.seg_start, p.depth_order = self.seg_start.data_ptr(), self.depth_order.data_ptr()
+        p.out, p.dz = self.out.data_ptr(), self.dz.data_ptr()
+        self._p, self._keep = p, None
+
+    def _check_rows(self, t, what):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (self.R, self.E) \
+                or t.device != self.device:
+            raise ValueError(f"GumbelRelax: {what} must be a contiguous fp32 [{self.R}, {self.E}] tensor on {self.device}")
+
+    def run(self, z: torch.Tensor, seeds_dev: torch.Tensor, draw_dev: torch.Tensor, sub: int, codebook: bool = False) -> torch.Tensor:
+        """one launch on the current stream; returns `out`, which the next run() overwrites"""
+        self.bind(z, seeds_dev, draw_dev, sub, codebook)
+        _lib.check(self._lib.aptp_gumbel_relax(ctypes.byref(self._p), _stream()), "aptp_gumbel_relax")
+        return self.out
+
+    def bind(self, z, seeds_dev, draw_dev, sub, codebook=False):
+        """the operands run() and backward() launch on (run() binds its own; autograd.GumbelRelaxFn re-binds a node's before its
+        backward, so two nodes may share a stage as long as each one's `out` is consumed before the next run())"""
+        z = z.detach()
+        self._check_rows(z, "z")
+        _check_noise_source("GumbelRelax", self.R, seeds_dev, draw_dev, sub, self.device)
+        p = self._p
+        p.z, p.seeds, p.draw, p.sub, p.codebook = z.data_ptr(), seeds_dev.data_ptr(), draw_dev.data_ptr(), int(sub), int(bool(codebook))
+        self._keep = (z, seeds_dev, draw_dev, int(sub), bool(codebook))
+
+    def backward(self, dout: torch.Tensor) -> torch.Tensor:
+        """one launch after run(): d out / d z applied to dout, for the z, seeds and draw of that run; returns `dz`"""
+        if self._keep is None:
+            raise RuntimeError("GumbelRelax.backward: call run() first")
+        dout = dout.detach()
+        self._check_rows(dout, "dout")
+        self._p.dout = dout.data_ptr()
+        _lib.check(self._lib.aptp_gumbel_relax_bwd(ctypes.byref(self._p), _stream()), "aptp_gumbel_relax_bwd")
+        return self.dz
 
 
 def fold_rows(partials: torch.Tensor, n_rows: int, C: int, out: Optional[torch.Tensor] = None,

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -21,6 +21,40 @@ from torch import nn
 
 from .dist_utils import _span
 from .estimation_utils import sample_gumbel, sample_gumbel_blocks, gumbel_softmax_sample, hard_concrete, importance_gumbel_softmax_sample
+
+
+ROUTER_ASSIGN_SUBDRAW, ROUTER_RELAX_SUBDRAW = 6, 7          # csrc/gumbel_relax.h
+
+
+class RouterNoise(NamedTuple):
+    """Where a seeded training step's router noise comes from (csrc/gumbel_relax.h), all of it device memory read at
+    launch time: the samples' seeds (int64 [B]) and the batch's draw (int64 [1]); the codes' seeds (int64 [n_e], router_seed + k)
+    and the count of steps run (int64 [1])."""
+    seeds_dev: torch.Tensor
+    draw_dev: torch.Tensor
+    code_seeds_dev: torch.Tensor
+    step_dev: torch.Tensor
+
+    @classmethod
+    def of(cls, seeds, draw: int, router_seed: int, noise_step: int, n_e: int, device) -> "RouterNoise":
+        """the record of one eager step from host values (four small uploads): seeds as ops.randn takes them"""
+        from . import ops
+        seeds = [int(v) for v in (seeds.tolist() if isinstance(seeds, torch.Tensor) else seeds)]
+        i64 = lambda v: torch.tensor([int(v)], dtype=torch.int64, device=device)      # noqa: E731
+        return cls(ops._seed_tensor(seeds, len(seeds), torch.device(device), "RouterNoise"), i64(draw),
+                   ops._seed_tensor([wrap_seed(int(router_seed) + k) for k in range(n_e)], n_e, torch.device(device), "RouterNoise"),
+                   i64(noise_step))
+
+    def samples(self, sub: int):
+        return self.seeds_dev, self.draw_dev, sub, False
+
+    def codes(self):
+        return self.code_seeds_dev, self.step_dev, ROUTER_RELAX_SUBDRAW, True
+
+
+def wrap_seed(v: int) -> int:
+    """a seed sum read as uint64 and handed on in ops' range [-2^63, 2^64)"""
+    return int(v) & ((1 << 64) - 1)
 
 
 class StructureVectorQuantizer(nn.Module):
@@ -68,18 +102,27 @@ class StructureVectorQuantizer(nn.Module):
         self.fused_sinkhorn_allreduce = fused_sinkhorn_allreduce
 
     # ---- forward (quantizer.py:136-169) ---------------------------------------------------------------------------
-    def forward(self, z: torch.Tensor, valid: torch.Tensor = None) -> Tuple[torch.Tensor, Tuple]:
+    def forward(self, z: torch.Tensor, valid: torch.Tensor = None, noise: Optional[RouterNoise] = None) -> Tuple[torch.Tensor, Tuple]:
         """valid: fp32 [B] of 0 and 1 on z's device (a short batch staged into a full one): the optimal-transport assignment then
-        couples the valid samples only, and a sample that is not valid gets the code nearest to it (the eval branch's rule)"""
+        couples the valid samples only, and a sample that is not valid gets the code nearest to it (the eval branch's rule).
+        noise: a RouterNoise (training mode, GPU): the codebook's relaxation and the assignment's draw their Gumbel noise on the
+        device from the seeds (sub-draw 7 on the codebook draw, sub-draw 6 of the samples); None: the host generator, as ever."""
         z = z.contiguous()
         z_flat = z.view(-1, self.vq_embed_dim)
+        if noise is not None and not self.training:
+            raise ValueError("StructureVectorQuantizer.forward(noise=): eval mode has the fixed seed-0 host stream, which is not a sample's")
         if self.training:
-            codes = self.gumbel_sigmoid_trick(self.embedding.weight)      # gradient reaches the codebook
-            self.embedding_gs.data = codes.detach()
-            if self.optimal_transport:
-                idx = self.get_optimal_transport_min_encoding_indices(z_flat, valid)
+            if noise is None:
+                codes = self.gumbel_sigmoid_trick(self.embedding.weight)      # gradient reaches the codebook
+                self.embedding_gs.data = codes.detach()
             else:
-                idx = self.get_cosine_sim_min_encoding_indices(z_flat)
+                codes = self.gumbel_sigmoid_trick(self.embedding.weight, noise.codes())
+                self.embedding_gs.data = codes.detach().clone()            # (codes is the stage's buffer: the next step overwrites it)
+            assign = None if noise is None else noise.samples(ROUTER_ASSIGN_SUBDRAW)
+            if self.optimal_transport:
+                idx = self.get_optimal_transport_min_encoding_indices(z_flat, valid, assign)
+            else:
+                idx = self.get_cosine_sim_min_encoding_indices(z_flat, assign)
         else:
             codes = self.embedding_gs.detach()
             idx = self.get_cosine_sim_min_encoding_indices(z_flat)
@@ -133,11 +176,37 @@ class StructureVectorQuantizer(nn.Module):
             self._seg_cache = m
         return m
 
-    def gumbel_sigmoid_trick(self, z_q: torch.Tensor):
+    def _relax_stage(self, rows: int, device, sub: int, codebook: bool):
+        """the ops.GumbelRelax of this structure for `rows` rows on `device`, built once.  One per role of a call as well (sub-draw,
+        codebook): the three calls of a step each keep their `out` and `dz` buffers, also where the batch has n_e rows."""
+        from . import ops
+        cache = self.__dict__.setdefault("_relax_stages", {})
+        key = (int(rows), str(device), int(sub), bool(codebook))
+        st = cache.get(key)
+        if st is None:
+            st = cache[key] = ops.GumbelRelax(self.width_list, self.depth_order, self.temperature, self.base, self.non_zero_width,
+                                              rows, device)
+        return st
+
+    def _seeded_gumbel_sigmoid_trick(self, z_q: torch.Tensor, noise):
+        seeds_dev, draw_dev, sub, codebook = noise
+        if not self.training:
+            raise ValueError("gumbel_sigmoid_trick(noise=): eval mode has the fixed seed-0 host stream, which is not a sample's")
+        if not z_q.is_cuda:
+            raise NotImplementedError("gumbel_sigmoid_trick(noise=) needs the GPU: the seeded relaxation is a HIP kernel")
+        from . import autograd as AG
+        z_q = z_q.float().contiguous()
+        return AG.gumbel_relax(self._relax_stage(z_q.shape[0], z_q.device, sub, codebook), z_q, seeds_dev, draw_dev, sub, codebook)
+
+    def gumbel_sigmoid_trick(self, z_q: torch.Tensor, noise=None):
         """quantizer.py:196-213.  The noise is drawn on the HOST generator in the reference's order (depth block first, then
         one draw per width segment: quirk Q6), but moved to the device in ONE copy, and the 70 per-segment relaxations are
         evaluated as one elementwise pass over the whole width block (they are elementwise; only the non-zero-width rule
-        looks at a segment as a whole).  Same values as the per-segment loop, ~600 fewer launches per call."""
+        looks at a segment as a whole).  Same values as the per-segment loop, ~600 fewer launches per call.
+        noise: (seeds_dev int64 [rows], draw_dev int64 [1], sub, codebook) -- training mode on the GPU only: the whole relaxation is
+        then ONE launch that draws its noise on the project's Philox stream (ops.GumbelRelax); None: the code below."""
+        if noise is not None:
+            return self._seeded_gumbel_sigmoid_trick(z_q, noise)
         nw = sum(self.width_list)
         zw, zd = z_q[:, :nw], z_q[:, nw:]
         fixed = not self.training
@@ -202,8 +271,8 @@ class StructureVectorQuantizer(nn.Module):
         return x / x.norm(dim=-1, keepdim=True)
 
     @torch.no_grad()
-    def get_cosine_sim_min_encoding_indices(self, z: torch.Tensor) -> torch.Tensor:
-        u = self._unit(self.gumbel_sigmoid_trick(z))
+    def get_cosine_sim_min_encoding_indices(self, z: torch.Tensor, noise=None) -> torch.Tensor:
+        u = self._unit(self.gumbel_sigmoid_trick(z, noise))
         v = self._unit(self.embedding_gs)
         return torch.argmax(u @ v.t(), dim=-1)
 
@@ -241,8 +310,8 @@ class StructureVectorQuantizer(nn.Module):
         return full[rank * n:(rank + 1) * n]
 
     @torch.no_grad()
-    def get_optimal_transport_min_encoding_indices(self, a: torch.Tensor, valid: torch.Tensor = None) -> torch.Tensor:
-        a = self._unit(self.gumbel_sigmoid_trick(a))
+    def get_optimal_transport_min_encoding_indices(self, a: torch.Tensor, valid: torch.Tensor = None, noise=None) -> torch.Tensor:
+        a = self._unit(self.gumbel_sigmoid_trick(a, noise))
         codes = self._unit(self.embedding_gs)
         out = a @ codes.t()
         if valid is not None:

@@ -31,6 +31,7 @@ from .graph_utils import concurrent_stream, new_graph, node_count, warmup_stream
 from . import ops
 from .dist_utils import _rank, _span, _world
 from .losses import ContrastiveLoss, ResourceLoss, compute_snr
+from .quantizer import ROUTER_RELAX_SUBDRAW, RouterNoise
 from .router_optim import RouterAdamW
 
 
@@ -502,9 +503,42 @@ def _validate_eager(eval_fn, batches, keys, reduce: bool) -> Dict[str, float]:
     return {k: v / len(batches) for k, v in zip(keys, totals)}
 
 
+def _require_seeds(batch: dict) -> None:
+    """a seeded step's batch names its samples' seeds: checked before anything is staged, drawn or replayed"""
+    if batch.get("seeds") is None:
+        raise ValueError('a step built with router_seed needs batch["seeds"] (int64 [n]: one seed per sample) and takes batch["draw"] (an int, default 0)')
+    if len(batch["seeds"]) != int(batch["mpnet_embeddings"].shape[0]):
+        raise ValueError(f'batch["seeds"] has {len(batch["seeds"])} entries for {int(batch["mpnet_embeddings"].shape[0])} samples')
+    _check_draw(int(batch.get("draw", 0)), 0)
+
+
+def _check_draw(draw, noise_step) -> None:
+    if not isinstance(draw, int) or isinstance(draw, bool) or not 0 <= draw < (1 << 59):
+        raise ValueError(f"draw must be an int in [0, 2^59), got {draw!r}")
+    if not isinstance(noise_step, int) or isinstance(noise_step, bool) or not 0 <= noise_step < (1 << 62):
+        raise ValueError(f"noise_step must be an int in [0, 2^62), got {noise_step!r}")
+
+
+def _stage_seeds(noise, seeds, draw: int, noise_step: int) -> None:
+    """a batch's seeds, its draw and the count of steps run into a RouterNoise's static tensors, on the current stream: rows behind
+    a short batch repeat seed 0 of the batch, like every other staged row (_stage_short_rows).  No host sync for device seeds."""
+    with torch.no_grad():
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.tensor([int(v) for v in seeds], dtype=torch.int64)
+        _stage_short_rows(noise.seeds_dev, seeds.to(torch.int64))
+        noise.draw_dev.fill_(int(draw))
+        noise.step_dev.fill_(int(noise_step))
+
+
 class PrunerStep:
     def __init__(self, unet, hyper_net, quantizer, cfg: Optional[PruningLossConfig] = None,
-                 schedule: Optional[NoiseSchedule] = None):
+                 schedule: Optional[NoiseSchedule] = None, router_seed: Optional[int] = None):
+        """router_seed (an int; None: off): the router's Gumbel noise comes from the samples' seeds on the device instead of the
+        host generator -- step(seeds=, draw=, noise_step=), or batch["seeds"] / batch["draw"] in train_step; code k
+        of the codebook has seed router_seed + k and draws by the count of steps run, `noise_steps` (a host int: set it on resume)"""
+        if router_seed is not None and (not isinstance(router_seed, int) or isinstance(router_seed, bool)):
+            raise ValueError(f"router_seed must be an int or None, got {router_seed!r}")
+        self.router_seed, self.noise_steps = router_seed, 0
         self.unet, self.hyper_net, self.quantizer = unet, hyper_net, quantizer
         self.cfg = cfg or PruningLossConfig()
         self.schedule = schedule or NoiseSchedule()
@@ -531,28 +565,34 @@ class PrunerStep:
         self.resource.p = float(1 - (1 - p) * info["total_macs"] / float(torch.as_tensor(info["cur_prunable_macs"]).flatten()[0]))
 
     # ---- the router head and the MAC losses: one definition for the eager, the validation and the captured paths ----------------
-    def _route_head(self, text_embeddings, pretrain: bool, valid: Optional[torch.Tensor] = None):
+    def _route_head(self, text_embeddings, pretrain: bool, valid: Optional[torch.Tensor] = None, noise=None):
         """hyper-net -> quantiser -> Gumbel-sigmoid relaxation -> normalisation (trainer.py:1129-1138, 1165-1168).  Returns
         (arch_vector, arch_vector_quantized, arch_used, arch_wdn): arch_used is the code the student runs under, arch_wdn the
         width_depth_normalize'd vectors the contrastive loss reads.  valid (fp32 [B] of 0 and 1 on the device: a short batch
-        staged into a full one, no process group): the quantiser's assignment couples the valid samples only."""
+        staged into a full one, no process group): the quantiser's assignment couples the valid samples only.
+        noise (a quantizer.RouterNoise; None: the host generator): the three Gumbel draws come from the seeds, on the device --
+        the codebook's and the assignment's inside the quantiser, the relaxation's (sub-draw 7 of the samples) here."""
         arch_vector = self.hyper_net(text_embeddings)                                           # :1129
+        kw = {} if noise is None else {"noise": noise}
         if valid is None:
-            arch_vector_quantized, _ = self.quantizer(arch_vector)                              # :1130
+            arch_vector_quantized, _ = self.quantizer(arch_vector, **kw)                        # :1130
         else:
-            arch_vector_quantized, _ = self.quantizer(arch_vector, valid=valid)
-        arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)                          # :1132
+            arch_vector_quantized, _ = self.quantizer(arch_vector, valid=valid, **kw)
+        if noise is None:
+            arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector)                      # :1132
+        else:
+            arch_vector = self.quantizer.gumbel_sigmoid_trick(arch_vector, noise.samples(ROUTER_RELAX_SUBDRAW))
         arch_vector = self._single_arch_repeat(arch_vector, text_embeddings.shape[0])           # :1134-1136
         arch_wdn = self.quantizer.width_depth_normalize(arch_vector)                            # :1138
         arch_used = arch_vector if pretrain else arch_vector_quantized                          # :1165-1168
         return arch_vector, arch_vector_quantized, arch_used, arch_wdn
 
-    def _route(self, text_embeddings, pretrain: bool):
+    def _route(self, text_embeddings, pretrain: bool, noise=None):
         """_route_head -> cross-rank gather -> contrastive loss (trainer.py:1129-1171).
         Returns (arch_vector, arch_vector_quantized, arch_used, contrastive_loss).  A masked step does not come through here: it
         takes _route_head(valid=) and forms the contrastive loss with the MAC losses in one ops.RouterStage
         (_masked_router_losses, GraphedPrunerStep._router_forward)."""
-        arch_vector, arch_vector_quantized, arch_used, arch_wdn = self._route_head(text_embeddings, pretrain)
+        arch_vector, arch_vector_quantized, arch_used, arch_wdn = self._route_head(text_embeddings, pretrain, noise=noise)
         text_all, arch_all = gather_with_local_grad(text_embeddings, arch_wdn)                  # :1147-1162 (one collective)
         contrastive_loss = self.contrastive(text_all, arch_all)                                 # :1170-1171
         return arch_vector, arch_vector_quantized, arch_used, contrastive_loss
@@ -590,10 +630,10 @@ class PrunerStep:
             + cfg.distillation_weight * distillation_loss + cfg.block_weight * block_loss \
             + cfg.std_weight * std_loss + cfg.max_weight * max_loss
 
-    def _forward_pair(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, pretrain: bool):
+    def _forward_pair(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, pretrain: bool, noise=None):
         """router, dense teacher pass under no_grad, student pass under the routed code:
         (_route's tuple, full_pred, teacher_acts, model_pred, student_acts)"""
-        route = self._route(text_embeddings, pretrain)
+        route = self._route(text_embeddings, pretrain, noise)
         arch_vector, _, arch_used, _ = route
         sep = self.hyper_net.transform_structure_vector(arch_used)
         with torch.no_grad():                                                                   # :1185-1190 teacher
@@ -604,9 +644,26 @@ class PrunerStep:
         model_pred = self.unet(noisy_latents, timesteps, encoder_hidden_states).sample
         return route, full_pred, teacher_acts, model_pred, dict(self.block_activations)
 
-    def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False):
+    def _router_noise(self, seeds, draw: int, noise_step: int, rows: int, device):
+        """the RouterNoise of an eager seeded step (None without seeds); a process group is refused: the seeds are not gathered"""
+        if seeds is None:
+            return None
+        if self.router_seed is None:
+            raise ValueError("step(seeds=): the step was built without router_seed")
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise NotImplementedError("seeded router noise under a process group: the seeds are not gathered")
+        if len(seeds) != rows:
+            raise ValueError(f"{len(seeds)} seeds for {rows} samples")
+        _check_draw(draw, noise_step)
+        return RouterNoise.of(seeds, draw, self.router_seed, noise_step, self.quantizer.n_e, device)
+
+    def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False,
+             seeds=None, draw: int = 0, noise_step: int = 0):
+        """seeds (int64 [B] or B ints; needs router_seed), draw (the batch's draw, as batch_from_images(seeds=, draw=) takes it)
+        and noise_step (the count of steps run): the eager SEEDED step, the yardstick of the captured one"""
+        noise = self._router_noise(seeds, draw, noise_step, int(text_embeddings.shape[0]), text_embeddings.device)
         (_, arch_vector_quantized, _, contrastive_loss), full_pred, teacher_acts, model_pred, student_acts = \
-            self._forward_pair(noisy_latents, timesteps, encoder_hidden_states, text_embeddings, pretrain)
+            self._forward_pair(noisy_latents, timesteps, encoder_hidden_states, text_embeddings, pretrain, noise)
         w = _min_snr_weights(self.cfg, self.schedule, timesteps)
         loss, distillation_loss, block_loss = self._unet_losses(model_pred, student_acts, full_pred, teacher_acts, w, target)
         ratios, resource_loss, max_loss, std_loss = self._mac_losses(self.unet.calc_macs())
@@ -714,17 +771,27 @@ class PrunerStep:
                 out["grad_norm"] = optimizer.grad_norm.norm.clone()
         return out
 
+    def _seed_args(self, batch: dict) -> dict:
+        """step()'s seeded arguments from a batch (nothing without router_seed); the count of steps run advances by one"""
+        if self.router_seed is None:
+            return {}
+        _require_seeds(batch)
+        kw = dict(seeds=batch["seeds"], draw=int(batch.get("draw", 0)), noise_step=self.noise_steps)
+        self.noise_steps += 1
+        return kw
+
     def _step_on(self, batch: dict, pretrain: bool):
         return self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
-                         batch["mpnet_embeddings"], batch["target"], pretrain=pretrain)
+                         batch["mpnet_embeddings"], batch["target"], pretrain=pretrain, **self._seed_args(batch))
 
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
         """forward + backward + fused gradient all-reduce + optimizer step (trainer.py:913-933)"""
+        if self.router_seed is not None:
+            _require_seeds(batch)
         if isinstance(optimizer, RouterAdamW):
             return self._train_step_eager_router_hip(optimizer, batch, bool(pretrain))
         optimizer.zero_grad(set_to_none=True)
-        out = self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
-                        batch["mpnet_embeddings"], batch["target"], pretrain=pretrain)
+        out = self._step_on(batch, pretrain)
         out["loss"].backward()
         allreduce_mean_grads(self.trainable_parameters())
         optimizer.step()
@@ -753,13 +820,21 @@ class GraphedPrunerStep(PrunerStep):
     all reading `valid` on the device; the rows behind a short batch are its own first row and reach nothing.  The dict gains
     "n_valid" and "skipped"; an empty batch replays nothing, draws no noise and touches no state.  The Gumbel draws stay B rows
     per call from the host generator: the host stream advances by the same amount whatever n is, which is NOT the stream an eager
-    n-row step would consume.  Not under a process group."""
+    n-row step would consume, unless `router_seed` is given.  Not under a process group.
 
-    def __init__(self, *a, short_batches: bool = False, **k):
+    router_seed=<int>: the router's Gumbel noise is drawn on the device from batch["seeds"] (int64 [n]) and batch["draw"] (an int,
+    default 0) by ONE launch per relaxation (ops.GumbelRelax): a sample's noise is the same in any batch, the host
+    generator is neither read nor restored, no NoiseTape is made, and `noise_steps` (a host int, advanced once per non-empty
+    call, set it on resume) is the only state the noise adds.  Not under a process group (the seeds are not gathered)."""
+
+    def __init__(self, *a, short_batches: bool = False, router_seed: Optional[int] = None, **k):
         if short_batches and torch.distributed.is_available() and torch.distributed.is_initialized():
             raise NotImplementedError("GraphedPrunerStep(short_batches=True) under a process group: the router runs eagerly there, "
                                       "its collectives are not captured and `valid` is not gathered")
-        super().__init__(*a, **k)
+        if router_seed is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise NotImplementedError("GraphedPrunerStep(router_seed=) under a process group: the router runs eagerly there and "
+                                      "the seeds are not gathered")
+        super().__init__(*a, router_seed=router_seed, **k)
         self.short_batches = bool(short_batches)
         self._cap = None
         self.stream_probe = []          # what graph_utils.concurrent_stream measured when it chose the teacher's / router's side streams
@@ -794,7 +869,8 @@ class GraphedPrunerStep(PrunerStep):
         (and no process group is initialised: the router's collectives stay eager), the ROUTER is captured too -- hyper-net,
         quantiser incl. Sinkhorn, Gumbel relaxation, MAC losses as one graph ahead of the student's forward, and the chain rule
         into the router + the optimizer step as one graph behind the U-Net backward (trainer.py:1129-1138, :922-931) -- for this
-        value of `pretrain`; its Gumbel noise keeps coming from the host generator (estimation_utils.NoiseTape).
+        value of `pretrain`; its Gumbel noise keeps coming from the host generator (estimation_utils.NoiseTape) unless `router_seed`
+        is given: then the captured relaxations draw it on the device from static seeds / draw / step tensors.
         A torch optimizer here is for a FRESH optimizer at a CONSTANT rate (the capture zeroes its state and bakes the rate in); a
         router_optim.RouterAdamW serves both phases, a warm-up, the NaN batch skip and a resume from one capture."""
         cfg = self.cfg
@@ -807,6 +883,8 @@ class GraphedPrunerStep(PrunerStep):
         if short:
             st["valid"] = torch.ones(int(B), dtype=torch.float32, device=dev)
             st["text"] = batch["mpnet_embeddings"].clone()         # what the eager router reads; a captured phase has its own
+        if self.router_seed is not None:
+            st["noise"] = self._static_noise(int(B), dev)         # likewise: seeds / draw / step of the eager router
         ones = torch.ones((B, self.quantizer.vq_embed_dim), device=dev)
         full = self.hyper_net.transform_structure_vector(ones)
         # ONE static buffer holds the student's architecture code, SEGMENT-MAJOR: gate j's [B, w_j] block is contiguous, so
@@ -916,18 +994,23 @@ class GraphedPrunerStep(PrunerStep):
             self._capture_router(batch, optimizer, pretrain)           # (`dist` is the distillation loss in this scope)
         return self
 
+    def _static_noise(self, B: int, device) -> RouterNoise:
+        """the static seeds / draw / step tensors a seeded router reads (zeros until a batch is staged) and the codes' seeds"""
+        return RouterNoise.of([0] * B, 0, self.router_seed, 0, self.quantizer.n_e, device)
+
     # ---- the router as two more graphs per training phase (DESIGN 6b item 14, 6p) -------------------------------------------
-    def _router_forward(self, text_embeddings, pretrain: bool, valid: Optional[torch.Tensor] = None):
+    def _router_forward(self, text_embeddings, pretrain: bool, valid: Optional[torch.Tensor] = None, noise=None):
         """the router head and its own losses, MACs from the router-connected code (step() up to the student's code); with
-        `valid` everything that couples the samples of the batch runs masked (quantiser, one ops.RouterStage)"""
+        `valid` everything that couples the samples of the batch runs masked (quantiser, one ops.RouterStage); with `noise` (a
+        RouterNoise) the Gumbel draws come from the seeds on the device"""
         if valid is not None:
-            _, arch_vector_quantized, arch_used, arch_wdn = self._route_head(text_embeddings, pretrain, valid)
+            _, arch_vector_quantized, arch_used, arch_wdn = self._route_head(text_embeddings, pretrain, valid, noise)
             stage = self._masked_router_losses(text_embeddings, arch_wdn, self._cap["vmacs"](arch_used), valid)
             router_loss = AG.router_stage(stage)
             return dict(arch_used=arch_used, arch_vector_quantized=arch_vector_quantized, contrastive_loss=stage.contrastive,
                         resource_loss=stage.resource, ratios=stage.grad_inputs[1], resource_ratio=stage.mean_ratio,
                         std_loss=stage.std_loss, router_loss=router_loss, stage=stage)
-        _, arch_vector_quantized, arch_used, contrastive_loss = self._route(text_embeddings, pretrain)
+        _, arch_vector_quantized, arch_used, contrastive_loss = self._route(text_embeddings, pretrain, noise)
         # MAC accounting is differentiable in the gates (calc_macs family): VectorizedMacs evaluates it on the router-connected
         # architecture vector directly (same numbers as unet.calc_macs() after set_structure, tests/test_macs_pinned.py) in
         # ~10 kernels instead of ~2,000, before the student replay is queued, so the host never waits on the graphs.
@@ -973,17 +1056,26 @@ class GraphedPrunerStep(PrunerStep):
         # a phase's router graphs replay on the router's stream next to the NEXT step's staging on the caller's: they read a mask of
         # their own, staged on that stream like `text` (st["valid"] belongs to the loss stage and the eager router, on the caller's)
         valid = torch.ones_like(cap["st"]["valid"]) if self.short_batches else None
-        tape = EU.NoiseTape()
-        host_rng = torch.get_rng_state()
-        ph = dict(text=text, tape=tape, valid=valid)
+        # a seeded router draws nothing on the host: no tape, and the host generator is neither read nor restored; its seeds, draw
+        # and step are this phase's own, staged on the router's stream like `text` and `valid`
+        seeded = self.router_seed is not None
+        noise = self._static_noise(int(text.shape[0]), text.device) if seeded else None
+        tape = None if seeded else EU.NoiseTape()
+        host_rng = None if seeded else torch.get_rng_state()
+        # (the MAC constants of count_macs are operands of the captured MAC losses: the phase keeps them alive, so that a later
+        #  count_macs on a U-Net that several steps share cannot free what these graphs read)
+        ph = dict(text=text, tape=tape, valid=valid, noise=noise, resource_info=self.unet.resource_info_dict)
 
         def fwd():
-            tape.begin()
-            EU.NOISE_TAPE = tape
-            try:
-                r = self._router_forward(text, pretrain) if valid is None else self._router_forward(text, pretrain, valid)
-            finally:
-                EU.NOISE_TAPE = None
+            if seeded:
+                r = self._router_forward(text, pretrain, valid, noise)
+            else:
+                tape.begin()
+                EU.NOISE_TAPE = tape
+                try:
+                    r = self._router_forward(text, pretrain) if valid is None else self._router_forward(text, pretrain, valid)
+                finally:
+                    EU.NOISE_TAPE = None
             with torch.no_grad():
                 cap["install_code"](r["arch_used"])
             return r
@@ -1048,7 +1140,8 @@ class GraphedPrunerStep(PrunerStep):
         ph["g_bwd"] = new_graph()
         with torch.cuda.graph(ph["g_bwd"], pool=ph["g_fwd"].pool()):
             bwd(ph["out"])
-        torch.set_rng_state(host_rng)
+        if host_rng is not None:
+            torch.set_rng_state(host_rng)
         if not rt:
             rt = cap["router"] = dict(hip=hip, optimizer=optimizer, stream=concurrent_stream(log=self.stream_probe),
                                       ev_entry=torch.cuda.Event(), ev_code=torch.cuda.Event(), ev_bwd=torch.cuda.Event(),
@@ -1082,13 +1175,25 @@ class GraphedPrunerStep(PrunerStep):
 
     # ---- one step -------------------------------------------------------------------------------------------------------
     def step(self, noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain: bool = False,
-             valid: Optional[torch.Tensor] = None):
-        """valid: short_batches only -- one entry per sample of this batch (samples masked without compacting them)"""
+             valid: Optional[torch.Tensor] = None, seeds=None, draw: int = 0, noise_step: int = 0):
+        """valid: short_batches only -- one entry per sample of this batch (samples masked without compacting them).
+        seeds / draw / noise_step: router_seed only -- as PrunerStep.step takes them"""
         if self._cap is None:
             assert valid is None and not self.short_batches, "GraphedPrunerStep(short_batches=True): call capture(batch) first"
-            return super().step(noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain)
+            return super().step(noisy_latents, timesteps, encoder_hidden_states, text_embeddings, target, pretrain,
+                                seeds=seeds, draw=draw, noise_step=noise_step)
         cap = self._cap
         assert valid is None or self.short_batches, "step(valid=): only under short_batches=True"
+        noise = None
+        if self.router_seed is not None:
+            if seeds is None:
+                raise ValueError("GraphedPrunerStep(router_seed=).step: seeds= is required (one seed per sample)")
+            if len(seeds) != int(text_embeddings.shape[0]):
+                raise ValueError(f"{len(seeds)} seeds for {int(text_embeddings.shape[0])} samples")
+            _check_draw(draw, noise_step)
+            noise = cap["st"]["noise"]
+        elif seeds is not None:
+            raise ValueError("step(seeds=): the step was built without router_seed")
         # The teacher depends on the batch only: its graph replays on a side stream WHILE the router (launch-bound kernels of a
         # few microseconds each, during which the GPU is mostly idle) is being issued on this stream.
         # Order on the device: batch copies -> [teacher graph || router] -> student graph.
@@ -1099,11 +1204,15 @@ class GraphedPrunerStep(PrunerStep):
             if _stage_short_batch(cap["st"], batch) == 0:
                 return self._skipped_step()
             _stage_short_rows(cap["st"]["text"], text_embeddings)
+            if noise is not None:
+                _stage_seeds(noise, seeds, draw, noise_step)
             self._launch_teacher()
-            r = self._router_forward(cap["st"]["text"], pretrain, cap["st"]["valid"])
+            r = self._router_forward(cap["st"]["text"], pretrain, cap["st"]["valid"], noise)
         else:
             self._stage_batch_and_launch_teacher(noisy_latents, timesteps, encoder_hidden_states, target)
-            r = self._router_forward(text_embeddings, pretrain)
+            if noise is not None:
+                _stage_seeds(noise, seeds, draw, noise_step)
+            r = self._router_forward(text_embeddings, pretrain, None, noise)
         with torch.no_grad():
             cap["install_code"](r["arch_used"])
         cap["g_student"].replay()                                     # forward: needs the code only
@@ -1161,9 +1270,11 @@ class GraphedPrunerStep(PrunerStep):
     def _step_on(self, batch: dict, pretrain: bool):
         return self.step(batch["noisy_latents"], batch["timesteps"], batch["encoder_hidden_states"],
                          batch["mpnet_embeddings"], batch["target"], pretrain=pretrain,
-                         valid=batch.get("valid") if self.short_batches else None)
+                         valid=batch.get("valid") if self.short_batches else None, **self._seed_args(batch))
 
     def train_step(self, optimizer, batch: dict, pretrain: bool = False):
+        if self.router_seed is not None:
+            _require_seeds(batch)                        # before anything runs
         if self.short_batches:
             assert self._cap is not None, "GraphedPrunerStep(short_batches=True): call capture(batch) first"
             B, n = int(self._cap["st"]["valid"].shape[0]), int(batch["noisy_latents"].shape[0])
@@ -1187,7 +1298,8 @@ class GraphedPrunerStep(PrunerStep):
 
     def _train_step_captured_router(self, batch: dict, ph: dict):
         """the whole step from five graphs: [teacher || router] -> student forward -> losses + U-Net backward -> chain rule into the
-        router + optimizer.  The host only stages the batch and refills the Gumbel uniforms from its generator.
+        router + optimizer.  The host only stages the batch and refills the Gumbel uniforms from its generator (under router_seed:
+        stages the seeds, and draws nothing).
 
         The two router graphs are chains of a few hundred tiny launches (0.9 + 1.3 ms during which the chip idles).  With
         overlap_router (default) they replay on a stream of their own: the NEXT step's batch staging and teacher forward do not
@@ -1216,7 +1328,12 @@ class GraphedPrunerStep(PrunerStep):
             else:
                 with torch.no_grad():
                     ph["text"].copy_(batch["mpnet_embeddings"])
-            ph["tape"].refill()                               # host-RNG stream, consumed exactly as the eager calls consume it
+            if ph["noise"] is not None:
+                # the seeds, the draw and the count of steps run, staged where `text` is: nothing is drawn on the host
+                _stage_seeds(ph["noise"], batch["seeds"], int(batch.get("draw", 0)), self.noise_steps)
+                self.noise_steps += 1
+            else:
+                ph["tape"].refill()                           # host-RNG stream, consumed exactly as the eager calls consume it
             ph["g_fwd"].replay()                              # router -> architecture code installed for the student
             rt["ev_code"].record(rs)
         main.wait_event(rt["ev_code"])

@@ -1051,6 +1051,50 @@ int64_t aptp_router_stage_work_floats(int32_t B, int32_t E, int32_t D);    /* 0 
 int aptp_router_stage(const AptpRouterStageParams* p, aptp_stream_t stream);
 int aptp_router_stage_bwd(const AptpRouterStageParams* p, aptp_stream_t stream);
 
+/* The router's Gumbel-sigmoid relaxation in training mode (pdm/models/vq/quantizer.py:196-213) on SEEDED noise: the project's
+ * Philox stream instead of the host generator, so a value is a pure function of (seed of the row, draw, element).  The stream,
+ * the draw map and the arithmetic are csrc/gumbel_relax.h.  Row r has seed seeds[r] (int64 [R], device); the Philox draw of
+ * the call is formed IN THE KERNEL from draw[0] (int64 [1], device): 8 * draw[0] + sub for sample rows (sub = 6: the noise of the
+ * optimal-transport assignment, 7: of the relaxation), 2^63 | draw[0] when `codebook` is set (draw[0] is then the count of
+ * steps run).  Element e = c for width column c, e = nw + j for the depth entry at SORTED position j.
+ *   aptp_gumbel_relax, ONE launch: z fp32 [R, E] -> out fp32 [R, E], E = nw + nd, both contiguous.
+ *     width  w = sigmoid((z + G + base) / T); with non_zero_width, a segment [seg_start[s], seg_start[s + 1]) with no
+ *            w >= 0.5 gets + 0.5 on its first entry
+ *     depth  p = flip(cumsum(softmax(z[nw:]))), x = log(p + 1e-6) - log1p(-(p - 1e-6)), d_sorted = sigmoid((x + G + base) / T),
+ *            out[nw + depth_order[j]] = d_sorted[j]
+ *   aptp_gumbel_relax_bwd, ONE launch: dout fp32 [R, E] -> dz fp32 [R, E] = d out / d z with the noise and the bump as
+ *     constants; z, seeds and draw as the forward had them, everything else is recomputed (out is not read).
+ *   aptp_philox_gumbel, ONE launch: out fp32 [R, n] = G of (seeds[r], that draw, offset + i), and / or words uint32 [R, n], the
+ *     Philox word behind each value (either pointer may be null, not both).
+ * seg_start int32 [n_seg + 1] and depth_order int32 [nd] are DEVICE tables; seg_start_host / depth_order_host are the same
+ * values in host memory, read by the validation only.  fp32, every sum in index order, no atomics: the same bits at every replay.
+ * APTP_EINVAL and nothing launched (no HIP call is made) for: a null block or pointer, R outside 1..65535, E outside 1..4096,
+ * n_seg above 1024 (or 0 with nw > 0), nd above 64, sub outside {6, 7}, T <= 0, a seg_start that does not start at 0, end at nw
+ * and strictly increase, a depth_order entry outside [0, nd) or named twice, n outside 1..2^31, offset outside [0, 2^62]. */
+#define APTP_GUMBEL_RELAX_MAX_R 65535
+#define APTP_GUMBEL_RELAX_MAX_E 4096
+#define APTP_GUMBEL_RELAX_MAX_SEG 1024
+#define APTP_GUMBEL_RELAX_MAX_ND 64
+typedef struct {
+  const float* z; float* out;
+  const float* dout; float* dz;
+  const int64_t* seeds; const int64_t* draw;
+  const int32_t* seg_start; const int32_t* depth_order;
+  const int32_t* seg_start_host; const int32_t* depth_order_host;
+  int32_t R, nw, nd, n_seg;
+  int32_t sub, codebook, non_zero_width, reserved;
+  float T, base;
+} AptpGumbelRelaxParams;
+int aptp_gumbel_relax(const AptpGumbelRelaxParams* p, aptp_stream_t stream);
+int aptp_gumbel_relax_bwd(const AptpGumbelRelaxParams* p, aptp_stream_t stream);
+typedef struct {
+  float* out; uint32_t* words;
+  const int64_t* seeds; const int64_t* draw;
+  int64_t n, offset;
+  int32_t R, sub, codebook, reserved;
+} AptpPhiloxGumbelParams;
+int aptp_philox_gumbel(const AptpPhiloxGumbelParams* p, aptp_stream_t stream);
+
 /* Data-gradient operand from the forward operand of the same contraction (both in packed bf16 layout):
  * dst[c][taps-1-t][n] = src[n][t][c] for n < N, c < C, zero in the rest of dst's [dst_rows][taps][dst_ld] image.
  * (ops.pack_weight_dgrad of the same weights, without going through the diffusers layout.) */

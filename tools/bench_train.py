@@ -15,23 +15,19 @@ from diffusion_pruning_amd.train_step import GraphedPrunerStep, PrunerStep, synt
 from diffusion_pruning_amd.unet import UNet2DConditionModelGated  # noqa: E402
 
 
-def short_batches_ab(args, dev, unet, hn, qz):
-    """--short-batches: the default captured step and GraphedPrunerStep(short_batches=True), each with its own copy of the router
-    under a RouterAdamW with the router captured, in ONE process and in alternating rounds (the clocks of two processes differ by
-    more than these two steps do).  The switched step runs `--valid` samples of the batch (default: all but one)."""
+def _ab(args, unet, hn, qz, batch, specs, res, out_name):
+    """two captured steps, each with its own copy of the router under a RouterAdamW with the router captured, in ONE process and in
+    alternating rounds (the clocks of two processes differ by more than these steps do).  specs: (name, constructor keywords, the
+    batch it runs) per side; res: the head of the JSON line, which is also written to profiles/<out_name>"""
     import copy
     from diffusion_pruning_amd import graph_utils
     from diffusion_pruning_amd.router_optim import RouterAdamW
     graph_utils.KEEP_GRAPHS = True
-    batch = synthetic_batch(args.batch, args.latent, dev)
-    n_valid = args.batch - 1 if args.valid is None else args.valid
-    assert 1 <= n_valid <= args.batch, "--valid: 1..batch"
-    short = {k: v[:n_valid] for k, v in batch.items()}
     sides = {}
-    for name, kw, b in (("default", {}, batch), ("short_batches", {"short_batches": True}, short)):
+    for name, kw, b in specs:
         h, q = copy.deepcopy(hn), copy.deepcopy(qz)
         step = GraphedPrunerStep(unet, h, q, **kw)
-        step.count_macs(args.latent)
+        step.count_macs(args.latent)                          # (the shared U-Net's MAC constants: the same values for every side)
         opt = RouterAdamW([{"params": [p for p in h.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0},
                            {"params": [p for p in q.parameters() if p.requires_grad], "lr": 2e-4, "weight_decay": 0.0}])
         step.capture(batch, optimizer=opt)
@@ -51,8 +47,7 @@ def short_batches_ab(args, dev, unet, hn, qz):
             if r:
                 sd["ms"].append((time.perf_counter() - t0) / args.steps * 1e3)
             sd["loss"] = float(out["loss"])
-    res = {"metric": "pruning-train-steps/s, default captured step vs short_batches=True (same process, alternating rounds)",
-           "batch": args.batch, "latent": args.latent, "valid": n_valid, "steps_per_round": args.steps, "rounds": rounds}
+    res = dict(res, steps_per_round=args.steps, rounds=rounds)
     for name, sd in sides.items():
         best = min(sd["ms"])
         res[name] = {"steps_per_s": round(1e3 / best, 3), "ms_per_step_best": round(best, 3), "ms_per_step_rounds": [round(m, 3) for m in sd["ms"]],
@@ -61,9 +56,42 @@ def short_batches_ab(args, dev, unet, hn, qz):
     line = json.dumps(res)
     out_dir = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
     os.makedirs(out_dir, exist_ok=True)
-    with open(os.path.join(out_dir, "bench_train_short_batches.json"), "w") as f:
+    with open(os.path.join(out_dir, out_name), "w") as f:
         f.write(line + "\n")
     print(line)
+
+
+def _short_batch(args, batch):
+    n_valid = args.batch - 1 if args.valid is None else args.valid
+    assert 1 <= n_valid <= args.batch, "--valid: 1..batch"
+    return n_valid, {k: v[:n_valid] for k, v in batch.items()}
+
+
+def short_batches_ab(args, dev, unet, hn, qz):
+    """--short-batches: the default captured step against GraphedPrunerStep(short_batches=True).  The switched step runs
+    `--valid` samples of the batch (default: all but one)."""
+    batch = synthetic_batch(args.batch, args.latent, dev)
+    n_valid, short = _short_batch(args, batch)
+    _ab(args, unet, hn, qz, batch, (("default", {}, batch), ("short_batches", {"short_batches": True}, short)),
+        {"metric": "pruning-train-steps/s, default captured step vs short_batches=True (same process, alternating rounds)",
+         "batch": args.batch, "latent": args.latent, "valid": n_valid}, "bench_train_short_batches.json")
+
+
+def router_noise_ab(args, dev, unet, hn, qz):
+    """--router-seed S: the captured step with its Gumbel noise from the host generator (the default) against
+    GraphedPrunerStep(router_seed=S), whose router draws it on the device from the batch's seeds.  With
+    --short-batches both sides run `--valid` samples through short_batches=True.  The seeds are device memory, as a loader
+    that builds its batches on the device (train_step.batch_from_images(seeds=)) hands them over."""
+    batch = synthetic_batch(args.batch, args.latent, dev)
+    kw, n_valid, run = {}, args.batch, batch
+    if args.short_batches:
+        kw = {"short_batches": True}
+        n_valid, run = _short_batch(args, batch)
+    seeded = dict(run, seeds=torch.arange(1000, 1000 + n_valid, dtype=torch.int64, device=dev), draw=3)
+    _ab(args, unet, hn, qz, batch, (("default", kw, run), ("seeded", dict(kw, router_seed=args.router_seed), seeded)),
+        {"metric": "pruning-train-steps/s, host-generator router noise vs router_seed (same process, alternating rounds)",
+         "batch": args.batch, "latent": args.latent, "valid": n_valid, "short_batches": bool(args.short_batches),
+         "router_seed": args.router_seed}, "bench_train_router_noise.json")
 
 
 def main():
@@ -88,6 +116,9 @@ def main():
                     help="A/B of the default captured step and GraphedPrunerStep(short_batches=True) in one process; writes "
                          "profiles/bench_train_short_batches.json")
     ap.add_argument("--valid", type=int, default=None, help="with --short-batches: samples per step of the switched side (default batch - 1)")
+    ap.add_argument("--router-seed", type=int, default=None,
+                    help="with --router-optimizer hip: A/B of the default captured step and GraphedPrunerStep(router_seed=S) in one "
+                         "process (with --short-batches: both under short_batches=True); writes profiles/bench_train_router_noise.json")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     unet = UNet2DConditionModelGated().init_synthetic(seed=0).to(dev)
@@ -99,6 +130,10 @@ def main():
                                   depth_order=[-1, -2, 0, 1, -3, -4, 2, 3, -5, -6, 4, 5, -7, 6],
                                   resource_aware_normalization=False, optimal_transport=True).to(dev)
     hn.train(); qz.train()
+    if args.router_seed is not None:
+        if args.router_optimizer != "hip" or args.eager:
+            ap.error("--router-seed compares two captured routers: it needs --router-optimizer hip and no --eager")
+        return router_noise_ab(args, dev, unet, hn, qz)
     if args.short_batches:
         return short_batches_ab(args, dev, unet, hn, qz)
     step = (PrunerStep if args.eager else GraphedPrunerStep)(unet, hn, qz)
