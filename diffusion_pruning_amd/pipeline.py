@@ -22,6 +22,7 @@ MI355X-first differences:
 """
 from __future__ import annotations
 
+import contextlib
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Optional
@@ -424,6 +425,7 @@ class DispatchOutput(PipelineOutput):
     """PipelineOutput of ExpertDispatchLoop: the parent's fields (latents / images in the caller's prompt order) plus the groups
     the batch ran as"""
     groups: Optional[list] = None        # [(expert index, row indices, bucket size, graph_was_reused)]
+    lanes: Optional[list] = None         # the stream lane every entry of ``groups`` ran on, in that order (None: built with lanes=1)
 
 
 class PruningDenoiseLoop:
@@ -674,6 +676,84 @@ def plan_groups(idx_list, group_sizes=(1, 2, 4, 8)):
     return groups
 
 
+MAX_LANES = 4      # a process opens four hardware queues (HIP's default): a lane beyond that only queues behind another
+
+
+def plan_lanes(groups, n_lanes, key_of, pinned=None, cost=None):
+    """The stream lane of every group of a plan (``plan_groups``' ``(expert, rows, bucket)`` tuples): a list of lane indices
+    in ``range(n_lanes)``, one per group, in plan order.  Pure host logic, deterministic.
+
+    Groups with equal ``key_of(group)`` get the same lane -- the chunks of an expert whose rows were cut at the largest bucket
+    share one captured step and its static buffers, so they must run in order on one stream.  A key found in ``pinned``
+    (``{key: lane}``: a captured step replays only on the lane it was captured for) keeps that lane.  The remaining keys are
+    placed longest first on the lane that is least loaded so far; equal costs go by plan order, equal loads to the lowest
+    lane.  The cost of a key is the sum of ``cost(bucket)`` over its groups.
+
+    ``cost`` defaults to ``4 + bucket``: a rough relative model read off three per-call times of the U-Net under CFG (4.4 /
+    4.8 / 12.1 ms at buckets 1 / 2 / 8).  Nobody has measured it for this purpose.  It steers where time goes, never
+    what is computed."""
+    n_lanes = int(n_lanes)
+    if n_lanes < 1:
+        raise ValueError(f"plan_lanes: n_lanes must be at least 1, got {n_lanes}")
+    cost = cost or (lambda bucket: 4 + bucket)
+    pinned = pinned or {}
+    keys = [key_of(g) for g in groups]
+    total = {}                                     # key -> summed cost, in order of first appearance
+    for g, k in zip(groups, keys):
+        total[k] = total.get(k, 0) + cost(g[2])
+    load = [0] * n_lanes
+    lane_of = {}
+    for k, c in total.items():
+        if k in pinned:
+            lane = int(pinned[k])
+            if not 0 <= lane < n_lanes:
+                raise ValueError(f"plan_lanes: a key is pinned to lane {lane}, outside range({n_lanes})")
+            lane_of[k] = lane
+            load[lane] += c
+    order = {k: i for i, k in enumerate(total)}
+    for k in sorted((k for k in total if k not in lane_of), key=lambda k: (-total[k], order[k])):
+        lane = min(range(n_lanes), key=lambda j: (load[j], j))
+        lane_of[k] = lane
+        load[lane] += total[k]
+    return [lane_of[k] for k in keys]
+
+
+def plan_waves(keys, max_keys):
+    """Cut a plan into waves of consecutive groups with at most ``max_keys`` distinct keys each: ``keys[i]`` is group i's key;
+    returns lists of group indices.  A wave's captured steps all fit the LRU at once.  Pure host logic."""
+    max_keys = int(max_keys)
+    if max_keys < 1:
+        raise ValueError(f"plan_waves: max_keys must be at least 1, got {max_keys}")
+    waves, cur, seen = [], [], set()
+    for i, k in enumerate(keys):
+        if k not in seen and len(seen) == max_keys:
+            waves.append(cur)
+            cur, seen = [], set()
+        cur.append(i)
+        seen.add(k)
+    if cur:
+        waves.append(cur)
+    return waves
+
+
+def round_robin(queues):
+    """The order in which the host issues the work of a wave: ``queues[lane]`` is that lane's groups in plan order, each a list
+    of items in order; yields ``(lane, item)``, one item per lane in turn (lanes ascending) until every lane is empty.  Per
+    lane the items keep their order across groups.  Pure host logic."""
+    flat = [[item for group in lane for item in group] for lane in queues]
+    pos = [0] * len(flat)
+    left = sum(len(f) for f in flat)
+    while left:
+        for lane, f in enumerate(flat):
+            if pos[lane] < len(f):
+                yield lane, f[pos[lane]]
+                pos[lane] += 1
+                left -= 1
+
+
+_side_streams = {}     # device index -> (side streams, probe record): chosen once per device and process, shared by every loop
+
+
 class ExpertDispatchLoop(PruningDenoiseLoop):
     """The routed call of StableDiffusionPruningPipeline (pruning_pipelines.py:746-759: route, ``set_structure``, loop) for a
     batch whose prompts go to MORE than one expert, at each expert's own cost: the batch is routed once, grouped by expert
@@ -683,7 +763,34 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
     are independent: the padded rows are computed and dropped), so a handful of captured steps serves any split.  Results
     come back in the caller's prompt order.  Every step is the fused one (``fused_step`` of the scheduler).
 
-    Groups run one after another on the current stream.
+    lanes=1 (the default): groups run one after another on the current stream.
+
+    lanes in 2..4 (graph path only): groups of different experts run SIDE BY SIDE on stream lanes.  At the small batch of a
+    group the forward is a chain of dependent launches that leaves the chip mostly idle, and groups of different experts
+    cannot be merged into one chain, so a second chain fills the gaps of the first.  Lane 0 is the caller's current stream,
+    lanes 1.. are side streams that a spin-kernel probe found to overlap it and each other
+    (``graph_utils.concurrent_streams``; once per device and process, so every loop shares them).  When the probe finds fewer
+    than asked for, the loop runs with the lanes it has; ``stream_probe`` says so and ``lane_streams`` holds the streams of the
+    last call.  A caller's stream that happens to be the very stream of a side lane only serialises that lane.  How a call
+    runs:
+      * the prologue is the one of lanes=1 (route, one device-to-host copy, ``plan_groups``, encoders); then every side lane
+        waits for the caller's stream;
+      * the groups are cut into waves of at most ``max_graphs`` distinct keys (``plan_waves``) and every wave is spread over
+        the lanes by ``plan_lanes``; the host synchronises a wave's lanes before the next wave starts;
+      * set-up of a wave, serial on the host, each group on its lane's stream and, for lanes >= 1, under
+        ``ops.scratch_domain(("dispatch", lane))`` (lane 0 keeps the caller's domain: its graphs are the graphs of lanes=1):
+        install, row gathers, ``precompute_context``, look-up or capture.  A group's set-up waits for the previous group's,
+        so packs built for one lane are complete before another lane reads them.  All captures of a wave precede its
+        replays (``torch.cuda.graph`` synchronises the device).  A captured step records its lane and replays only there for
+        as long as it lives -- its scratch belongs to that domain;
+      * replay: per group the items [refresh the static buffers, one item per model call, collect the result]; the host
+        issues one item per lane in turn (``round_robin``).  Groups of one key share a lane, so a refresh never overtakes the
+        previous group's collect.  Every lane replays whole graphs; lanes are never merged into one graph;
+      * join: the caller's stream waits for every lane, then scatters the rows back and fills the ratios;
+      * a graph is evicted or replaced only after the host has synchronised the lane it ran on.
+    Overlapping replays share nothing but what scratch.py hands out per (stream, domain): every other buffer a replay writes
+    is in its own graph pool or is one of its static buffers; packs and tables are only read.  The results are those of
+    lanes=1 bit for bit; whether lanes save time is a measurement, not a promise.
 
     experts: ``{index: UNet2DConditionModelPruned | UNet2DConditionModelGated}`` -- fine-tuned experts with weights of their
     own (checkpoint.from_pretrained).  Group e then runs on ``experts[e]`` as it is installed, without ``set_structure``;
@@ -697,8 +804,13 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
     two ``invalidate_plans()``; every further distinct code that is captured pins one more."""
 
     def __init__(self, unet, hyper_net=None, quantizer=None, scheduler=None, vae=None, text_encoder=None, prompt_encoder=None,
-                 experts=None, group_sizes=(1, 2, 4, 8), max_graphs: int = 16):
+                 experts=None, group_sizes=(1, 2, 4, 8), max_graphs: int = 16, lanes: int = 1):
         super().__init__(unet, hyper_net, quantizer, scheduler, vae, text_encoder, prompt_encoder)
+        if not isinstance(lanes, int) or not 1 <= lanes <= MAX_LANES:
+            raise ValueError(f"lanes must be an int in 1..{MAX_LANES}, got {lanes!r}")
+        self.lanes = lanes
+        self.lane_streams = []                     # the streams of the last call with lanes > 1: [caller's, side lanes ...]
+        self.stream_probe = None                   # what the choice of the side lanes measured (set by the first such call)
         self.experts = None if experts is None else dict(experts)
         self.group_sizes = tuple(sorted({int(s) for s in group_sizes}))
         if not self.group_sizes or self.group_sizes[0] < 1:
@@ -735,9 +847,11 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
                  fused_step: bool = True, seeds=None, latent_shape=None) -> DispatchOutput:
         """The arguments of PruningDenoiseLoop.__call__; hyper_net_input or router_ids is required (there is nothing to
         dispatch on otherwise), and the step is always the fused one.  Returns latents / images in the caller's prompt order,
-        ``arch_indices`` [B], ``resource_ratios`` [B] and ``groups``."""
+        ``arch_indices`` [B], ``resource_ratios`` [B], ``groups`` and, from a loop built with lanes > 1, ``lanes``."""
         if not fused_step:
             raise ValueError("ExpertDispatchLoop runs the fused step only")
+        if self.lanes > 1 and not use_graph:
+            raise ValueError(f"lanes={self.lanes} needs use_graph=True: the lanes overlap captured steps, eager groups run with lanes=1")
         if self.hyper_net is None or self.quantizer is None:
             raise ValueError("ExpertDispatchLoop needs a hyper_net and a quantizer to route with")
         prompt_embeds, negative_prompt_embeds, hyper_net_input = self._inputs(
@@ -768,6 +882,12 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
         ratios = None
         report = []
         rescale = float(guidance_rescale) if do_cfg else 0.0
+        if self.lanes > 1:
+            report, lane_of, ratios = self._run_lanes(groups, codes, arch_q, latents, seeds, prompt_embeds, negative_prompt_embeds, ts,
+                                                      out, do_cfg, guidance_scale, rescale)
+            images = self.decode_latents(out, output_type) if output_type != "latent" else None
+            return DispatchOutput(latents=out, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios,
+                                  images=images, groups=report, lanes=lane_of)
         for e, rows, bucket in groups:
             code = codes[rows[0]]
             assert all(codes[r] == code for r in rows), f"rows {rows} of expert {e} carry different codes"
@@ -816,3 +936,143 @@ class ExpertDispatchLoop(PruningDenoiseLoop):
             images = self.decode_latents(out, output_type)
         return DispatchOutput(latents=out, arch_indices=idx, arch_vectors_quantized=arch_q, resource_ratios=ratios,
                               images=images, groups=report)
+
+    # ---- lanes > 1 -----------------------------------------------------------------------------------------------------------
+    def _lane_streams(self, dev):
+        """[the caller's current stream, side lanes ...] of this call; the side lanes are probed for on the first call per
+        device and process (always for MAX_LANES, a loop takes the first ``lanes - 1``)"""
+        from . import graph_utils
+        caller = torch.cuda.current_stream(dev)
+        ent = _side_streams.get(caller.device.index)
+        if ent is None:
+            log = []
+            sides = graph_utils.concurrent_streams(MAX_LANES, caller, log=log)
+            ent = _side_streams[caller.device.index] = (sides, log[0])
+        sides = ent[0][:self.lanes - 1]
+        self.lane_streams = [caller] + sides
+        self.stream_probe = dict(ent[1], lanes_asked=self.lanes, lanes_effective=len(self.lane_streams))
+        return self.lane_streams
+
+    def _replay_items(self, g, latents, ts, ctx, B, seeds, sink, caller):
+        """``_replay`` cut into the items a lane issues one at a time -- the same launches in the same order: refresh the
+        static buffers, one item per model call, collect (the result goes to ``sink``; the caller's stream will read it)"""
+        def refresh():
+            g["lat"].copy_(latents)
+            g["ctx"].ehs.copy_(ctx.ehs)
+            for k_, v_ in ctx.kv.items():
+                g["ctx"].kv[k_].copy_(v_)
+            for name, t_ in self._state(latents, seeds).items():
+                g["state"][name].copy_(t_)
+
+        def call(i):
+            def item():
+                g["t"].copy_(ts[i].expand(B))
+                self.scheduler.load_step(g["state"], i)
+                g["graph"].replay()
+                g["lat"].copy_(g["out"])
+            return item
+
+        def collect():
+            res = g["lat"].clone()
+            res.record_stream(caller)
+            sink(res)
+        return [refresh] + [call(i) for i in range(self.scheduler.n_model_calls())] + [collect]
+
+    def _run_lanes(self, groups, codes, arch_q, latents, seeds, prompt_embeds, negative_prompt_embeds, ts, out, do_cfg,
+                   guidance_scale, rescale):
+        """the groups of a routed batch on stream lanes (class docstring); fills ``out`` on the caller's stream and returns
+        (groups report, lane of every group, resource ratios)"""
+        from . import ops
+        dev = latents.device
+        nB = latents.shape[0]
+        streams = self._lane_streams(dev)
+        caller = streams[0]
+        for s in streams[1:]:
+            s.wait_stream(caller)
+
+        def model_of(e):
+            return self.unet if self.experts is None else self.experts[e]
+
+        def key_of(group):
+            e, rows, bucket = group
+            return (e, id(model_of(e)), codes[rows[0]], bucket, type(self.scheduler).__name__, self.scheduler.prediction_type,
+                    (bucket,) + tuple(latents.shape[1:]), latents.dtype, do_cfg, float(guidance_scale), rescale, str(dev),
+                    self._stochastic())
+        keys = [key_of(grp) for grp in groups]
+        results, model_ratio = [None] * len(groups), [None] * len(groups)
+        lane_of, reused_of = [None] * len(groups), [False] * len(groups)
+        used = []
+        for wave in plan_waves(keys, self.max_graphs):
+            for s in used:
+                s.synchronize()                    # the previous wave is done: its graphs may be evicted or replaced
+            wave_keys = {keys[i] for i in wave}
+            pinned = {k: self._graphs[k]["lane"] for k in wave_keys if k in self._graphs}
+            plan = plan_lanes([groups[i] for i in wave], len(streams), key_of, pinned)
+            queues = [[] for _ in streams]
+            prev = None
+            for i, lane in zip(wave, plan):
+                e, rows, bucket = groups[i]
+                stream = streams[lane]
+                if prev is not None and prev is not stream:
+                    stream.wait_stream(prev)       # set-up is in plan order on the device too: packs are built before they are read
+                prev = stream
+                with torch.cuda.stream(stream), (ops.scratch_domain(("dispatch", lane)) if lane else contextlib.nullcontext()):
+                    code = codes[rows[0]]
+                    assert all(codes[r] == code for r in rows), f"rows {rows} of expert {e} carry different codes"
+                    model = model_of(e)
+                    if self.experts is None:
+                        self._install(arch_q[rows[0]:rows[0] + 1], code)
+                    take = torch.tensor(rows + [rows[-1]] * (bucket - len(rows)), dtype=torch.long, device=dev)
+                    lat_g = latents.index_select(0, take)
+                    seeds_g = None if seeds is None else seeds.index_select(0, take)
+                    ehs = prompt_embeds.index_select(0, take)
+                    if do_cfg:
+                        ehs = torch.cat([negative_prompt_embeds.index_select(0, take), ehs])
+                    ctx = model.precompute_context(ehs)
+                    Bm = bucket * (2 if do_cfg else 1)
+                    g = self._graphs.get(keys[i])
+                    reused = g is not None and ctx.key is not None and g["ctx"].key == ctx.key
+                    if not reused:
+                        # room is made before the capture; what leaves is no key of this wave (least recently used first) and is
+                        # released only once the host has synchronised the lane it ran on
+                        leaving = [self._graphs.pop(keys[i], None)]
+                        while len(self._graphs) >= self.max_graphs:
+                            leaving.append(self._graphs.pop(next(k for k in self._graphs if k not in wave_keys)))
+                        for lane_ in {old["lane"] for old in leaving if old is not None}:
+                            streams[lane_].synchronize()
+                        g = None
+                        del leaving
+                        g = self._capture(lat_g, ts, ctx, Bm, guidance_scale, do_cfg, rescale, True, model, seeds_g)
+                        g["lane"] = lane
+                        if ctx.key is not None:
+                            self._graphs[keys[i]] = g
+                    else:
+                        self._graphs.move_to_end(keys[i])
+                    if getattr(model, "resource_info_dict", None) is not None:
+                        # pruning_pipelines.py:822-824, per group, while the group's code is the installed one
+                        model_ratio[i] = model.calc_macs()["cur_prunable_macs"] / model.resource_info_dict["cur_prunable_macs"]
+
+                    def sink(res, i=i):
+                        results[i] = res
+                    queues[lane].append(self._replay_items(g, lat_g, ts, ctx, Bm, seeds_g, sink, caller))
+                lane_of[i], reused_of[i] = lane, reused
+            for lane, item in round_robin(queues):
+                with torch.cuda.stream(streams[lane]):
+                    item()
+            used = [streams[lane] for lane in sorted(set(plan))]
+        for s in streams[1:]:
+            caller.wait_stream(s)
+        ratios = None
+        report = []
+        for i, (e, rows, bucket) in enumerate(groups):
+            rows_t = torch.tensor(rows, dtype=torch.long, device=dev)
+            out.index_copy_(0, rows_t, results[i][:len(rows)].to(out.dtype))
+            r = model_ratio[i]
+            if r is not None:
+                if ratios is None:
+                    ratios = torch.zeros(nB, dtype=torch.float32, device=dev)
+                if torch.is_tensor(r) and r.is_cuda:
+                    r.record_stream(caller)
+                ratios.index_copy_(0, rows_t, torch.as_tensor(r, dtype=torch.float32, device=dev).reshape(-1)[:1].expand(len(rows)))
+            report.append((e, list(rows), bucket, reused_of[i]))
+        return report, lane_of, ratios

@@ -14,7 +14,8 @@ graph, see ``workspace``.
 
 The counter pool grows in chunks of ``N_SLABS`` slabs, outside capture only, and a slab handed out keeps its address for the life
 of the process.  The number of keys is bounded: torch hands out stream handles from a fixed pool per device and the domains are
-a few literals ("teacher", "val_teacher", the VAE's); a slab is 256 KiB.
+a few literals ("teacher", "val_teacher", the VAE's) and ("dispatch", lane) for the at most three side lanes of
+pipeline.ExpertDispatchLoop; a slab is 256 KiB.
 """
 from __future__ import annotations
 

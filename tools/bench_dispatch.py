@@ -7,9 +7,11 @@ benchmark experts (bench.expert_mask), through
 in ms per image, plus the graph-node count and the steady-state ms of one step with the fused step off and on (one expert, the
 whole batch).  --seeds: the latents are drawn in the loop from one seed per prompt (ops.randn) instead of handed in.
 --eta X (DDIM) / --sde (SDE-DPM-Solver++): the stochastic samplers, seeded; the JSON line then also carries "noise_node": the
-fused step of the same scheduler class without and with the noise launch, measured in this same run.  Prints one JSON line.
+fused step of the same scheduler class without and with the noise launch, measured in this same run.
+--lanes N (1..4): ExpertDispatchLoop(lanes=N), the expert groups side by side on stream lanes; the JSON line carries "lanes", the
+effective number of lanes and what the side-stream probe measured.  Prints one JSON line.
 usage: python tools/bench_dispatch.py [--scheduler pndm|ddim|dpmpp] [--steps 25] [--prompts 8] [--ks 1,2,4,8] [--seeds]
-       [--eta X | --sde]"""
+       [--eta X | --sde] [--lanes N]"""
 import argparse
 import json
 import os
@@ -37,6 +39,7 @@ ap.add_argument("--guidance", type=float, default=7.5)
 ap.add_argument("--seeds", action="store_true", help="draw the latents in the loop from one seed per prompt")
 ap.add_argument("--eta", type=float, default=0.0, help="stochastic DDIM (implies --scheduler ddim and --seeds)")
 ap.add_argument("--sde", action="store_true", help="SDE-DPM-Solver++ (implies --scheduler dpmpp and --seeds)")
+ap.add_argument("--lanes", type=int, default=1, help="stream lanes of ExpertDispatchLoop (1 = groups one after another)")
 a = ap.parse_args()
 if a.eta > 0.0 and a.sde:
     ap.error("--eta and --sde exclude each other")
@@ -104,7 +107,7 @@ def timed(fn):
 
 res = {"tool": "bench_dispatch", "prompts": a.prompts, "steps": a.steps, "unet_calls": n_calls,
        "scheduler": {"pndm": "PNDM", "ddim": "DDIM", "dpmpp": "DPM-Solver++ (2M)"}[a.scheduler] + (" SDE" if a.sde else ""), "cfg": True,
-       "eta": a.eta, "seeded_latents": a.seeds, "guidance_scale": a.guidance, "by_k": {}}
+       "eta": a.eta, "seeded_latents": a.seeds, "guidance_scale": a.guidance, "lanes": a.lanes, "lanes_effective": 1, "stream_probe": None, "by_k": {}}
 for k in [int(v) for v in a.ks.split(",")]:
     assign = [i % k for i in range(a.prompts)]
     parent = PruningDenoiseLoop(model, hn, qz, scheduler=Scheduler())
@@ -112,7 +115,7 @@ for k in [int(v) for v in a.ks.split(",")]:
     assert out.arch_indices.tolist() == assign, (out.arch_indices.tolist(), assign)
     ta = sorted(timed(lambda: parent(**batch(assign)))[0] for _ in range(3))[1]
     model.invalidate_plans()
-    loop = ExpertDispatchLoop(model, hn, qz, scheduler=Scheduler())
+    loop = ExpertDispatchLoop(model, hn, qz, scheduler=Scheduler(), lanes=a.lanes)
     tb, out = timed(lambda: loop(**batch(assign)))
     assert out.arch_indices.tolist() == assign and torch.isfinite(out.latents).all()
     warm = [timed(lambda: loop(**batch(assign))) for _ in range(3)]
@@ -121,6 +124,9 @@ for k in [int(v) for v in a.ks.split(",")]:
     res["by_k"][str(k)] = {"per_sample_gates_ms_per_image": round(ta / a.prompts, 2), "dispatch_cold_ms_per_image": round(tb / a.prompts, 2),
                            "dispatch_warm_ms_per_image": round(tc / a.prompts, 2), "groups": [(e, len(r), b) for e, r, b, _ in out.groups],
                            "graphs": len(loop._graphs)}
+    if a.lanes > 1:
+        res["by_k"][str(k)]["group_lanes"] = out.lanes
+        res["lanes_effective"], res["stream_probe"] = len(loop.lane_streams), loop.stream_probe
     del parent, loop
 # one step, fused off / on: one expert, the whole batch
 model.set_structure(bench.expert_mask(st, 2, dev))
